@@ -8,7 +8,13 @@ One "step" = one full image (160,000 rays) through run_one_iter_of_nerf -> predi
 this rank's GPU, inputs (ray bundle, packed weights) resident in HBM before the timed region.
 
     python bench.py --gpus N --steps K --warmup W            (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W --full     (+ every informational leg, a few minutes)
+    python bench.py ... --dump-outputs DIR                   (+ the last timed step's maps as DIR/<name>.npy)
 
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step, dtype, config).
+--full adds what takes runs of its own: the fine-net kernel's roofline (HIP events, PMC record, library-GEMM
+yardstick), the CPU oracle baseline with PSNR / Dex agreement, the fp16-policy and exact-fp32 renders, the other
+BASELINE configs, the training-iteration rates and, at N > 1, the data-parallel step and the sharded image.
 Multi-GPU: rays/images are independent units -> each rank renders its own view of the scene (weak scaling,
 no data-path collective); the barrier + max-over-ranks timing uses RCCL.
 Prints ONE JSON line on rank 0.
@@ -467,15 +473,34 @@ def cpu_baseline(sample_rays=16384, return_aux=False):
     return (cb, sel, out, aux) if return_aux else (cb, sel, out)
 
 
+OUTPUT_NAMES = ("rgb_coarse", "depth_coarse", "acc_coarse", "rgb_fine", "depth_fine", "acc_fine")
+
+
+def dump_outputs(out, path):
+    """What the timed render returned (run_one_iter_of_nerf, validation mode) as float32 .npy files under `path`: the six image maps
+    by name and the K Dex depth maps stacked as dex_depth (K, H, W) - 400 x 400 x 30 floats, 19.2 MB."""
+    os.makedirs(path, exist_ok=True)
+    arrays = dict(zip(OUTPUT_NAMES, out[:6]))
+    arrays["dex_depth"] = torch.stack(list(out[6:]))
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train", action="store_true", help="skip the secondary training-iteration measurement")
+    ap.add_argument("--full", action="store_true", help="also every informational leg (roofline, CPU baseline, other precisions / "
+                                                        "configs, training rates); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the maps of the last timed step as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle and the legs compared with it")
+    ap.add_argument("--no-train", action="store_true", help="with --full: skip the training-iteration measurements")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -549,8 +574,11 @@ def main():
     value = rays_total / elapsed
 
     note(f"timed region: {elapsed:.3f} s for {args.steps} steps")
+    if args.dump_outputs and rank == 0:
+        names = dump_outputs(out, args.dump_outputs)
+        note(f"outputs of the last timed step: {', '.join(names)} -> {args.dump_outputs}")
     train_dp = None
-    if world > 1 and not args.no_train:
+    if world > 1 and args.full and not args.no_train:
         # the data-parallel training step (BASELINE configs 4 / 5 are training configs): collective inside, so every rank runs it
         train_dp = train_rate(models, cfg, ro, rd, ex, ed, dist=dist, pose_id=7 + rank)
         note(f"data-parallel training step: {train_dp['ms_per_step']:.2f} ms, all-reduce alone {train_dp['allreduce_ms']:.3f} ms")
@@ -559,10 +587,6 @@ def main():
     result = None
     if rank == 0:
         rdt = render_dtype()   # 'bf16' runs its no-grad renders in fp16 under the default render policy (nerf.set_render_policy)
-        kt, ktf = time_dominant_kernel(models, ro, rd)
-        note(f"dominant kernel ({rdt}) {kt * 1e3:.2f} ms = {ktf:.0f} TFLOP/s")
-        peak = PEAK_TFLOPS[rdt]
-        whole_tf = value / world * POINTS_PER_RAY * FLOP_PER_POINT / 1e12
         result = {
             "metric": "rays/sec (64+128 samples) + PSNR vs ref, 400x400 scene", "value": value, "unit": "rays/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
@@ -579,146 +603,159 @@ def main():
                                    "FlexibleNeRFModel D8/W256/skip4 + viewdirs, PE L=10/4, 20 Dex thresholds, "
                                    "validation mode (det. resampling, no noise)",
                        "rays_per_step_per_gpu": H * W, "sharding": f"{world} ranks x own view (no collective in the path)"},
-            "roofline": {"bound": "mfma", "achieved": ktf, "peak": peak, "unit": "TFLOP/s", "frac": ktf / peak,
-                         "traffic": pmc_record(rdt).get("hbm_bytes_per_launch"),
-                         "traffic_record": pmc_record(rdt).get("record"),
-                         "algorithmic_bytes": H * W * (NC + NF) * 20 + H * W * 44,
-                         "matrix_pipe_busy_frac_pmc": pmc_record(rdt).get("matrix_pipe_busy_frac"),
-                         "kernel": headline_kernel_name(rdt) + " (fine net, 160000x192 points)",
-                         "kernel_ms": kt * 1e3, "whole_path_tflops": whole_tf},
         }
-        if train_dp is not None:
-            result["train_dp"] = train_dp
-        if world > 1:
-            args.no_cpu_baseline = True   # the CPU baseline is reported at N=1 only
-        if not args.no_cpu_baseline:
-            cb, sel, ref = cpu_baseline()
-            result["cpu_baseline"] = cb
-            rgb = out[3].reshape(-1, 3)[torch.from_numpy(sel).to(dev)].cpu().numpy()
-            mse = float(np.mean((rgb - ref[3].numpy()) ** 2))
-            result["psnr_vs_oracle_db"] = float(-10.0 * np.log10(max(mse, 1e-12)))
-            result["dex_vs_oracle"] = dex_agreement(out, ref, sel, dev)
-            result["gpu_over_cpu"] = value / world / cb["value"]
-        if args.precision == "bf16" and not args.no_cpu_baseline:
-            # the same render on the library's default policy: the fp16 instance of the kernel (range-guarded), round 3's headline
-            nerf.set_render_policy(None)
-            try:
-                render(models, cfg, ro, rd, ex, ed)
-                torch.cuda.synchronize()
-                t1 = time.perf_counter()
-                for _ in range(3):
-                    out16 = render(models, cfg, ro, rd, ex, ed)
-                torch.cuda.synchronize()
-                dt16 = (time.perf_counter() - t1) / 3
-                kt16, ktf16 = time_dominant_kernel(models, ro, rd, reps=3)
-                rgb16 = out16[3].reshape(-1, 3)[torch.from_numpy(sel).to(dev)].cpu().numpy()
-                mse16 = float(np.mean((rgb16 - ref[3].numpy()) ** 2))
-                result["default_policy_fp16_render"] = {"value": H * W / dt16, "unit": "rays/s", "dtype": render_dtype(), "kernel_ms": kt16 * 1e3,
-                                                        "tflops": ktf16, "frac": ktf16 / PEAK_TFLOPS["fp16"],
-                                                        "kernel": headline_kernel_name(render_dtype()),
-                                                        "traffic": pmc_record(render_dtype()).get("hbm_bytes_per_launch"),
-                                                        "traffic_record": pmc_record(render_dtype()).get("record"),
-                                                        "psnr_vs_oracle_db": float(-10.0 * np.log10(max(mse16, 1e-12))),
-                                                        "dex_vs_oracle": dex_agreement(out16, ref, sel, dev)}
-            finally:
-                nerf.set_render_policy("bf16")
-        if args.precision == "bf16" and not args.no_cpu_baseline:
-            # the same render in the exact-fp32 parity mode (north_star's 1e-4 tolerance holds in this mode only): 3 steps
-            nerf.set_precision("fp32")
-            try:
-                render(models, cfg, ro, rd, ex, ed)
-                torch.cuda.synchronize()
-                t1 = time.perf_counter()
-                for _ in range(3):
-                    out32 = render(models, cfg, ro, rd, ex, ed)
-                torch.cuda.synchronize()
-                dt32 = (time.perf_counter() - t1) / 3
-                kt32, ktf32 = time_dominant_kernel(models, ro, rd, "fp32", reps=2)
-                rgb32 = out32[3].reshape(-1, 3)[torch.from_numpy(sel).to(dev)].cpu().numpy().astype(np.float64)
-                per_ray = np.abs(rgb32 - ref[3].numpy()).max(-1) / np.abs(ref[3].numpy()).max()
-                # max over 16,384 rays sits on a handful of rays where an ulp in sigma moves a resampled depth: two fp32-level
-                # evaluations of the reference itself differ by 6.0e-4 there (3 rays over 1e-4, p99.9 9.4e-6:
-                # profiles/r02_fp32_noise_floor.md); the 1e-4 gate of the parity tests is on the golden rays
-                result["fp32_mode"] = {"value": H * W / dt32, "unit": "rays/s", "kernel_ms": kt32 * 1e3, "tflops": ktf32,
-                                       "peak": PEAK_TFLOPS["fp32"], "frac": ktf32 / PEAK_TFLOPS["fp32"],
-                                       "rgb_fine_rel_err_vs_oracle": {"max": float(per_ray.max()), "p99_9": float(np.quantile(per_ray, 0.999)),
-                                                                      "rays_over_1e-4": int((per_ray > 1e-4).sum()), "rays": int(per_ray.size)},
-                                       "dex_vs_oracle": dex_agreement(out32, ref, sel, dev)}
-            finally:
-                nerf.set_precision(args.precision)
-        if world == 1 and not args.no_cpu_baseline:
-            # BASELINE configs[2] (Dex-NeRF transparent-object scene on the as-shipped 4 x 128 nets: 270x480 after the fork's half-res
-            # rule, 64+64, near 0.3 / far 4 - config/messytable-obj-remote.yml) and configs[3] as a single-GPU render (800x800, 64+192,
-            # D8/W256), 3 images each, with the fine-net launch's own roofline
-            kw_shipped = dict(MODEL_KW, num_layers=4, hidden_size=128)
-            result["c3_render"] = other_config_render(dev, rank, "C3 render: 270x480, 64+64 samples, 4x128 nets (as shipped), near 0.3 far 4",
-                                                      270, 480, 64, 64, kw_shipped, 167680, 0.3, 4.0)
-            result["c4_render"] = other_config_render(dev, rank, "C4 render: 800x800, 64+192 samples, D8/W256 nets",
-                                                      800, 800, 64, 192, MODEL_KW, FLOP_PER_POINT, 2.0, 6.0)
-            result["c3_render_128_192"] = other_config_render(dev, rank, "C3 render, the fork's second sampling (config/messytable-obj-edward.yml:136-138): "
-                                                              "270x480, 128+192 samples, 4x128 nets, near 0.3 far 4", 270, 480, 128, 192, kw_shipped, 167680, 0.3, 4.0)
-            note(f"C3 {result['c3_render']['value'] / 1e6:.2f} M rays/s ({result['c3_render']['frac']:.3f} of peak), "
-                 f"C3 128+192 {result['c3_render_128_192']['value'] / 1e6:.2f} M rays/s ({result['c3_render_128_192']['frac']:.3f}), "
-                 f"C4 {result['c4_render']['value'] / 1e6:.2f} M rays/s ({result['c4_render']['frac']:.3f})")
-            # BASELINE configs[4] as configured: the IR scene's 128 + 256 samples in exact fp32 (train_dexnerf_ir.py; D8/W256 nets on the
-            # MessyTable frame, 270x480) - one image; its training step (luminance loss head, train_nerf_ir.py:260-263) below
-            nerf.set_precision("fp32")
-            try:
-                result["c5_render"] = other_config_render(dev, rank, "C5 render: 270x480, 128+256 samples, D8/W256 nets, exact fp32, near 0.3 far 4",
-                                                          270, 480, 128, 256, MODEL_KW, FLOP_PER_POINT, 0.3, 4.0, steps=1)
-                if not args.no_train:
-                    m5, cfg5, ro5, rd5, _, _ = build_scene(dev, rank, 270, 480, 128, 256, MODEL_KW, 0.3, 4.0)
-                    result["c5_train"] = train_rate(m5, cfg5, ro5, rd5, ex, ed, n_rays=1024, steps=4, nc=128, nf=256, luminance=True, h=270, w=480,
-                                                    near=0.3, far=4.0, what_tail="128+256 samples, perturb + noise 0.2, D8/W256 x2, exact fp32, "
-                                                    "IR loss head (MSE on the luminance of both passes: train_nerf_ir.py:260-263)")
-            finally:
-                nerf.set_precision(args.precision)
-            note(f"C5 render {result['c5_render']['value'] / 1e6:.3f} M rays/s ({result['c5_render']['frac']:.3f} of the fp32 peak)")
-        if not args.no_train and world == 1:
-            result["train"] = train_rate(models, cfg, ro, rd, ex, ed)
-        if not args.no_train and world == 1 and args.precision == "bf16":
-            # the same iteration with the tensors saved for the backward at 16 bits on the 32-point training kernels (what 'bf16' meant up to
-            # round 3; 'bf16' now saves at 8 bits on the 48-point kernels - same forward bits; HISTORY.md section 4.6)
-            nerf.set_precision("bf16-s16")
-            try:
-                models16, cfg16, _, _, _, _ = build_scene(dev, rank)
-                result["train_s16_mode"] = train_rate(models16, cfg16, ro, rd, ex, ed)
-            finally:
-                nerf.set_precision(args.precision)
-            # the same iteration in the exact-fp32 parity mode (BASELINE config 5 trains in fp32): informational
-            nerf.set_precision("fp32")
-            try:
-                models32, cfg32, _, _, _, _ = build_scene(dev, rank)
-                result["train_fp32_mode"] = train_rate(models32, cfg32, ro, rd, ex, ed, steps=4)
-            finally:
-                nerf.set_precision(args.precision)
-            # BASELINE config 3 as a shape: the as-shipped 4 x 128 nets, 1024 rays per step, 64+64 samples, whole iteration
-            # replayed as one HIP graph by the build-owned driver (informational; a few seconds)
-            try:
-                sys.path.insert(0, os.path.join(REPO, "dex-nerf_amd"))
-                import train_dexnerf
-                for key, prec in (("train_as_shipped", "bf16"), ("train_as_shipped_s16_mode", "bf16-s16")):
-                    res = train_dexnerf.main(["--iters", "4000", "--size", "64", "--views", "8", "--num-random-rays", "1024", "--layers", "4",
-                                              "--width", "128", "--num-fine", "64", "--validate-every", "0", "--quiet", "--precision", prec])
-                    result[key] = {"rays_per_s": res["rays_per_s"], "rays_per_step": 1024, "final_train_psnr_db": res["history"][-1][2],
-                                   "steady_ms_per_iter": res.get("steady_ms_per_iter"),
-                                   "steady_rays_per_s": 1024.0 / (res["steady_ms_per_iter"] * 1e-3) if res.get("steady_ms_per_iter") else None,
-                                   "hip_graphs_per_iter": res.get("hip_graphs"),
-                                   "what": f"train_dexnerf.py --precision {prec}, 4x128 nets, 64+64 samples, nerf.FusedTrainStep + nerf.FlatAdam "
-                                           "replayed as one HIP graph; rays_per_s over all 4000 iterations incl. the eager ones and the capture, "
-                                           "steady_*: from iteration 20 on"}
-            except Exception as exc:  # noqa: BLE001
-                result["train_as_shipped"] = {"error": f"{type(exc).__name__}: {exc}"}
-            finally:
-                nerf.set_precision(args.precision)
-        if world == 1 and not args.no_cpu_baseline and not args.no_train:
-            result["train_psnr_vs_oracle"] = train_psnr_vs_oracle(dev, precision=args.precision)
-            note(f"training PSNR at the last mark: {result['train_psnr_vs_oracle']['marks'][-1]}")
-        result["roofline"]["library_gemm"] = library_gemm_tflops(dev, rdt)
+        if args.full:
+            full_legs(args, result, dev, rank, world, value, train_dp, models, cfg, ro, rd, ex, ed, out, note)
         print(json.dumps(result), flush=True)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def full_legs(args, result, dev, rank, world, value, train_dp, models, cfg, ro, rd, ex, ed, out, note):
+    """The informational legs of `--full`, added to `result` (rank 0): the headline kernel's roofline first, then the CPU baseline and
+    the legs compared with it, the other BASELINE configs, the training rates and the library-GEMM yardstick."""
+    import nerf
+    rdt = result["render_dtype"]
+    kt, ktf = time_dominant_kernel(models, ro, rd)
+    note(f"dominant kernel ({rdt}) {kt * 1e3:.2f} ms = {ktf:.0f} TFLOP/s")
+    peak = PEAK_TFLOPS[rdt]
+    whole_tf = value / world * POINTS_PER_RAY * FLOP_PER_POINT / 1e12
+    result["roofline"] = {"bound": "mfma", "achieved": ktf, "peak": peak, "unit": "TFLOP/s", "frac": ktf / peak,
+                          "traffic": pmc_record(rdt).get("hbm_bytes_per_launch"),
+                          "traffic_record": pmc_record(rdt).get("record"),
+                          "algorithmic_bytes": H * W * (NC + NF) * 20 + H * W * 44,
+                          "matrix_pipe_busy_frac_pmc": pmc_record(rdt).get("matrix_pipe_busy_frac"),
+                          "kernel": headline_kernel_name(rdt) + " (fine net, 160000x192 points)",
+                          "kernel_ms": kt * 1e3, "whole_path_tflops": whole_tf}
+    if train_dp is not None:
+        result["train_dp"] = train_dp
+    if world > 1:
+        args.no_cpu_baseline = True   # the CPU baseline is reported at N=1 only
+    if not args.no_cpu_baseline:
+        cb, sel, ref = cpu_baseline()
+        result["cpu_baseline"] = cb
+        rgb = out[3].reshape(-1, 3)[torch.from_numpy(sel).to(dev)].cpu().numpy()
+        mse = float(np.mean((rgb - ref[3].numpy()) ** 2))
+        result["psnr_vs_oracle_db"] = float(-10.0 * np.log10(max(mse, 1e-12)))
+        result["dex_vs_oracle"] = dex_agreement(out, ref, sel, dev)
+        result["gpu_over_cpu"] = value / world / cb["value"]
+    if args.precision == "bf16" and not args.no_cpu_baseline:
+        # the same render on the library's default policy: the fp16 instance of the kernel (range-guarded), round 3's headline
+        nerf.set_render_policy(None)
+        try:
+            render(models, cfg, ro, rd, ex, ed)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for _ in range(3):
+                out16 = render(models, cfg, ro, rd, ex, ed)
+            torch.cuda.synchronize()
+            dt16 = (time.perf_counter() - t1) / 3
+            kt16, ktf16 = time_dominant_kernel(models, ro, rd, reps=3)
+            rgb16 = out16[3].reshape(-1, 3)[torch.from_numpy(sel).to(dev)].cpu().numpy()
+            mse16 = float(np.mean((rgb16 - ref[3].numpy()) ** 2))
+            result["default_policy_fp16_render"] = {"value": H * W / dt16, "unit": "rays/s", "dtype": render_dtype(), "kernel_ms": kt16 * 1e3,
+                                                    "tflops": ktf16, "frac": ktf16 / PEAK_TFLOPS["fp16"],
+                                                    "kernel": headline_kernel_name(render_dtype()),
+                                                    "traffic": pmc_record(render_dtype()).get("hbm_bytes_per_launch"),
+                                                    "traffic_record": pmc_record(render_dtype()).get("record"),
+                                                    "psnr_vs_oracle_db": float(-10.0 * np.log10(max(mse16, 1e-12))),
+                                                    "dex_vs_oracle": dex_agreement(out16, ref, sel, dev)}
+        finally:
+            nerf.set_render_policy("bf16")
+    if args.precision == "bf16" and not args.no_cpu_baseline:
+        # the same render in the exact-fp32 parity mode (north_star's 1e-4 tolerance holds in this mode only): 3 steps
+        nerf.set_precision("fp32")
+        try:
+            render(models, cfg, ro, rd, ex, ed)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for _ in range(3):
+                out32 = render(models, cfg, ro, rd, ex, ed)
+            torch.cuda.synchronize()
+            dt32 = (time.perf_counter() - t1) / 3
+            kt32, ktf32 = time_dominant_kernel(models, ro, rd, "fp32", reps=2)
+            rgb32 = out32[3].reshape(-1, 3)[torch.from_numpy(sel).to(dev)].cpu().numpy().astype(np.float64)
+            per_ray = np.abs(rgb32 - ref[3].numpy()).max(-1) / np.abs(ref[3].numpy()).max()
+            # max over 16,384 rays sits on a handful of rays where an ulp in sigma moves a resampled depth: two fp32-level
+            # evaluations of the reference itself differ by 6.0e-4 there (3 rays over 1e-4, p99.9 9.4e-6:
+            # profiles/r02_fp32_noise_floor.md); the 1e-4 gate of the parity tests is on the golden rays
+            result["fp32_mode"] = {"value": H * W / dt32, "unit": "rays/s", "kernel_ms": kt32 * 1e3, "tflops": ktf32,
+                                   "peak": PEAK_TFLOPS["fp32"], "frac": ktf32 / PEAK_TFLOPS["fp32"],
+                                   "rgb_fine_rel_err_vs_oracle": {"max": float(per_ray.max()), "p99_9": float(np.quantile(per_ray, 0.999)),
+                                                                  "rays_over_1e-4": int((per_ray > 1e-4).sum()), "rays": int(per_ray.size)},
+                                   "dex_vs_oracle": dex_agreement(out32, ref, sel, dev)}
+        finally:
+            nerf.set_precision(args.precision)
+    if world == 1 and not args.no_cpu_baseline:
+        # BASELINE configs[2] (Dex-NeRF transparent-object scene on the as-shipped 4 x 128 nets: 270x480 after the fork's half-res
+        # rule, 64+64, near 0.3 / far 4 - config/messytable-obj-remote.yml) and configs[3] as a single-GPU render (800x800, 64+192,
+        # D8/W256), 3 images each, with the fine-net launch's own roofline
+        kw_shipped = dict(MODEL_KW, num_layers=4, hidden_size=128)
+        result["c3_render"] = other_config_render(dev, rank, "C3 render: 270x480, 64+64 samples, 4x128 nets (as shipped), near 0.3 far 4",
+                                                  270, 480, 64, 64, kw_shipped, 167680, 0.3, 4.0)
+        result["c4_render"] = other_config_render(dev, rank, "C4 render: 800x800, 64+192 samples, D8/W256 nets",
+                                                  800, 800, 64, 192, MODEL_KW, FLOP_PER_POINT, 2.0, 6.0)
+        result["c3_render_128_192"] = other_config_render(dev, rank, "C3 render, the fork's second sampling (config/messytable-obj-edward.yml:136-138): "
+                                                          "270x480, 128+192 samples, 4x128 nets, near 0.3 far 4", 270, 480, 128, 192, kw_shipped, 167680, 0.3, 4.0)
+        note(f"C3 {result['c3_render']['value'] / 1e6:.2f} M rays/s ({result['c3_render']['frac']:.3f} of peak), "
+             f"C3 128+192 {result['c3_render_128_192']['value'] / 1e6:.2f} M rays/s ({result['c3_render_128_192']['frac']:.3f}), "
+             f"C4 {result['c4_render']['value'] / 1e6:.2f} M rays/s ({result['c4_render']['frac']:.3f})")
+        # BASELINE configs[4] as configured: the IR scene's 128 + 256 samples in exact fp32 (train_dexnerf_ir.py; D8/W256 nets on the
+        # MessyTable frame, 270x480) - one image; its training step (luminance loss head, train_nerf_ir.py:260-263) below
+        nerf.set_precision("fp32")
+        try:
+            result["c5_render"] = other_config_render(dev, rank, "C5 render: 270x480, 128+256 samples, D8/W256 nets, exact fp32, near 0.3 far 4",
+                                                      270, 480, 128, 256, MODEL_KW, FLOP_PER_POINT, 0.3, 4.0, steps=1)
+            if not args.no_train:
+                m5, cfg5, ro5, rd5, _, _ = build_scene(dev, rank, 270, 480, 128, 256, MODEL_KW, 0.3, 4.0)
+                result["c5_train"] = train_rate(m5, cfg5, ro5, rd5, ex, ed, n_rays=1024, steps=4, nc=128, nf=256, luminance=True, h=270, w=480,
+                                                near=0.3, far=4.0, what_tail="128+256 samples, perturb + noise 0.2, D8/W256 x2, exact fp32, "
+                                                "IR loss head (MSE on the luminance of both passes: train_nerf_ir.py:260-263)")
+        finally:
+            nerf.set_precision(args.precision)
+        note(f"C5 render {result['c5_render']['value'] / 1e6:.3f} M rays/s ({result['c5_render']['frac']:.3f} of the fp32 peak)")
+    if not args.no_train and world == 1:
+        result["train"] = train_rate(models, cfg, ro, rd, ex, ed)
+    if not args.no_train and world == 1 and args.precision == "bf16":
+        # the same iteration with the tensors saved for the backward at 16 bits on the 32-point training kernels (what 'bf16' meant up to
+        # round 3; 'bf16' now saves at 8 bits on the 48-point kernels - same forward bits; HISTORY.md section 4.6)
+        nerf.set_precision("bf16-s16")
+        try:
+            models16, cfg16, _, _, _, _ = build_scene(dev, rank)
+            result["train_s16_mode"] = train_rate(models16, cfg16, ro, rd, ex, ed)
+        finally:
+            nerf.set_precision(args.precision)
+        # the same iteration in the exact-fp32 parity mode (BASELINE config 5 trains in fp32): informational
+        nerf.set_precision("fp32")
+        try:
+            models32, cfg32, _, _, _, _ = build_scene(dev, rank)
+            result["train_fp32_mode"] = train_rate(models32, cfg32, ro, rd, ex, ed, steps=4)
+        finally:
+            nerf.set_precision(args.precision)
+        # BASELINE config 3 as a shape: the as-shipped 4 x 128 nets, 1024 rays per step, 64+64 samples, whole iteration
+        # replayed as one HIP graph by the build-owned driver (informational; a few seconds)
+        try:
+            sys.path.insert(0, os.path.join(REPO, "dex-nerf_amd"))
+            import train_dexnerf
+            for key, prec in (("train_as_shipped", "bf16"), ("train_as_shipped_s16_mode", "bf16-s16")):
+                res = train_dexnerf.main(["--iters", "4000", "--size", "64", "--views", "8", "--num-random-rays", "1024", "--layers", "4",
+                                          "--width", "128", "--num-fine", "64", "--validate-every", "0", "--quiet", "--precision", prec])
+                result[key] = {"rays_per_s": res["rays_per_s"], "rays_per_step": 1024, "final_train_psnr_db": res["history"][-1][2],
+                               "steady_ms_per_iter": res.get("steady_ms_per_iter"),
+                               "steady_rays_per_s": 1024.0 / (res["steady_ms_per_iter"] * 1e-3) if res.get("steady_ms_per_iter") else None,
+                               "hip_graphs_per_iter": res.get("hip_graphs"),
+                               "what": f"train_dexnerf.py --precision {prec}, 4x128 nets, 64+64 samples, nerf.FusedTrainStep + nerf.FlatAdam "
+                                       "replayed as one HIP graph; rays_per_s over all 4000 iterations incl. the eager ones and the capture, "
+                                       "steady_*: from iteration 20 on"}
+        except Exception as exc:  # noqa: BLE001
+            result["train_as_shipped"] = {"error": f"{type(exc).__name__}: {exc}"}
+        finally:
+            nerf.set_precision(args.precision)
+    if world == 1 and not args.no_cpu_baseline and not args.no_train:
+        result["train_psnr_vs_oracle"] = train_psnr_vs_oracle(dev, precision=args.precision)
+        note(f"training PSNR at the last mark: {result['train_psnr_vs_oracle']['marks'][-1]}")
+    result["roofline"]["library_gemm"] = library_gemm_tflops(dev, rdt)
 
 
 if __name__ == "__main__":

@@ -4,11 +4,12 @@ import numpy as np, torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "dex-nerf_amd")); sys.path.insert(0, os.path.join(REPO, "tests"))
 import nerf
+from conftest import load_golden
 from golden_cases import CASES, M_THRES, draws_of
 from test_hip_parity import make_models, make_cfg, G, C
 dev = torch.device("cuda:0")
 name = sys.argv[1] if len(sys.argv) > 1 else "train_d8w256"
-g = dict(np.load(os.path.join(REPO, "tests", "golden", name + ".npz")))
+g = load_golden(name)
 mkw, wfn, rkw = CASES[name]
 for prec in ("fp32", "bf16"):
     nerf.set_precision(prec)

@@ -5,11 +5,12 @@ import numpy as np, torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "dex-nerf_amd")); sys.path.insert(0, os.path.join(REPO, "tests"))
 import nerf
+from conftest import load_golden
 from golden_cases import CASES
 from test_hip_parity import make_models, G, C
 dev = torch.device("cuda:0")
 name = sys.argv[1] if len(sys.argv) > 1 else "train_d8w256"
-g = dict(np.load(os.path.join(REPO, "tests", "golden", name + ".npz")))
+g = load_golden(name)
 mkw, wfn, _ = CASES[name]
 pts = G(g["pts_fine"], dev); rd = G(g["rd"], dev)
 vd = torch.nn.functional.normalize(rd, dim=-1)

@@ -1,3 +1,4 @@
+import glob
 import os
 import sys
 
@@ -17,7 +18,12 @@ def pytest_configure(config):
 
 
 def load_golden(name):
-    return dict(np.load(os.path.join(GOLDEN, name + ".npz")))
+    """<name>.npz, merged with its <name>.part<k>.npz when the fixture is split to keep every file under 1 MiB
+    (tests/golden/make_golden.py save_fixture)."""
+    g = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
+    for part in sorted(glob.glob(os.path.join(GOLDEN, glob.escape(name) + ".part*.npz"))):
+        g.update(np.load(part))
+    return g
 
 
 @pytest.fixture(scope="session")

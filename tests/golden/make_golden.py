@@ -18,7 +18,9 @@ The D8/W256 skip-4 net needs the one-line harness alias documented in SURVEY.md 
 (`m.__dict__["linear_layers"] = m.layers_xyz`): the reference class references an attribute it
 never defines (models.py:243).
 """
+import glob
 import importlib.util
+import io
 import os
 import sys
 import types
@@ -27,6 +29,34 @@ import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+MAX_FIXTURE_BYTES = 1 << 20
+
+
+def save_fixture(path, d):
+    """The arrays of `d` as a compressed .npz at `path`, split into <stem>.npz + <stem>.part<k>.npz (consecutive keys) where one file
+    would be larger than MAX_FIXTURE_BYTES: tests/conftest.py load_golden merges the parts.  Packed by each array's compressed size
+    alone (an upper bound of its share of a combined file: zip compresses entry by entry)."""
+    stem = path[:-len(".npz")]
+    for old in glob.glob(glob.escape(stem) + ".part*.npz"):
+        os.remove(old)
+    groups, size = [[]], 0
+    for key, a in d.items():
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **{key: a})
+        n = len(buf.getvalue())
+        if n > MAX_FIXTURE_BYTES:
+            raise ValueError(f"{path}: array {key} alone is {n} bytes compressed, over {MAX_FIXTURE_BYTES}")
+        if groups[-1] and size + n > MAX_FIXTURE_BYTES:
+            groups.append([])
+            size = 0
+        groups[-1].append(key)
+        size += n
+    paths = [path] + [f"{stem}.part{k}.npz" for k in range(1, len(groups))]
+    for p, keys in zip(paths, groups):
+        np.savez_compressed(p, **{key: d[key] for key in keys})
+    return paths
+
+
 REPO = os.path.dirname(os.path.dirname(HERE))
 REF = "/root/reference/nerf-pytorch"
 
@@ -197,7 +227,7 @@ def capture_render(tag, model_c, model_f, cfg, ro, rd, mode, l_xyz, l_dir, extra
     if extra:
         d.update(extra)
     path = os.path.join(HERE, tag + ".npz")
-    np.savez_compressed(path, **d)
+    save_fixture(path, d)
     print(f"{tag}: {os.path.getsize(path) / 1e6:.2f} MB, rays={ro.shape[0]}")
     return d, out
 
@@ -312,7 +342,7 @@ def kat():
         with torch.no_grad():
             d[tag] = npf(m(xin))
     path = os.path.join(HERE, "kat.npz")
-    np.savez_compressed(path, **d)
+    save_fixture(path, d)
     print(f"kat: {os.path.getsize(path) / 1e6:.2f} MB")
 
 
@@ -326,7 +356,7 @@ def lego():
     mf.load_state_dict(ck["model_fine_state_dict"])
     w = {"wc_" + k: npf(v) for k, v in ck["model_coarse_state_dict"].items()}
     w.update({"wf_" + k: npf(v) for k, v in ck["model_fine_state_dict"].items()})
-    np.savez_compressed(os.path.join(HERE, "lego_weights.npz"), **w)
+    save_fixture(os.path.join(HERE, "lego_weights.npz"), w)
     E, K, ro, rd, sel = rays_for(100, 100, 5, 256, seed=1)
     cfg = make_cfg(64, 64, 2.0, 6.0, perturb=False, noise_std=0.0, white=True)
     capture_render("render_lego_val", mc, mf, cfg, ro, rd, "validation", 10, 4,
@@ -353,7 +383,7 @@ def lego():
     opt.step()
     post = {"pc_" + k: npf(v) for k, v in mc.state_dict().items()}
     post.update({"pf_" + k: npf(v) for k, v in mf.state_dict().items()})
-    np.savez_compressed(os.path.join(HERE, "train_lego_post_adam.npz"), **post)
+    save_fixture(os.path.join(HERE, "train_lego_post_adam.npz"), post)
 
 
 def d8w256():
@@ -446,7 +476,7 @@ def val_extras():
     angles = np.array([[-180.0, -30.0, 4.0], [37.5, -30.0, 4.0], [90.0, 15.0, 2.5], [171.0, -89.0, 0.3]])
     d.update(pose_angles=angles, pose_out=np.stack([ref.load_blender.pose_spherical(*a) for a in angles]))
     path = os.path.join(HERE, "val_extras.npz")
-    np.savez_compressed(path, **d)
+    save_fixture(path, d)
     print(f"val_extras: {os.path.getsize(path) / 1e6:.2f} MB")
 
 

@@ -1613,7 +1613,7 @@ def test_second_device_gets_its_own_launch_attributes():
 
 
 def test_bench_multi_gpu_leg_rehearsal_two_ranks_one_gpu(dev):
-    """`bench.py --gpus 2` under torch.distributed.run, as the driver launches it, with two gloo ranks sharing this GPU (RCCL
+    """`bench.py --gpus 2 --full` under torch.distributed.run, as the driver launches it, with two gloo ranks sharing this GPU (RCCL
     refuses two ranks on one device): the render timing, the data-parallel training step (`train_dp`: broadcast, per-network
     all-reduce through the FlatGradBucket, fused Adam) and the one JSON line on rank 0.  Numbers are meaningless here (one GPU,
     gloo); the path must run and the line must carry the fields the N > 1 contract asks for."""
@@ -1622,7 +1622,7 @@ def test_bench_multi_gpu_leg_rehearsal_two_ranks_one_gpu(dev):
     import sys
     env = dict(os.environ, DEXNERF_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                          "--master-port", "29541", os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1"],
+                          "--master-port", "29541", os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--full"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -1655,6 +1655,31 @@ def test_bench_started_plainly_with_two_gpus_launches_its_own_ranks(dev):
     line = json.loads(lines[0])
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["dtype"] == line["config_dtype"] == "bf16"
     assert abs(line["value"] - 2 * 160000 / (line["ms_per_step"] * 1e-3)) / line["value"] < 1e-6
+
+
+def test_bench_plain_run_times_the_headline_and_dumps_its_outputs(dev, tmp_path):
+    """A plain `bench.py --gpus 1` run: exactly --steps timed steps, the headline fields only (the legs of --full stay out of it), and
+    --dump-outputs writes the last timed step's maps as float32 .npy - the six image maps and the 20 Dex depth maps."""
+    import json
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path / "outputs")], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["dtype"] == "bf16"
+    assert line["unit"] == "rays/s" and line["higher_is_better"] is True and line["metric"].startswith("rays/sec")
+    assert abs(line["value"] - 160000 / (line["ms_per_step"] * 1e-3)) / line["value"] < 1e-6
+    assert not {"roofline", "cpu_baseline", "train", "fp32_mode", "c3_render"} & set(line)
+    shapes = {"rgb_coarse": (400, 400, 3), "depth_coarse": (400, 400), "acc_coarse": (400, 400), "rgb_fine": (400, 400, 3),
+              "depth_fine": (400, 400), "acc_fine": (400, 400), "dex_depth": (20, 400, 400)}
+    assert sorted(p.name for p in (tmp_path / "outputs").iterdir()) == sorted(k + ".npy" for k in shapes)
+    for name, shape in shapes.items():
+        a = np.load(tmp_path / "outputs" / (name + ".npy"))
+        assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all(), name
+    assert np.load(tmp_path / "outputs" / "rgb_fine.npy").std() > 0.0      # an image, not a cleared buffer
 
 
 def test_training_psnr_at_matched_iterations_against_the_cpu_oracle(dev):
