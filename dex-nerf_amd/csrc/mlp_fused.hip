@@ -501,16 +501,21 @@ int dispatch_forward(const dn_mlp_desc& d, int precision, FwdParams& p, hipStrea
   if (p.act != nullptr && hf) { set_error("mlp_forward(train): fp16 is a render-only mode"); return DN_E_UNSUPPORTED; }
   if (p.act != nullptr && p.save8) {   // training forward with 8-bit saved units: the 48-point geometry (mlp_fused48.hip, SAVE = 2)
     if (!bf || p.mode == 2 || !g48_train_supported(d) || p.n_points >= (1LL << 31) - 1024) {
-      set_error("mlp_forward(train, 8-bit saved tensors): bf16 arithmetic, rays / points input, W in {128, 256}, L_xyz = 10, a depth the 48-point kernel holds in LDS");
+      set_error("mlp_forward(train, 8-bit saved tensors): bf16 arithmetic, rays / points input, W in {128, 256}, L_xyz in {6, 10}, a depth the 48-point kernel holds in LDS");
       return DN_E_UNSUPPORTED;
     }
     return launch_forward48(d, precision, p, p.packed + p.bias_bytes + static_cast<size_t>(p.total_pieces) * kPieceBytes, stream);
   }
-  if (p.act != nullptr) {  // training forward: LX=10 nets, PT=1
+  if (p.act != nullptr) {  // training forward: LX in {10, 6} nets, PT=1
     if (d.num_encoding_fn_xyz == 10 && d.hidden_size == 256)
       return bf ? launch_forward<256, 10, 4, true, 1, true>(p, stream) : launch_forward<256, 10, 4, false, 1, true>(p, stream);
     if (d.num_encoding_fn_xyz == 10 && d.hidden_size == 128)
       return bf ? launch_forward<128, 10, 4, true, 1, true>(p, stream) : launch_forward<128, 10, 4, false, 1, true>(p, stream);
+    // (L_xyz = 6: the forward-facing nets of the reference's LLFF configs; the saved xyz panel's slots past 3 + 6 L are zeros)
+    if (d.num_encoding_fn_xyz == 6 && d.hidden_size == 256)
+      return bf ? launch_forward<256, 6, 4, true, 1, true>(p, stream) : launch_forward<256, 6, 4, false, 1, true>(p, stream);
+    if (d.num_encoding_fn_xyz == 6 && d.hidden_size == 128)
+      return bf ? launch_forward<128, 6, 4, true, 1, true>(p, stream) : launch_forward<128, 6, 4, false, 1, true>(p, stream);
     set_error("mlp_forward(train): no kernel instance for W=%d L_xyz=%d", d.hidden_size, d.num_encoding_fn_xyz);
     return DN_E_UNSUPPORTED;
   }

@@ -225,9 +225,11 @@ inline int g48_train_groups(long long n_points, int cus) {
 }
 
 // Which networks train in the 48-point geometry (DN_PREC_BF16_S8): W = 128 needs whole 64-feature units for layers_dir.0's
-// 64 outputs (it has them), both widths need L_xyz = 10 panels like the other training kernels
+// 64 outputs (it has them), both widths need L_xyz in {6, 10} like the other training kernels (train_lxyz_supported).  An L_xyz = 6
+// panel holds 39 live columns of 64: the other slots carry table entries of frequency, phase and weights 0 (pack48), so the forward
+// stores sin(0) = +0 there - exact zero bytes in the saved xyz unit - and the weight-gradient epilogue drops them (g48_pe_col = -1).
 inline bool g48_train_supported(const dn_mlp_desc& d) {
-  return g48_supported(d, DN_PREC_BF16) && d.num_encoding_fn_xyz == 10;
+  return g48_supported(d, DN_PREC_BF16) && train_lxyz_supported(d);
 }
 
 // Backward-data stream of the 48-point chain: 16-row tiles of the TRANSPOSED weights, 32-deep pieces whose k order is the

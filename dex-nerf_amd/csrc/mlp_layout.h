@@ -206,6 +206,10 @@ inline int build_backward_layout(const dn_mlp_desc& d, int precision, NetLayout*
   return 0;
 }
 
+// xyz encodings the training kernels (forward with saved tensors, backward-data chain, weight gradients) are instantiated for: the
+// 64-wide xyz panel holds 3 + 6 L live columns, the rest is zero padding (pe_slot_col / g48_pe_col = -1)
+inline bool train_lxyz_supported(const dn_mlp_desc& d) { return d.num_encoding_fn_xyz == 10 || d.num_encoding_fn_xyz == 6; }
+
 inline int validate_desc(const dn_mlp_desc* d, int precision) {
   if (!d) { set_error("mlp: NULL descriptor"); return DN_E_INVAL; }
   if (precision != DN_PREC_F32 && precision != DN_PREC_BF16 && precision != DN_PREC_F16) { set_error("mlp: unknown precision %d", precision); return DN_E_INVAL; }

@@ -311,10 +311,13 @@ extern "C" int dn_mlp_train_sizes(const dn_mlp_desc* desc, int precision, int64_
   if (rc) return rc;
   DN_REQUIRE(precision != DN_PREC_F16, "training kernels exist for fp32 and bf16 (fp16 is a render-only mode)");
   DN_REQUIRE(n_points >= 0 && act_bytes && mask_bytes && grad_bytes, "dn_mlp_train_sizes: bad arguments");
-  DN_REQUIRE(desc->num_encoding_fn_xyz == 10, "dn_mlp_train_sizes: training kernels are built for L_xyz = 10");
+  if (!train_lxyz_supported(*desc)) {
+    set_error("dn_mlp_train_sizes: training kernels are built for L_xyz in {6, 10} (got %d)", desc->num_encoding_fn_xyz);
+    return DN_E_UNSUPPORTED;
+  }
   if (s8) {   // s8-48 layout (mlp_geo48.h): units per 16-point group, two groups per 32-point record, whole 384-point tiles
     if (!g48_train_supported(*desc)) {
-      set_error("dn_mlp_train_sizes: the 8-bit-saved-tensor training kernels run the 48-point geometry (W in {128, 256}, L_xyz = 10, a depth whose bias rows fit its LDS); train this network with DN_PREC_BF16");
+      set_error("dn_mlp_train_sizes: the 8-bit-saved-tensor training kernels run the 48-point geometry (W in {128, 256}, L_xyz in {6, 10}, a depth whose bias rows fit its LDS); train this network with DN_PREC_BF16");
       return DN_E_UNSUPPORTED;
     }
     TrainLayout48 t8;
@@ -1377,7 +1380,8 @@ __device__ __forceinline__ void weight_grad_unit_f32(const WgParams& p, int wg, 
   });
 }
 
-// the instantiated layer shapes: W = 256 and W = 128 nets (L_xyz = 10: a 64-wide xyz panel = 2 tiles; L_dir: 1 tile)
+// the instantiated layer shapes: W = 256 and W = 128 nets (L_xyz in {6, 10}: a 64-wide xyz panel = 2 tiles, columns past 3 + 6 L_xyz
+// are padding the epilogue drops; L_dir: 1 tile)
 #define DN_WG_SHAPES(X)                                                                                        \
   X(0, 8, 0, 2, false) X(1, 8, 8, 0, false) X(2, 8, 8, 2, false) X(3, 4, 8, 1, false) X(4, 1, 8, 0, true)     \
   X(5, 1, 4, 0, true)  X(6, 4, 0, 2, false) X(7, 4, 4, 0, false) X(8, 4, 4, 2, false) X(9, 2, 4, 1, false)    \
@@ -1610,7 +1614,10 @@ static int wg_add_network(const dn_mlp_desc* desc, int precision, bool s8, const
                           float* const* h_dW, float* const* h_db, WgBatch& b, long long* unit_tiles, const char* who) {
   const bool f32 = precision == DN_PREC_F32;
   DN_REQUIRE(act && grads && h_dW && h_db && n_points > 0, "%s: bad arguments", who);
-  DN_REQUIRE(desc->num_encoding_fn_xyz == 10, "%s: training kernels are built for L_xyz = 10", who);
+  if (!train_lxyz_supported(*desc)) {
+    set_error("%s: training kernels are built for L_xyz in {6, 10} (got %d)", who, desc->num_encoding_fn_xyz);
+    return DN_E_UNSUPPORTED;
+  }
   int rc;
   TrainLayout t;
   if (s8) {

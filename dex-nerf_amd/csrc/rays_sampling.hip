@@ -48,6 +48,26 @@ __global__ void ray_bundle_kernel(RayBundleArgs a, float* __restrict__ ro, float
   }
 }
 
+// Forward-facing NDC warp of one ray (reference nerf/nerf_helpers.py:172-199), op for op (compiled -ffp-contract=off): the body of
+// dn_ndc_rays, and of dn_select_rays_draw_ndc, whose rows must equal a plain draw followed by dn_ndc_rays bit for bit.
+__device__ __forceinline__ void ndc_warp(double h, double w, double focal, double near_d, const float (&o)[3], const float (&d)[3],
+                                         float* __restrict__ ro_out, float* __restrict__ rd_out) {
+  const float dx = d[0], dy = d[1], dz = d[2];
+  const float near = static_cast<float>(near_d);
+  const float t = -(near + o[2]) / dz;
+  const float ox = o[0] + t * dx, oy = o[1] + t * dy, oz = o[2] + t * dz;
+  // python-float constants are computed in double and then meet fp32 tensors as fp32 scalars
+  const float cw = static_cast<float>(-1.0 / (w / (2.0 * focal)));
+  const float ch = static_cast<float>(-1.0 / (h / (2.0 * focal)));
+  const float two_near = static_cast<float>(2.0 * near_d);
+  ro_out[0] = cw * ox / oz;
+  ro_out[1] = ch * oy / oz;
+  ro_out[2] = 1.0f + two_near / oz;
+  rd_out[0] = cw * (dx / dz - ox / oz);
+  rd_out[1] = ch * (dy / dz - oy / oz);
+  rd_out[2] = -two_near / oz;
+}
+
 // Training-ray selection (reference train_dexnerf_rgb.py:229-242 + the packing of train_utils.py:225-250): for each
 // chosen pixel build the packed ray row [ro3, rd3, near, far, viewdir3] directly (same arithmetic as
 // ray_bundle_kernel for rd; viewdir = rd / ||rd||, train_utils.py:225) and gather the target pixel's RGB.
@@ -92,10 +112,14 @@ __global__ void select_rays_kernel(RayBundleArgs a, float near, float far, const
 // pix == NULL: the pixels are DRAWN here - element i of this iteration's draw without replacement, a keyed permutation of the
 // H W pixels (dn_rng.h feistel_permute; reference train_dexnerf_rgb.py:229-236: np.random.choice(H W, n, replace=False)) - from
 // the RNG state's NEXT iteration counter, which thread 0 then publishes as the CURRENT one for the rest of the iteration.
+// NDC: the origin and direction of every row warped to NDC (ndc_warp with the image's height / width, `focal`, `ndc_near`); the view
+// direction (columns 8:11) stays that of the unwarped direction, as in run_one_iter_of_nerf (reference train_utils.py:240-262).
+template <bool NDC>
 __global__ void select_rays_indirect_kernel(const float* __restrict__ cams, const int* __restrict__ view, int n_views, int height, int width,
                                             float near, float far, const int64_t* __restrict__ pix, int64_t n,
                                             const float* __restrict__ images, int channels, float* __restrict__ rays,
-                                            float* __restrict__ target, uint32_t* __restrict__ rng_state, int64_t* __restrict__ pix_out) {
+                                            float* __restrict__ target, uint32_t* __restrict__ rng_state, int64_t* __restrict__ pix_out,
+                                            double focal, double ndc_near) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   uint32_t iteration = 0;
   if (pix == nullptr) {
@@ -133,11 +157,18 @@ __global__ void select_rays_indirect_kernel(const float* __restrict__ cams, cons
   }
   const float nrm = sqrtf((rd[0] * rd[0] + rd[1] * rd[1]) + rd[2] * rd[2]);
   float* r = rays + i * 11;
+  if constexpr (NDC) {
+    const float o[3] = {cam[9], cam[10], cam[11]};
+    ndc_warp(static_cast<double>(height), static_cast<double>(width), focal, ndc_near, o, rd, r, r + 3);
 #pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    r[j] = cam[9 + j];
-    r[3 + j] = rd[j];
-    r[8 + j] = rd[j] / nrm;
+    for (int j = 0; j < 3; ++j) r[8 + j] = rd[j] / nrm;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      r[j] = cam[9 + j];
+      r[3 + j] = rd[j];
+      r[8 + j] = rd[j] / nrm;
+    }
   }
   r[6] = near;
   r[7] = far;
@@ -154,20 +185,9 @@ __global__ void ndc_rays_kernel(double h, double w, double focal, double near_d,
                                 float* __restrict__ rd_out) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float dx = rd[i * 3 + 0], dy = rd[i * 3 + 1], dz = rd[i * 3 + 2];
-  const float near = static_cast<float>(near_d);
-  const float t = -(near + ro[i * 3 + 2]) / dz;
-  const float ox = ro[i * 3 + 0] + t * dx, oy = ro[i * 3 + 1] + t * dy, oz = ro[i * 3 + 2] + t * dz;
-  // python-float constants are computed in double and then meet fp32 tensors as fp32 scalars
-  const float cw = static_cast<float>(-1.0 / (w / (2.0 * focal)));
-  const float ch = static_cast<float>(-1.0 / (h / (2.0 * focal)));
-  const float two_near = static_cast<float>(2.0 * near_d);
-  ro_out[i * 3 + 0] = cw * ox / oz;
-  ro_out[i * 3 + 1] = ch * oy / oz;
-  ro_out[i * 3 + 2] = 1.0f + two_near / oz;
-  rd_out[i * 3 + 0] = cw * (dx / dz - ox / oz);
-  rd_out[i * 3 + 1] = ch * (dy / dz - oy / oz);
-  rd_out[i * 3 + 2] = -two_near / oz;
+  const float o[3] = {ro[i * 3 + 0], ro[i * 3 + 1], ro[i * 3 + 2]};
+  const float d[3] = {rd[i * 3 + 0], rd[i * 3 + 1], rd[i * 3 + 2]};
+  ndc_warp(h, w, focal, near_d, o, d, ro_out + i * 3, rd_out + i * 3);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -490,8 +510,9 @@ extern "C" int dn_select_rays_indirect(int height, int width, const float* cams,
   DN_REQUIRE(target == nullptr || (images != nullptr && channels >= 3), "dn_select_rays_indirect: target requested without images of >= 3 channels");
   const int block = 256;
   const unsigned grid = static_cast<unsigned>((n_rays + block - 1) / block);
-  hipLaunchKernelGGL(select_rays_indirect_kernel, dim3(grid), dim3(block), 0, as_stream(stream), cams, view, 0, height, width, near,
-                     far, pixel_index, n_rays, images, channels, rays, target, static_cast<uint32_t*>(nullptr), static_cast<int64_t*>(nullptr));
+  hipLaunchKernelGGL(select_rays_indirect_kernel<false>, dim3(grid), dim3(block), 0, as_stream(stream), cams, view, 0, height, width, near,
+                     far, pixel_index, n_rays, images, channels, rays, target, static_cast<uint32_t*>(nullptr), static_cast<int64_t*>(nullptr),
+                     0.0, 0.0);
   return check_launch("dn_select_rays_indirect");
 }
 
@@ -504,9 +525,25 @@ extern "C" int dn_select_rays_draw(int height, int width, const float* cams, con
   DN_REQUIRE(target == nullptr || (images != nullptr && channels >= 3), "dn_select_rays_draw: target requested without images of >= 3 channels");
   const int block = 256;
   const unsigned grid = static_cast<unsigned>((n_rays + block - 1) / block);
-  hipLaunchKernelGGL(select_rays_indirect_kernel, dim3(grid), dim3(block), 0, as_stream(stream), cams, view, n_views, height, width, near,
-                     far, static_cast<const int64_t*>(nullptr), n_rays, images, channels, rays, target, rng_state, pixel_index_out);
+  hipLaunchKernelGGL(select_rays_indirect_kernel<false>, dim3(grid), dim3(block), 0, as_stream(stream), cams, view, n_views, height, width, near,
+                     far, static_cast<const int64_t*>(nullptr), n_rays, images, channels, rays, target, rng_state, pixel_index_out, 0.0, 0.0);
   return check_launch("dn_select_rays_draw");
+}
+
+extern "C" int dn_select_rays_draw_ndc(int height, int width, const float* cams, const int32_t* view, int n_views, float near, float far,
+                                       uint32_t* rng_state, int64_t n_rays, const float* images, int channels, float* rays, float* target,
+                                       int64_t* pixel_index_out, double focal, double ndc_near, dn_stream_t stream) {
+  DN_REQUIRE(height > 0 && width > 0 && cams && (view || n_views >= 1) && rng_state && rays && n_rays >= 1, "dn_select_rays_draw_ndc: bad arguments");
+  DN_REQUIRE(n_rays <= static_cast<int64_t>(height) * width, "dn_select_rays_draw_ndc: more rays than pixels (the draw is without replacement)");
+  DN_REQUIRE(static_cast<int64_t>(height) * width < (1LL << 31), "dn_select_rays_draw_ndc: image too large");
+  DN_REQUIRE(target == nullptr || (images != nullptr && channels >= 3), "dn_select_rays_draw_ndc: target requested without images of >= 3 channels");
+  DN_REQUIRE(std::isfinite(focal) && focal > 0.0 && std::isfinite(ndc_near), "dn_select_rays_draw_ndc: focal must be positive and finite, the near plane finite");
+  const int block = 256;
+  const unsigned grid = static_cast<unsigned>((n_rays + block - 1) / block);
+  hipLaunchKernelGGL(select_rays_indirect_kernel<true>, dim3(grid), dim3(block), 0, as_stream(stream), cams, view, n_views, height, width, near,
+                     far, static_cast<const int64_t*>(nullptr), n_rays, images, channels, rays, target, rng_state, pixel_index_out, focal,
+                     ndc_near);
+  return check_launch("dn_select_rays_draw_ndc");
 }
 
 // ---- S9 loss head on the device: mse(rgb_coarse, target) + mse(rgb_fine, target) (train_dexnerf_rgb.py:264-277; with

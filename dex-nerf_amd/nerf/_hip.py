@@ -30,6 +30,7 @@ EXPORTS = (
     "dn_set_s8_grad_scale", "dn_mlp_pack_parts", "dn_fp16_range_guard", "dn_select_rays_draw", "dn_mse2_loss", "dn_rng_fill", "dn_mlp_pack_train_pair",
     "dn_adam_step", "dn_pack_ray_rows", "dn_mlp_weight_grad_pair",
     "dn_mlp_weight_grad_scratch_bytes", "dn_mlp_weight_grad_all_ws", "dn_mlp_weight_grad_pair_ws", "dn_render_rays_backward_ws",
+    "dn_select_rays_draw_ndc",
 )
 
 
@@ -105,6 +106,8 @@ def _declare(lib):
                                                c_float, c_int, fp, fp, fp, fp, fp, fp, fp, fp, vp, vp, vp, vp, vp, vp, vp,
                                                POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), c_int, vp, vp, c_size_t, vp]
     lib.dn_select_rays_draw.argtypes = [c_int, c_int, fp, vp, c_int, c_float, c_float, vp, c_int64, fp, c_int, fp, fp, vp, vp]
+    lib.dn_select_rays_draw_ndc.argtypes = [c_int, c_int, fp, vp, c_int, c_float, c_float, vp, c_int64, fp, c_int, fp, fp, vp,
+                                            ctypes.c_double, ctypes.c_double, vp]
     lib.dn_mse2_loss.argtypes = [fp, fp, fp, c_int64, c_int, fp, fp, fp, vp, vp]
     lib.dn_rng_fill.argtypes = [vp, ctypes.c_uint32, c_int64, c_int, fp, vp]
     lib.dn_pack_ray_rows.argtypes = [fp, fp, fp, c_float, c_float, c_int64, fp, vp]

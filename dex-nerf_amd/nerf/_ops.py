@@ -198,9 +198,11 @@ def pack_ray_rows(ro, rd, view_d, near, far):
     return rows
 
 
-def select_rays_draw(height, width, cams, view, near, far, rng_state, n_rays, images=None, want_pixels=False):
+def select_rays_draw(height, width, cams, view, near, far, rng_state, n_rays, images=None, want_pixels=False, ndc_focal=None, ndc_near=1.0):
     """select_rays_indirect with the pixels drawn on the device, without replacement, from `rng_state`'s next iteration.
-    view=None: the training view is drawn in the kernel too (uniformly from the cameras in `cams`)."""
+    view=None: the training view is drawn in the kernel too (uniformly from the cameras in `cams`).
+    ndc_focal: forward-facing rows (dn_select_rays_draw_ndc) - origin and direction warped to NDC as ndc_rays(height, width,
+    ndc_focal, ndc_near, ...) warps them, the view direction that of the unwarped ray, near / far as given."""
     assert (view is None or view.dtype == torch.int32) and cams.dtype == torch.float32 and cams.is_contiguous() and rng_state.dtype == torch.int32
     dev = cams.device
     rays = torch.empty((n_rays, 11), dtype=torch.float32, device=dev)
@@ -210,8 +212,13 @@ def select_rays_draw(height, width, cams, view, near, far, rng_state, n_rays, im
         channels = img.shape[-1]
         target = torch.empty((n_rays, 3), dtype=torch.float32, device=dev)
     pix = torch.empty((n_rays,), dtype=torch.int64, device=dev) if want_pixels else None
-    check(lib().dn_select_rays_draw(height, width, ptr(cams), ptr(view), int(cams.shape[0]), float(near), float(far), ptr(rng_state), n_rays, ptr(img), channels,
-                                    ptr(rays), ptr(target), ptr(pix), stream()), "dn_select_rays_draw")
+    if ndc_focal is not None:
+        check(lib().dn_select_rays_draw_ndc(height, width, ptr(cams), ptr(view), int(cams.shape[0]), float(near), float(far), ptr(rng_state), n_rays,
+                                            ptr(img), channels, ptr(rays), ptr(target), ptr(pix), float(ndc_focal), float(ndc_near), stream()),
+              "dn_select_rays_draw_ndc")
+    else:
+        check(lib().dn_select_rays_draw(height, width, ptr(cams), ptr(view), int(cams.shape[0]), float(near), float(far), ptr(rng_state), n_rays, ptr(img), channels,
+                                        ptr(rays), ptr(target), ptr(pix), stream()), "dn_select_rays_draw")
     return (rays, target, pix) if want_pixels else (rays, target)
 
 

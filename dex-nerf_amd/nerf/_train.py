@@ -1,7 +1,7 @@
 """Dispatch between the fused HIP network kernels and PyTorch autograd.
 
 Inference: one fused kernel (positional encoding + MLP).  Training, for the nets the training kernels cover
-(W in {128, 256}, L_xyz = 10): `FusedNetFn` - a fused forward that keeps every stage's output and ReLU masks in a
+(W in {128, 256}, L_xyz in {6, 10}): `FusedNetFn` - a fused forward that keeps every stage's output and ReLU masks in a
 wave-native layout, and a fused backward-data chain on the transposed weight stream (dn_mlp_backward_data);
 the weight/bias gradients come from one weight-gradient kernel launch per network on the saved native buffers
 (bf16 MFMA, or exact-fp32 MFMA in the parity mode; DEXNERF_FP32_DW=gemm selects the older fp32 route: unpack to plain rows
@@ -27,8 +27,11 @@ def inputs_need_grad(*tensors):
     return torch.is_grad_enabled() and any(t is not None and torch.is_tensor(t) and t.requires_grad for t in tensors)
 
 
+TRAIN_L_XYZ = (6, 10)   # xyz encodings the training kernels are instantiated for (csrc/mlp_layout.h train_lxyz_supported)
+
+
 def train_fused_ok(model):
-    return model.fused_ok() and model.num_encoding_fn_xyz == 10 and _ops._precision != _hip.PREC_F16
+    return model.fused_ok() and model.num_encoding_fn_xyz in TRAIN_L_XYZ and _ops._precision != _hip.PREC_F16
 
 
 def _slots(model, precision):

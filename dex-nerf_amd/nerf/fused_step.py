@@ -2,6 +2,8 @@
 fine render -> mse + mse -> backward -> Adam) with nothing in it but this library's kernels - 16 launches on the as-shipped nets:
 
     dn_select_rays_draw      view + pixels drawn without replacement on the device, packed ray rows, target pixels   (1 kernel)
+                             (forward-facing captures, no_ndc: False: dn_select_rays_draw_ndc - the rows warped to NDC in the
+                             same kernel, near plane 1, as run_one_iter_of_nerf does)
     dn_mlp_pack_train_pair   both weight streams of both networks                                                     (2 kernels)
     dn_render_rays_train     coarse depths / net / composite, resampling, fine net / composite; the jitter, the resampling u and
                              the density noise drawn inside the kernels that consume them                             (6 kernels)
@@ -11,6 +13,7 @@ fine render -> mse + mse -> backward -> Adam) with nothing in it but this librar
                              fine network's all-reduce overlaps the coarse half)                                       (5 kernels)
     dn_adam_step             nerf.FlatAdam: step, learning-rate schedule and gradient clearing                         (1 kernel)
 
+The networks: W in {128, 256} with L_xyz in {6, 10} (the shipped fern / LLFF nets are 4 x 128, L_xyz = 6), view directions.
 No autograd graph, no ATen elementwise / reduction / RNG launches (profiles/r03_as_shipped_kernel_summary.md).  The gradients land in
 a parallel.FlatGradBucket (the `.grad` tensors of the parameters).  GraphedTrainStep replays the iteration as HIP graphs (three
 around the exchange when world > 1).  The explicit-draw path (predict_and_render_radiance under autograd, draws as tensors) stays
@@ -29,8 +32,12 @@ _SPLIT_BACKWARD = os.environ.get("DEXNERF_SPLIT_BACKWARD", "") == "1"   # develo
 
 class FusedTrainStep:
     def __init__(self, model_coarse, model_fine, selector, options, bucket, encode_position_fn, encode_direction_fn, num_rays, seed=0,
-                 luminance=False, first_iteration=0, draw_view=False):
+                 luminance=False, first_iteration=0, draw_view=False, ndc_focal=None):
         opt = options.nerf.train
+        self.ndc = getattr(options.dataset, "no_ndc", True) is False
+        if self.ndc and ndc_focal is None:
+            raise ValueError("FusedTrainStep: NDC rays (dataset.no_ndc: False) need the capture's focal length (ndc_focal)")
+        self.ndc_focal = float(ndc_focal) if self.ndc else None
         self.models = (model_coarse, model_fine)
         self.selector, self.bucket = selector, bucket
         self.num_rays = int(num_rays)
@@ -39,7 +46,7 @@ class FusedTrainStep:
         self.noise_std, self.white = float(opt.radiance_field_noise_std), bool(opt.white_background)
         self.luminance = bool(luminance)
         self.logs = (encode_position_fn.log_sampling, encode_direction_fn.log_sampling if model_coarse.use_viewdirs else True)
-        if not self.applicable(model_coarse, model_fine, options, encode_position_fn, encode_direction_fn, num_rays):
+        if not self.applicable(model_coarse, model_fine, options, encode_position_fn, encode_direction_fn, num_rays, ndc_focal):
             raise ValueError("FusedTrainStep: configuration outside the fused training kernels (see FusedTrainStep.applicable)")
         dev = next(model_coarse.parameters()).device
         self.rng_state = _ops.new_rng_state(seed, dev, first_iteration)
@@ -48,11 +55,12 @@ class FusedTrainStep:
         self.zero_in_step = True     # False: the optimizer leaves the gradient bucket cleared (FlatAdam(zero_grads=True))
 
     @staticmethod
-    def applicable(model_coarse, model_fine, options, encode_position_fn, encode_direction_fn, num_rays):
-        """Both networks on the fused training kernels, a fine pass, one ray chunk, world-space rays."""
+    def applicable(model_coarse, model_fine, options, encode_position_fn, encode_direction_fn, num_rays, ndc_focal=None):
+        """Both networks on the fused training kernels, a fine pass, one ray chunk; world-space rays, or NDC rays when the focal
+        length of the capture is given."""
         opt = options.nerf.train
         return (model_fine is not None and int(opt.num_fine) > 0 and int(num_rays) <= int(opt.chunksize)
-                and getattr(options.dataset, "no_ndc", True) is not False
+                and (getattr(options.dataset, "no_ndc", True) is not False or ndc_focal is not None)
                 and _fusable(model_coarse, encode_position_fn, encode_direction_fn) and _fusable(model_fine, encode_position_fn, encode_direction_fn)
                 and train_fused_ok(model_coarse) and train_fused_ok(model_fine) and model_coarse.use_viewdirs and model_fine.use_viewdirs)
 
@@ -83,7 +91,7 @@ class FusedTrainStep:
         mc, mf = self.models
         sel = self.selector
         rays, target = _ops.select_rays_draw(sel.height, sel.width, sel.cams, None if self.draw_view else sel.view, sel.near, sel.far,
-                                             self.rng_state, self.num_rays, sel.images)
+                                             self.rng_state, self.num_rays, sel.images, ndc_focal=self.ndc_focal, ndc_near=1.0)
         pc, pf, prec = _ops.pack_train_pair(mc, mf, self.logs)
         maps, saved = _ops.render_rays_train(pc, pf, rays, self.nc, self.nf, self.lindisp, self.noise_std, self.white, [], None, prec=prec,
                                              rng_state=self.rng_state, perturb=self.perturb)

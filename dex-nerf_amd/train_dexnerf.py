@@ -158,6 +158,11 @@ def main(argv=None):
     ap.add_argument("--near", type=float, default=None, help="default 2 (synthetic scene) / 0.3 (MessyTable)")
     ap.add_argument("--far", type=float, default=None, help="default 6 (synthetic scene) / 4 (MessyTable)")
     ap.add_argument("--quiet", action="store_true")
+    ap.add_argument("--xyz-freqs", type=int, default=10, choices=[6, 10],
+                    help="frequencies of the xyz encoding (num_encoding_fn_xyz): 10 as in the reference's blender / MessyTable configs, 6 as "
+                         "in its fern / llff configs and the shipped fern-lowres checkpoint")
+    ap.add_argument("--linear-freqs", action="store_true",
+                    help="linearly spaced encoding frequencies for both encodings (log_sampling_xyz / _dir: False, as in llff.yml)")
     ap.add_argument("--autograd-step", action="store_true",
                     help="run the iteration as torch ops + autograd over the fused kernels (torch.randperm / rand / randn draws, mse_loss, "
                          "loss.backward()) instead of nerf.FusedTrainStep")
@@ -197,10 +202,11 @@ def main(argv=None):
     _nerf_ops.set_deterministic_weight_gradients(not args.atomic_weight_gradients)
     s8_warned, s8_saturated_max = False, 0.0
 
-    kw = dict(num_layers=args.layers, hidden_size=args.width, skip_connect_every=4, num_encoding_fn_xyz=10,
+    kw = dict(num_layers=args.layers, hidden_size=args.width, skip_connect_every=4, num_encoding_fn_xyz=args.xyz_freqs,
               num_encoding_fn_dir=4, use_viewdirs=True)
     cfg = make_cfg(args)
-    ex, ed = nerf.get_embedding_function(10, True, True), nerf.get_embedding_function(4, True, True)
+    ex = nerf.get_embedding_function(args.xyz_freqs, True, not args.linear_freqs)
+    ed = nerf.get_embedding_function(4, True, not args.linear_freqs)
     thres = np.arange(5, args.m_thres + 5, 5)
     if args.llff:
         data = llff_dataset(args, dev)
@@ -220,9 +226,11 @@ def main(argv=None):
     use_graph = not args.no_hip_graph         # (world > 1: graphs around the exchange, nerf.GraphedTrainStep; the autograd step only with one rank)
     # The whole iteration on this library's kernels (nerf.FusedTrainStep: pixel draw, jitter, resampling and density noise drawn
     # inside the kernels, loss head + upstream gradients in one launch, no autograd graph) wherever the fused training kernels
-    # cover the configuration; --autograd-step keeps the torch composition (torch.randperm / rand / randn, autograd).
-    fused_ok = (not args.autograd_step and not args.ndc
-                and nerf.FusedTrainStep.applicable(student[0], student[1], cfg, ex, ed, args.num_random_rays))
+    # cover the configuration - NDC rays included (the draw kernel warps them); --autograd-step keeps the torch composition
+    # (torch.randperm / rand / randn, autograd).
+    ndc_focal = data["focal"] if args.ndc else None
+    fused_ok = (not args.autograd_step
+                and nerf.FusedTrainStep.applicable(student[0], student[1], cfg, ex, ed, args.num_random_rays, ndc_focal))
     flat_adam = fused_ok and not args.torch_adam
     lr_t = torch.tensor(args.lr, dtype=torch.float32, device=dev)   # (torch's Adam) a device scalar: the schedule is applied by fill_()
     if flat_adam:
@@ -253,12 +261,12 @@ def main(argv=None):
     fused = None
     if fused_ok:
         fused = nerf.FusedTrainStep(student[0], student[1], selector, cfg, bucket, ex, ed, args.num_random_rays, seed=args.seed + 7919 * rank,
-                                    luminance=args.ir, first_iteration=start, draw_view=True)
+                                    luminance=args.ir, first_iteration=start, draw_view=True, ndc_focal=ndc_focal)
     graphed = nerf.GraphedTrainStep(fused, opt, eager_iterations=3, use_graphs=use_graph) if fused is not None else None
     use_graph = use_graph and world == 1      # (the autograd step's single graph below: one rank only)
 
     def iteration():
-        """The torch composition (--autograd-step, NDC rays, configurations outside nerf.FusedTrainStep): select rays -> coarse +
+        """The torch composition (--autograd-step, configurations outside nerf.FusedTrainStep): select rays -> coarse +
         fine render -> loss -> backward -> (all-reduce) -> Adam; device-side state only."""
         rays, target = selector.select(selector.random_pixels(args.num_random_rays))
         if args.ndc:
