@@ -7,8 +7,6 @@
 
 #include "mlp_layout.h"
 
-#include "dn_ablation.h"
-
 namespace dn {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -28,10 +26,6 @@ __device__ __forceinline__ void static_for(F&& f) {
 constexpr int kRingPhases = 5;
 constexpr int kSlotBytes = kPhasePieces * kPieceBytes;  // 16 KiB
 constexpr int kRingBytes = kRingPhases * kSlotBytes;    // 80 KiB
-#ifndef DN_PREFETCH
-#define DN_PREFETCH 4
-#endif
-constexpr int kPrefetch = DN_PREFETCH;                  // A-fragment pieces read ahead of the MFMA that uses them
 constexpr int kInRows = 10;                             // per-wave input staging rows
 
 // arithmetic mode (the template parameter is still called BF16: 0 = fp32, 1 = bf16, 2 = fp16; non-zero = 16-bit MFMA)
@@ -97,7 +91,7 @@ struct FwdParams {
 // ---- weight pipeline: LDS ring fed by LDS-DMA -------------------------------------------------------
 // Ring of 5 x 16 KiB phases.  At the barrier that opens phase p every wave has waited for its own DMAs of
 // phases <= p+1, so after the barrier phases p AND p+1 are fully landed: the A-fragment read stream (a FIFO of
-// kPrefetch pieces per wave) runs continuously across phase boundaries.  Phases p+2, p+3 stay in flight
+// G::PREFETCH pieces per wave) runs continuously across phase boundaries.  Phases p+2, p+3 stay in flight
 // (counted vmcnt, never 0 in the loop); phase p+4 is issued into the slot phase p-1 just vacated.
 // Extra VMEM ops (input DMAs, the output store) are younger or older than the DMAs a wait must cover and,
 // because VMEM ops retire in order, can only make a counted wait stricter, never weaker.
@@ -105,7 +99,7 @@ struct FwdParams {
 //   ASM_READS     the A-fragment / bias LDS reads and their COUNTED waits are opaque asm statements (below)
 //   LEADER_DMA    waves 0-3 fetch the whole weight stream, four pieces each per phase; waves 4-7 issue MFMAs only (mlp_stage48.h)
 //   SCALAR_STATE  the wave-uniform ring bookkeeping is pinned to SGPRs
-//   PREFETCH      depth of the A-fragment FIFO (= the translation unit's kPrefetch)
+//   PREFETCH      depth of the A-fragment FIFO
 // PipeGeo32 (here): the 32-points-per-wave kernels of mlp_fused.hip / mlp_train.hip; PipeGeo48 (mlp_stage48.h): the 48-point kernels.
 // Members only one form uses cost nothing (a Pipe lives in registers; unused fields are never materialised); member functions of a
 // class template are instantiated only where they are called.
@@ -116,7 +110,6 @@ struct PipeGeometry {
 };
 template <int WAVES, class G>
 struct PipeT {
-  static_assert(G::PREFETCH == kPrefetch, "the FIFO depth of a geometry is its translation unit's kPrefetch");
   static constexpr int PER_WAVE = kPhasePieces / WAVES;
   char* ring;           // LDS
   unsigned ring_addr;   // its 32-bit LDS byte address (for M0)
@@ -129,7 +122,7 @@ struct PipeT {
   const char* rd_cur;   // LDS read pointers (+ lane*16) of the current and the next phase
   const char* rd_nxt;
   unsigned lane16;
-  f32x4 af[kPrefetch];  // A-fragment FIFO: af[pos % kPrefetch] holds piece `pos` when it is consumed
+  f32x4 af[G::PREFETCH];  // A-fragment FIFO: af[pos % G::PREFETCH] holds piece `pos` when it is consumed
   // ---- ASM_READS: explicit LDS read pipeline (mlp_fused48.hip).  hipcc's own waitcnt insertion turns a depth-2 software pipeline of
   // ds_read_b128 into "issue the read for piece p+2, then s_waitcnt lgkmcnt(0)": every other piece, and every tile's bias
   // read, exposed a full LDS round trip in front of the MFMAs (r02 PMC: waves parked in s_waitcnt 39 % of their cycles).
@@ -139,44 +132,9 @@ struct PipeT {
   // use a fragment before its wait; tests/test_asm_hazards.py checks in the disassembly that nothing touches a fragment
   // register between its ds_read and its wait.
   unsigned rda_cur;            // 32-bit LDS byte address (+ lane * 16) of the current phase slot; the next slot's is formed
-                               // where it is needed (the last kPrefetch pieces of a phase) from the scalar slot base
-#ifdef DN_STAMP   // diagnostic build only: where a wave's cycles go at the phase boundaries (s_memtime, accumulated in SGPRs)
-  unsigned st_vm = 0, st_bar = 0, st_dma = 0, st_seg = 0, st_n = 0, st_prev = 0;
-  unsigned st_sub[4] = {0, 0, 0, 0}, st_last = 0;   // MFMA time of the four quarters of a phase (4 pieces each)
-  unsigned st_top = 0, st_top_pending = 0;          // end of a pass (tail pieces, output store, next tile's encodings) up to the next phase
-  __device__ __forceinline__ void pass_end() {       // after the last full quarter of a pass
-    const unsigned t = stamp();
-    if (st_n) st_tail += t - st_last;     // light mode: st_tail = the whole pass minus its top
-    st_last = t;
-    st_top_pending = 1;
-  }
-  unsigned st_tail = 0;
-  unsigned st_cls[3] = {0, 0, 0};                    // DN_STAMP == 4: time per stage class (layer1 / trunk / heads)
-  template <int CLS>
-  __device__ __forceinline__ void stage_end() {
-    const unsigned t = stamp();
-    st_cls[CLS] += t - st_last;
-    st_last = t;
-  }
-  template <int I>
-  __device__ __forceinline__ void substamp() {       // at piece 4 * I of a phase, I = 1..3
-    const unsigned t = stamp();
-    st_sub[I - 1] += t - st_last;
-    st_last = t;
-  }
-  __device__ __forceinline__ unsigned stamp() {
-    unsigned long long t;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
-    return __builtin_amdgcn_readfirstlane(static_cast<unsigned>(t));
-  }
-#endif
+                               // where it is needed (the last G::PREFETCH pieces of a phase) from the scalar slot base
   unsigned slot_cur_base;      // (scalar) LDS byte address of the slot of the NEXT phase (becomes rda_cur at phase_begin)
   f32x4 bias_nxt;              // bias rows of the NEXT 16-row tile, read two pieces ahead of its first MFMA
-#ifdef DN_EXP_REGSTAGE
-  f32x4 stage[PER_WAVE];
-  unsigned stage_dst;
-  bool have_stage = false;
-#endif
 
   // DMA of one phase = PER_WAVE consecutive pieces per wave, as ONE opaque asm statement: SGPR-base form of
   // global_load_lds (32-bit lane offset), M0 saved/restored inside the statement, and a wave-uniform skip
@@ -187,7 +145,6 @@ struct PipeT {
   // VMEM reads it: 5 wait states = the five scalar instructions ahead of the load, s_nop 1 for margin) and M0 is
   // written one instruction + nop before the LDS-DMA reads it.
   __device__ __forceinline__ void dma_phase(unsigned src_off, unsigned dst_off, unsigned go) {
-#ifndef DN_EXP_NODMA
     // every "s" operand must be provably wave-uniform: readfirstlane them (they are uniform by construction)
     const unsigned long long src_bits = reinterpret_cast<unsigned long long>(wsrc + src_off);
     const unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(src_bits));
@@ -227,15 +184,10 @@ struct PipeT {
           : [go] "s"(go), [lds] "s"(lds), [voff] "v"(lane16), [sbase] "s"(src)
           : "memory", "scc");
     }
-#endif
   }
 
   __device__ __forceinline__ void advance_issue() {
-#ifdef DN_EXP_ROTATE  // experiment: which wave fetches which pieces of a phase rotates with the workgroup's index in its XCD
-    const unsigned who = (wave + (blockIdx.x >> 3)) % WAVES;
-#else
     const unsigned who = wave;
-#endif
     if constexpr (G::LEADER_DMA) {
       // waves 0-3 fetch the whole phase, four pieces each (two right after the barrier, two at mid-phase); waves 4-7 none
       pend_src = q_issue + who * (2 * PER_WAVE * kPieceBytes);
@@ -273,90 +225,20 @@ struct PipeT {
     // (kRingPhases-3) younger phases may stay outstanding; lgkmcnt(0): this wave's LDS reads of the previous
     // phase are complete before its slot is recycled (and the FIFO entries for this phase have arrived).
     static_assert(kRingPhases == 5, "the counted waits below assume two younger phases in flight");
-#ifdef DN_EXP_SHALLOW  // ablation: only one younger phase in flight
-    if constexpr (PER_WAVE == 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-#elif defined(DN_EXP_LOOSEWAIT)  // timing experiment only (UNSAFE: lets 8 more VMEM ops stay outstanding)
-#if DN_EXP_LOOSEWAIT >= 2
-    if constexpr (PER_WAVE == 2) asm volatile("s_waitcnt vmcnt(36) lgkmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(40) lgkmcnt(0)" ::: "memory");
-#else
-    if constexpr (PER_WAVE == 2) asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory");
-#endif
-#else
-#ifdef DN_STAMP   // (diagnostic builds of the 48-point kernels)
-    unsigned st0 = 0, st1 = 0, st2 = 0;
-#endif
     if constexpr (G::ASM_READS) {
       // No LDS wait here: every read of the slot being recycled (phase p-1) was waited for by the take() in front of its
       // MFMAs, which precede this point in program order; the reads still in flight belong to phases p and p+1.
       static_assert(!G::ASM_READS || PER_WAVE == 2, "the asm-read pipeline is the 8-wave geometry");
-#if defined(DN_STAMP) && DN_STAMP == 2   // light mode: only the top-of-tile time (two stamps per pass)
-      if (st_top_pending) { st_top += stamp() - st_last; st_top_pending = 0; ++st_n; }
-#elif defined(DN_STAMP) && DN_STAMP == 4   // stage mode: the top-of-tile ends at the first phase boundary of a pass
-      if (st_top_pending) { const unsigned t = stamp(); st_top += t - st_last; st_last = t; st_top_pending = 0; ++st_n; }
-#elif defined(DN_STAMP) && DN_STAMP == 3   // barrier mode: arrival / release of every phase barrier (two stamps per phase)
-      st0 = stamp();
-      if (st_top_pending) { st_top += st0 - st_last; st_top_pending = 0; }
-      else if (st_n) st_seg += st0 - st_prev;
-#elif defined(DN_STAMP)
-      st0 = stamp();
-      if (st_top_pending) { st_top += st0 - st_last; st_top_pending = 0; }
-      else if (st_n) { st_seg += st0 - st_prev; st_sub[3] += st0 - st_last; }
-#endif
       // a fetching wave of the LEADER_DMA form has four DMAs per phase, otherwise every wave two: two younger phases stay in flight
       if constexpr (G::LEADER_DMA) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-#if defined(DN_STAMP) && DN_STAMP == 1
-      st1 = stamp();
-      st_vm += st1 - st0;
-#endif
     } else {
       if constexpr (PER_WAVE == 2) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
     }
-#endif
-#ifdef DN_EXP_REGSTAGE
-    // experiment: weights through registers (global_load_dwordx4 -> ds_write_b128) instead of LDS-DMA
-    if (have_stage) {
-#pragma unroll
-      for (int e = 0; e < PER_WAVE; ++e)
-        *reinterpret_cast<f32x4*>(ring + stage_dst + e * kPieceBytes + lane16) = stage[e];
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    advance_issue();
-#pragma unroll
-    for (int e = 0; e < PER_WAVE; ++e)
-      stage[e] = *reinterpret_cast<const f32x4*>(wsrc + pend_src + e * kPieceBytes + lane16);
-    stage_dst = pend_dst;
-    have_stage = true;
-#else
-#ifndef DN_EXP_NOBARRIER   // timing experiment only (UNSAFE: no cross-wave ordering of ring slots)
-    __builtin_amdgcn_s_barrier();
-#endif
-#if defined(DN_STAMP) && DN_STAMP == 1
-    st2 = stamp();
-    st_bar += st2 - st1;
-#elif defined(DN_STAMP) && DN_STAMP == 3
-    st_prev = stamp();
-    st_bar += st_prev - st0;
-    st_last = st_prev;
-    ++st_n;
-#endif
-#if defined(DN_G48_PRIO) && DN_G48_PRIO == 2   // first half of a phase: the younger waves (4-7) lead, second half: the older ones
-    if (wave >= 4) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
-#endif
     advance_issue();
     dma_phase(pend_src, pend_dst, (WAVES == 4 || wave < 4) ? 1u : 0u);
-#if defined(DN_STAMP) && DN_STAMP == 1
-    st_prev = stamp();
-    st_dma += st_prev - st2;
-    st_last = st_prev;
-    ++st_n;
-#endif
-#endif
     slot_nxt = (slot_nxt + 1 == kRingPhases) ? 0 : slot_nxt + 1;
     if constexpr (G::ASM_READS) {
       rda_cur = slot_cur_base + lane16;
@@ -368,22 +250,8 @@ struct PipeT {
   }
 
   __device__ __forceinline__ void mid_phase() {
-#if defined(DN_G48_PRIO) && DN_G48_PRIO == 2
-    if (wave >= 4) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(1);
-#endif
-#ifndef DN_EXP_REGSTAGE
-#if defined(DN_STAMP) && DN_STAMP == 1
-    const unsigned m0 = stamp();
-#endif
     if constexpr (WAVES == 8 && G::LEADER_DMA) dma_phase(pend_src + PER_WAVE * kPieceBytes, pend_dst + PER_WAVE * kPieceBytes, wave < 4 ? 1u : 0u);
     else if constexpr (WAVES == 8) dma_phase(pend_src, pend_dst, wave >= 4 ? 1u : 0u);
-#if defined(DN_STAMP) && DN_STAMP == 1
-    const unsigned m1 = stamp();
-    st_dma += m1 - m0;
-    st_prev += m1 - m0;   // keep the DMA issue out of the MFMA-segment figure
-    st_last = m1;
-#endif
-#endif
   }
 
   // (the forms below - two-phase barrier period, spread fetch - are the ASM_READS + LEADER_DMA geometry's: nothing else calls them)
@@ -395,14 +263,9 @@ struct PipeT {
   // the slot rotation.  The ring holds p, p+1, p+2 landed and p+3, p+4 in flight: 5 slots; flight time 1.5-2 phases (~1.5 us).
   template <bool EVEN>
   __device__ __forceinline__ void phase_begin2() {
-#if defined(DN_STAMP) && DN_STAMP == 2
-    if (st_top_pending) { st_top += stamp() - st_last; st_top_pending = 0; ++st_n; }
-#endif
     if constexpr (EVEN) {
-#ifndef DN_EXP_NOBARRIER   // timing experiment only (UNSAFE: no cross-wave ordering of ring slots)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
-#endif
       advance_issue();
       dma_phase(pend_src, pend_dst, wave < 4 ? 1u : 0u);
       dma_phase(pend_src + PER_WAVE * kPieceBytes, pend_dst + PER_WAVE * kPieceBytes, wave < 4 ? 1u : 0u);
@@ -436,9 +299,7 @@ struct PipeT {
     static_assert(PERIOD == kPhasePieces || PERIOD == 2 * kPhasePieces, "barrier period: one or two phases");
     if constexpr (PERIOD == 2 * kPhasePieces) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-#ifndef DN_EXP_NOBARRIER
     __builtin_amdgcn_s_barrier();
-#endif
 #pragma unroll
     for (int h = 0; h < PERIOD / kPhasePieces; ++h) {
       advance_issue();   // (pend_src / pend_dst: this wave's 4 KiB of the phase)
@@ -452,7 +313,6 @@ struct PipeT {
   // fetch step Q of the period (0 .. PERIOD / 2 - 1): ONE wave issues two loads (1 KiB each); everyone else skips (branch inside the statement)
   template <int PERIOD, int Q>
   __device__ __forceinline__ void xs_dma_step() {
-#ifndef DN_EXP_NODMA
     constexpr int STEPS = PERIOD / 8;          // steps per fetching wave: 4 (two phases x two pairs) or 2
     constexpr int H = (Q % STEPS) / 2;         // which of the period's phases
     constexpr int OFF = (Q % 2) * 2048;        // which pair of this wave's four pieces of that phase
@@ -470,7 +330,6 @@ struct PipeT {
         : [keep] "=&s"(keep)
         : [wave] "s"(wave), [who] "n"(Q / STEPS), [lds] "s"(xs_dst[H]), [voff] "v"(lane16), [sbase] "s"(xs_src[H]), [o0] "n"(OFF), [o1] "n"(OFF + 1024)
         : "memory", "scc");
-#endif
   }
   template <int PERIOD, int POS>
   __device__ __forceinline__ void at_position_xs() {
@@ -508,9 +367,9 @@ struct PipeT {
       constexpr int pos = POS + decltype(i_c)::value;
       static_assert(pos % kPhasePieces != 0 || decltype(i_c)::value == 0, "padding never crosses a phase");
       if constexpr (pos % kPhasePieces == kPhasePieces / 2) at_position<PH, pos>();
-      // ASM_READS: only the last kPrefetch skipped positions fetch pieces that will be consumed (the first pieces of the next pass);
+      // ASM_READS: only the last G::PREFETCH skipped positions fetch pieces that will be consumed (the first pieces of the next pass);
       // with fewer padding pieces than FIFO entries the stage before has already fetched the rest (run_stage48, PAD)
-      if constexpr (!G::ASM_READS || decltype(i_c)::value >= N - kPrefetch) prefetch<pos>();
+      if constexpr (!G::ASM_READS || decltype(i_c)::value >= N - G::PREFETCH) prefetch<pos>();
     });
     settle<BIAS>();
   }
@@ -523,27 +382,21 @@ struct PipeT {
       static_assert(pos % kPhasePieces != 0 || decltype(i_c)::value == 0, "padding never crosses a phase");
       static_assert(pos % PERIOD != 0, "padding never opens a barrier period");
       xs_after_piece<PERIOD, pos>();
-      if constexpr (decltype(i_c)::value >= N - kPrefetch) prefetch<pos>();
+      if constexpr (decltype(i_c)::value >= N - G::PREFETCH) prefetch<pos>();
     });
     settle<true>();
   }
 
-  // after consuming piece POS (position within the 16-piece phase), read piece POS + kPrefetch into its FIFO slot
+  // after consuming piece POS (position within the 16-piece phase), read piece POS + G::PREFETCH into its FIFO slot
   template <int POS>
   __device__ __forceinline__ void prefetch() {
-    constexpr int q = (POS % kPhasePieces) + kPrefetch;
+    constexpr int q = (POS % kPhasePieces) + G::PREFETCH;
     if constexpr (G::ASM_READS) {
       const unsigned base = (q < kPhasePieces) ? rda_cur : slot_cur_base + lane16;
-#ifdef DN_EXP_NOREAD   // timing experiment only: no A-fragment traffic (the FIFO keeps whatever it held)
-      asm volatile("; no read %1" : "+v"(af[POS % kPrefetch]) : "v"(base));
-#else
-      asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(af[POS % kPrefetch]) : "v"(base), "n"((q % kPhasePieces) * kPieceBytes));
-#endif
+      asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(af[POS % G::PREFETCH]) : "v"(base), "n"((q % kPhasePieces) * kPieceBytes));
     } else {
       const char* base = (q < kPhasePieces) ? rd_cur : rd_nxt;
-#ifndef DN_EXP_NOREAD
-      af[POS % kPrefetch] = *reinterpret_cast<const f32x4*>(base + (q % kPhasePieces) * kPieceBytes);
-#endif
+      af[POS % G::PREFETCH] = *reinterpret_cast<const f32x4*>(base + (q % kPhasePieces) * kPieceBytes);
     }
   }
 
@@ -556,12 +409,8 @@ struct PipeT {
   // piece POS is about to be consumed: wait until at most NEWER of our younger reads are outstanding
   template <int POS, int NEWER>
   __device__ __forceinline__ f32x4 take() {
-#ifdef DN_EXP_NOWAIT   // timing experiment only (UNSAFE: fragments are consumed before they have arrived)
-    asm volatile("; no wait %1" : "+v"(af[POS % kPrefetch]) : "n"(NEWER));
-#else
-    asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(af[POS % kPrefetch]) : "n"(NEWER));
-#endif
-    return af[POS % kPrefetch];
+    asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(af[POS % G::PREFETCH]) : "n"(NEWER));
+    return af[POS % G::PREFETCH];
   }
   // bias rows of the next tile: addr = LDS byte address of this lane group's 16 bytes of a bias tile, OFF = byte offset
   template <int OFF>
@@ -580,25 +429,18 @@ struct PipeT {
   template <bool BIAS = true>   // BIAS = false: a stream without bias rows (the backward chain) - bias_nxt is not a live register
   __device__ __forceinline__ void settle() {
     if constexpr (!G::ASM_READS) return;   // (compiler-issued reads: the compiler places its own waits)
-#ifdef DN_EXP_NOSETTLE   // timing experiment only (UNSAFE: phi copies may read fragments in flight)
-    return;
-#endif
-    static_assert(kPrefetch >= 2 && kPrefetch <= 4, "settle() names every FIFO entry");
+    static_assert(G::PREFETCH >= 2 && G::PREFETCH <= 4, "settle() names every FIFO entry");
     if constexpr (!BIAS) {
-      static_assert(kPrefetch == 2, "the bias-less form is the 48-point pipeline's");
+      static_assert(G::PREFETCH == 2, "the bias-less form is the 48-point pipeline's");
       asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(af[0]), "+v"(af[1]));
     } else
-    if constexpr (kPrefetch == 2) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(af[0]), "+v"(af[1]), "+v"(bias_nxt));
-    else if constexpr (kPrefetch == 3) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(af[0]), "+v"(af[1]), "+v"(af[2]), "+v"(bias_nxt));
-    else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(af[0]), "+v"(af[1]), "+v"(af[2]), "+v"(af[kPrefetch - 1]), "+v"(bias_nxt));
+    if constexpr (G::PREFETCH == 2) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(af[0]), "+v"(af[1]), "+v"(bias_nxt));
+    else if constexpr (G::PREFETCH == 3) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(af[0]), "+v"(af[1]), "+v"(af[2]), "+v"(bias_nxt));
+    else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(af[0]), "+v"(af[1]), "+v"(af[2]), "+v"(af[G::PREFETCH - 1]), "+v"(bias_nxt));
   }
 };
-// the 32-points-per-wave kernels (mlp_fused.hip, mlp_train.hip): compiler-issued reads, every wave fetches, FIFO of kPrefetch = 4
-#ifdef DN_PREFETCH_SET_BY_KERNEL_SOURCE   // (a 48-point translation unit: kPrefetch is that geometry's; this alias is not instantiated there)
+// the 32-points-per-wave kernels (mlp_fused.hip, mlp_train.hip): compiler-issued reads, every wave fetches, FIFO of 4
 using PipeGeo32 = PipeGeometry<false, false, false, 4>;
-#else
-using PipeGeo32 = PipeGeometry<false, false, false, kPrefetch>;
-#endif
 template <int WAVES>
 using Pipe = PipeT<WAVES, PipeGeo32>;
 
@@ -644,30 +486,22 @@ __device__ __forceinline__ void run_stage(PipeT& pipe, const BH& bh /* [PT][KH] 
       a[t][8] = b2[0]; a[t][9] = b2[1]; a[t][10] = b2[2]; a[t][11] = b2[3];
       a[t][12] = b3[0]; a[t][13] = b3[1]; a[t][14] = b3[2]; a[t][15] = b3[3];
     }
-#ifdef DN_EXP_SETPRIO
-    __builtin_amdgcn_s_setprio(1);
-#endif
     static_for<KT>([&](auto k_c) {
       constexpr int k = decltype(k_c)::value;
       constexpr int pos = POS0 + nt * KT + k;
       if constexpr (pos % kPhasePieces == 0) pipe.phase_begin();
       if constexpr (pos % kPhasePieces == kPhasePieces / 2) pipe.mid_phase();
-      const f32x4 araw = pipe.af[pos % kPrefetch];
+      const f32x4 araw = pipe.af[pos % PipeGeo32::PREFETCH];
       static_for<PT>([&](auto t_c) {
         constexpr int t = decltype(t_c)::value;
         if constexpr (k < KH) a[t] = mma_piece<BF16>(a[t], araw, bh[t][k]);
         else a[t] = mma_piece<BF16>(a[t], araw, bp(t, k - KH));
       });
       pipe.template prefetch<pos>();
-#ifndef DN_EXP_NOPIN
       // pin the interleave: the MFMAs of this piece, then the one LDS read that refills its FIFO slot
       __builtin_amdgcn_sched_group_barrier(0x008, (BF16 ? 1 : 4) * PT, 0);
       __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-#endif
     });
-#ifdef DN_EXP_SETPRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
     // region boundary BEFORE the epilogue: emit(nt)'s VALU work may overlap tile nt+1's MFMAs, but whole tiles
     // are not interleaved (that would keep several accumulator tiles live and spill)
     __builtin_amdgcn_sched_barrier(0);
@@ -731,15 +565,7 @@ __device__ __forceinline__ void store16_uniform(const char* base, unsigned lane1
   //   write to them there corrupts the stored dwords (seen: hipcc reuses the piece registers at once).
   // Non-temporal: the saved activations / gradients are a write-once stream; with the default policy their lines
   // crowd the 1.2 MB weight stream out of L2 (nt: forward 1.36 -> 1.26 ms, backward 1.21 -> 0.92 ms at 786 k points).
-#if !defined(DN_STORE_POLICY_ID) || DN_STORE_POLICY_ID == 1
 #define DN_STORE_POLICY " nt"
-#elif DN_STORE_POLICY_ID == 0   // ablation hooks
-#define DN_STORE_POLICY ""
-#elif DN_STORE_POLICY_ID == 2
-#define DN_STORE_POLICY " sc1"
-#else
-#define DN_STORE_POLICY " sc0 sc1"
-#endif
   asm volatile("s_nop 4\n\tglobal_store_dwordx4 %[voff], %[data], %[sbase]" DN_STORE_POLICY "\n\ts_nop 1"
                : : [voff] "v"(voff), [data] "v"(data), [sbase] "s"(b) : "memory");
 }

@@ -111,7 +111,7 @@ __global__ __launch_bounds__((waves_of<BF16, PT>() * 64), ((BF16 && PT == 1) ? 2
   pipe.rd_cur = ring + lane * 16;
   pipe.rd_nxt = ring + lane * 16;  // phase_begin() of phase 0 turns this into rd_cur
 #pragma unroll
-  for (int e = 0; e < kPrefetch; ++e)
+  for (int e = 0; e < PipeGeo32::PREFETCH; ++e)
     pipe.af[e] = *reinterpret_cast<const f32x4*>(pipe.rd_nxt + e * kPieceBytes);
 
   const char* bias_half = bias_lds + h * 64;
@@ -198,7 +198,6 @@ __global__ __launch_bounds__((waves_of<BF16, PT>() * 64), ((BF16 && PT == 1) ? 2
     // (the piece arrays are passed by reference to their array type and indexed with compile-time constants only: a
     // decayed pointer sends the whole register-resident activation set to scratch memory in the fp32 instances)
     auto save_pieces = [&](auto nt_c, int t, int slot0, const auto& pieces) {
-#ifndef DN_EXP_NOSAVE
       if constexpr (SAVE == 2) {
         constexpr int nt = decltype(nt_c)::value;
         static_assert(P::PPT == 2, "8-bit saved tensors pair the two pieces of a 32-row tile");
@@ -210,7 +209,6 @@ __global__ __launch_bounds__((waves_of<BF16, PT>() * 64), ((BF16 && PT == 1) ? 2
           save_piece(t, slot0 + nt * P::PPT + s2, pieces[nt * P::PPT + s2]);
         });
       }
-#endif
     };
     unsigned maskw[PT][4];
     auto mask_clear = [&]() {
@@ -490,13 +488,12 @@ int dispatch_forward(const dn_mlp_desc& d, int precision, FwdParams& p, hipStrea
   const bool bf = precision == DN_PREC_BF16;
   const bool hf = precision == DN_PREC_F16;
   // bf16 geometry: PT=1 (8 waves x 32 points, two waves per SIMD) measured fastest (1327 vs 1277 TFLOP/s for
-  // PT=2 = 4 waves x 64 points, one wave per SIMD); DEXNERF_BF16_PT=2 selects the latter for experiments
-  static const int bf16_pt = [] { const char* e = getenv("DEXNERF_BF16_PT"); return (e && atoi(e) == 2) ? 2 : 1; }();
+  // PT=2 = 4 waves x 64 points, one wave per SIMD)
   // bf16 / fp16 inference from rays / points: the 48-points-per-wave geometry (mlp_fused48.hip) when the net fits it;
   // DEXNERF_BF16_GEOM=32 keeps the 32-point kernels (same results up to bf16 accumulation order and the cosine's phase form)
   const char* geom_env = getenv("DEXNERF_BF16_GEOM");   // read per call: tests and probes switch it within one process
   const bool geom48 = !(geom_env && atoi(geom_env) == 32);
-  if ((bf || hf) && geom48 && bf16_pt == 1 && p.act == nullptr && p.mode != 2 && p.n_points < (1LL << 31) - 1024 && g48_supported(d, precision))
+  if ((bf || hf) && geom48 && p.act == nullptr && p.mode != 2 && p.n_points < (1LL << 31) - 1024 && g48_supported(d, precision))
     return launch_forward48(d, precision, p, p.packed + p.bias_bytes + static_cast<size_t>(p.total_pieces) * kPieceBytes, stream, comp, composited);
   if (p.act != nullptr && hf) { set_error("mlp_forward(train): fp16 is a render-only mode"); return DN_E_UNSUPPORTED; }
   if (p.act != nullptr && p.save8) {   // training forward with 8-bit saved units: the 48-point geometry (mlp_fused48.hip, SAVE = 2)
@@ -528,8 +525,6 @@ int dispatch_forward(const dn_mlp_desc& d, int precision, FwdParams& p, hipStrea
 #define DN_CASE(W_, LX_)                                                                     \
   if (d.hidden_size == W_ && d.num_encoding_fn_xyz == LX_)                                   \
     return bf ? launch_forward<W_, LX_, 4, true, 1>(p, stream) : launch_forward<W_, LX_, 4, false, 1>(p, stream);
-  if (bf && bf16_pt == 2 && d.hidden_size == 256 && d.num_encoding_fn_xyz == 10)
-    return launch_forward<256, 10, 4, true, 2>(p, stream);  // experimental 4-wave x 64-point geometry
   DN_CASE(256, 10)
   DN_CASE(128, 10)
   DN_CASE(256, 6)

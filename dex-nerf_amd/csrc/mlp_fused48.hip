@@ -7,8 +7,6 @@
 // Every A fragment read from LDS feeds three MFMAs: 384 points per pass of the weight stream instead of 256.
 // A-fragment FIFO of 2 pieces here (4 in the 32-point kernels): a piece lasts three MFMAs = 48 cycles, and the 256-VGPR
 // budget of two waves per SIMD is spent on the two 96-register activation sets
-#include <vector>
-
 #include "mlp_fused48_kernel.h"
 
 namespace dn {
@@ -187,43 +185,7 @@ int launch_forward48(const dn_mlp_desc& d, int precision, const FwdParams& p_in,
   long long grid = p.n_tiles < cus ? p.n_tiles : cus;
   auto launch = [&](auto kern) -> int {
     if (int rc = ensure_big_lds(reinterpret_cast<const void*>(kern))) return rc;
-#ifdef DN_STAMP   // diagnostic build: synchronous, allocates, prints - never part of the shipped library
-    static unsigned* dbg = nullptr;
-    const size_t words = static_cast<size_t>(grid) * kG48Waves * 16;
-    if (!dbg) (void)hipMalloc(&dbg, 256 * kG48Waves * 16 * sizeof(unsigned));
-    (void)hipMemsetAsync(dbg, 0, words * sizeof(unsigned), stream);
-    q.dbg = dbg;
-#endif
     hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(kG48Waves * 64), lds, stream, p, q);
-#ifdef DN_STAMP
-    (void)hipStreamSynchronize(stream);
-    std::vector<unsigned> h(words);
-    (void)hipMemcpy(h.data(), dbg, words * sizeof(unsigned), hipMemcpyDeviceToHost);
-    double acc[2][16] = {};
-    for (size_t w = 0; w < words / 16; ++w)
-      for (int i = 0; i < 16; ++i) acc[(w % kG48Waves) >= 4][i] += h[w * 16 + i];
-#if DN_STAMP == 2
-    for (int g = 0; g < 2; ++g)
-      fprintf(stderr, "[stamp] waves %d-%d: per pass: top-of-tile %.0f cycles, rest of the pass %.0f (%.1f passes per wave)\n", g * 4, g * 4 + 3,
-              acc[g][8] / acc[g][4], acc[g][9] / acc[g][4], acc[g][4] / (words / 32.0));
-#endif
-#if DN_STAMP == 4
-    for (int g = 0; g < 2; ++g)
-      fprintf(stderr, "[stamp] waves %d-%d: per pass: top %.0f, layer1 (32 pieces, 16 tiles) %.0f, trunk (928 pieces, 112 tiles) %.0f, heads (212 pieces + 12 pad, 26 tiles) %.0f cycles\n",
-              g * 4, g * 4 + 3, acc[g][8] / acc[g][4], acc[g][10] / acc[g][4], acc[g][11] / acc[g][4], acc[g][9] / acc[g][4]);
-#endif
-#if DN_STAMP == 3
-    for (int g = 0; g < 2; ++g)
-      fprintf(stderr, "[stamp] waves %d-%d: per phase: release -> next arrival %.1f, barrier (arrival -> release, incl. the vmcnt wait) %.1f cycles; per pass: top-of-tile %.0f\n",
-              g * 4, g * 4 + 3, acc[g][3] / acc[g][4], acc[g][1] / acc[g][4], acc[g][8] / (acc[g][4] / 74.0));
-#endif
-    for (int g = 0; g < 2 && DN_STAMP == 1; ++g) {
-      const double n = acc[g][4] > 0 ? acc[g][4] : 1;
-      fprintf(stderr, "[stamp] waves %d-%d: per phase: vmcnt wait %.1f, barrier %.1f, DMA issue %.1f, quarters %.1f %.1f %.1f %.1f cycles (%.0f phases per wave); per PASS: tail %.0f, top-of-tile %.0f\n",
-              g * 4, g * 4 + 3, acc[g][0] / n, acc[g][1] / n, acc[g][2] / n, acc[g][5] / n, acc[g][6] / n, acc[g][7] / n, acc[g][3] / n,
-              n / (words / 32.0), acc[g][9] / (n / 74.0), acc[g][8] / (n / 74.0));
-    }
-#endif
     return check_launch("mlp_forward48");
   };
   // fixed-shape instances: the paper network (D8 / W256 / skip 4, view directions - BASELINE configs 2, 4, 5) and the fork's
@@ -231,14 +193,6 @@ int launch_forward48(const dn_mlp_desc& d, int precision, const FwdParams& p_in,
   const bool paper = d.hidden_size == 256 && d.num_layers == 8 && L.skip_mask == 0x10u && d.use_viewdirs;
   const bool shipped = d.hidden_size == 128 && d.num_layers == 4 && L.skip_mask == 0u && d.use_viewdirs;
   const bool fixed_ok = std::getenv("DEXNERF_G48_RUNTIME_SHAPE") == nullptr;
-#ifdef DN_EXP_ONLY_PAPER   // experiment builds: only the headline instances are compiled (minutes -> seconds per build)
-  if (paper && p.act == nullptr && p.mode == 0 && std::getenv("DEXNERF_G48_NO_OVERLAP") == nullptr)
-    return precision == DN_PREC_F16 ? launch(mlp_forward48_kernel<256, 2, 8, 0x10u, 1, 0, 2>) : launch(mlp_forward48_kernel<256, 1, 8, 0x10u, 1, 0, 2>);
-  if (paper && p.act == nullptr && precision == DN_PREC_F16) return launch(mlp_forward48_kernel<256, 2, 8, 0x10u, 1>);
-  if (paper && p.act == nullptr) return launch(mlp_forward48_kernel<256, 1, 8, 0x10u, 1>);
-  set_error("mlp_forward48: experiment build (DN_EXP_ONLY_PAPER)");
-  return DN_E_UNSUPPORTED;
-#else
   if (p.act != nullptr) {   // training forward (DN_PREC_BF16_S8): saved units + mask words
     if (precision != DN_PREC_BF16 || !p.save8) { set_error("mlp_forward48(train): the 48-point training forward is the bf16 / 8-bit-saved-tensor mode"); return DN_E_UNSUPPORTED; }
     if (g48_two_group_shape(d) && g48_train_groups(p.n_points, cus) == 2) {   // small launch: 256-point tiles (mlp_geo48.h; the backward asks the same question)
@@ -279,7 +233,6 @@ int launch_forward48(const dn_mlp_desc& d, int precision, const FwdParams& p_in,
   if (paper && fixed_ok) return launch(mlp_forward48_kernel<256, 1, 8, 0x10u, 1>);
   if (shipped && fixed_ok) return launch(mlp_forward48_kernel<128, 1, 4, 0u, 1>);
   return d.hidden_size == 256 ? launch(mlp_forward48_kernel<256, 1>) : launch(mlp_forward48_kernel<128, 1>);
-#endif
 }
 
 }  // namespace dn

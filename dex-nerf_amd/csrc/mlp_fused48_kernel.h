@@ -73,20 +73,12 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
   constexpr int IN_ROWS = 7 + 3 * VSETS;
   constexpr bool FIXED = DC > 0;
   // explicit-schedule tile pass (run_stage48x): the paper network's render instances
-#ifdef DN_G48_NO_XS
-  constexpr bool XS = false;
-#else
   constexpr bool XS = FIXED && SAVE == 0 && (OVLP == 0 || OVLP == 2) && COMP == 0 && VIEWC != 0;
-#endif
   constexpr bool ST = !FIXED;   // settle at stage ends
-#if defined(DN_PIPE_ASM_READS) && defined(DN_PIPE_LEADER_DMA) && !defined(DN_G48_BARRIER_EVERY_PHASE)
   // barrier period in pieces: every second phase where a phase's parity is a compile-time position - the fixed-shape W = 256
   // instance (every stage boundary of D8 / skip 4 falls on an even phase, 74 phases per pass) - every phase elsewhere.
   // (The two-phase form waits with vmcnt(0): with the training forward's stores in the queue that wait would be for HBM.)
   constexpr int PH = (FIXED && W == 256 && SAVE == 0) ? 2 * kPhasePieces : kPhasePieces;
-#else
-  constexpr int PH = kPhasePieces;
-#endif
   using BP8 = typename Prec<F>::BPiece;
   using Elem = typename Prec<F>::Elem;
   constexpr int PT = SAVE == 3 ? 2 : 3;   // point groups per wave
@@ -184,7 +176,7 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
   pipe.wave = wave;
 #pragma unroll
   for (int ph = 0; ph < (PH == kPhasePieces ? kRingPhases - 1 : kRingPhases - 2); ++ph) pipe.issue_phase();
-  if constexpr (PH == kPhasePieces && kG48LeaderDma && kG48AsmReads) {
+  if constexpr (PH == kPhasePieces) {
     // The first barrier period needs what every later one needs: phases 0 and 1 landed (Pipe48::phase_begin).  A fetching wave leaves
     // its eight youngest loads - its shares of phases 2 and 3 - in flight (everything older - the inputs - has then landed); waves 4-7
     // have nothing but their input DMAs outstanding and wait for all of them.  (A launch of one or two tiles per workgroup - a training
@@ -195,29 +187,16 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __syncthreads();
   }
-#ifdef DN_EXP_HALF   // timing experiment only: one wave per SIMD does the work (what a wave sustains ALONE); 1: waves 0-3, 2: waves 4-7 (+ the fetching by 0-3 is lost: combine with DN_EXP_NODMA)
-  if ((DN_EXP_HALF == 1) ? wave >= 4 : wave < 4) return;
-#endif
   pipe.slot_nxt = 0;
   // this lane group's 4 rows of bias tile 0 (LDS byte address; the stages add tile offsets)
   // (rebuilt at every use from an opaque copy of the thread index - see fresh_lane - instead of being carried in a VGPR)
   auto bias_at = [&](int tile) { return pipe.ring_addr + kRingBytes + ((fresh_lane() >> 4) << 4) + tile * 64; };
-#ifdef DN_PIPE_ASM_READS
   pipe.rda_cur = pipe.ring_addr + lane * 16;
   pipe.slot_cur_base = pipe.ring_addr;       // phase 0 lives in slot 0: phase_begin() of phase 0 turns this into rda_cur
-  static_for<kPrefetch - 1>([&](auto e_c) { pipe.template prologue_read<decltype(e_c)::value>(); });
+  static_for<PipeGeo48::PREFETCH - 1>([&](auto e_c) { pipe.template prologue_read<decltype(e_c)::value>(); });
   pipe.template bias_prefetch<0>(bias_at(0));    // same order as in steady state: ..., bias, one more A read
-  pipe.template prologue_read<kPrefetch - 1>();
-#else
-  pipe.rd_cur = ring + lane * 16;
-  pipe.rd_nxt = ring + lane * 16;
-#pragma unroll
-  for (int e = 0; e < kPrefetch; ++e) pipe.af[e] = *reinterpret_cast<const f32x4*>(pipe.rd_nxt + e * kPieceBytes);
-#endif
+  pipe.template prologue_read<PipeGeo48::PREFETCH - 1>();
 
-#if defined(DN_G48_PRIO) && DN_G48_PRIO == 1   // static priority for the younger half of the workgroup (MI355X_MICROARCH.md, two waves per SIMD, item 4)
-  if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
   unsigned trk = 0;   // fp16 instances: running maximum of the stage inputs' 16-bit patterns (run_stage48, TRK)
   int vset = 0;  // which view-direction rows hold this tile's directions (wave-uniform, next set every tile)
   // OVL: this lane group's 16 xyz table entries in registers for the whole kernel (a slot mid-stage must not read LDS: the
@@ -260,20 +239,14 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
     // ---- xyz encoding of this lane's three points, its 16 columns each, into the per-wave LDS stash ----
     // (OVL: only a workgroup's first tile is encoded here; every later one was encoded during the tile before it)
     const bool first_tile = tile == static_cast<int>(blockIdx.x);
-#ifdef DN_EXP_NOTOP   // timing experiment only: no top-of-tile block (the stash keeps whatever it held; inputs are not staged)
-    if (false) {
-#else
     if ((!OVL && !OVX) || first_tile) {
-#endif
       const int ln = fresh_lane();
       const int j = ln & 15;
       const f32x4* tabx = reinterpret_cast<const f32x4*>(tab_lds) + (ln >> 4) * 16;
       char* pex = pex_of(ln);
-#ifdef DN_PIPE_LEADER_DMA
       // waves 4-7 issue no weight DMAs, so no counted wait of theirs ever pushes this tile's input DMAs (issued one tile
       // ago) through: they wait for them here - by now their VMEM queue holds nothing else but the last output stores
       if (wave >= 4) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
       float in[PT][7];
 #pragma unroll
       for (int t = 0; t < PT; ++t)
@@ -335,9 +308,6 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
     };
     // after emit48 of output tile nt of group t into bo: ReLU mask bits off the packed outputs, and every fourth tile one unit
     auto mask_tail = [&](auto nt_c, auto t_c, const auto& bo) {
-#ifdef DN_EXP_TF_NOMASK   // timing experiment only: no ReLU mask bits
-      return;
-#endif
       if constexpr (SAVE != 0) {
         constexpr int nt = decltype(nt_c)::value, t = decltype(t_c)::value;
         const u32x4 w = __builtin_bit_cast(u32x4, bo[nt / 2]);
@@ -358,9 +328,6 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
       }
     };
     auto unit_tail = [&](auto nt_c, auto t_c, const auto& bo, int slot0) {
-#ifdef DN_EXP_TF_NOUNIT   // timing experiment only: no saved units (no 8-bit conversion, no store)
-      return;
-#endif
       if constexpr (SAVE != 0) {
         constexpr int nt = decltype(nt_c)::value;
         if constexpr (nt % 4 == 3) save_unit(t_c, slot0 + nt / 4, bo[nt / 2 - 1], bo[nt / 2]);
@@ -583,9 +550,6 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
       });
     }
     bias_tile += NT;
-#if defined(DN_STAMP) && DN_STAMP == 4
-    pipe.template stage_end<0>();
-#endif
     if constexpr (OVL) {
       // the next tile's inputs - their DMAs were issued a whole tile ago (the first tile's: at its top) - become this lane's three
       // rotated points, then the rows are handed to the DMAs of the tile after next.  Waves 4-7 issue no weight DMAs, so no counted
@@ -744,25 +708,18 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
         };
         mask_clear();
         if constexpr ((MASKC >> i) & 1u) {
-#ifdef DN_G48_SKIP_PE_FROM_LDS
-          run_stage48<F, NT, KH, KXP, 0, false, false, 0, PH>(pipe, bin, pe_xyz, bias_at(bias_tile), 0u, emit);
-#else
           BP8 pe[PT][KXP];   // the skip layer's second K panel, in registers for the stage (see layer1)
 #pragma unroll
           for (int t = 0; t < PT; ++t)
 #pragma unroll
             for (int k = 0; k < KXP; ++k) pe[t][k] = pe_xyz(t, k);
           run_stage48<F, NT, KH, KXP, 0, false, false, 0, PH, (i == 0 ? 2 : 1)>(pipe, bin, [&](int t, int k) { return pe[t][k]; }, bias_at(bias_tile), 0u, emit, &trk);
-#endif
         } else {
           run_stage48<F, NT, KH, 0, 0, false, false, 0, PH, (i == 0 ? 2 : 1)>(pipe, bin, no_pe, bias_at(bias_tile), 0u, emit, &trk);
         }
         mask_store(i);
         bias_tile += NT;
       });
-#if defined(DN_STAMP) && DN_STAMP == 4
-      pipe.template stage_end<1>();
-#endif
       if constexpr ((DC - 1) % 2 == 0) heads(ba, bb, std::integral_constant<bool, VIEWC != 0>{});
       else heads(bb, ba, std::integral_constant<bool, VIEWC != 0>{});
     } else {
@@ -798,9 +755,6 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
       else heads(ba, bb, std::false_type{});
     }
     }   // !XS
-#ifdef DN_STAMP
-    pipe.pass_end();
-#endif
     const int lo = fresh_lane();
     if constexpr (COMP != 0) {
       // the tile's 384 raw rows go into the xyz stash (dead from the trunk to the next tile's top; one 6 KiB image, point order)
@@ -846,14 +800,6 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
     const bool out_of_range = (trk & 0xFFFFu) >= 0x7C00u || (trk >> 16) >= 0x7C00u;
     if (p.range_flag != nullptr && __ballot(out_of_range) != 0ull && (threadIdx.x & 63) == 0) atomicAdd(p.range_flag, 1u);
   }
-#ifdef DN_STAMP
-  if ((threadIdx.x & 63) == 0) {
-    unsigned* d = q.dbg + (blockIdx.x * WAVES + wave) * 16;
-    d[0] = pipe.st_vm; d[1] = pipe.st_bar; d[2] = pipe.st_dma; d[3] = pipe.st_seg; d[4] = pipe.st_n;
-    d[5] = pipe.st_sub[0]; d[6] = pipe.st_sub[1]; d[7] = pipe.st_sub[2]; d[3] = pipe.st_sub[3];
-    d[8] = pipe.st_top; d[9] = pipe.st_tail; d[10] = pipe.st_cls[0]; d[11] = pipe.st_cls[1];
-  }
-#endif
 }
 
 }  // namespace dn

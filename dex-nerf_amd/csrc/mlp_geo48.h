@@ -49,9 +49,6 @@ struct G48Params {
   int bias_bytes;    // bias rows (padded to 1 KiB); the tables follow, then the pieces
   int total_pieces;
   CompParams comp;   // the instances that composite their own rays (COMP): where the maps go; otherwise unread
-#ifdef DN_STAMP
-  unsigned* dbg;     // diagnostic build: 8 words per wave
-#endif
 };
 
 

@@ -1,45 +1,21 @@
 // Shared by the 48-points-per-wave kernels (mlp_fused48.hip: inference + training forward; mlp_train48.hip: backward-data chain):
 // the Pipe configuration of this geometry and the per-stage MFMA loop.  Included by those two translation units only.
 #pragma once
-#if defined(DN_PREFETCH) && !defined(DN_ABLATION_BUILD)
-#error "DN_PREFETCH is set by this file (the 48-point kernel's FIFO depth); a command-line value is an ablation hook (scripts/build_exp.sh)"
-#endif
-#ifdef DN_G48_PREFETCH   // (ablation hook, refused by mlp_device.h outside an ablation build)
-#define DN_PREFETCH DN_G48_PREFETCH
-#else
-#define DN_PREFETCH 2
-#endif
-#define DN_PREFETCH_SET_BY_KERNEL_SOURCE 1
-#define DN_PIPE_SCALAR_STATE 1   // ring bookkeeping in SGPRs: frees the VGPRs that were spilling (0.5 % on the launch)
-#ifndef DN_G48_COMPILER_READS    // (ablation hook: the r01 pipeline with compiler-issued reads and waits)
-#define DN_PIPE_ASM_READS 1      // A-fragment / bias LDS reads and their counted waits as opaque asm (mlp_device.h Pipe)
-#endif
-#ifndef DN_G48_SYMMETRIC_DMA     // (ablation hook: every wave fetches two pieces per phase, as in round 1)
-// Asymmetric roles.  The two waves of a SIMD do not share the matrix pipe fairly: the older one (waves 0-3) wins the
-// arbitration, runs a phase ahead and then sits at the phase barrier (s_memtime stamps, profiles/r02_fine_net_stalls.md:
-// ~640 cycles per phase against ~160 for waves 4-7), while the younger one - the critical path - also paid ~300 cycles per
-// phase of its own LDS-DMA issue.  So the waves with the slack fetch the whole weight stream (four pieces each) and
-// waves 4-7 issue MFMAs only.
-#define DN_PIPE_LEADER_DMA 1
-#endif
 #include <type_traits>
 #include "mlp_geo48.h"
 
 namespace dn {
 
-// the weight pipeline of this geometry (mlp_device.h PipeT): explicit LDS reads, waves 0-3 fetch, scalar ring state, FIFO of 2 - each
-// switchable by the ablation hooks above
-#ifdef DN_PIPE_ASM_READS
-constexpr bool kG48AsmReads = true;
-#else
-constexpr bool kG48AsmReads = false;
-#endif
-#ifdef DN_PIPE_LEADER_DMA
-constexpr bool kG48LeaderDma = true;
-#else
-constexpr bool kG48LeaderDma = false;
-#endif
-using PipeGeo48 = PipeGeometry<kG48AsmReads, kG48LeaderDma, true, kPrefetch>;
+// the weight pipeline of this geometry (mlp_device.h PipeT):
+//   ASM_READS     A-fragment / bias LDS reads and their counted waits as opaque asm
+//   LEADER_DMA    asymmetric roles.  The two waves of a SIMD do not share the matrix pipe fairly: the older one (waves 0-3) wins
+//                 the arbitration, runs a phase ahead and then sits at the phase barrier (s_memtime stamps,
+//                 profiles/r02_fine_net_stalls.md: ~640 cycles per phase against ~160 for waves 4-7), while the younger one - the
+//                 critical path - also paid ~300 cycles per phase of its own LDS-DMA issue.  So the waves with the slack fetch the
+//                 whole weight stream (four pieces each) and waves 4-7 issue MFMAs only.
+//   SCALAR_STATE  ring bookkeeping in SGPRs: frees the VGPRs that were spilling (0.5 % on the launch)
+//   PREFETCH      a FIFO of 2 A-fragment pieces
+using PipeGeo48 = PipeGeometry<true, true, true, 2>;
 template <int WAVES>
 using Pipe48 = PipeT<WAVES, PipeGeo48>;
 
@@ -77,7 +53,7 @@ constexpr int g48_issued(int q0, int q1) {
 // One GEMM stage: NT_OUT 16-row output tiles, KH hidden pieces + KP encoding pieces per tile, three point groups.
 // bias_addr: LDS byte address of this lane group's 16 bytes of the stage's bias tile 0; the bias tiles of a tile pass are
 // contiguous in stream order, so "the next tile's bias" is the next 64 bytes, except after the last stage of the pass
-// (LAST): there it is next_addr (tile 0 of layer1).  Read pipeline (DN_PIPE_ASM_READS): step k of a tile = take A(p),
+// (LAST): there it is next_addr (tile 0 of layer1).  Read pipeline (ASM_READS): step k of a tile = take A(p),
 // three MFMAs, read A(p+2); the next tile's bias read goes out right after the A read of step KT-2, i.e. between A(next
 // tile, 0) and A(next tile, 1) - so with a FIFO of P pieces the wait counts are P - 1 everywhere and P at k = KT-1; the
 // bias take at k = 0 waits with 1 (one A read was issued after the bias read), which also lands every older A read.
@@ -99,11 +75,7 @@ __device__ __forceinline__ void run_stage48(PipeT& pipe, const BH& bh, BP&& bp, 
     static_for<KT>([&](auto k_c) {
       constexpr int k = decltype(k_c)::value;
       constexpr int pos = POS0 + nt * KT + k;
-#if defined(DN_STAMP) && DN_STAMP == 1
-      if constexpr (pos % 4 == 0 && pos % kPhasePieces != 0) pipe.template substamp<(pos % kPhasePieces) / 4>();
-#endif
       pipe.template at_position<PH, pos>();   // phase boundary (barrier + weight DMA) / mid-phase DMA, if this is one
-#ifdef DN_PIPE_ASM_READS
       if constexpr (k == 0) {
         f32x4 b = {0.0f, 0.0f, 0.0f, 0.0f};
         if constexpr (BIAS) b = pipe.template bias_take<1>();   // issued before A(pos + 1): one younger read may stay in flight
@@ -112,51 +84,21 @@ __device__ __forceinline__ void run_stage48(PipeT& pipe, const BH& bh, BP&& bp, 
       }
       // younger reads of ours than A(pos): the other FIFO entries - those that were issued at all (see PAD below) - plus
       // the next tile's bias at k = KT - 1
-      constexpr int newer = g48_issued<LAST, POS0 + NT_OUT * KT, PAD>(pos + 1, pos + kPrefetch) + ((BIAS && k == KT - 1) ? 1 : 0);
+      constexpr int newer = g48_issued<LAST, POS0 + NT_OUT * KT, PAD>(pos + 1, pos + PipeGeo48::PREFETCH) + ((BIAS && k == KT - 1) ? 1 : 0);
       const auto a = __builtin_bit_cast(typename Prec<F>::BPiece, pipe.template take<pos, newer>());
-#else
-      if constexpr (k == 0) {
-        const f32x4 b = *reinterpret_cast<const f32x4*>(pipe.ring + (bias_addr - pipe.ring_addr) + nt * 64);
-#pragma unroll
-        for (int t = 0; t < PT; ++t) acc[t] = b;
-      }
-      const auto a = __builtin_bit_cast(typename Prec<F>::BPiece, pipe.af[pos % kPrefetch]);
-#endif
-#ifdef DN_G48_EPI_PIN
-      // the previous tile's epilogue (12 conversions / ReLUs, same scheduling region: it follows the sched_barrier below) goes ONE
-      // vector instruction per MFMA gap - an MFMA holds the SIMD's vector issue for 8 of its 16 cycles, one 4-5-cycle instruction
-      // fits the rest - after DN_G48_EPI_PIN leading MFMAs (distance to the accumulators' last writes: no hazard nops)
-      if constexpr (k == 0) {
-        __builtin_amdgcn_sched_group_barrier(0x008, DN_G48_EPI_PIN, 0);
-#pragma unroll
-        for (int i = 0; i < 12; ++i) {
-          __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        }
-      }
-#endif
       static_for<PT>([&](auto t_c) {
         constexpr int t = decltype(t_c)::value;
         if constexpr (k < KH) acc[t] = mfma48<F>(a, bh[t][k], acc[t]);
         else acc[t] = mfma48<F>(a, bp(t, k - KH), acc[t]);
       });
-#ifdef DN_PIPE_ASM_READS
       // PAD padding pieces follow the last stage of a pass (Pipe::skip): a read of one of THOSE would never be consumed, and
       // a fragment nobody consumes is a dead value to the compiler - it reuses the registers while the read is in flight
-      if constexpr (g48_issued<LAST, POS0 + NT_OUT * KT, PAD>(pos + kPrefetch, pos + kPrefetch + 1) == 1) pipe.template prefetch<pos>();
-#else
-      pipe.template prefetch<pos>();
-#endif
-#ifdef DN_PIPE_ASM_READS
+      if constexpr (g48_issued<LAST, POS0 + NT_OUT * KT, PAD>(pos + PipeGeo48::PREFETCH, pos + PipeGeo48::PREFETCH + 1) == 1) pipe.template prefetch<pos>();
       if constexpr (BIAS && k == KT - 2) {
         if constexpr (nt + 1 < NT_OUT) pipe.template bias_prefetch<(nt + 1) * 64>(bias_addr);
         else if constexpr (LAST) pipe.template bias_prefetch<0>(next_addr);
         else pipe.template bias_prefetch<NT_OUT * 64>(bias_addr);
       }
-#else
-      __builtin_amdgcn_sched_group_barrier(0x008, PT, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-#endif
     });
     __builtin_amdgcn_sched_barrier(0);
     static_for<PT>([&](auto t_c) { emit(nt_c, t_c, acc[decltype(t_c)::value]); });
@@ -190,11 +132,9 @@ __device__ __forceinline__ void run_stage48(PipeT& pipe, const BH& bh, BP&& bp, 
       }
     }
   });
-#ifdef DN_PIPE_ASM_READS
   // run-time network shape: no read stays in flight across a stage boundary (control flow merges there: see Pipe::settle);
   // the fixed-shape instances are straight-line code from the top of a tile pass to its end and settle once, there
   if constexpr (SETTLE) pipe.template settle<BIAS>();
-#endif
 }
 
 // ===== explicit-schedule stage (the fixed-shape W = 256 render instances) ==========================================================
@@ -219,11 +159,7 @@ __device__ __forceinline__ void mfma48_first(f32x4& d, const f32x4& a, const typ
 // a block's FIRST MFMA carries the counted wait for its A fragment in the same statement (as two statements hipcc puts an `s_nop 0`
 // between them: it takes the wait statement for an unknown writer of the fragment registers); the fragment is an in-out operand, so the
 // compiler cannot touch it between its read statement and this one (tests/test_asm_hazards.py replays the counter on the result)
-#ifdef DN_EXP_NOWAIT
-#define DN_XS_WAIT "; no wait %[n]\n\t"
-#else
 #define DN_XS_WAIT "s_waitcnt lgkmcnt(%[n])\n\t"
-#endif
 template <int F, int NEWER>
 __device__ __forceinline__ void mfma48_first_w(f32x4& d, f32x4& a, const typename Prec<F>::BPiece& b, const f32x4& c) {
   if constexpr (F == 1) asm volatile(DN_XS_WAIT "v_mfma_f32_16x16x32_bf16 %[d], %[a], %[b], %[c]" : [d] "=&v"(d), [a] "+v"(a) : [b] "v"(b), [c] "v"(c), [n] "n"(NEWER));
@@ -383,8 +319,8 @@ __device__ __forceinline__ void run_stage48x(PipeT& pipe, const BH& bh, BP&& bp,
       pipe.template at_position_xs<PX, pos>();
       f32x4 b = {0.0f, 0.0f, 0.0f, 0.0f};
       if constexpr (k == 0) b = pipe.template bias_take<1>();
-      constexpr int newer = g48_issued<LAST, POS0 + NT_OUT * KT, PAD>(pos + 1, pos + kPrefetch) + ((k == KT - 1) ? 1 : 0);
-      f32x4& a = pipe.af[pos % kPrefetch];
+      constexpr int newer = g48_issued<LAST, POS0 + NT_OUT * KT, PAD>(pos + 1, pos + PipeGeo48::PREFETCH) + ((k == KT - 1) ? 1 : 0);
+      f32x4& a = pipe.af[pos % PipeGeo48::PREFETCH];
       static_for<PT>([&](auto t_c) {
         constexpr int t = decltype(t_c)::value;
         if constexpr (t == 0) {   // (with the wait for A(pos): at most `newer` of our younger reads stay in flight)
@@ -409,7 +345,7 @@ __device__ __forceinline__ void run_stage48x(PipeT& pipe, const BH& bh, BP&& bp,
         static_for<NTRK>([&](auto q_c) { run_trk(q_c); });
       pipe.template xs_after_piece<PX, pos>();
       hook(std::integral_constant<int, nt * KT + k>{}, std::integral_constant<int, 3>{});
-      if constexpr (g48_issued<LAST, POS0 + NT_OUT * KT, PAD>(pos + kPrefetch, pos + kPrefetch + 1) == 1) pipe.template prefetch<pos>();
+      if constexpr (g48_issued<LAST, POS0 + NT_OUT * KT, PAD>(pos + PipeGeo48::PREFETCH, pos + PipeGeo48::PREFETCH + 1) == 1) pipe.template prefetch<pos>();
       if constexpr (k == KT - 2) {
         if constexpr (nt + 1 < NT_OUT) pipe.template bias_prefetch<(nt + 1) * 64>(bias_addr);
         else if constexpr (LAST) pipe.template bias_prefetch<0>(next_addr);
@@ -433,12 +369,6 @@ __device__ __forceinline__ void emit48(const f32x4& acc, BO& bo) {
   typedef short s16x2 __attribute__((ext_vector_type(2)));
   typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
   u32x4 w = __builtin_bit_cast(u32x4, bo[NT / 2]);
-#ifdef DN_EXP_NOEPI   // timing experiment only: raw accumulator bits as the piece's dwords - no convert, no ReLU (1: two moves per tile, 2: one)
-  w[(NT & 1) * 2] = __builtin_bit_cast(unsigned, acc[0]);
-  if (DN_EXP_NOEPI < 2) w[(NT & 1) * 2 + 1] = __builtin_bit_cast(unsigned, acc[2]);
-  bo[NT / 2] = __builtin_bit_cast(typename Prec<F>::BPiece, w);
-  return;
-#endif
 #pragma unroll
   for (int d = 0; d < 2; ++d) {
     f32x2 f = {acc[2 * d], acc[2 * d + 1]};

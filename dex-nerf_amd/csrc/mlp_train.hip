@@ -12,7 +12,6 @@
 #include "mlp_internal.h"
 #include "mlp_geo48.h"
 #include <atomic>
-#include <vector>
 #include <cmath>
 
 namespace dn {
@@ -92,7 +91,7 @@ __global__ __launch_bounds__((waves_of<BF16, 1>() * 64), (BF16 ? 2 : 1)) void ml
   pipe.rd_cur = ring + lane * 16;
   pipe.rd_nxt = ring + lane * 16;
 #pragma unroll
-  for (int e = 0; e < kPrefetch; ++e) pipe.af[e] = *reinterpret_cast<const f32x4*>(pipe.rd_nxt + e * kPieceBytes);
+  for (int e = 0; e < PipeGeo32::PREFETCH; ++e) pipe.af[e] = *reinterpret_cast<const f32x4*>(pipe.rd_nxt + e * kPieceBytes);
 
   int g_slot = 0;
   for (long long tile = blockIdx.x; tile < p.n_tiles; tile += gridDim.x) {
@@ -101,20 +100,16 @@ __global__ __launch_bounds__((waves_of<BF16, 1>() * 64), (BF16 ? 2 : 1)) void ml
     const f32x4 g = *reinterpret_cast<const f32x4*>(wbuf + g_slot * kPieceBytes + lane * 16);
     const char* grad_tile = uniform_ptr(p.grads + tile32 * p.grad_pieces * kPieceBytes);
     auto store_grad = [&](int slot, const BPiece& v) {
-#ifndef DN_EXP_NOSAVE
       if constexpr (!S8) store16_uniform(grad_tile + static_cast<long long>(slot) * kPieceBytes, pipe.lane16, v);
-#endif
     };
     // S8: pieces `slot` (even) and `slot + 1` as one unit of 8 + 8 bytes per lane
     auto store_grad_pair = [&](int slot, const BPiece& lo, const BPiece& hi) {
-#ifndef DN_EXP_NOSAVE
       if constexpr (S8 && BF16 == 1) {
         unsigned w[4];
         piece_to_8bit<true>(lo, p.grad_scale, w[0], w[1]);
         piece_to_8bit<true>(hi, p.grad_scale, w[2], w[3]);
         store16_uniform(grad_tile + static_cast<long long>(slot >> 1) * kPieceBytes, pipe.lane16, make_uint4(w[0], w[1], w[2], w[3]));
       }
-#endif
     };
     // Start of stage q: fetch this stage's mask word from its LDS slot, then stage what will be needed two stages on
     // (same tile, or the first two stages / the output gradient of the next tile) into the slot just read or one idle
@@ -530,18 +525,9 @@ extern "C" int dn_mlp_unpack(const dn_mlp_desc* desc, int precision, int which, 
 // tile buffers, all but one in flight, with counted vmcnt waits.
 // HBM-bound: (N + K) x 2 B per point against 2 N K FLOP per point (146 FLOP/B at 256 x 320).
 // ==============================================================================================================
-#ifndef DN_WG_EPI
-#define DN_WG_EPI 0
-#endif
-// cache policy of the weight-gradient kernel's streaming loads: non-temporal (read-once data; -DDN_WG_LOAD_POLICY_ID=0
-// plain / 2 sc1 are ablation hooks: 2.11 / 1.98 vs 1.92 ms for all layers at 786 k points)
-#if !defined(DN_WG_LOAD_POLICY_ID) || DN_WG_LOAD_POLICY_ID == 1
+// cache policy of the weight-gradient kernel's streaming loads: non-temporal (read-once data; plain / sc1 measured 2.11 / 1.98
+// vs 1.92 ms for all layers at 786 k points)
 #define DN_WG_LOAD_POLICY " nt"
-#elif DN_WG_LOAD_POLICY_ID == 0
-#define DN_WG_LOAD_POLICY ""
-#else
-#define DN_WG_LOAD_POLICY " sc1"
-#endif
 namespace dn {
 
 struct WgParams {
@@ -570,9 +556,6 @@ struct WgParams {
   int dy_odd;
   const unsigned* scale_word;     // bits of the scale the backward-data launch recorded behind the saved gradients (kS8BlockScale)
   unsigned* stats_block;          // that record: the 8-bit kernel counts saturated / floor-level gradient bytes into it (mlp_geo48.h)
-#ifdef DN_WG_STAMP
-  unsigned long long* stamp;      // diagnostic build: [workgroup][wave][8] accumulated s_memtime ticks
-#endif
 };
 
 constexpr int kWgLdsBytes = 144 * 1024;
@@ -624,7 +607,7 @@ struct WgShape {
   static constexpr int TPI = (K64 && TPI0 < 2) ? 2 : TPI0;
   static constexpr int STAGES = wg_stages_for(PIECES, TPI, S8, LDSB_); // tile buffers in LDS; STAGES - TPI tiles in flight
   static constexpr int PSTRIDE = S8 ? kPieceBytes : kWgPieceStride16;   // LDS distance of consecutive staged pieces
-  // Cycles one 32-point tile costs a workgroup of this shape in the 8-bit kernel, fitted to -DDN_WG_STAMP runs (profiles/r02_train_s8.md;
+  // Cycles one 32-point tile costs a workgroup of this shape in the 8-bit kernel, fitted to s_memtime stamps of the tile loop (profiles/r02_train_s8.md;
   // measured / model for the W = 256 shapes: (8,0,2) 678 / 746, (8,8,0) 1131 / 1134, (4,8,1) 940 / 1000, (1,8,0) 868 / 904, (8,8,2)
   // 2123 / 2138): wait + barrier, ~100 issue cycles per LDS-DMA of the busiest wave, and the MFMAs of the two waves of a SIMD - K = 64:
   // 64 cycles per accumulator tile and PAIR of tiles, but never less than the LDS round trips of a tile (~260); K = 16: 128 per tile.
@@ -731,9 +714,6 @@ __device__ __forceinline__ void weight_grad_unit(const WgParams& p, int wg, int 
       const unsigned go = __builtin_amdgcn_readfirstlane((wave + 8 * e < S::PIECES) ? 1u : 0u);
       const unsigned voff = lane16;  // (asm operands do not capture: name a local)
       unsigned keep;
-#ifdef DN_WG_NOSTAGE
-      asm volatile("" : [keep] "=s"(keep) : [go] "s"(go), [lds] "s"(lds), [voff] "v"(voff), [sbase] "s"(usrc) : "memory");
-#else
       asm volatile(
           "s_cmp_lg_u32 %[go], 0\n\t"
           "s_cbranch_scc0 .Ldn_wg_skip%=\n\t"
@@ -746,7 +726,6 @@ __device__ __forceinline__ void weight_grad_unit(const WgParams& p, int wg, int 
           : [keep] "=&s"(keep)
           : [go] "s"(go), [lds] "s"(lds), [voff] "v"(voff), [sbase] "s"(usrc)
           : "memory", "scc");
-#endif
     });
   };
   // this wave issues PER_WAVE or PER_WAVE-1 DMAs per tile; while TPI tiles are consumed, STAGES - 2*TPI younger tiles may
@@ -793,13 +772,9 @@ __device__ __forceinline__ void weight_grad_unit(const WgParams& p, int wg, int 
       if constexpr (S::KGROUPS == 1) {
         if constexpr (j == S::KT - 1) { b0 = ones; b1 = ones; }
         else {
-#ifndef DN_WG_NOREAD
           const char* pb = base + (S::N_DY + 2 * j) * PS;
           b0 = tr_frag(pb, 0);
           b1 = tr_frag(pb, 16);
-#else
-          b0 = ones; b1 = ones;
-#endif
         }
       } else {
         const int kt = kgroup + j * S::KGROUPS;           // wave-uniform; kt >= KT: an unused accumulator
@@ -872,12 +847,7 @@ __device__ __forceinline__ void weight_grad_unit(const WgParams& p, int wg, int 
 #pragma unroll
           for (int d = 0; d < 8; ++d) bv[d] = kOnes;
         } else {
-#ifndef DN_WG_NOREAD
           bv = read32(frag_at(j < S::XT ? S::N_DY : S::N_DY + S::N_X, j < S::XT ? j : j - S::XT));
-#else
-#pragma unroll
-          for (int d = 0; d < 8; ++d) bv[d] = kOnes;
-#endif
         }
       } else {
         const int kt = kgroup + j * S::KGROUPS;           // wave-uniform; kt >= KT: an unused accumulator
@@ -928,97 +898,41 @@ __device__ __forceinline__ void weight_grad_unit(const WgParams& p, int wg, int 
     long long tile = wg;
 #pragma unroll 1
     for (int st = 0; st + 1 < S::STAGES; ++st) stage(tile + static_cast<long long>(st) * n_wg, st);
-#ifdef DN_WG_STAMP
-    unsigned long long st_wait = 0, st_bar = 0, st_stage = 0, st_cons = 0, st_n = 0;
-    const unsigned long long st_begin = __builtin_amdgcn_s_memtime();
-#endif
 #pragma unroll 1
     for (; tile < tiles; tile += n_wg) {
-#ifdef DN_WG_STAMP
-      const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-#endif
       // this wave's DMAs of tile `tile` are done, and so are its LDS reads of the previous tile ...
       wait_tiles();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#ifdef DN_WG_STAMP
-      const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-#endif
       // ... after the barrier everyone's are: the tile is resident and the previous tile's buffer is free
       __builtin_amdgcn_s_barrier();
-#ifdef DN_WG_STAMP
-      const unsigned long long t2 = __builtin_amdgcn_s_memtime();
-#endif
       {
         int nb = buf + S::STAGES - 1;
         if (nb >= S::STAGES) nb -= S::STAGES;
         stage(tile + static_cast<long long>(S::STAGES - 1) * n_wg, nb);
       }
-#ifdef DN_WG_STAMP
-      const unsigned long long t3 = __builtin_amdgcn_s_memtime();
-#endif
       consume(tile, buf);
-#ifdef DN_WG_STAMP
-      __builtin_amdgcn_sched_barrier(0);
-      const unsigned long long t4 = __builtin_amdgcn_s_memtime();
-      st_wait += t1 - t0; st_bar += t2 - t1; st_stage += t3 - t2; st_cons += t4 - t3; st_n += 1;
-#endif
       buf = (buf + 1 == S::STAGES) ? 0 : buf + 1;
     }
-#ifdef DN_WG_STAMP
-    if (lane == 0 && p.stamp != nullptr) {
-      unsigned long long* o = p.stamp + (static_cast<long long>(blockIdx.x) * 8 + wave) * 8;
-      o[0] = st_wait; o[1] = st_bar; o[2] = st_stage; o[3] = st_cons; o[4] = st_n; o[5] = __builtin_amdgcn_s_memtime() - st_begin;
-      o[6] = static_cast<unsigned long long>(p.shape); o[7] = static_cast<unsigned long long>(S::J);
-    }
-#endif
   } else if constexpr (S::K64 && S::TPI == 2) {
     // one PAIR of tiles per barrier, K = 64 (the big 8-bit shapes: the same minimal loop as above, two tiles at a time)
     long long tile = wg;
 #pragma unroll 1
     for (int st = 0; st + 2 < S::STAGES; ++st) stage(tile + static_cast<long long>(st) * n_wg, st);
-#ifdef DN_WG_STAMP
-    unsigned long long st_wait = 0, st_bar = 0, st_stage = 0, st_cons = 0, st_n = 0;
-    const unsigned long long st_begin = __builtin_amdgcn_s_memtime();
-#endif
 #pragma unroll 1
     for (; tile < tiles; tile += 2LL * n_wg) {
-#ifdef DN_WG_STAMP
-      const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-#endif
       wait_tiles();   // this pair landed; STAGES - 4 younger tiles may be in flight
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#ifdef DN_WG_STAMP
-      const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-#endif
       __builtin_amdgcn_s_barrier();
-#ifdef DN_WG_STAMP
-      const unsigned long long t2 = __builtin_amdgcn_s_memtime();
-#endif
       int nb = buf + S::STAGES - 2;
       if (nb >= S::STAGES) nb -= S::STAGES;
       stage(tile + static_cast<long long>(S::STAGES - 2) * n_wg, nb);
       nb = (nb + 1 == S::STAGES) ? 0 : nb + 1;
       stage(tile + static_cast<long long>(S::STAGES - 1) * n_wg, nb);
       const int cb1 = (buf + 1 == S::STAGES) ? 0 : buf + 1;
-#ifdef DN_WG_STAMP
-      const unsigned long long t3 = __builtin_amdgcn_s_memtime();
-#endif
       consume_pair_s8(tile, buf, tile + n_wg, cb1);
-#ifdef DN_WG_STAMP
-      __builtin_amdgcn_sched_barrier(0);
-      const unsigned long long t4 = __builtin_amdgcn_s_memtime();
-      st_wait += t1 - t0; st_bar += t2 - t1; st_stage += t3 - t2; st_cons += t4 - t3; st_n += 2;   // (per TILE: two per iteration)
-#endif
       buf += 2;
       if (buf >= S::STAGES) buf -= S::STAGES;
     }
-#ifdef DN_WG_STAMP
-    if (lane == 0 && p.stamp != nullptr) {
-      unsigned long long* o = p.stamp + (static_cast<long long>(blockIdx.x) * 8 + wave) * 8;
-      o[0] = st_wait; o[1] = st_bar; o[2] = st_stage; o[3] = st_cons; o[4] = st_n; o[5] = __builtin_amdgcn_s_memtime() - st_begin;
-      o[6] = static_cast<unsigned long long>(p.shape); o[7] = static_cast<unsigned long long>(S::J);
-    }
-#endif
   } else {
     // TPI tiles per barrier (small shapes: a tile is a few MFMAs per wave, the barrier + wait + LDS latency dominate)
     auto tile_of = [&](long long k) { return wg + k * n_wg; };
@@ -1153,12 +1067,8 @@ __device__ __forceinline__ void weight_grad_unit(const WgParams& p, int wg, int 
       const int qq = (q + q0 >= ROW_GROUPS) ? q + q0 - ROW_GROUPS : q + q0;
       const int n = wave + 8 * qq;
       if (n < n_rows && lane < n_cols) {
-#if DN_WG_EPI == 1
-        if (img[n * IMG_LD + lane] == 1.2345f) p.dW[static_cast<long long>(n) * p.ldw + col0 + lane] = 1.0f;
-#else
         if (p.part != nullptr) part_w[static_cast<long long>(n) * p.ldw + col0 + lane] = img[n * IMG_LD + lane];   // 256 contiguous bytes of this workgroup's partial
         else atomicAdd(p.dW + static_cast<long long>(n) * p.ldw + col0 + lane, img[n * IMG_LD + lane]);
-#endif
       }
     }
   };
@@ -1199,10 +1109,8 @@ __device__ __forceinline__ void weight_grad_unit(const WgParams& p, int wg, int 
     __syncthreads();
     const int n = 64 * wave + lane;
     if (n < n_rows) {
-#if DN_WG_EPI != 1
       if (p.part != nullptr) part_w[static_cast<long long>(p.n_real) * p.ldw + n] = img[n * IMG_LD];
       else atomicAdd(p.db + n, img[n * IMG_LD]);
-#endif
     }
   }
 }
@@ -1408,11 +1316,7 @@ static int wg_shape_lds(int shape) {
 
 __device__ __forceinline__ void weight_grad_dispatch(const WgParams& p, int wg, int n_wg, char* smem) {
   switch (p.shape) {  // workgroup-uniform
-#ifdef DN_WG_ONLY   // developer hook: compile a single shape (register-pressure bisection)
-#define X(id, a, b, c, d) case id: if constexpr (id == DN_WG_ONLY) weight_grad_unit<WgShape<a, b, c, d>>(p, wg, n_wg, smem); break;
-#else
 #define X(id, a, b, c, d) case id: weight_grad_unit<WgShape<a, b, c, d>>(p, wg, n_wg, smem); break;
-#endif
     DN_WG_SHAPES(X)
 #undef X
     default: break;
@@ -1678,7 +1582,7 @@ static int wg_launch_batch(WgBatch& b, const long long* unit_tiles, bool f32, bo
   // launches are bound by the wait / barrier / LDS round trip of a tile, which the second resident workgroup hides.  (Round 3 tried
   // this with the atomics reduction and dropped it - the tile loop got 13-26 us shorter, the reduction of twice as many partials
   // 50 us longer, HISTORY.md section 4.7c; with partial slabs and the fixed-order second launch the reduction no longer grows that way.)
-  bool small = s8 && !f32 && std::getenv("DEXNERF_WG_ONE_PER_CU") == nullptr;
+  bool small = s8 && !f32;
   for (int i = 0; i < n_units; ++i) small = small && b.u[i].shape >= kWgFirstSmallShape;
   int total_wg = device_cus() * (small ? 2 : 1);
   if (total_wg < n_units) total_wg = n_units;
@@ -1723,13 +1627,6 @@ static int wg_launch_batch(WgBatch& b, const long long* unit_tiles, bool f32, bo
     two_phase = true;
   }
   if ((rc = f32 ? wg_attr(weight_grad_batch_kernel_f32) : (small ? wg_attr(weight_grad_batch_kernel_s8_small) : (s8 ? wg_attr(weight_grad_batch_kernel_s8) : wg_attr(weight_grad_batch_kernel))))) return rc;
-#ifdef DN_WG_STAMP   // diagnostic build: synchronous, allocates, prints - never part of the shipped library
-  static unsigned long long* stamp_buf = nullptr;
-  const size_t stamp_words = static_cast<size_t>(b.wg_begin[n_units]) * 8 * 8;
-  if (!stamp_buf) (void)hipMalloc(&stamp_buf, 1024 * 8 * 8 * sizeof(unsigned long long));
-  (void)hipMemsetAsync(stamp_buf, 0, stamp_words * sizeof(unsigned long long), as_stream(stream));
-  for (int i = 0; i < n_units; ++i) b.u[i].stamp = stamp_buf;
-#endif
   if (small)
     hipLaunchKernelGGL(weight_grad_batch_kernel_s8_small, dim3(static_cast<unsigned>(b.wg_begin[n_units])), dim3(512), kWgLdsBytesSmall,
                        as_stream(stream), b);
@@ -1742,26 +1639,6 @@ static int wg_launch_batch(WgBatch& b, const long long* unit_tiles, bool f32, bo
   else
     hipLaunchKernelGGL(weight_grad_batch_kernel, dim3(static_cast<unsigned>(b.wg_begin[n_units])), dim3(512), kWgLdsBytes16,
                        as_stream(stream), b);
-#ifdef DN_WG_STAMP
-  {
-    (void)hipStreamSynchronize(as_stream(stream));
-    std::vector<unsigned long long> h(stamp_words);
-    (void)hipMemcpy(h.data(), stamp_buf, stamp_words * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    for (int i = 0; i < n_units; ++i) {
-      double a[6] = {}; int waves = 0; double shape = -1, jj = 0;
-      for (int wgi = b.wg_begin[i]; wgi < b.wg_begin[i + 1]; ++wgi)
-        for (int w = 0; w < 8; ++w) {
-          const unsigned long long* o = &h[(static_cast<size_t>(wgi) * 8 + w) * 8];
-          if (o[4] == 0) continue;
-          for (int k = 0; k < 6; ++k) a[k] += static_cast<double>(o[k]);
-          shape = static_cast<double>(o[6]); jj = static_cast<double>(o[7]); ++waves;
-        }
-      if (waves)
-        fprintf(stderr, "[wg-stamp] unit %2d shape %2.0f J %2.0f, %3d workgroups: per tile: wait %.0f, barrier %.0f, stage %.0f, consume %.0f ticks; %.0f tiles per wave, loop %.0f ticks per wave\n",
-                i, shape, jj, b.wg_begin[i + 1] - b.wg_begin[i], a[0] / a[4], a[1] / a[4], a[2] / a[4], a[3] / a[4], a[4] / waves, a[5] / waves);
-    }
-  }
-#endif
   if ((rc = check_launch("dn_mlp_weight_grad_all"))) return rc;
   if (two_phase) {
     hipLaunchKernelGGL(wg_reduce_kernel, dim3(48, static_cast<unsigned>(n_units)), dim3(256), 0, as_stream(stream), b);

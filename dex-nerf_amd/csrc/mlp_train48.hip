@@ -144,17 +144,12 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_backward48_kernel(Bwd48
   if (n_masks > 1) issue_mask(blockIdx.x, 1);
 #pragma unroll
   for (int ph = 0; ph < kRingPhases - 1; ++ph) pipe.issue_phase();
-  if constexpr (kG48LeaderDma && kG48AsmReads) {   // phases 0 and 1 landed is all the first barrier period needs (mlp_stage48.h g48_prologue_wait)
-    g48_prologue_wait(wave);
-    __builtin_amdgcn_s_barrier();
-  } else {
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
+  g48_prologue_wait(wave);   // phases 0 and 1 landed is all the first barrier period needs (mlp_stage48.h g48_prologue_wait)
+  __builtin_amdgcn_s_barrier();
   pipe.slot_nxt = 0;
   pipe.rda_cur = pipe.ring_addr + lane * 16;
   pipe.slot_cur_base = pipe.ring_addr;       // phase 0 lives in slot 0: phase_begin() of phase 0 turns this into rda_cur
-  static_for<kPrefetch>([&](auto e_c) { pipe.template prologue_read<decltype(e_c)::value>(); });
+  static_for<PipeGeo48::PREFETCH>([&](auto e_c) { pipe.template prologue_read<decltype(e_c)::value>(); });
 
   int g_slot = 0;
   for (int tile = blockIdx.x; tile < p.n_tiles; tile += gridDim.x) {
@@ -485,24 +480,15 @@ int launch_backward48(const dn_mlp_desc& d, Bwd48Params p, hipStream_t stream) {
   if (g48_two_group_shape(d) && g48_train_groups(p.n_points, cus) == 2) {
     p.n_tiles = static_cast<int>((p.n_points + 255) / 256);
     grid = p.n_tiles < cus ? p.n_tiles : cus;
-#ifndef DN_T48_ONLY128
     if (d.hidden_size == 256) return launch(mlp_backward48_kernel<256, 8, 1, 2>);
-#endif
     return launch(mlp_backward48_kernel<128, 4, 1, 2>);
   }
   const bool paper = d.hidden_size == 256 && d.num_layers == 8 && d.use_viewdirs;
   const bool shipped = d.hidden_size == 128 && d.num_layers == 4 && d.use_viewdirs;
   const bool fixed_ok = std::getenv("DEXNERF_G48_RUNTIME_SHAPE") == nullptr;
-#ifndef DN_T48_ONLY128
   if (paper && fixed_ok) return launch(mlp_backward48_kernel<256, 8, 1>);
-#endif
   if (shipped && fixed_ok) return launch(mlp_backward48_kernel<128, 4, 1>);
-#ifdef DN_T48_FIXED_ONLY   // developer hook: skip the run-time-shape instances (compile time)
-  set_error("mlp_backward48: built with the fixed-shape instances only");
-  return DN_E_UNSUPPORTED;
-#else
   return d.hidden_size == 256 ? launch(mlp_backward48_kernel<256>) : launch(mlp_backward48_kernel<128>);
-#endif
 }
 
 }  // namespace dn

@@ -4,11 +4,8 @@ Inference: one fused kernel (positional encoding + MLP).  Training, for the nets
 (W in {128, 256}, L_xyz in {6, 10}): `FusedNetFn` - a fused forward that keeps every stage's output and ReLU masks in a
 wave-native layout, and a fused backward-data chain on the transposed weight stream (dn_mlp_backward_data);
 the weight/bias gradients come from one weight-gradient kernel launch per network on the saved native buffers
-(bf16 MFMA, or exact-fp32 MFMA in the parity mode; DEXNERF_FP32_DW=gemm selects the older fp32 route: unpack to plain rows
-+ library GEMMs).  Other configurations
-differentiate the nn.Linear composition directly."""
-import os
-
+(bf16 MFMA, or exact-fp32 MFMA in the parity mode).  Other configurations differentiate the nn.Linear composition
+directly."""
 import torch
 
 from . import _hip, _ops
@@ -83,61 +80,19 @@ class FusedNetFn(torch.autograd.Function):
         act, masks = ctx.saved_tensors
         g_out = g_out.contiguous().float()
         grads = _ops.mlp_backward_data(pk, g_out, masks, n, prec=ctx.prec)
-        slots, gslots, kh = _slots(model, pk.precision)
-        w, d, dev = model.hidden_size, model.num_layers, g_out.device
-
-        def rows(width):
-            return torch.empty((n, width), dtype=torch.float32, device=dev)
-
-        def act_hidden(slot, width, out=None, col0=0):
-            out = rows(width) if out is None else out
-            return _ops.mlp_unpack(pk, 0, act, n, slot, width, 0, out, col0)
-
-        def grad_hidden(slot, width):
-            return _ops.mlp_unpack(pk, 1, grads, n, slot, width, 0, rows(width))
-
-        results = {}
-
-        def put(mod, dy, x):
-            results[mod] = (dy.t() @ x, dy.sum(0))
-
-        if pk.precision == _hip.PREC_BF16 or os.environ.get("DEXNERF_FP32_DW", "kernel") != "gemm":
-            # every layer's weight/bias gradient straight from the native buffers, one launch (MFMA kernel, fp32 atomics)
-            mods = model.linear_modules()
-            views = ctx.sink.views(model) if ctx.sink is not None else None
-            if views is not None:
-                # the parameters' `.grad` are views of a FlatGradBucket: accumulate straight into them (nothing goes back
-                # through autograd's accumulation), then let the bucket start this network's all-reduce
-                _ops.mlp_weight_grad_all_into(pk, act, grads, n, views, prec=ctx.prec)
-                ctx.sink.backward_done()
-                return (None,) * (6 + 2 * len(mods))
-            res = _ops.mlp_weight_grad_all(pk, act, grads, n, [tuple(m.weight.shape) for m in mods], prec=ctx.prec)
-            flat = []
-            for d_w, d_b in res:
-                flat.extend((d_w, d_b))
-            return (None, None, None, None, None, None) + tuple(flat)
-
-        pe_xyz = _ops.mlp_unpack(pk, 0, act, n, slots["xyz"], model.dim_xyz, 1, rows(model.dim_xyz))
-        put(model.layer1, grad_hidden(gslots["layer1"], w), pe_xyz)
-        x_prev = act_hidden(slots["layer1"], w)
-        for i, layer in enumerate(model.layers_xyz):
-            dy = grad_hidden(gslots["trunk0"] + i * kh, w)
-            x = torch.cat((x_prev, pe_xyz), dim=-1) if i in model.skip_layers else x_prev
-            put(layer, dy, x)
-            x_prev = act_hidden(slots["trunk0"] + i * kh, w)
-        if model.use_viewdirs:
-            put(model.fc_feat, grad_hidden(gslots["feat"], w), x_prev)
-            put(model.fc_alpha, g_out[:, 3:4], x_prev)
-            x_dir = rows(w + model.dim_dir)
-            act_hidden(slots["feat"], w, x_dir, 0)
-            _ops.mlp_unpack(pk, 0, act, n, slots["dir"], model.dim_dir, 2, x_dir, w)
-            put(model.layers_dir[0], grad_hidden(gslots["dirout"], w // 2), x_dir)
-            put(model.fc_rgb, g_out[:, :3], act_hidden(slots["dirout"], w // 2))
-        else:
-            put(model.fc_out, g_out, x_prev)
+        # every layer's weight/bias gradient straight from the native buffers, one launch (MFMA kernel, fp32 atomics)
+        mods = model.linear_modules()
+        views = ctx.sink.views(model) if ctx.sink is not None else None
+        if views is not None:
+            # the parameters' `.grad` are views of a FlatGradBucket: accumulate straight into them (nothing goes back
+            # through autograd's accumulation), then let the bucket start this network's all-reduce
+            _ops.mlp_weight_grad_all_into(pk, act, grads, n, views, prec=ctx.prec)
+            ctx.sink.backward_done()
+            return (None,) * (6 + 2 * len(mods))
+        res = _ops.mlp_weight_grad_all(pk, act, grads, n, [tuple(m.weight.shape) for m in mods], prec=ctx.prec)
         flat = []
-        for m in model.linear_modules():
-            flat.extend(results[m])
+        for d_w, d_b in res:
+            flat.extend((d_w, d_b))
         return (None, None, None, None, None, None) + tuple(flat)
 
 

@@ -18,16 +18,11 @@ No autograd graph, no ATen elementwise / reduction / RNG launches (profiles/r03_
 a parallel.FlatGradBucket (the `.grad` tensors of the parameters).  GraphedTrainStep replays the iteration as HIP graphs (three
 around the exchange when world > 1).  The explicit-draw path (predict_and_render_radiance under autograd, draws as tensors) stays
 what the parity tests drive."""
-import os
-
 import torch
 
 from . import _ops
 from ._train import train_fused_ok
 from .train_utils import _fusable
-
-
-_SPLIT_BACKWARD = os.environ.get("DEXNERF_SPLIT_BACKWARD", "") == "1"   # developer switch (A/B timing): the two networks' backward as two calls even with one rank
 
 
 class FusedTrainStep:
@@ -73,7 +68,7 @@ class FusedTrainStep:
         mc._grad_sink.forward_issued(); mf._grad_sink.forward_issued()
         if self.zero_in_step:
             self.bucket.zero()
-        if world_info()[1] == 1 and not _SPLIT_BACKWARD:
+        if world_info()[1] == 1:
             self.forward_and_fine_backward(_zero=False, both=True)    # one rank: nothing to overlap, one weight-gradient launch for both networks
             mf._grad_sink.backward_done(); mc._grad_sink.backward_done()
             return self.loss3
@@ -156,9 +151,7 @@ class GraphedTrainStep:
         if world == 1:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, **mode):
-                self.fused.forward_and_fine_backward(both=not _SPLIT_BACKWARD)
-                if _SPLIT_BACKWARD:
-                    self.fused.coarse_backward()
+                self.fused.forward_and_fine_backward(both=True)
                 self.opt.step()
             return [g]
         ga, gb, gc = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()

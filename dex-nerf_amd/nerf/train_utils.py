@@ -279,8 +279,7 @@ def run_one_iter_of_nerf(height, width, focal_length, model_coarse, model_fine, 
     thres = _thresholds(m_thres_cand)
     # device rays that need no gradient: the rows are packed by one kernel (dn_pack_ray_rows), op for op what follows
     one_launch = (ray_directions.is_cuda and ray_origins.is_cuda and ray_directions.dtype == torch.float32
-                  and ray_origins.dtype == torch.float32 and not ray_directions.requires_grad and not ray_origins.requires_grad
-                  and os.environ.get("DEXNERF_TORCH_RAY_ROWS", "") != "1")   # (developer switch: the torch composition, for A/B timing)
+                  and ray_origins.dtype == torch.float32 and not ray_directions.requires_grad and not ray_origins.requires_grad)
     viewdirs = None
     if options.nerf.use_viewdirs and not one_launch:
         viewdirs = ray_directions / ray_directions.norm(p=2, dim=-1).unsqueeze(-1)

@@ -44,7 +44,7 @@ __global__ __launch_bounds__(512, 2) void geo_kernel(const char* wstream, int pa
   pipe.rd_cur = ring + lane * 16;
   pipe.rd_nxt = ring + lane * 16;
 #pragma unroll
-  for (int e = 0; e < kPrefetch; ++e) pipe.af[e] = *reinterpret_cast<const f32x4*>(pipe.rd_nxt + e * kPieceBytes);
+  for (int e = 0; e < PipeGeo32::PREFETCH; ++e) pipe.af[e] = *reinterpret_cast<const f32x4*>(pipe.rd_nxt + e * kPieceBytes);
 
   float check = 0.0f;
   if constexpr (MODE == 0) {
@@ -95,7 +95,7 @@ __global__ __launch_bounds__(512, 2) void geo_kernel(const char* wstream, int pa
           constexpr int pos = nt * KH + k;
           if constexpr (pos % kPhasePieces == 0) pipe.phase_begin();
           if constexpr (pos % kPhasePieces == kPhasePieces / 2) pipe.mid_phase();
-          const bf16x8 a = __builtin_bit_cast(bf16x8, pipe.af[pos % kPrefetch]);
+          const bf16x8 a = __builtin_bit_cast(bf16x8, pipe.af[pos % PipeGeo32::PREFETCH]);
           static_for<PT>([&](auto t_c) {
             constexpr int t = decltype(t_c)::value;
             acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bin[t][k], acc[t], 0, 0, 0);
