@@ -15,8 +15,9 @@
 //     materialises a (P,90) tensor and recomputes the direction encoding per sample);
 //   * bf16 / fp16 modes: v_mfma_f32_32x32x16_{bf16,f16}, 8 waves x 32 points per workgroup, 2 waves / SIMD;
 //     fp32 mode: v_mfma_f32_32x32x2_f32 (exact fp32 FMA chains), 4 waves x 32 points, 1 wave / SIMD.
-// MFMA-bound: 1,186,816 FLOP per point (D8/W256) against 16 B written per point.  SAVE = the training forward: the same
-// chain also streams every stage's output pieces (non-temporal, scalar-base stores) and ReLU mask words to HBM.
+// MFMA-bound: 1,186,816 FLOP per point (D8/W256) against 16 B written per point.  SAVE = 1 is the bf16 / fp32 training forward:
+// the same chain also streams every stage's output pieces (non-temporal, scalar-base stores) and ReLU mask words to HBM.  (The
+// training forward with 8-bit saved tensors is a 48-point kernel: mlp_fused48*.hip.)
 #include "mlp_device.h"
 #include "mlp_internal.h"
 #include "mlp_geo48.h"
@@ -25,7 +26,7 @@ namespace dn {
 
 // SAVE = training forward: every stage's output pieces (and both encodings) are also written to `p.act` in the
 // wave-native piece layout, plus one 128-bit ReLU mask word per lane per masked stage to `p.masks`.
-template <int W, int LX, int LD, int BF16, int PT, int SAVE>   // SAVE: 0 inference, 1 training forward (bf16 / fp32 pieces), 2 training forward with 8-bit saved pieces
+template <int W, int LX, int LD, int BF16, int PT, int SAVE>   // SAVE: 0 inference, 1 training forward (bf16 / fp32 pieces)
 __global__ __launch_bounds__((waves_of<BF16, PT>() * 64), ((BF16 && PT == 1) ? 2 : 1)) void mlp_forward_kernel(FwdParams p) {
   using P = Prec<BF16>;
   using BPiece = typename P::BPiece;
@@ -186,23 +187,10 @@ __global__ __launch_bounds__((waves_of<BF16, PT>() * 64), ((BF16 && PT == 1) ? 2
     auto save_piece = [&](int t, int slot, const BPiece& v) {
       store16_uniform(act_tile[t] + static_cast<long long>(slot) * kPieceBytes, pipe.lane16, v);
     };
-    // SAVE == 2: pieces `slot` (even) and `slot + 1` as ONE 1 KiB unit of 8 + 8 bytes per lane (e4m3)
-    auto save_pair = [&](int t, int slot, const BPiece& lo, const BPiece& hi) {
-      if constexpr (SAVE == 2 && BF16 == 1) {
-        unsigned w[4];
-        piece_to_8bit<false>(lo, 1.0f, w[0], w[1]);
-        piece_to_8bit<false>(hi, 1.0f, w[2], w[3]);
-        store16_uniform(act_tile[t] + static_cast<long long>(slot >> 1) * kPieceBytes, pipe.lane16, make_uint4(w[0], w[1], w[2], w[3]));
-      }
-    };
     // (the piece arrays are passed by reference to their array type and indexed with compile-time constants only: a
     // decayed pointer sends the whole register-resident activation set to scratch memory in the fp32 instances)
     auto save_pieces = [&](auto nt_c, int t, int slot0, const auto& pieces) {
-      if constexpr (SAVE == 2) {
-        constexpr int nt = decltype(nt_c)::value;
-        static_assert(P::PPT == 2, "8-bit saved tensors pair the two pieces of a 32-row tile");
-        save_pair(t, slot0 + nt * 2, pieces[nt * 2], pieces[nt * 2 + 1]);
-      } else if constexpr (SAVE) {
+      if constexpr (SAVE) {
         constexpr int nt = decltype(nt_c)::value;
         static_for<P::PPT>([&](auto s_c) {
           constexpr int s2 = decltype(s_c)::value;
@@ -250,24 +238,12 @@ __global__ __launch_bounds__((waves_of<BF16, PT>() * 64), ((BF16 && PT == 1) ? 2
     if constexpr (SAVE) {
 #pragma unroll
       for (int t = 0; t < PT; ++t) {
-        if constexpr (SAVE == 2) {
-          static_assert(KXP % 2 == 0 && KDP % 2 == 0, "encoding panels are whole units");
-#pragma unroll
-          for (int k = 0; k < KXP; k += 2) save_pair(t, p.slot_xyz + k, pe_xyz(t, k), pe_xyz(t, k + 1));
-          if (p.use_viewdirs) {
-#pragma unroll
-            for (int k = 0; k < KDP; k += 2)
-              save_pair(t, p.slot_dir + k, *reinterpret_cast<const BPiece*>(ped + (t * KDP + k) * kPieceBytes),
-                        *reinterpret_cast<const BPiece*>(ped + (t * KDP + k + 1) * kPieceBytes));
-          }
-        } else {
 #pragma unroll
         for (int k = 0; k < KXP; ++k) save_piece(t, p.slot_xyz + k, pe_xyz(t, k));
         if (p.use_viewdirs) {
 #pragma unroll
           for (int k = 0; k < KDP; ++k)
             save_piece(t, p.slot_dir + k, *reinterpret_cast<const BPiece*>(ped + (t * KDP + k) * kPieceBytes));
-        }
         }
       }
     }
@@ -496,7 +472,7 @@ int dispatch_forward(const dn_mlp_desc& d, int precision, FwdParams& p, hipStrea
   if ((bf || hf) && geom48 && p.act == nullptr && p.mode != 2 && p.n_points < (1LL << 31) - 1024 && g48_supported(d, precision))
     return launch_forward48(d, precision, p, p.packed + p.bias_bytes + static_cast<size_t>(p.total_pieces) * kPieceBytes, stream, comp, composited);
   if (p.act != nullptr && hf) { set_error("mlp_forward(train): fp16 is a render-only mode"); return DN_E_UNSUPPORTED; }
-  if (p.act != nullptr && p.save8) {   // training forward with 8-bit saved units: the 48-point geometry (mlp_fused48.hip, SAVE = 2)
+  if (p.act != nullptr && p.save8) {   // training forward with 8-bit saved units: a kernel of the 48-point geometry (mlp_fused48.hip)
     if (!bf || p.mode == 2 || !g48_train_supported(d) || p.n_points >= (1LL << 31) - 1024) {
       set_error("mlp_forward(train, 8-bit saved tensors): bf16 arithmetic, rays / points input, W in {128, 256}, L_xyz in {6, 10}, a depth the 48-point kernel holds in LDS");
       return DN_E_UNSUPPORTED;

@@ -1,4 +1,5 @@
-// Host-side helpers shared between mlp_fused.hip (inference + packing) and mlp_train.hip (training kernels).
+// Host-side helpers shared between mlp_fused.hip (inference + packing), mlp_train.hip (training forward / backward-data entry
+// points) and mlp_wgrad.hip (weight gradients).
 #pragma once
 #include "mlp_device.h"
 

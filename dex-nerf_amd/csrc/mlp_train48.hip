@@ -9,7 +9,7 @@
 // kernel (mlp_stage48.h).  The ReLU mask words come from the 48-point forward lane for lane: accumulator register r of tile nt
 // of a backward stage is the same (feature, point) as in the forward stage whose output it differentiates, so no bit
 // transpose is needed (mlp_geo48.h).  Every masked dL/d(pre-activation) is stored once, as e5m2 of (gradient x scale), in the
-// s8-48 unit layout the weight-gradient kernel contracts (mlp_train.hip).
+// s8-48 unit layout the weight-gradient kernel contracts (mlp_wgrad.hip).
 #include "mlp_stage48.h"
 
 namespace dn {
