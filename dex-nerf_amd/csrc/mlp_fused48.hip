@@ -11,23 +11,12 @@
 
 namespace dn {
 
-// the explicit-schedule instances of the paper network are compiled in mlp_fused48_paper_{bf16,fp16}.hip, the W = 128 instances in
-// mlp_fused48_w128.hip (same lists there): the instance list builds as four translation units in parallel
-extern template __global__ void mlp_forward48_kernel<256, 1, 8, 0x10u, 1, 0, 2>(FwdParams, G48Params);
-extern template __global__ void mlp_forward48_kernel<256, 1, 8, 0x10u, 1>(FwdParams, G48Params);
-extern template __global__ void mlp_forward48_kernel<256, 2, 8, 0x10u, 1, 0, 2>(FwdParams, G48Params);
-extern template __global__ void mlp_forward48_kernel<256, 2, 8, 0x10u, 1>(FwdParams, G48Params);
-extern template __global__ void mlp_forward48_kernel<128, 1>(FwdParams, G48Params);
-extern template __global__ void mlp_forward48_kernel<128, 2>(FwdParams, G48Params);
-extern template __global__ void mlp_forward48_kernel<128, 1, 4, 0u, 1>(FwdParams, G48Params);
-extern template __global__ void mlp_forward48_kernel<128, 2, 4, 0u, 1>(FwdParams, G48Params);
-extern template __global__ void mlp_forward48_kernel<128, 1, 4, 0u, 1, 0, 1>(FwdParams, G48Params);
-extern template __global__ void mlp_forward48_kernel<128, 2, 4, 0u, 1, 0, 1>(FwdParams, G48Params);
-extern template __global__ void mlp_forward48_kernel<128, 1, 4, 0u, 1, 0, 0, 1>(FwdParams, G48Params);
-extern template __global__ void mlp_forward48_kernel<128, 2, 4, 0u, 1, 0, 0, 1>(FwdParams, G48Params);
-extern template __global__ void mlp_forward48_kernel<128, 1, 4, 0u, 1, 2>(FwdParams, G48Params);
-extern template __global__ void mlp_forward48_kernel<128, 1, 4, 0u, 1, 3>(FwdParams, G48Params);
-extern template __global__ void mlp_forward48_kernel<128, 1, 0, 0u, 0, 2>(FwdParams, G48Params);
+// the instance list (mlp_fused48_kernel.h) builds as four translation units in parallel: this one compiles its own rows and only
+// declares the others
+DN_FWD48_PAPER_BF16(DN_FWD48_EXTERN)
+DN_FWD48_PAPER_FP16(DN_FWD48_EXTERN)
+DN_FWD48_W128(DN_FWD48_EXTERN)
+DN_FWD48_HOST_UNIT(DN_FWD48_INSTANTIATE)
 
 // ---- pack: nn.Linear tensors -> bias rows + encoding tables + 16x32 A pieces -----------------------------------
 template <int F>

@@ -1,6 +1,6 @@
-// The 48-points-per-wave forward kernel (template): included by the translation units that instantiate it - mlp_fused48.hip (the
-// W = 256 instances and the host side) and mlp_fused48_w128.hip (the W = 128 instances) - so the two halves of the instance list
-// compile in parallel.  Design notes: the comment at the top of mlp_fused48.hip.
+// The 48-points-per-wave forward kernel (template) and, below it, the one list of its instances: included by the translation units
+// that instantiate their rows of it - mlp_fused48_{paper_bf16,paper_fp16,w128}.hip and mlp_fused48.hip (the remaining W = 256
+// instances and the host side) - so the instance list compiles in parallel.  Design notes: the comment at the top of mlp_fused48.hip.
 #pragma once
 #include "mlp_stage48.h"
 
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
                  wave * (IN_ROWS * PPW);   // wave-uniform
   static_assert(OVL || IN_ROWS == kG48InRows, "g48_lds_bytes sizes the input rows");
 
-  // inputs of a tile by 4-byte LDS-DMA: lane l < 48 stages point l of this wave (mlp_fused.hip issue_inputs)
+  // inputs of a tile by 4-byte LDS-DMA: lane l < 48 stages point l of this wave (mlp_fused_kernel.h issue_inputs)
   // 32-bit point indices throughout (the dispatcher sends launches of >= 2^31 - 1024 points to the 32-point kernel): the
   // 64-bit forms cost a loop-invariant VGPR pair (spilled) and a 64-bit division per lane per tile
   const int n_points = static_cast<int>(p.n_points);
@@ -801,5 +801,27 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
     if (p.range_flag != nullptr && __ballot(out_of_range) != 0ull && (threadIdx.x & 63) == 0) atomicAdd(p.range_flag, 1u);
   }
 }
+
+// ---- the instances: one row each, X(W, F, DC, MASKC, VIEWC, SAVE, OVLP, COMP), all eight template arguments --------------------
+// One sub-list per translation unit; DN_FWD48_INSTANCES is the whole family.  mlp_fused48.hip launch_forward48 picks among them.
+#define DN_FWD48_PAPER_BF16(X) /* mlp_fused48_paper_bf16.hip: the explicit-schedule bf16 instances of the paper network */ \
+  X(256, 1, 8, 0x10u, 1, 0, 2, 0) X(256, 1, 8, 0x10u, 1, 0, 0, 0)
+#define DN_FWD48_PAPER_FP16(X) /* mlp_fused48_paper_fp16.hip: the same in fp16 */ \
+  X(256, 2, 8, 0x10u, 1, 0, 2, 0) X(256, 2, 8, 0x10u, 1, 0, 0, 0)
+#define DN_FWD48_W128(X) /* mlp_fused48_w128.hip: every W = 128 instance */ \
+  X(128, 1, 0, 0u, 0, 0, 0, 0) X(128, 2, 0, 0u, 0, 0, 0, 0) /* run-time shape */ \
+  X(128, 1, 4, 0u, 1, 0, 0, 0) X(128, 2, 4, 0u, 1, 0, 0, 0) /* as-shipped 4 x 128 */ \
+  X(128, 1, 4, 0u, 1, 0, 1, 0) X(128, 2, 4, 0u, 1, 0, 1, 0) /* ... encoding tile t + 1 inside tile t */ \
+  X(128, 1, 4, 0u, 1, 0, 0, 1) X(128, 2, 4, 0u, 1, 0, 0, 1) /* ... compositing in the kernel */ \
+  X(128, 1, 4, 0u, 1, 2, 0, 0) X(128, 1, 4, 0u, 1, 3, 0, 0) X(128, 1, 0, 0u, 0, 2, 0, 0) /* training forward */
+#define DN_FWD48_HOST_UNIT(X) /* mlp_fused48.hip: the remaining W = 256 instances */ \
+  X(256, 1, 0, 0u, 0, 0, 0, 0) X(256, 2, 0, 0u, 0, 0, 0, 0)       /* run-time shape */ \
+  X(256, 1, 8, 0x10u, 1, 0, 0, 1) X(256, 2, 8, 0x10u, 1, 0, 0, 1) /* paper network, compositing in the kernel */ \
+  X(256, 1, 8, 0x10u, 1, 2, 0, 0) X(256, 1, 8, 0x10u, 1, 3, 0, 0) X(256, 1, 0, 0u, 0, 2, 0, 0) /* training forward */
+#define DN_FWD48_INSTANCES(X) DN_FWD48_PAPER_BF16(X) DN_FWD48_PAPER_FP16(X) DN_FWD48_W128(X) DN_FWD48_HOST_UNIT(X)
+
+#define DN_FWD48_INSTANTIATE(W, F, DC, MASKC, VIEWC, SAVE, OVLP, COMP) \
+  template __global__ void mlp_forward48_kernel<W, F, DC, MASKC, VIEWC, SAVE, OVLP, COMP>(FwdParams, G48Params);
+#define DN_FWD48_EXTERN(W, F, DC, MASKC, VIEWC, SAVE, OVLP, COMP) extern DN_FWD48_INSTANTIATE(W, F, DC, MASKC, VIEWC, SAVE, OVLP, COMP)
 
 }  // namespace dn

@@ -1,5 +1,6 @@
-// Host-side helpers shared between mlp_fused.hip (inference + packing), mlp_train.hip (training forward / backward-data entry
-// points) and mlp_wgrad.hip (weight gradients).
+// Host-side helpers shared between mlp_fused.hip (packing, forward dispatch, inference entry points; the forward kernel itself is
+// mlp_fused_kernel.h, compiled in mlp_fused_*.hip), mlp_train.hip (training forward / backward-data entry points) and mlp_wgrad.hip
+// (weight gradients).
 #pragma once
 #include "mlp_device.h"
 

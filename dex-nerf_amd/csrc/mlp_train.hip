@@ -1,6 +1,6 @@
 // Training kernels of the fused network path: the backward-data (dL/dX) chain and the native->plain unpack.
 //
-// The training forward is mlp_forward_kernel<..., SAVE=true> (mlp_fused.hip): it keeps every stage's output
+// The training forward is mlp_forward_kernel<..., SAVE=true> (mlp_fused_kernel.h): it keeps every stage's output
 // pieces and a 128-bit ReLU mask word per lane per stage.  The backward chain below is the same register-resident
 // MFMA chain run on the TRANSPOSED weight stream: for 32 points per wave,
 //     dX^T[K x 32] = W^T[K x N] . dY^T[N x 32],   dY = dX_next (.) relu'(Y)

@@ -1,5 +1,5 @@
 // Weight / bias gradient kernels of the training path (all precisions), the two-phase deterministic reduction and their entry
-// points.  They read the saved activations and the masked gradients that the training forward (mlp_fused.hip, mlp_fused48*.hip) and
+// points.  They read the saved activations and the masked gradients that the training forward (mlp_fused_kernel.h, mlp_fused48_kernel.h) and
 // the backward-data chains (mlp_train.hip, mlp_train48.hip) wrote in the wave-native piece layouts.
 #include "mlp_internal.h"
 #include "mlp_geo48.h"
