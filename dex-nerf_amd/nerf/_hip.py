@@ -31,6 +31,7 @@ EXPORTS = (
     "dn_adam_step", "dn_pack_ray_rows", "dn_mlp_weight_grad_pair",
     "dn_mlp_weight_grad_scratch_bytes", "dn_mlp_weight_grad_all_ws", "dn_mlp_weight_grad_pair_ws", "dn_render_rays_backward_ws",
     "dn_select_rays_draw_ndc",
+    "dn_mlp_input_grad_packed_bytes", "dn_mlp_pack_input_grad", "dn_mlp_backward_input_workspace_bytes", "dn_mlp_backward_input",
 )
 
 
@@ -115,9 +116,17 @@ def _declare(lib):
     lib.dn_adam_step.argtypes = [fp, fp, fp, fp, c_int64, fp, fp, dbl, dbl, dbl, dbl, dbl, c_int, vp]
     lib.dn_mlp_pack_train_pair.argtypes = [POINTER(MlpDesc), POINTER(c_void_p), POINTER(c_void_p), vp, vp, POINTER(c_void_p), POINTER(c_void_p),
                                            vp, vp, vp]
+    lib.dn_mlp_input_grad_packed_bytes.argtypes = [POINTER(MlpDesc), c_int]
+    lib.dn_mlp_input_grad_packed_bytes.restype = c_size_t
+    lib.dn_mlp_pack_input_grad.argtypes = [POINTER(MlpDesc), c_int, POINTER(c_void_p), vp, vp]
+    lib.dn_mlp_backward_input_workspace_bytes.argtypes = [POINTER(MlpDesc), c_int64, c_int]
+    lib.dn_mlp_backward_input_workspace_bytes.restype = c_size_t
+    lib.dn_mlp_backward_input.argtypes = [POINTER(MlpDesc), c_int, vp, vp, fp, fp, fp, c_int, fp, c_int64, c_int, fp, fp, fp, fp, vp,
+                                          c_size_t, vp]
     for name in EXPORTS:
         if name not in ("dn_last_error", "dn_mlp_packed_bytes", "dn_render_workspace_bytes",
-                        "dn_mlp_backward_packed_bytes", "dn_render_train_workspace_bytes"):
+                        "dn_mlp_backward_packed_bytes", "dn_render_train_workspace_bytes",
+                        "dn_mlp_input_grad_packed_bytes", "dn_mlp_backward_input_workspace_bytes"):
             getattr(lib, name).restype = c_int
 
 

@@ -304,6 +304,8 @@ class PackedMLP:
         self.key48 = None        # ... and the stream of the 48-point inference kernel: a training loop leaves it stale until a render
         self.buffers_bwd = {}    # transposed streams for the backward-data chain, per training precision code (the 8-bit-saved-tensor
         self.keys_bwd = {}       # mode runs the 48-point chain: another stream), packed on first training use
+        self.buffer_ig = None    # transposed stream of the encoding blocks (dn_mlp_backward_input), packed on first use by a call
+        self.key_ig = None       # whose points / rays require grad
 
     def pack(self, weights, biases, parts=_hip.PACK_ALL):
         """weights/biases: lists of device tensors in the reference parameter order; parts: _hip.PACK_CORE | _hip.PACK_G48."""
@@ -349,6 +351,50 @@ def ensure_backward_stream(model, packed, prec=None):
         pack_backward(packed, [m.weight for m in model.linear_modules()], prec)
         packed.keys_bwd[prec] = key
     return packed.buffers_bwd[prec]
+
+
+def ensure_input_grad_stream(model, packed):
+    """The input-gradient stream of `packed` (dn_mlp_pack_input_grad), re-packed when the parameters changed (or under capture)."""
+    key = model.param_key()
+    if packed.key_ig != key or torch.cuda.is_current_stream_capturing():
+        if packed.buffer_ig is None:
+            nbytes = lib().dn_mlp_input_grad_packed_bytes(ctypes.byref(packed.desc), packed.precision)
+            if nbytes == 0:
+                check(-1001, "dn_mlp_input_grad_packed_bytes")
+            packed.buffer_ig = torch.empty(nbytes, dtype=torch.uint8, device=packed.buffer.device)
+        ws = [f32c(m.weight.detach()) for m in model.linear_modules()]
+        wp = (c_void_p * len(ws))(*[w.data_ptr() for w in ws])
+        check(lib().dn_mlp_pack_input_grad(ctypes.byref(packed.desc), packed.precision, wp, ptr(packed.buffer_ig), stream()),
+              "dn_mlp_pack_input_grad")
+        packed._keep_ig = ws
+        packed.key_ig = key
+    return packed.buffer_ig
+
+
+def mlp_backward_input(packed, grads, n_rays, samples_per_ray, pts=None, viewdirs=None, rays=None, z_vals=None):
+    """dn_mlp_backward_input on the `grads` records of mlp_backward_data (precision = packed.precision: fp32, or bf16 with 16-bit
+    saves).  Points form: (d_pts (P,3), d_viewdirs (N,3) | None); rays form: (d_rays (N,stride), d_z (N,S))."""
+    ray_form = pts is None
+    dev = grads.device
+    n_pts = n_rays * samples_per_ray
+    nbytes = int(lib().dn_mlp_backward_input_workspace_bytes(ctypes.byref(packed.desc), n_pts, int(ray_form)))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    d_pts = d_vd = d_rays = d_z = None
+    stride = 0
+    if ray_form:
+        rays, z_vals = f32c(rays), f32c(z_vals)
+        stride = rays.shape[1]
+        d_rays, d_z = torch.empty_like(rays), torch.empty_like(z_vals)
+    else:
+        pts = f32c(pts).reshape(-1, 3)
+        d_pts = torch.empty_like(pts)
+        if packed.desc.use_viewdirs:
+            viewdirs = f32c(viewdirs).reshape(-1, 3)
+            d_vd = torch.empty_like(viewdirs)
+    check(lib().dn_mlp_backward_input(ctypes.byref(packed.desc), packed.precision, ptr(packed.buffer_ig), ptr(grads), ptr(pts), ptr(viewdirs),
+                                      ptr(rays), stride, ptr(z_vals), n_rays, samples_per_ray, ptr(d_pts), ptr(d_vd), ptr(d_rays), ptr(d_z),
+                                      ptr(ws), nbytes, stream()), "dn_mlp_backward_input")
+    return (d_rays, d_z) if ray_form else (d_pts, d_vd)
 
 
 def pack_train_pair(model_a, model_b, logs):

@@ -4,8 +4,10 @@ Inference: one fused kernel (positional encoding + MLP).  Training, for the nets
 (W in {128, 256}, L_xyz in {6, 10}): `FusedNetFn` - a fused forward that keeps every stage's output and ReLU masks in a
 wave-native layout, and a fused backward-data chain on the transposed weight stream (dn_mlp_backward_data);
 the weight/bias gradients come from one weight-gradient kernel launch per network on the saved native buffers
-(bf16 MFMA, or exact-fp32 MFMA in the parity mode).  Other configurations differentiate the nn.Linear composition
-directly."""
+(bf16 MFMA, or exact-fp32 MFMA in the parity mode).  Calls whose points, ray rows, depths or view directions require grad
+(pose / ray optimisation) take `FusedNetInputFn`: the same forward and backward-data chain on the 32-point record layout, then
+dn_mlp_backward_input on the gradient records, and the weight-gradient launch only when some parameter requires grad.  Other
+configurations (fp16, nets outside the training kernels) differentiate the nn.Linear composition directly."""
 import torch
 
 from . import _hip, _ops
@@ -18,9 +20,10 @@ def needs_grad(model, *tensors):
 
 
 def inputs_need_grad(*tensors):
-    """True when a gradient is wanted w.r.t. points / rays / depths / view directions (pose or ray optimisation).  The fused
-    training kernels differentiate w.r.t. the PARAMETERS only (the reference's own loop never asks for more:
-    train_dexnerf_rgb.py:246-278), so such calls take the nn.Linear autograd path instead of silently getting no gradient."""
+    """True when a gradient is wanted w.r.t. points / rays / depths / view directions (pose or ray optimisation).  FusedNetFn
+    differentiates w.r.t. the PARAMETERS only (the reference's own loop never asks for more: train_dexnerf_rgb.py:246-278), so
+    such calls go to FusedNetInputFn - or, for nets and precisions outside the training kernels, to the nn.Linear autograd path -
+    instead of silently getting no gradient."""
     return torch.is_grad_enabled() and any(t is not None and torch.is_tensor(t) and t.requires_grad for t in tensors)
 
 
@@ -58,7 +61,8 @@ class FusedNetFn(torch.autograd.Function):
         """`pts` (P,3) + `viewdirs` (N,3), or - when `samples_per_ray` is None - packed ray rows (N,11) + depths (N,S)."""
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:   # (inside forward the tensors themselves are detached views)
             raise RuntimeError("FusedNetFn differentiates w.r.t. the model parameters only; points / rays / view directions that "
-                               "require grad must go through the nn.Linear composition (run_network does that by itself)")
+                               "require grad must go through FusedNetInputFn, or the nn.Linear composition for nets outside the "
+                               "training kernels (run_network routes them by itself)")
         pk = model.packed(log_xyz, log_dir, train=True)
         prec = _ops.train_precision(pk)
         _ops.ensure_backward_stream(model, pk, prec)
@@ -94,6 +98,81 @@ class FusedNetFn(torch.autograd.Function):
         for d_w, d_b in res:
             flat.extend((d_w, d_b))
         return (None, None, None, None, None, None) + tuple(flat)
+
+
+def _packed_core(model, log_xyz, log_dir):
+    """The packed network with its CORE stream fresh - what a 16-bit-saved training forward reads in every mode.  (In the default
+    'bf16' mode `model.packed(train=True)` refreshes the 48-point stream instead; that stream and its key are left alone here.)"""
+    pk = model._packed_slot(log_xyz, log_dir)
+    key = model.param_key()
+    if pk.key != key or torch.cuda.is_current_stream_capturing():
+        mods = model.linear_modules()
+        pk.pack([m.weight for m in mods], [m.bias for m in mods], _hip.PACK_CORE)
+        pk.key = key
+    return pk
+
+
+class FusedNetInputFn(torch.autograd.Function):
+    """run_network for a FlexibleNeRFModel, differentiable w.r.t. points / view directions (or ray rows / depths) AND the parameters:
+    FusedNetFn's forward and backward-data chain, then dn_mlp_backward_input on the gradient records; the weight-gradient launch
+    runs only when some parameter requires grad (pose refinement against frozen weights skips it).  Always on the 32-point record
+    layout: in the default 'bf16' mode such a call keeps 16-bit saves (an e5m2 gradient through a Jacobian that multiplies by up
+    to 2^9 is not worth having); parameter-only calls stay on their 8-bit path."""
+
+    @staticmethod
+    def forward(ctx, model, pts, viewdirs, samples_per_ray, log_xyz, log_dir, *params):
+        """`pts` (..., 3) + `viewdirs` (N,3), or - when `samples_per_ray` is None - packed ray rows (N, 8|11) + depths (N,S)."""
+        pk = _packed_core(model, log_xyz, log_dir)
+        prec = pk.precision
+        _ops.ensure_backward_stream(model, pk, prec)
+        _ops.ensure_input_grad_stream(model, pk)
+        a = _hip.f32c(pts)
+        b = None if viewdirs is None else _hip.f32c(viewdirs)
+        if samples_per_ray is None:
+            out, act, masks = _ops.run_network_train(pk, None, None, None, rays=a, z_vals=b, prec=prec)
+            ctx.n_rays, ctx.s = b.shape
+        else:
+            out, act, masks = _ops.run_network_train(pk, a, b, samples_per_ray, prec=prec)
+            ctx.n_rays, ctx.s = out.shape[0] // samples_per_ray, samples_per_ray
+        ctx.model, ctx.pk, ctx.prec, ctx.ray_form = model, pk, prec, samples_per_ray is None
+        ctx.n_points = out.shape[0]
+        ctx.in_meta = tuple(None if t is None else (t.shape, t.dtype) for t in (pts, viewdirs))
+        ctx.save_for_backward(act, masks, a, b)
+        ctx.params_need_grad = any(ctx.needs_input_grad[6:])
+        ctx.sink = getattr(model, "_grad_sink", None) if ctx.params_need_grad else None
+        if ctx.sink is not None:
+            ctx.sink.forward_issued()
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        model, pk, n = ctx.model, ctx.pk, ctx.n_points
+        act, masks, a, b = ctx.saved_tensors
+        grads = _ops.mlp_backward_data(pk, g_out.contiguous().float(), masks, n, prec=ctx.prec)
+        if ctx.ray_form:
+            d_in = _ops.mlp_backward_input(pk, grads, ctx.n_rays, ctx.s, rays=a, z_vals=b)
+        else:
+            d_in = _ops.mlp_backward_input(pk, grads, ctx.n_rays, ctx.s, pts=a, viewdirs=b)
+        d_in = [None if (d is None or meta is None or not need) else d.reshape(meta[0]).to(meta[1])
+                for d, meta, need in zip(d_in, ctx.in_meta, ctx.needs_input_grad[1:3])]
+        mods = model.linear_modules()
+        head = (None, d_in[0], d_in[1], None, None, None)
+        if not ctx.params_need_grad:
+            return head + (None,) * (2 * len(mods))
+        views = ctx.sink.views(model) if ctx.sink is not None else None
+        if views is not None:
+            _ops.mlp_weight_grad_all_into(pk, act, grads, n, views, prec=ctx.prec)
+            ctx.sink.backward_done()
+            return head + (None,) * (2 * len(mods))
+        res = _ops.mlp_weight_grad_all(pk, act, grads, n, [tuple(m.weight.shape) for m in mods], prec=ctx.prec)
+        return head + tuple(t for pair in res for t in pair)
+
+
+def _params_of(model):
+    params = []
+    for m in model.linear_modules():
+        params += [m.weight, m.bias]
+    return params
 
 
 class RenderRaysTrainFn(torch.autograd.Function):
@@ -210,6 +289,8 @@ def run_network_fused_rays(model, rays, z_vals, log_xyz=True, log_dir=True):
     kernel (reference train_utils.py:136,177 materialise them).  Returns (N, S, 4)."""
     n, s = z_vals.shape
     if inputs_need_grad(rays, z_vals):
+        if train_fused_ok(model):
+            return FusedNetInputFn.apply(model, rays, z_vals, None, log_xyz, log_dir, *_params_of(model)).reshape(n, s, 4)
         ro, rd = rays[..., :3], rays[..., 3:6]
         pts = ro[..., None, :] + rd[..., None, :] * z_vals[..., :, None]
         return _modules_on_points(model, pts, rays[..., -3:] if model.use_viewdirs else None, log_xyz, log_dir).reshape(n, s, 4)
@@ -222,9 +303,12 @@ def run_network_fused_rays(model, rays, z_vals, log_xyz=True, log_dir=True):
 
 
 def run_network_fused(model, pts, viewdirs, samples_per_ray, log_xyz=True, log_dir=True):
-    """run_network on raw points: positional encoding + MLP in one kernel; differentiable w.r.t. the parameters.  Inputs
-    that require grad (pose / ray optimisation) take the differentiable torch composition instead."""
+    """run_network on raw points: positional encoding + MLP in one kernel; differentiable w.r.t. the parameters and - through
+    FusedNetInputFn - w.r.t. points / view directions that require grad (pose / ray optimisation).  Only nets or precisions
+    outside the training kernels take the differentiable torch composition for that."""
     if inputs_need_grad(pts, viewdirs):
+        if train_fused_ok(model):
+            return FusedNetInputFn.apply(model, pts, viewdirs, samples_per_ray, log_xyz, log_dir, *_params_of(model))
         return _modules_on_points(model, pts.reshape(-1, samples_per_ray, 3), viewdirs, log_xyz, log_dir)
     if needs_grad(model) and train_fused_ok(model):
         params = []

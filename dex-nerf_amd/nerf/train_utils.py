@@ -171,7 +171,7 @@ def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, mo
     fused_models = (_fusable(model_coarse, encode_position_fn, encode_direction_fn)
                     and (not fine or _fusable(model_fine, encode_position_fn, encode_direction_fn))
                     and model_coarse.use_viewdirs == use_viewdirs)
-    if fused_models and not _wants_grad(model_coarse, model_fine):
+    if fused_models and not _wants_grad(model_coarse, model_fine) and not inputs_need_grad(ray_batch):
         # whole chunk in one C-ABI call (dn_render_rays); draws generated in the reference's order
         draws = {}
         if perturb:
