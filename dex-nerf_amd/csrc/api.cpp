@@ -8,6 +8,7 @@
 #include "dn_common.h"
 #include "composite_body.h"
 #include "dn_rng.h"
+#include "mlp_layout.h"
 
 namespace dn {
 
@@ -71,6 +72,32 @@ static Workspace carve(void* base, int64_t n, int nc, int nf, bool train = false
   }
   if (train) w.g_rf = take(static_cast<size_t>(n) * (nc + nf) * 4);   // d loss / d raw radiance field, one network at a time
   if (train) w.absmax_part = reinterpret_cast<unsigned*>(take(static_cast<size_t>((n + 3) / 4)));
+  w.status = reinterpret_cast<unsigned*>(take(64));
+  w.bytes = off;
+  return w;
+}
+
+// dn_render_rays_depth: depths and raw rows only - the coarse weights stay inside density_resample_kernel
+struct DepthWorkspace {
+  float *z_c, *rf_c, *z_f, *rf_f;
+  unsigned* status;   // the last 256 bytes, as in Workspace
+  size_t bytes;
+};
+
+static DepthWorkspace carve_depth(void* base, int64_t n, int nc, int nf) {
+  DepthWorkspace w{};
+  size_t off = 0;
+  auto take = [&](size_t floats) {
+    float* p = base ? reinterpret_cast<float*>(static_cast<char*>(base) + off) : nullptr;
+    off += align256(floats * sizeof(float));
+    return p;
+  };
+  w.z_c = take(static_cast<size_t>(n) * nc);
+  w.rf_c = take(static_cast<size_t>(n) * nc * 4);
+  if (nf > 0) {
+    w.z_f = take(static_cast<size_t>(n) * (nc + nf));
+    w.rf_f = take(static_cast<size_t>(n) * (nc + nf) * 4);
+  }
   w.status = reinterpret_cast<unsigned*>(take(64));
   w.bytes = off;
   return w;
@@ -143,6 +170,55 @@ extern "C" int dn_render_rays(const dn_mlp_desc* desc_coarse, const void* packed
   if (done) return 0;
   return volume_render_counting(w.rf_f, w.z_f, rays + 3, ray_stride, noise_f, noise_std, white_background, h_m_thres, n_thres,
                                 n_rays, num_coarse + num_fine, rgb_f, nullptr, acc_f, nullptr, depth_f, dex_f, w.status, stream);
+}
+
+// ---- the depth-only render: density sub-networks + sigma-only compositing (depth, acc, Dex depths; no colour) -----------------
+extern "C" size_t dn_render_depth_workspace_bytes(int64_t n_rays, int num_coarse, int num_fine) {
+  if (n_rays < 0 || num_coarse < 1 || num_fine < 0) return 0;
+  return carve_depth(nullptr, n_rays, num_coarse, num_fine).bytes;
+}
+
+extern "C" int dn_render_rays_depth(const dn_mlp_desc* desc_coarse, const void* packed_coarse, const dn_mlp_desc* desc_fine,
+                                    const void* packed_fine, int precision, const float* rays, int ray_stride, int64_t n_rays,
+                                    int num_coarse, int num_fine, int lindisp, float noise_std, const float* d_m_thres, int n_thres,
+                                    const float* t_rand, const float* noise_c, const float* u, const float* noise_f, float* depth_c,
+                                    float* acc_c, float* depth_f, float* acc_f, float* dex_f, void* workspace, dn_stream_t stream) {
+  // every argument is judged before any GPU work
+  DN_REQUIRE(desc_coarse && packed_coarse && rays && workspace && n_rays >= 0, "dn_render_rays_depth: bad arguments");
+  DN_REQUIRE(num_coarse >= 1 && num_fine >= 0 && ray_stride >= 8, "dn_render_rays_depth: bad sample counts / ray stride");
+  DN_REQUIRE(num_fine == 0 || (desc_fine && packed_fine), "dn_render_rays_depth: fine pass requested without a fine net");
+  DN_REQUIRE(n_thres >= 0, "dn_render_rays_depth: negative threshold count");
+  DN_REQUIRE(n_thres == 0 || (d_m_thres && dex_f), "dn_render_rays_depth: thresholds given without dex output");
+  DN_REQUIRE(!desc_coarse->use_viewdirs && (num_fine == 0 || !desc_fine->use_viewdirs),
+             "dn_render_rays_depth: takes density sub-networks (dn_mlp_density_desc / dn_mlp_pack_density): use_viewdirs must be 0");
+  DN_REQUIRE(num_fine == 0 || (num_coarse >= 10 && num_coarse <= 512 && num_coarse + num_fine <= 2048),
+             "dn_render_rays_depth: need 10 <= num_coarse <= 512 and num_coarse + num_fine <= 2048");
+  DN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "dn_render_rays_depth: workspace must be 256-byte aligned");
+  int rc;
+  if ((rc = validate_desc(desc_coarse, precision))) return rc;
+  if (num_fine > 0 && (rc = validate_desc(desc_fine, precision))) return rc;
+  if (n_rays == 0) return 0;
+  DepthWorkspace w = carve_depth(workspace, n_rays, num_coarse, num_fine);
+  {
+    hipError_t e = hipMemsetAsync(w.status, 0, 256, as_stream(stream));
+    if (e != hipSuccess) { set_error("dn_render_rays_depth: hipMemsetAsync: %s", hipGetErrorString(e)); return -static_cast<int>(e); }
+  }
+  if ((rc = dn_coarse_depths(rays, ray_stride, n_rays, num_coarse, lindisp, t_rand, w.z_c, stream))) return rc;
+  if ((rc = run_network_flagged(desc_coarse, precision, packed_coarse, nullptr, nullptr, rays, ray_stride, w.z_c, n_rays, num_coarse,
+                                w.rf_c, w.status + 1, stream)))
+    return rc;
+  // Dex depths come from the fine pass (train_utils.py:199-201); coarse-only renders report the coarse ones.
+  if (num_fine == 0)
+    return composite_density_counting(w.rf_c, w.z_c, rays + 3, ray_stride, noise_c, noise_std, d_m_thres, n_thres, n_rays, num_coarse,
+                                      depth_c, acc_c, dex_f, w.status, stream);
+  if ((rc = density_resample_counting(w.rf_c, w.z_c, rays + 3, ray_stride, noise_c, noise_std, u, n_rays, num_coarse, num_fine, depth_c,
+                                      acc_c, w.z_f, w.status, stream)))
+    return rc;
+  if ((rc = run_network_flagged(desc_fine, precision, packed_fine, nullptr, nullptr, rays, ray_stride, w.z_f, n_rays,
+                                num_coarse + num_fine, w.rf_f, w.status + 1, stream)))
+    return rc;
+  return composite_density_counting(w.rf_f, w.z_f, rays + 3, ray_stride, noise_f, noise_std, d_m_thres, n_thres, n_rays,
+                                    num_coarse + num_fine, depth_f, acc_f, dex_f, w.status, stream);
 }
 
 // ---- predict_and_render_radiance under autograd (reference nerf/train_utils.py:92-202 + loss.backward(),

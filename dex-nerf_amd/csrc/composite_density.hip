@@ -1,0 +1,102 @@
+// The sigma-only render kernels of the depth path (dn_render_rays_depth): expected depth, accumulation and Dex depths need the
+// density column alone (reference nerf/volume_rendering_utils.py:33-58), so neither kernel evaluates a sigmoid or a colour sum.
+//   density_resample_kernel : coarse compositing fused with the fine-depth generation (nerf/train_utils.py:163-173) - one wave per
+//                             ray forms the coarse weights in registers, drops weights[1:-1] + 1e-5 straight into the sampler's
+//                             LDS row and runs the sampler's own code on it: the (N, Nc) weights never reach HBM.
+//   composite_density_kernel: depth, acc and dex (K, N) for any K (thresholds in device memory, 64 per pass).
+// One wave64 per ray, four rays per workgroup, like composite.hip / the sampler.
+#include "composite_density_body.h"
+#include "sampler_body.h"
+
+namespace dn {
+
+__global__ __launch_bounds__(256) void density_resample_kernel(const float4* __restrict__ rf, const float* __restrict__ z,
+                                                               const float* __restrict__ rd, int rd_stride, const float* __restrict__ noise,
+                                                               float noise_std, const float* __restrict__ u, int64_t n_rays, int nc, int nf,
+                                                               float* __restrict__ depth, float* __restrict__ acc, float* __restrict__ z_fine,
+                                                               int sort_len, unsigned* __restrict__ nonfinite) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int wave = threadIdx.x >> 6;
+  const int lane = lane_id();
+  const int64_t ray_raw = static_cast<int64_t>(blockIdx.x) * kSamplerWaves + wave;
+  const bool live = ray_raw < n_rays;
+  const int64_t ray = live ? ray_raw : (n_rays - 1);
+  const int B = nc - 1;
+  const int per_wave = 3 * (B + 1) + sort_len;   // sampler_kernel's rows (mode 1)
+  float* w = lds + wave * per_wave;
+  float* cdf = w + (B + 1);
+  float* bins = cdf + (B + 1);
+  float* sbuf = bins + (B + 1);
+  const float* zc = z + ray * nc;
+  for (int i = lane; i < B; i += 64) bins[i] = 0.5f * (zc[i + 1] + zc[i]);
+  for (int i = lane; i < nc; i += 64) sbuf[i] = zc[i];
+  density_ray(rf + ray * nc, zc, rd + ray * rd_stride, ray, live, lane, noise, noise_std, static_cast<const float*>(nullptr), 0, n_rays, nc,
+              acc, depth, static_cast<float*>(nullptr), nonfinite,
+              [&](int s, float wt) { if (s >= 1 && s <= nc - 2) w[s - 1] = wt + 1e-5f; });   // weights[..., 1:-1] + 1e-5
+  sampler_resample<1>(w, cdf, bins, sbuf, u, ray, live, B, nf, static_cast<float*>(nullptr), static_cast<int64_t*>(nullptr), z_fine,
+                      sort_len, RngRef{nullptr, 0u});
+}
+
+__global__ __launch_bounds__(256) void composite_density_kernel(const float4* __restrict__ rf, const float* __restrict__ z,
+                                                                const float* __restrict__ rd, int rd_stride, const float* __restrict__ noise,
+                                                                float noise_std, const float* __restrict__ d_thres, int n_thres, int64_t n_rays,
+                                                                int S, float* __restrict__ depth, float* __restrict__ acc,
+                                                                float* __restrict__ dex, unsigned* __restrict__ nonfinite) {
+  const int lane = lane_id();
+  const int64_t ray = static_cast<int64_t>(blockIdx.x) * kSamplerWaves + (threadIdx.x >> 6);
+  if (ray >= n_rays) return;  // wave-uniform exit; no block-level sync in this kernel
+  density_ray(rf + ray * S, z + ray * S, rd + ray * rd_stride, ray, true, lane, noise, noise_std, d_thres, n_thres, n_rays, S, acc, depth,
+              dex, nonfinite, [](int, float) {});
+}
+
+static int next_pow2(int v) {
+  int p = 1;
+  while (p < v) p <<= 1;
+  return p;
+}
+
+int density_resample_counting(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise, float noise_std,
+                              const float* u, int64_t n_rays, int num_coarse, int num_fine, float* depth, float* acc, float* z_fine,
+                              unsigned* nonfinite, dn_stream_t stream) {
+  if (n_rays == 0) return 0;
+  DN_REQUIRE(rf && z && rd && z_fine && n_rays >= 0 && num_fine >= 1 && rd_stride >= 3, "dn_density_resample: bad arguments");
+  DN_REQUIRE(num_coarse >= 10 && num_coarse <= 512 && num_coarse + num_fine <= 2048,
+             "dn_density_resample: need 10 <= num_coarse <= 512 and num_coarse + num_fine <= 2048");
+  DN_REQUIRE((reinterpret_cast<uintptr_t>(rf) & 15) == 0, "dn_density_resample: rf must be 16-byte aligned");
+  const int sort_len = next_pow2(num_coarse + num_fine);
+  const size_t lds = static_cast<size_t>(kSamplerWaves) * (3 * num_coarse + sort_len) * sizeof(float);
+  const unsigned grid = static_cast<unsigned>((n_rays + kSamplerWaves - 1) / kSamplerWaves);
+  hipLaunchKernelGGL(density_resample_kernel, dim3(grid), dim3(256), lds, as_stream(stream), reinterpret_cast<const float4*>(rf), z, rd,
+                     rd_stride, noise, noise_std, u, n_rays, num_coarse, num_fine, depth, acc, z_fine, sort_len, nonfinite);
+  return check_launch("dn_density_resample");
+}
+
+int composite_density_counting(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise, float noise_std,
+                               const float* d_m_thres, int n_thres, int64_t n_rays, int n_samples, float* depth, float* acc, float* dex,
+                               unsigned* nonfinite, dn_stream_t stream) {
+  if (n_rays == 0) return 0;
+  DN_REQUIRE(rf && z && rd && n_rays >= 0 && n_samples >= 1 && rd_stride >= 3, "dn_composite_density: bad arguments");
+  DN_REQUIRE(n_thres >= 0, "dn_composite_density: negative threshold count");
+  DN_REQUIRE(n_thres == 0 || (d_m_thres && dex), "dn_composite_density: thresholds given without dex output");
+  DN_REQUIRE((reinterpret_cast<uintptr_t>(rf) & 15) == 0, "dn_composite_density: rf must be 16-byte aligned");
+  const unsigned grid = static_cast<unsigned>((n_rays + kSamplerWaves - 1) / kSamplerWaves);
+  hipLaunchKernelGGL(composite_density_kernel, dim3(grid), dim3(256), 0, as_stream(stream), reinterpret_cast<const float4*>(rf), z, rd,
+                     rd_stride, noise, noise_std, d_m_thres, n_thres, n_rays, n_samples, depth, acc, n_thres > 0 ? dex : nullptr, nonfinite);
+  return check_launch("dn_composite_density");
+}
+
+}  // namespace dn
+
+using namespace dn;
+
+extern "C" int dn_density_resample(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise,
+                                   float noise_std, const float* u, int64_t n_rays, int num_coarse, int num_fine, float* depth,
+                                   float* acc, float* z_fine, dn_stream_t stream) {
+  return density_resample_counting(rf, z, rd, rd_stride, noise, noise_std, u, n_rays, num_coarse, num_fine, depth, acc, z_fine, nullptr, stream);
+}
+
+extern "C" int dn_composite_density(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise,
+                                    float noise_std, const float* d_m_thres, int n_thres, int64_t n_rays, int n_samples,
+                                    float* depth, float* acc, float* dex, dn_stream_t stream) {
+  return composite_density_counting(rf, z, rd, rd_stride, noise, noise_std, d_m_thres, n_thres, n_rays, n_samples, depth, acc, dex, nullptr, stream);
+}

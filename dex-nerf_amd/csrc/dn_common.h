@@ -39,6 +39,14 @@ int volume_render_counting(const float* rf, const float* z, const float* rd, int
                            float* disp, float* acc, float* weights, float* depth, float* dex, unsigned* nonfinite,
                            dn_stream_t stream, const uint32_t* rng_state = nullptr, uint32_t rng_stream = 0);
 
+// composite_density.hip: the sigma-only kernels of dn_render_rays_depth, counting non-finite raw sigma like volume_render_counting
+int density_resample_counting(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise, float noise_std,
+                              const float* u, int64_t n_rays, int num_coarse, int num_fine, float* depth, float* acc, float* z_fine,
+                              unsigned* nonfinite, dn_stream_t stream);
+int composite_density_counting(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise, float noise_std,
+                               const float* d_m_thres, int n_thres, int64_t n_rays, int n_samples, float* depth, float* acc, float* dex,
+                               unsigned* nonfinite, dn_stream_t stream);
+
 // mlp_fused.hip: dn_run_network with the fp16 range flag (a device word the 48-point fp16 kernel bumps when a hidden activation
 // left fp16's range; NULL = not wanted)
 bool weight_grad_pair_fits(const dn_mlp_desc& d);   // mlp_wgrad.hip: the layers of two such networks fit one weight-gradient batch

@@ -10,7 +10,9 @@ DN_FWD32_INSTANCES(DN_FWD32_EXTERN)
 
 // ---- pack kernel: nn.Linear tensors -> bias tiles + MFMA-A piece stream ---------------------------------
 
-template <int BF16>
+// DENS = 1 (dn_mlp_pack_density): L is the layout of the no-view-direction net of the same trunk and the last stage's source is
+// fc_alpha - its one row becomes row 3 of the 4-row head, rows 0-2 and their biases are +0
+template <int BF16, int DENS = 0>
 __global__ void pack_kernel(NetLayout L, PackPtrs ptrs, char* __restrict__ packed) {
   using P = Prec<BF16>;
   const int KX = kXyzPanel, KD = round_up(3 + 6 * L.LD, 16);
@@ -32,7 +34,8 @@ __global__ void pack_kernel(NetLayout L, PackPtrs ptrs, char* __restrict__ packe
         else { const int n = (ts - 1) * 32 + row_in_tile; v = (n < st.n_real) ? ptrs.b[st.src][n] : 0.0f; }
       } else {
         const int n = ts * 32 + row_in_tile;
-        v = (n < st.n_real) ? ptrs.b[st.src][n] : 0.0f;
+        if (DENS && s == L.n_stages - 1) v = (n == 3) ? ptrs.b[st.src][0] : 0.0f;
+        else v = (n < st.n_real) ? ptrs.b[st.src][n] : 0.0f;
       }
     }
     bias_out[idx] = v;
@@ -92,7 +95,8 @@ __global__ void pack_kernel(NetLayout L, PackPtrs ptrs, char* __restrict__ packe
           else { const int n = (ts - 1) * 32 + i; v = (n < st.n_real) ? ptrs.w[st.src][static_cast<long long>(n) * st.ld + col] : 0.0f; }
         } else {
           const int n = ts * 32 + i;
-          v = (n < st.n_real) ? ptrs.w[st.src][static_cast<long long>(n) * st.ld + col] : 0.0f;
+          if (DENS && s == L.n_stages - 1) v = (n == 3) ? ptrs.w[st.src][col] : 0.0f;
+          else v = (n < st.n_real) ? ptrs.w[st.src][static_cast<long long>(n) * st.ld + col] : 0.0f;
         }
       }
     }
@@ -176,7 +180,16 @@ int setup_params(const dn_mlp_desc* desc, int precision, const void* packed, Fwd
   return 0;
 }
 
-int launch_pack(const NetLayout& L, const PackPtrs& ptrs, void* packed, int precision, hipStream_t stream) {
+int launch_pack(const NetLayout& L, const PackPtrs& ptrs, void* packed, int precision, hipStream_t stream, bool density) {
+  if (density) {
+    if (precision == DN_PREC_BF16)
+      hipLaunchKernelGGL((pack_kernel<1, 1>), dim3(512), dim3(256), 0, stream, L, ptrs, static_cast<char*>(packed));
+    else if (precision == DN_PREC_F16)
+      hipLaunchKernelGGL((pack_kernel<2, 1>), dim3(512), dim3(256), 0, stream, L, ptrs, static_cast<char*>(packed));
+    else
+      hipLaunchKernelGGL((pack_kernel<0, 1>), dim3(512), dim3(256), 0, stream, L, ptrs, static_cast<char*>(packed));
+    return check_launch("mlp_pack_density");
+  }
   if (precision == DN_PREC_BF16)
     hipLaunchKernelGGL(pack_kernel<1>, dim3(512), dim3(256), 0, stream, L, ptrs, static_cast<char*>(packed));
   else if (precision == DN_PREC_F16)
@@ -228,6 +241,48 @@ extern "C" int dn_mlp_pack_parts(const dn_mlp_desc* desc, int precision, const f
   if (rc == 0 && (parts & DN_PACK_G48) && g48_supported(*desc, precision))
     rc = launch_pack48(*desc, precision, ptrs, static_cast<char*>(packed) + L.bias_bytes + static_cast<size_t>(L.total_pieces) * kPieceBytes,
                        as_stream(stream));
+  return rc;
+}
+
+// ---- the density sub-network of a view-direction net: its trunk + fc_alpha as row 3 of a 4-row head (models.py:239-249) ----
+extern "C" int dn_mlp_density_desc(const dn_mlp_desc* full, dn_mlp_desc* out) {
+  DN_REQUIRE(full && out, "dn_mlp_density_desc: NULL descriptor");
+  *out = *full;
+  out->use_viewdirs = 0;
+  return 0;
+}
+
+extern "C" size_t dn_mlp_density_packed_bytes(const dn_mlp_desc* full, int precision) {
+  dn_mlp_desc d;
+  if (dn_mlp_density_desc(full, &d) || validate_desc(full, precision)) return 0;
+  return dn_mlp_packed_bytes(&d, precision);
+}
+
+extern "C" int dn_mlp_pack_density(const dn_mlp_desc* full, int precision, const float* const* h_weights,
+                                   const float* const* h_biases, void* packed, dn_stream_t stream) {
+  int rc = validate_desc(full, precision);
+  if (rc) return rc;
+  if (!full->use_viewdirs) return dn_mlp_pack(full, precision, h_weights, h_biases, packed, stream);   // already its own density net
+  DN_REQUIRE(h_weights && h_biases && packed, "dn_mlp_pack_density: NULL pointer");
+  DN_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 15) == 0, "dn_mlp_pack_density: packed buffer must be 16-byte aligned");
+  dn_mlp_desc d;
+  dn_mlp_density_desc(full, &d);
+  NetLayout L;
+  build_layout(d, precision, &L);
+  const int D = full->num_layers;
+  PackPtrs ptrs{};
+  for (int i = 0; i < D; ++i) {   // layer1 + the trunk
+    DN_REQUIRE(h_weights[i] && h_biases[i], "dn_mlp_pack_density: parameter %d is NULL", i);
+    ptrs.w[i] = h_weights[i];
+    ptrs.b[i] = h_biases[i];
+  }
+  DN_REQUIRE(h_weights[D + 1] && h_biases[D + 1], "dn_mlp_pack_density: fc_alpha is NULL");
+  ptrs.w[D] = h_weights[D + 1];   // the head stage's source: fc_alpha (pack_kernel, DENS)
+  ptrs.b[D] = h_biases[D + 1];
+  rc = launch_pack(L, ptrs, packed, precision, as_stream(stream), true);
+  if (rc == 0 && g48_supported(d, precision))
+    rc = launch_pack48(d, precision, ptrs, static_cast<char*>(packed) + L.bias_bytes + static_cast<size_t>(L.total_pieces) * kPieceBytes,
+                       as_stream(stream), true);
   return rc;
 }
 

@@ -11,20 +11,27 @@
 
 namespace dn {
 
-// the instance list (mlp_fused48_kernel.h) builds as four translation units in parallel: this one compiles its own rows and only
-// declares the others
+// the instance list (mlp_fused48_kernel.h) builds as four translation units in parallel (+ mlp_fused48_density.hip for the
+// no-view-direction instances): this one compiles its own rows and only declares the others
 DN_FWD48_PAPER_BF16(DN_FWD48_EXTERN)
 DN_FWD48_PAPER_FP16(DN_FWD48_EXTERN)
 DN_FWD48_W128(DN_FWD48_EXTERN)
 DN_FWD48_HOST_UNIT(DN_FWD48_INSTANTIATE)
+// mlp_fused48_density.hip: the same template under another name (declared here, defined there)
+template <int W, int F, int DC, unsigned MASKC, int VIEWC, int SAVE, int OVLP, int COMP>
+__global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward_density48_kernel(FwdParams p, G48Params q);
+#define DN_FWD48_DENSITY_EXTERN(W, F, DC, MASKC, VIEWC, SAVE, OVLP, COMP) \
+  extern template __global__ void mlp_forward_density48_kernel<W, F, DC, MASKC, VIEWC, SAVE, OVLP, COMP>(FwdParams, G48Params);
+DN_FWD48_DENSITY(DN_FWD48_DENSITY_EXTERN)
 
 // ---- pack: nn.Linear tensors -> bias rows + encoding tables + 16x32 A pieces -----------------------------------
-template <int F>
+// DENS = 1 (dn_mlp_pack_density): the no-view-direction layout with fc_alpha as the last stage's source - row 3 of the head
+template <int F, int DENS = 0>
 __device__ __forceinline__ void pack48_body(const NetLayout& L, const PackPtrs& ptrs, const G48Tables& tabs, char* __restrict__ region);
 
-template <int F>
+template <int F, int DENS = 0>
 __global__ void pack48_kernel(NetLayout L, PackPtrs ptrs, G48Tables tabs, char* __restrict__ region) {
-  pack48_body<F>(L, ptrs, tabs, region);
+  pack48_body<F, DENS>(L, ptrs, tabs, region);
 }
 
 // two networks of one architecture (the coarse and the fine net of a training step) in one launch: blockIdx.y picks the net
@@ -35,7 +42,7 @@ __global__ void pack48_pair_kernel(NetLayout L, PackPtrs ptrs_a, PackPtrs ptrs_b
   else pack48_body<F>(L, ptrs_b, tabs, region_b);
 }
 
-template <int F>
+template <int F, int DENS>
 __device__ __forceinline__ void pack48_body(const NetLayout& L, const PackPtrs& ptrs, const G48Tables& tabs, char* __restrict__ region) {
   using Elem = typename Prec<F>::Elem;
   const int n_rows = L.total_bias_tiles * 16;
@@ -53,7 +60,8 @@ __device__ __forceinline__ void pack48_body(const NetLayout& L, const PackPtrs& 
         else { const int n = (ts - 1) * 16 + r; v = (n < st.n_real) ? ptrs.b[st.src][n] : 0.0f; }
       } else {
         const int n = ts * 16 + r;
-        v = (n < st.n_real) ? ptrs.b[st.src][n] : 0.0f;
+        if (DENS && s == L.n_stages - 1) v = (n == 3) ? ptrs.b[st.src][0] : 0.0f;
+        else v = (n < st.n_real) ? ptrs.b[st.src][n] : 0.0f;
       }
     }
     bias_out[idx] = v;
@@ -105,7 +113,8 @@ __device__ __forceinline__ void pack48_body(const NetLayout& L, const PackPtrs& 
           else { const int n = (ts - 1) * 16 + i; v = (n < st.n_real) ? ptrs.w[st.src][static_cast<long long>(n) * st.ld + col] : 0.0f; }
         } else {
           const int n = ts * 16 + i;
-          v = (n < st.n_real) ? ptrs.w[st.src][static_cast<long long>(n) * st.ld + col] : 0.0f;
+          if (DENS && s == L.n_stages - 1) v = (n == 3) ? ptrs.w[st.src][col] : 0.0f;
+          else v = (n < st.n_real) ? ptrs.w[st.src][static_cast<long long>(n) * st.ld + col] : 0.0f;
         }
       }
     }
@@ -115,13 +124,18 @@ __device__ __forceinline__ void pack48_body(const NetLayout& L, const PackPtrs& 
 
 void fill_freqs(float* f, int num_fns, int log_sampling);  // rays_sampling.hip
 
-int launch_pack48(const dn_mlp_desc& d, int precision, const PackPtrs& ptrs, char* region, hipStream_t stream) {
+int launch_pack48(const dn_mlp_desc& d, int precision, const PackPtrs& ptrs, char* region, hipStream_t stream, bool density) {
   NetLayout L;
   build_layout48(d, &L);
   G48Tables tabs{};
   fill_freqs(tabs.fx, d.num_encoding_fn_xyz, d.log_sampling_xyz);
   if (d.use_viewdirs) fill_freqs(tabs.fd, d.num_encoding_fn_dir, d.log_sampling_dir);
   tabs.LX = d.num_encoding_fn_xyz; tabs.LD = d.num_encoding_fn_dir;
+  if (density) {
+    if (precision == DN_PREC_F16) hipLaunchKernelGGL((pack48_kernel<2, 1>), dim3(pack48_blocks(L)), dim3(256), 0, stream, L, ptrs, tabs, region);
+    else hipLaunchKernelGGL((pack48_kernel<1, 1>), dim3(pack48_blocks(L)), dim3(256), 0, stream, L, ptrs, tabs, region);
+    return check_launch("mlp_pack48_density");
+  }
   if (precision == DN_PREC_F16) hipLaunchKernelGGL(pack48_kernel<2>, dim3(pack48_blocks(L)), dim3(256), 0, stream, L, ptrs, tabs, region);
   else hipLaunchKernelGGL(pack48_kernel<1>, dim3(pack48_blocks(L)), dim3(256), 0, stream, L, ptrs, tabs, region);
   return check_launch("mlp_pack48");
@@ -133,7 +147,7 @@ bool g48_range_guard_complete(const dn_mlp_desc& d) {
   if (!g48_supported(d, DN_PREC_F16)) return false;
   NetLayout L;
   build_layout48(d, &L);
-  const bool paper = d.hidden_size == 256 && d.num_layers == 8 && L.skip_mask == 0x10u && d.use_viewdirs;
+  const bool paper = d.hidden_size == 256 && d.num_layers == 8 && L.skip_mask == 0x10u;   // (with or without view directions: both fixed)
   return paper || d.hidden_size == 128;
 }
 
@@ -192,6 +206,13 @@ int launch_forward48(const dn_mlp_desc& d, int precision, const FwdParams& p_in,
     if (paper && fixed_ok) return launch(mlp_forward48_kernel<256, 1, 8, 0x10u, 1, 2>);
     if (shipped && fixed_ok) return launch(mlp_forward48_kernel<128, 1, 4, 0u, 1, 2>);
     return d.hidden_size == 256 ? launch(mlp_forward48_kernel<256, 1, 0, 0u, 0, 2>) : launch(mlp_forward48_kernel<128, 1, 0, 0u, 0, 2>);
+  }
+  // the same two shapes without view directions - the density sub-network (dn_mlp_pack_density): straight-line trunk + fc_out head
+  if (!d.use_viewdirs && fixed_ok) {
+    const bool paper_nv = d.hidden_size == 256 && d.num_layers == 8 && L.skip_mask == 0x10u;
+    const bool shipped_nv = d.hidden_size == 128 && d.num_layers == 4 && L.skip_mask == 0u;
+    if (paper_nv) return precision == DN_PREC_F16 ? launch(mlp_forward_density48_kernel<256, 2, 8, 0x10u, 0, 0, 0, 0>) : launch(mlp_forward_density48_kernel<256, 1, 8, 0x10u, 0, 0, 0, 0>);
+    if (shipped_nv) return precision == DN_PREC_F16 ? launch(mlp_forward_density48_kernel<128, 2, 4, 0u, 0, 0, 0, 0>) : launch(mlp_forward_density48_kernel<128, 1, 4, 0u, 0, 0, 0, 0>);
   }
   // a render that asked for its rays to be composited by the launch itself (dn_render_rays): the fixed-shape instances, whole rays
   // per 384-point tile

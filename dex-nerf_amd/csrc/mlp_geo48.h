@@ -267,7 +267,7 @@ inline int build_backward_layout48(const dn_mlp_desc& d, NetLayout* out) {
   return 0;
 }
 
-int launch_pack48(const dn_mlp_desc& d, int precision, const PackPtrs& ptrs, char* region, hipStream_t stream);
+int launch_pack48(const dn_mlp_desc& d, int precision, const PackPtrs& ptrs, char* region, hipStream_t stream, bool density = false);
 // comp != NULL: the caller would like the launch to composite its rays itself (rays + depths input, no density noise); *composited
 // says whether it did (the fixed-shape instances, samples per ray dividing the 384-point workgroup tile) - if not, `out` holds the
 // raw radiance field as always and the caller runs the compositing kernel

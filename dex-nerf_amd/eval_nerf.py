@@ -2,6 +2,8 @@
 """Build-owned counterpart of the reference's eval_nerf.py (:116-206): load a checkpoint (the reference's dict format:
 model_coarse_state_dict / model_fine_state_dict, optional height / width / focal_length), render a sweep of spherical
 poses in validation mode, optionally save RGB / disparity-style depth PNGs, and print the average time per image.
+`--depth-only --m-thres M` renders the depth and Dex depth maps alone (nerf.render_dex_depth): no colour is evaluated, no RGB PNG
+is written, and the maps go to dex_<view>.npz beside depth_<view>.png.
 
     python dex-nerf_amd/eval_nerf.py --checkpoint ckpt.ckpt --size 400 --views 8 --precision fp16 --savedir out/
 
@@ -51,11 +53,15 @@ def main(argv=None):
     ap.add_argument("--far", type=float, default=6.0)
     ap.add_argument("--white-background", action="store_true")
     ap.add_argument("--m-thres", type=int, default=0, help="> 0: also produce the Dex depth maps for thresholds 5..m")
+    ap.add_argument("--depth-only", action="store_true",
+                    help="render depth / Dex depth maps only (nerf.render_dex_depth: density sub-networks, no colour); needs --m-thres > 0")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"])
     ap.add_argument("--savedir", default="")
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
 
+    if args.depth_only and args.m_thres <= 0:
+        ap.error("--depth-only renders the Dex depth maps: give --m-thres > 0")
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     nerf.set_precision(args.precision)
     ck = torch.load(args.checkpoint, map_location="cpu")
@@ -79,6 +85,23 @@ def main(argv=None):
         pose = torch.from_numpy(syn.scene_pose(i, n_views=args.views)).to(dev)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        if args.depth_only:
+            with torch.no_grad():
+                ro, rd = nerf.get_ray_bundle(size, size, float(k_mat[0, 0]), pose, k_mat)
+                out = nerf.render_dex_depth(size, size, float(k_mat[0, 0]), coarse, fine, ro, rd, cfg, mode="validation",
+                                            encode_position_fn=ex, encode_direction_fn=ed, m_thres_cand=thres)
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+            depth = out[2] if fine is not None else out[0]
+            frames.append((None, depth, out[4:]))
+            if args.savedir:   # the expected depth as a PNG, every map (depth + one Dex depth per threshold) as float32
+                from PIL import Image
+                d = depth.cpu().numpy()
+                d = (255 * (d - d.min()) / max(d.max() - d.min(), 1e-8)).astype(np.uint8)
+                Image.fromarray(d).save(os.path.join(args.savedir, f"depth_{i:04d}.png"))
+                np.savez(os.path.join(args.savedir, f"dex_{i:04d}.npz"), depth=depth.cpu().numpy(), m_thres=np.asarray(thres, np.float32),
+                         dex=torch.stack(list(out[4:])).cpu().numpy())
+            continue
         with torch.no_grad():
             ro, rd = nerf.get_ray_bundle(size, size, float(k_mat[0, 0]), pose, k_mat)
             out = nerf.run_one_iter_of_nerf(size, size, float(k_mat[0, 0]), coarse, fine, ro, rd, cfg, mode="validation",

@@ -32,6 +32,8 @@ EXPORTS = (
     "dn_mlp_weight_grad_scratch_bytes", "dn_mlp_weight_grad_all_ws", "dn_mlp_weight_grad_pair_ws", "dn_render_rays_backward_ws",
     "dn_select_rays_draw_ndc",
     "dn_mlp_input_grad_packed_bytes", "dn_mlp_pack_input_grad", "dn_mlp_backward_input_workspace_bytes", "dn_mlp_backward_input",
+    "dn_mlp_density_desc", "dn_mlp_density_packed_bytes", "dn_mlp_pack_density", "dn_composite_density", "dn_density_resample",
+    "dn_render_depth_workspace_bytes", "dn_render_rays_depth",
 )
 
 
@@ -123,8 +125,18 @@ def _declare(lib):
     lib.dn_mlp_backward_input_workspace_bytes.restype = c_size_t
     lib.dn_mlp_backward_input.argtypes = [POINTER(MlpDesc), c_int, vp, vp, fp, fp, fp, c_int, fp, c_int64, c_int, fp, fp, fp, fp, vp,
                                           c_size_t, vp]
+    lib.dn_mlp_density_desc.argtypes = [POINTER(MlpDesc), POINTER(MlpDesc)]
+    lib.dn_mlp_density_packed_bytes.argtypes = [POINTER(MlpDesc), c_int]
+    lib.dn_mlp_density_packed_bytes.restype = c_size_t
+    lib.dn_mlp_pack_density.argtypes = [POINTER(MlpDesc), c_int, POINTER(c_void_p), POINTER(c_void_p), vp, vp]
+    lib.dn_composite_density.argtypes = [fp, fp, fp, c_int, fp, c_float, fp, c_int, c_int64, c_int, fp, fp, fp, vp]
+    lib.dn_density_resample.argtypes = [fp, fp, fp, c_int, fp, c_float, fp, c_int64, c_int, c_int, fp, fp, fp, vp]
+    lib.dn_render_depth_workspace_bytes.argtypes = [c_int64, c_int, c_int]
+    lib.dn_render_depth_workspace_bytes.restype = c_size_t
+    lib.dn_render_rays_depth.argtypes = [POINTER(MlpDesc), vp, POINTER(MlpDesc), vp, c_int, fp, c_int, c_int64, c_int, c_int, c_int,
+                                         c_float, fp, c_int, fp, fp, fp, fp, fp, fp, fp, fp, fp, vp, vp]
     for name in EXPORTS:
-        if name not in ("dn_last_error", "dn_mlp_packed_bytes", "dn_render_workspace_bytes",
+        if name not in ("dn_last_error", "dn_mlp_density_packed_bytes", "dn_render_depth_workspace_bytes", "dn_mlp_packed_bytes", "dn_render_workspace_bytes",
                         "dn_mlp_backward_packed_bytes", "dn_render_train_workspace_bytes",
                         "dn_mlp_input_grad_packed_bytes", "dn_mlp_backward_input_workspace_bytes"):
             getattr(lib, name).restype = c_int

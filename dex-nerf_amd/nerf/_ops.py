@@ -60,10 +60,15 @@ def render_precision():
     return _precision
 
 
-def fp16_range_guard(model):
+def fp16_range_guard(model, density=False):
     """True when an fp16 render of this FlexibleNeRFModel reports every hidden activation that leaves fp16's range
-    (dn_fp16_range_guard: the kernel instances that carry the tracker) - the condition for the fp16 render policy."""
+    (dn_fp16_range_guard: the kernel instances that carry the tracker) - the condition for the fp16 render policy.
+    density=True: the same question for its density sub-network (render_dex_depth)."""
     desc = MlpDesc(**{k: int(v) for k, v in model.desc_kwargs().items()})
+    if density:
+        full = desc
+        desc = MlpDesc()
+        check(lib().dn_mlp_density_desc(ctypes.byref(full), ctypes.byref(desc)), "dn_mlp_density_desc")
     return bool(lib().dn_fp16_range_guard(ctypes.byref(desc)))
 
 
@@ -326,6 +331,37 @@ class PackedMLP:
             raise RuntimeError(f"{what}: the packed network's 48-point inference stream is older than its core stream or the other "
                                "way round (it was last packed by a training entry point, which refreshes only the stream it reads) - "
                                "obtain the packed network with model.packed() (no train=True) before rendering")
+
+
+class PackedDensityMLP:
+    """MFMA fragment streams of the DENSITY sub-network of a FlexibleNeRFModel (dn_mlp_pack_density): its trunk and fc_alpha as
+    row 3 of a 4-row head - an ordinary packed no-view-direction network (`desc` is the density descriptor), so the inference
+    entry points (run_network_pts / run_network_rays, render_rays_depth) take it like a PackedMLP."""
+
+    def __init__(self, desc_kwargs, device, precision=None):
+        self.full_desc = MlpDesc(**{k: int(v) for k, v in desc_kwargs.items()})
+        self.desc = MlpDesc()
+        check(lib().dn_mlp_density_desc(ctypes.byref(self.full_desc), ctypes.byref(self.desc)), "dn_mlp_density_desc")
+        self.precision = _precision if precision is None else precision
+        nbytes = lib().dn_mlp_density_packed_bytes(ctypes.byref(self.full_desc), self.precision)
+        if nbytes == 0:
+            check(-1001, "dn_mlp_density_packed_bytes")
+        self.buffer = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        self.key = None   # parameter key both streams were packed from (always packed together)
+
+    def pack(self, weights, biases):
+        """weights/biases: the FULL network's device tensors in the reference parameter order."""
+        n = len(weights)
+        ws = [f32c(w.detach()) for w in weights]
+        bs = [f32c(b.detach()) for b in biases]
+        wp = (c_void_p * n)(*[w.data_ptr() for w in ws])
+        bp = (c_void_p * n)(*[b.data_ptr() for b in bs])
+        check(lib().dn_mlp_pack_density(ctypes.byref(self.full_desc), self.precision, wp, bp, ptr(self.buffer), stream()),
+              "dn_mlp_pack_density")
+        self._keep = (ws, bs)  # keep sources alive until the pack kernels have run on this stream
+
+    def require_fresh_inference_stream(self, what):
+        pass   # one key: the two streams are never packed apart
 
 
 def pack_backward(packed, weights, prec=None):
@@ -715,6 +751,75 @@ def render_rays(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, noise_s
         "dn_render_rays")
     render_rays.last_workspace = ws
     return rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f, dex
+
+
+def composite_density(rf, z, rd, noise, noise_std, m_thres):
+    """dn_composite_density: (depth, acc, dex (K,N) or None) from the sigma column of rf (N,S,4); any number of thresholds."""
+    rf, z = f32c(rf), f32c(z)
+    n, s = z.shape
+    dev = rf.device
+    rd = rd if (rd.dtype == torch.float32 and rd.dim() == 2 and rd.stride(1) == 1) else f32c(rd).reshape(-1, 3)
+    rd_ptr, rd_stride = _row_view(rd)
+    k = len(m_thres)
+    depth = torch.empty((n,), dtype=torch.float32, device=dev)
+    acc = torch.empty_like(depth)
+    dex = torch.empty((k, n), dtype=torch.float32, device=dev) if k else None
+    th = torch.tensor([float(m) for m in m_thres], dtype=torch.float32, device=dev) if k else None
+    nz = None if (noise is None or noise_std <= 0.0) else f32c(noise)
+    check(lib().dn_composite_density(ptr(rf), ptr(z), rd_ptr, rd_stride, ptr(nz), float(noise_std), ptr(th), k, n, s, ptr(depth),
+                                     ptr(acc), ptr(dex), stream()), "dn_composite_density")
+    return depth, acc, dex
+
+
+def density_resample(rf, z, rd, num_fine, noise=None, noise_std=0.0, u=None):
+    """dn_density_resample: coarse sigma compositing fused with fine_depths -> (depth_c, acc_c, z_fine)."""
+    rf, z = f32c(rf), f32c(z)
+    n, nc = z.shape
+    dev = rf.device
+    rd = rd if (rd.dtype == torch.float32 and rd.dim() == 2 and rd.stride(1) == 1) else f32c(rd).reshape(-1, 3)
+    rd_ptr, rd_stride = _row_view(rd)
+    depth = torch.empty((n,), dtype=torch.float32, device=dev)
+    acc = torch.empty_like(depth)
+    z_fine = torch.empty((n, nc + num_fine), dtype=torch.float32, device=dev)
+    nz = None if (noise is None or noise_std <= 0.0) else f32c(noise)
+    uu = None if u is None else f32c(u)
+    check(lib().dn_density_resample(ptr(rf), ptr(z), rd_ptr, rd_stride, ptr(nz), float(noise_std), ptr(uu), n, nc, num_fine,
+                                    ptr(depth), ptr(acc), ptr(z_fine), stream()), "dn_density_resample")
+    return depth, acc, z_fine
+
+
+def render_rays_depth(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, noise_std, m_thres, draws=None):
+    """dn_render_rays_depth: the depth-only predict_and_render_radiance forward for one ray chunk (no autograd, no colour) on
+    density packs (FlexibleNeRFModel.packed_density).  m_thres: a device tensor of K thresholds (any K) or None."""
+    rays = f32c(rays)
+    n = rays.shape[0]
+    dev = rays.device
+    draws = draws or {}
+    k = 0 if m_thres is None else int(m_thres.numel())
+    fine = num_fine > 0 and packed_f is not None
+    nf = num_fine if fine else 0
+    nbytes = lib().dn_render_depth_workspace_bytes(n, num_coarse, nf)
+    key = (dev, torch.cuda.current_stream().cuda_stream)
+    ws = _ws_cache.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        _ws_cache[key] = ws
+    ws = ws[:nbytes]   # (the status block is the last 256 bytes of what THIS call asked for)
+
+    def new(*shape):
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    depth_c, acc_c = new(n), new(n)
+    depth_f, acc_f = (new(n), new(n)) if fine else (None, None)
+    dex = new(k, n) if k else None
+    t = {name: (None if draws.get(name) is None else f32c(draws[name])) for name in ("t_rand", "noise_c", "u", "noise_f")}
+    check(lib().dn_render_rays_depth(
+        ctypes.byref(packed_c.desc), ptr(packed_c.buffer),
+        ctypes.byref(packed_f.desc) if fine else None, ptr(packed_f.buffer) if fine else None, packed_c.precision,
+        ptr(rays), rays.shape[1], n, num_coarse, nf, int(bool(lindisp)), float(noise_std),
+        ptr(m_thres) if k else None, k, ptr(t["t_rand"]), ptr(t["noise_c"]), ptr(t["u"]), ptr(t["noise_f"]),
+        ptr(depth_c), ptr(acc_c), ptr(depth_f), ptr(acc_f), ptr(dex), ptr(ws), stream()), "dn_render_rays_depth")
+    render_rays.last_workspace = ws
+    return depth_c, acc_c, depth_f, acc_f, dex
 
 
 def render_status_words(ws=None):

@@ -62,6 +62,7 @@ class FlexibleNeRFModel(torch.nn.Module):
             self.fc_out = torch.nn.Linear(hidden_size, 4)
         self.relu = torch.nn.functional.relu
         self._packed = {}
+        self._packed_density = {}
 
     # ---- HIP side ---------------------------------------------------------------------------------
     def linear_modules(self):
@@ -116,6 +117,26 @@ class FlexibleNeRFModel(torch.nn.Module):
                 pk.key = key
             if parts & _hip.PACK_G48:
                 pk.key48 = key
+        return pk
+
+    def packed_density(self, log_sampling_xyz=True, log_sampling_dir=True, precision=None):
+        """MFMA fragment streams of the DENSITY sub-network - the trunk + fc_alpha, all that depth, accumulation and the Dex
+        readout depend on (render_dex_depth) - for the current parameters.  A cache of its own beside packed()'s, with the same
+        staleness rule: re-packed when param_key() changed (storage, tensor version, any optimizer step or
+        mark_parameters_updated()) and always under stream capture.  A net without view directions is its own density net."""
+        mods = self.linear_modules()
+        dev = mods[0].weight.device
+        prec = _ops._precision if precision is None else precision
+        slot = (prec, bool(log_sampling_xyz), bool(log_sampling_dir), dev)
+        pk = self._packed_density.get(slot)
+        if pk is None:
+            pk = _ops.PackedDensityMLP(self.desc_kwargs(log_sampling_xyz, log_sampling_dir), dev, prec)
+            self._packed_density[slot] = pk
+        key = self.param_key()
+        capturing = dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
+        if pk.key != key or capturing:
+            pk.pack([m.weight for m in mods], [m.bias for m in mods])
+            pk.key = key
         return pk
 
     def _packed_slot(self, log_sampling_xyz=True, log_sampling_dir=True, precision=None):

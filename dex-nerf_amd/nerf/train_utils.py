@@ -329,3 +329,102 @@ def run_one_iter_of_nerf(height, width, focal_length, model_coarse, model_fine, 
             shapes = restore_shapes
         images = [img.reshape(shape) if img is not None else None for img, shape in zip(images, shapes)]
     return tuple(images)
+
+
+def _depth_fusable(model, embed_fn):
+    return (isinstance(model, FlexibleNeRFModel) and model.fused_ok() and isinstance(embed_fn, Embedder)
+            and embed_fn.num_encoding_functions == model.num_encoding_fn_xyz and embed_fn.include_input)
+
+
+_THRESHOLDS_ON_DEVICE = {}   # (thresholds, device) -> device tensor: one host-to-device copy per threshold set, none per render
+
+
+def _threshold_tensor(thres, dev):
+    if not len(thres):
+        return None
+    key = (tuple(float(m) for m in thres), str(dev))
+    t = _THRESHOLDS_ON_DEVICE.get(key)
+    if t is None:
+        if len(_THRESHOLDS_ON_DEVICE) >= 64:
+            _THRESHOLDS_ON_DEVICE.clear()
+        t = _THRESHOLDS_ON_DEVICE[key] = torch.tensor(key[0], dtype=torch.float32, device=dev)
+    return t
+
+
+def render_dex_depth(height, width, focal_length, model_coarse, model_fine, ray_origins, ray_directions, options,
+                     mode="validation", encode_position_fn=None, encode_direction_fn=None, m_thres_cand=None):
+    """The depth half of run_one_iter_of_nerf and nothing else: expected depth, accumulation and the Dex first-crossing depths
+    depend on sigma alone (reference nerf/volume_rendering_utils.py:33-58), so this render evaluates only the density
+    sub-networks (trunk + fc_alpha: FlexibleNeRFModel.packed_density) and composites no colour (dn_render_rays_depth).
+
+    Returns (depth_coarse, acc_coarse, depth_fine, acc_fine, *dex_fine[K]) - flat (N,) in train mode, image-shaped in validation
+    mode; num_fine == 0 / model_fine None gives None for the fine maps and the coarse Dex depths.  Rays, chunking, NDC, lindisp,
+    perturb / noise draws (rand, randn, rand, randn: the generator ends where a full render leaves it) follow
+    run_one_iter_of_nerf; the number of thresholds is not limited.  No-grad only, device tensors only, networks the fused kernels
+    cover only: anything else raises.  Follows nerf.set_render_policy like every no-grad render (guarded fp16 under 'bf16')."""
+    _require_device(ray_directions, "render_dex_depth")
+    _require_device(ray_origins, "render_dex_depth")
+    opt = getattr(options.nerf, mode)
+    nc, nf = int(opt.num_coarse), int(opt.num_fine)
+    fine = nf > 0 and bool(model_fine)
+    models = [model_coarse] + ([model_fine] if fine else [])
+    for m in models:
+        if not _depth_fusable(m, encode_position_fn):
+            raise RuntimeError("render_dex_depth: needs FlexibleNeRFModel networks the fused HIP kernels cover (fused_ok()) and this "
+                               "package's position embedder with the network's encoding; there is no fallback")
+        _require_device(m.layer1.weight, "render_dex_depth")
+    if _wants_grad(*models) or inputs_need_grad(ray_origins, ray_directions):
+        raise RuntimeError("render_dex_depth is a no-grad render: call it under torch.no_grad() (or with parameters and rays that do "
+                           "not require grad); differentiable renders go through run_one_iter_of_nerf")
+    thres = _thresholds(m_thres_cand)
+    dev = ray_directions.device
+    img_shape = ray_directions.shape
+    if options.dataset.no_ndc is False:
+        ro, rd = ndc_rays(height, width, focal_length, 1.0, ray_origins, ray_directions)
+    else:
+        ro, rd = ray_origins, ray_directions
+    ro, rd = ro.reshape((-1, 3)).float(), rd.reshape((-1, 3)).float()
+    # ray rows without the view-direction columns: the density sub-network does not read them
+    rays = _ops.pack_ray_rows(ro.contiguous(), rd.contiguous(), None, options.dataset.near, options.dataset.far)
+    perturb = bool(opt.perturb)
+    std = float(opt.radiance_field_noise_std)
+    lindisp = bool(opt.lindisp)
+    lx = encode_position_fn.log_sampling
+    m_thres = _threshold_tensor(thres, dev)
+    prec = _ops.render_precision()
+    guarded = (prec != _ops._precision and not torch.cuda.is_current_stream_capturing() and not _FP16_RENDER_DISABLED[0]
+               and all(_ops.fp16_range_guard(m, density=True) for m in models))
+
+    def render_chunks(prec):
+        pc = model_coarse.packed_density(lx, True, precision=prec)
+        pf = model_fine.packed_density(lx, True, precision=prec) if fine else None
+        chunks, status = [], []
+        for batch in get_minibatches(rays, chunksize=opt.chunksize):
+            n = batch.shape[0]
+            draws = {}   # the reference's order (train_utils.py:92-202), as in predict_and_render_radiance
+            if perturb:
+                draws["t_rand"] = torch.rand((n, nc), dtype=torch.float32, device=dev)
+            if std > 0.0:
+                draws["noise_c"] = torch.randn((n, nc), dtype=torch.float32, device=dev)
+            if fine and perturb:
+                draws["u"] = torch.rand((n, nf), dtype=torch.float32, device=dev)
+            if fine and std > 0.0:
+                draws["noise_f"] = torch.randn((n, nc + nf), dtype=torch.float32, device=dev)
+            depth_c, acc_c, depth_f, acc_f, dex = _ops.render_rays_depth(pc, pf, batch, nc, nf if fine else 0, lindisp, std, m_thres,
+                                                                        draws)
+            status.append(_ops.render_status_words())
+            chunks.append([depth_c, acc_c, depth_f, acc_f] + ([] if dex is None else [dex[k] for k in range(dex.shape[0])]))
+        return chunks, status
+
+    chunks, status = render_chunks(prec if guarded else _ops._precision)
+    if guarded and status and int(torch.stack(status).sum().item()) > 0:
+        # some chunk's fp16 render left fp16's range: the whole call again in bf16 (one host read per image, not per chunk)
+        _warn_fp16_range()
+        chunks, _ = render_chunks(_ops._precision)
+    if len(chunks) == 1:
+        maps = list(chunks[0])
+    else:
+        maps = [torch.cat(col, dim=0) if col[0] is not None else None for col in zip(*chunks)]
+    if mode == "validation":
+        maps = [m.reshape(img_shape[:-1]) if m is not None else None for m in maps]
+    return tuple(maps)
