@@ -64,12 +64,8 @@ def fp16_range_guard(model, density=False):
     """True when an fp16 render of this FlexibleNeRFModel reports every hidden activation that leaves fp16's range
     (dn_fp16_range_guard: the kernel instances that carry the tracker) - the condition for the fp16 render policy.
     density=True: the same question for its density sub-network (render_dex_depth)."""
-    desc = MlpDesc(**{k: int(v) for k, v in model.desc_kwargs().items()})
-    if density:
-        full = desc
-        desc = MlpDesc()
-        check(lib().dn_mlp_density_desc(ctypes.byref(full), ctypes.byref(desc)), "dn_mlp_density_desc")
-    return bool(lib().dn_fp16_range_guard(ctypes.byref(desc)))
+    desc = _desc(model.desc_kwargs())
+    return bool(lib().dn_fp16_range_guard(ctypes.byref(_density_desc(desc) if density else desc)))
 
 
 def get_precision():
@@ -131,10 +127,74 @@ def s8_grad_stats(grads=None):
     return {"saturated": sat / max(sampled, 1), "floor": floor / max(sampled, 1), "sampled": sampled, "scale": scales}
 
 
-def _row_view(t):
-    """(pointer, row stride in floats) of a (N,3)-like fp32 view whose last dim is contiguous."""
-    assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1
-    return c_void_p(t.data_ptr()), int(t.stride(0))
+# ---- marshalling: each rule of the C ABI's calling convention once -----------------------------------------------------
+def _desc(desc_kwargs):
+    return MlpDesc(**{k: int(v) for k, v in desc_kwargs.items()})
+
+
+def _density_desc(full):
+    """Descriptor of the density sub-network (trunk + fc_alpha, no view directions) of the network `full` describes."""
+    desc = MlpDesc()
+    check(lib().dn_mlp_density_desc(ctypes.byref(full), ctypes.byref(desc)), "dn_mlp_density_desc")
+    return desc
+
+
+def _sized(nbytes, what):
+    """A *_bytes answer of the library; 0 means the shape is outside the kernels: raise its error."""
+    if nbytes == 0:
+        check(-1001, what)
+    return nbytes
+
+
+def _ptr_array(tensors, sources=False):
+    """(void* array of the tensors' device pointers, the tensors it points at).  sources=True: parameters a pack kernel reads -
+    detached and made fp32-contiguous first (possibly copies): the caller keeps the returned list alive until that kernel has
+    run on this stream.  Otherwise the pointers are those of the very tensors given (outputs: dense views)."""
+    if sources:
+        tensors = [f32c(t.detach()) for t in tensors]
+    return (c_void_p * len(tensors))(*[t.data_ptr() for t in tensors]), tensors
+
+
+def _view_ptrs(views):
+    """The (dW pointers, db pointers) arrays of [(dW, db)] in linear_modules() order; (None, None) for None."""
+    if views is None:
+        return None, None
+    return _ptr_array([w for w, _ in views])[0], _ptr_array([b for _, b in views])[0]
+
+
+def _dir_rows(rd):
+    """(pointer, row stride in floats, the tensor to keep until the launch) of ray directions: an fp32 (N,3)-like view whose last
+    dim is contiguous goes as it is (a column slice of the ray rows: no copy), anything else as a contiguous fp32 copy."""
+    if not (rd.dtype == torch.float32 and rd.dim() == 2 and rd.stride(1) == 1):
+        rd = f32c(rd).reshape(-1, 3)
+    assert rd.is_cuda
+    return c_void_p(rd.data_ptr()), int(rd.stride(0)), rd
+
+
+def _draw_tensors(draws):
+    """(t_rand, noise_c, u, noise_f) of a ray chunk's `draws` dict as fp32-contiguous tensors, None where not drawn - the order
+    of the render entry points' arguments."""
+    given = draws or {}
+    return [None if given.get(name) is None else f32c(given[name]) for name in ("t_rand", "noise_c", "u", "noise_f")]
+
+
+def _ray_outputs(n, image, dev):
+    """(rays (n,11), target (n,3) | None, fp32-contiguous image | None, its channel count) of the select_rays* wrappers."""
+    rays = torch.empty((n, 11), dtype=torch.float32, device=dev)
+    if image is None:
+        return rays, None, None, 0
+    img = f32c(image)
+    return rays, torch.empty((n, 3), dtype=torch.float32, device=dev), img, img.shape[-1]
+
+
+def zeroed_grad_views(shapes, dev):
+    """[(dW, db)] for `shapes` = [(out, in)] in linear_modules() order, as views of ONE zero-filled fp32 buffer."""
+    flat = torch.zeros(sum(o * i + o for o, i in shapes), dtype=torch.float32, device=dev)
+    out, off = [], 0
+    for o, i in shapes:
+        out.append((flat[off:off + o * i].view(o, i), flat[off + o * i:off + o * i + o]))
+        off += o * i + o
+    return out
 
 
 # ------------------------------------------------------------------------------------------------
@@ -151,12 +211,7 @@ def select_rays(height, width, rinv, origin, fx, cx, cy, near, far, pixel_index,
     pix = pixel_index.contiguous()
     assert pix.dtype == torch.int64 and pix.is_cuda
     n = pix.numel()
-    rays = torch.empty((n, 11), dtype=torch.float32, device=pix.device)
-    target, img, channels = None, None, 0
-    if image is not None:
-        img = f32c(image)
-        channels = img.shape[-1]
-        target = torch.empty((n, 3), dtype=torch.float32, device=pix.device)
+    rays, target, img, channels = _ray_outputs(n, image, pix.device)
     check(lib().dn_select_rays(height, width, host_floats(rinv), host_floats(origin), float(fx), float(cx), float(cy), float(near),
                                float(far), ptr(pix), n, ptr(img), channels, ptr(rays), ptr(target), stream()), "dn_select_rays")
     return rays, target
@@ -167,12 +222,7 @@ def select_rays_indirect(height, width, cams, view, near, far, pixel_index, imag
     pix = pixel_index.contiguous()
     assert pix.dtype == torch.int64 and view.dtype == torch.int32 and cams.dtype == torch.float32 and cams.is_contiguous()
     n = pix.numel()
-    rays = torch.empty((n, 11), dtype=torch.float32, device=pix.device)
-    target, img, channels = None, None, 0
-    if images is not None:
-        img = f32c(images)
-        channels = img.shape[-1]
-        target = torch.empty((n, 3), dtype=torch.float32, device=pix.device)
+    rays, target, img, channels = _ray_outputs(n, images, pix.device)
     check(lib().dn_select_rays_indirect(height, width, ptr(cams), ptr(view), float(near), float(far), ptr(pix), n, ptr(img), channels,
                                         ptr(rays), ptr(target), stream()), "dn_select_rays_indirect")
     return rays, target
@@ -210,12 +260,7 @@ def select_rays_draw(height, width, cams, view, near, far, rng_state, n_rays, im
     ndc_focal, ndc_near, ...) warps them, the view direction that of the unwarped ray, near / far as given."""
     assert (view is None or view.dtype == torch.int32) and cams.dtype == torch.float32 and cams.is_contiguous() and rng_state.dtype == torch.int32
     dev = cams.device
-    rays = torch.empty((n_rays, 11), dtype=torch.float32, device=dev)
-    target, img, channels = None, None, 0
-    if images is not None:
-        img = f32c(images)
-        channels = img.shape[-1]
-        target = torch.empty((n_rays, 3), dtype=torch.float32, device=dev)
+    rays, target, img, channels = _ray_outputs(n_rays, images, dev)
     pix = torch.empty((n_rays,), dtype=torch.int64, device=dev) if want_pixels else None
     if ndc_focal is not None:
         check(lib().dn_select_rays_draw_ndc(height, width, ptr(cams), ptr(view), int(cams.shape[0]), float(near), float(far), ptr(rng_state), n_rays,
@@ -295,17 +340,32 @@ def positional_encoding(x, num_fns, include_input=True, log_sampling=True):
 
 
 # ------------------------------------------------------------------------------------------------
-class PackedMLP:
+class _Packed:
+    """What the packed forms of a network share: the descriptor the kernels get, the precision, the device buffer (sized by the
+    library) and the marshalling of the parameters for a pack call.  The subclasses differ in `pack` and in
+    `require_fresh_inference_stream`."""
+
+    def __init__(self, desc, device, precision, packed_bytes, what):
+        self.desc = desc
+        self.precision = _precision if precision is None else precision
+        self.buffer = torch.empty(_sized(packed_bytes(self.precision), what), dtype=torch.uint8, device=device)
+        self.key = None          # parameter key the streams (PackedMLP: the core stream) were packed from
+
+    def _sources(self, weights, biases):
+        """(weight pointers, bias pointers) of device tensors in the reference parameter order."""
+        wp, ws = _ptr_array(weights, sources=True)
+        bp, bs = _ptr_array(biases, sources=True)
+        self._keep = (ws, bs)  # keep sources alive until the pack kernels have run on this stream
+        return wp, bp
+
+
+class PackedMLP(_Packed):
     """MFMA fragment stream of one FlexibleNeRFModel, rebuilt when the parameters change."""
 
     def __init__(self, desc_kwargs, device, precision=None):
-        self.desc = MlpDesc(**{k: int(v) for k, v in desc_kwargs.items()})
-        self.precision = _precision if precision is None else precision
-        nbytes = lib().dn_mlp_packed_bytes(ctypes.byref(self.desc), self.precision)
-        if nbytes == 0:
-            check(-1001, "dn_mlp_packed_bytes")
-        self.buffer = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        self.key = None          # parameter key the core stream (bias tiles + pieces: every kernel but one) was packed from
+        desc = _desc(desc_kwargs)
+        super().__init__(desc, device, precision, lambda prec: lib().dn_mlp_packed_bytes(ctypes.byref(desc), prec), "dn_mlp_packed_bytes")
+        # self.key: the core stream (bias tiles + pieces: every kernel but one)
         self.key48 = None        # ... and the stream of the 48-point inference kernel: a training loop leaves it stale until a render
         self.buffers_bwd = {}    # transposed streams for the backward-data chain, per training precision code (the 8-bit-saved-tensor
         self.keys_bwd = {}       # mode runs the 48-point chain: another stream), packed on first training use
@@ -314,14 +374,9 @@ class PackedMLP:
 
     def pack(self, weights, biases, parts=_hip.PACK_ALL):
         """weights/biases: lists of device tensors in the reference parameter order; parts: _hip.PACK_CORE | _hip.PACK_G48."""
-        n = len(weights)
-        ws = [f32c(w.detach()) for w in weights]
-        bs = [f32c(b.detach()) for b in biases]
-        wp = (c_void_p * n)(*[w.data_ptr() for w in ws])
-        bp = (c_void_p * n)(*[b.data_ptr() for b in bs])
+        wp, bp = self._sources(weights, biases)
         check(lib().dn_mlp_pack_parts(ctypes.byref(self.desc), self.precision, wp, bp, ptr(self.buffer), int(parts), stream()),
               "dn_mlp_pack_parts")
-        self._keep = (ws, bs)  # keep sources alive until the pack kernel has run on this stream
 
     def require_fresh_inference_stream(self, what):
         """The inference entry points may run the 48-point kernel, whose stream lives behind the core one in `buffer` and is
@@ -333,32 +388,22 @@ class PackedMLP:
                                "obtain the packed network with model.packed() (no train=True) before rendering")
 
 
-class PackedDensityMLP:
+class PackedDensityMLP(_Packed):
     """MFMA fragment streams of the DENSITY sub-network of a FlexibleNeRFModel (dn_mlp_pack_density): its trunk and fc_alpha as
     row 3 of a 4-row head - an ordinary packed no-view-direction network (`desc` is the density descriptor), so the inference
-    entry points (run_network_pts / run_network_rays, render_rays_depth) take it like a PackedMLP."""
+    entry points (run_network_pts / run_network_rays, render_rays_depth) take it like a PackedMLP.  One key: its two streams are
+    always packed together."""
 
     def __init__(self, desc_kwargs, device, precision=None):
-        self.full_desc = MlpDesc(**{k: int(v) for k, v in desc_kwargs.items()})
-        self.desc = MlpDesc()
-        check(lib().dn_mlp_density_desc(ctypes.byref(self.full_desc), ctypes.byref(self.desc)), "dn_mlp_density_desc")
-        self.precision = _precision if precision is None else precision
-        nbytes = lib().dn_mlp_density_packed_bytes(ctypes.byref(self.full_desc), self.precision)
-        if nbytes == 0:
-            check(-1001, "dn_mlp_density_packed_bytes")
-        self.buffer = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        self.key = None   # parameter key both streams were packed from (always packed together)
+        full = self.full_desc = _desc(desc_kwargs)
+        super().__init__(_density_desc(full), device, precision, lambda prec: lib().dn_mlp_density_packed_bytes(ctypes.byref(full), prec),
+                         "dn_mlp_density_packed_bytes")
 
     def pack(self, weights, biases):
         """weights/biases: the FULL network's device tensors in the reference parameter order."""
-        n = len(weights)
-        ws = [f32c(w.detach()) for w in weights]
-        bs = [f32c(b.detach()) for b in biases]
-        wp = (c_void_p * n)(*[w.data_ptr() for w in ws])
-        bp = (c_void_p * n)(*[b.data_ptr() for b in bs])
+        wp, bp = self._sources(weights, biases)
         check(lib().dn_mlp_pack_density(ctypes.byref(self.full_desc), self.precision, wp, bp, ptr(self.buffer), stream()),
               "dn_mlp_pack_density")
-        self._keep = (ws, bs)  # keep sources alive until the pack kernels have run on this stream
 
     def require_fresh_inference_stream(self, what):
         pass   # one key: the two streams are never packed apart
@@ -369,14 +414,10 @@ def pack_backward(packed, weights, prec=None):
     prec = train_precision(packed) if prec is None else prec
     buf = packed.buffers_bwd.get(prec)
     if buf is None:
-        nbytes = lib().dn_mlp_backward_packed_bytes(ctypes.byref(packed.desc), prec)
-        if nbytes == 0:
-            check(-1001, "dn_mlp_backward_packed_bytes")
+        nbytes = _sized(lib().dn_mlp_backward_packed_bytes(ctypes.byref(packed.desc), prec), "dn_mlp_backward_packed_bytes")
         buf = packed.buffers_bwd[prec] = torch.empty(nbytes, dtype=torch.uint8, device=packed.buffer.device)
-    ws = [f32c(w.detach()) for w in weights]
-    wp = (c_void_p * len(ws))(*[w.data_ptr() for w in ws])
+    wp, packed._keep_bwd = _ptr_array(weights, sources=True)
     check(lib().dn_mlp_pack_backward(ctypes.byref(packed.desc), prec, wp, ptr(buf), stream()), "dn_mlp_pack_backward")
-    packed._keep_bwd = ws
 
 
 def ensure_backward_stream(model, packed, prec=None):
@@ -394,15 +435,12 @@ def ensure_input_grad_stream(model, packed):
     key = model.param_key()
     if packed.key_ig != key or torch.cuda.is_current_stream_capturing():
         if packed.buffer_ig is None:
-            nbytes = lib().dn_mlp_input_grad_packed_bytes(ctypes.byref(packed.desc), packed.precision)
-            if nbytes == 0:
-                check(-1001, "dn_mlp_input_grad_packed_bytes")
+            nbytes = _sized(lib().dn_mlp_input_grad_packed_bytes(ctypes.byref(packed.desc), packed.precision),
+                            "dn_mlp_input_grad_packed_bytes")
             packed.buffer_ig = torch.empty(nbytes, dtype=torch.uint8, device=packed.buffer.device)
-        ws = [f32c(m.weight.detach()) for m in model.linear_modules()]
-        wp = (c_void_p * len(ws))(*[w.data_ptr() for w in ws])
+        wp, packed._keep_ig = _ptr_array([m.weight for m in model.linear_modules()], sources=True)
         check(lib().dn_mlp_pack_input_grad(ctypes.byref(packed.desc), packed.precision, wp, ptr(packed.buffer_ig), stream()),
               "dn_mlp_pack_input_grad")
-        packed._keep_ig = ws
         packed.key_ig = key
     return packed.buffer_ig
 
@@ -451,10 +489,10 @@ def pack_train_pair(model_a, model_b, logs):
         arrays, keep = [], []
         for model in (model_a, model_b):
             mods = model.linear_modules()
-            ws = [f32c(m.weight.detach()) for m in mods]
-            bs = [f32c(m.bias.detach()) for m in mods]
+            wp, ws = _ptr_array([m.weight for m in mods], sources=True)
+            bp, bs = _ptr_array([m.bias for m in mods], sources=True)
             keep.append((ws, bs))
-            arrays.append(((c_void_p * len(ws))(*[w.data_ptr() for w in ws]), (c_void_p * len(bs))(*[b.data_ptr() for b in bs])))
+            arrays.append((wp, bp))
         check(lib().dn_mlp_pack_train_pair(ctypes.byref(pa.desc), arrays[0][0], arrays[0][1], ptr(pa.buffer), ptr(pa.buffers_bwd[prec]),
                                            arrays[1][0], arrays[1][1], ptr(pb.buffer), ptr(pb.buffers_bwd[prec]), stream()),
               "dn_mlp_pack_train_pair")
@@ -552,33 +590,26 @@ def set_deterministic_weight_gradients(on):
     _DETERMINISTIC_WGRAD[0] = bool(on)
 
 
-def _wgrad_scratch(packed, n_networks):
-    """(tensor, bytes) of reduction scratch for this architecture, or (None, 0).  A fresh stream-ordered allocation per call (the
-    caching allocator hands the same block back every step; inside a graph capture it belongs to the graph's pool)."""
+def _wgrad_scratch(n_networks, *packs):
+    """(tensor, bytes) of reduction scratch for a launch over `n_networks` networks of these architectures - ONE allocation of
+    the largest need - or (None, 0).  A fresh stream-ordered allocation per call (the caching allocator hands the same block
+    back every step; inside a graph capture it belongs to the graph's pool)."""
     if not _DETERMINISTIC_WGRAD[0]:
         return None, 0
-    nbytes = int(lib().dn_mlp_weight_grad_scratch_bytes(ctypes.byref(packed.desc), int(n_networks)))
+    nbytes = max(int(lib().dn_mlp_weight_grad_scratch_bytes(ctypes.byref(pk.desc), int(n_networks))) for pk in packs)
     if nbytes <= 0:
         return None, 0
-    return torch.empty(nbytes, dtype=torch.uint8, device=packed.buffer.device), nbytes
+    return torch.empty(nbytes, dtype=torch.uint8, device=packs[0].buffer.device), nbytes
 
 
 def mlp_weight_grad_all(packed, act, grads, n_points, shapes, s8=False, prec=None):
     """bf16 buffers: every layer's (dW, db) in one launch.  `shapes` = [(out, in)] in linear_modules() order; returns
     [(dW, db)] as views of ONE zero-filled fp32 buffer.  s8: the buffers are in the 8-bit unit layout (convert_saved_s8)."""
-    dev = act.device
-    total = sum(o * i + o for o, i in shapes)
-    flat = torch.zeros(total, dtype=torch.float32, device=dev)
-    out, off = [], 0
-    for o, i in shapes:
-        d_w = flat[off:off + o * i].view(o, i); off += o * i
-        d_b = flat[off:off + o]; off += o
-        out.append((d_w, d_b))
-    wp = (c_void_p * len(out))(*[w.data_ptr() for w, _ in out])
-    bp = (c_void_p * len(out))(*[b.data_ptr() for _, b in out])
+    out = zeroed_grad_views(shapes, act.device)
+    wp, bp = _view_ptrs(out)
     if prec is None:
         prec = _hip.PREC_BF16_S8 if s8 else packed.precision
-    scratch, nbytes = _wgrad_scratch(packed, 1)
+    scratch, nbytes = _wgrad_scratch(1, packed)
     check(lib().dn_mlp_weight_grad_all_ws(ctypes.byref(packed.desc), prec, ptr(act), ptr(grads), n_points, wp, bp, ptr(scratch), nbytes, stream()),
           "dn_mlp_weight_grad_all")
     return out
@@ -587,9 +618,8 @@ def mlp_weight_grad_all(packed, act, grads, n_points, shapes, s8=False, prec=Non
 def mlp_weight_grad_all_into(packed, act, grads, n_points, views, prec=None):
     """The same launch accumulating into caller-owned (dW, db) tensors (dense fp32 with the nn.Linear shapes, e.g. the
     `.grad` views of a parallel.FlatGradBucket, already zeroed for this step)."""
-    wp = (c_void_p * len(views))(*[w.data_ptr() for w, _ in views])
-    bp = (c_void_p * len(views))(*[b.data_ptr() for _, b in views])
-    scratch, nbytes = _wgrad_scratch(packed, 1)
+    wp, bp = _view_ptrs(views)
+    scratch, nbytes = _wgrad_scratch(1, packed)
     check(lib().dn_mlp_weight_grad_all_ws(ctypes.byref(packed.desc), packed.precision if prec is None else prec, ptr(act), ptr(grads),
                                           n_points, wp, bp, ptr(scratch), nbytes, stream()), "dn_mlp_weight_grad_all")
 
@@ -631,8 +661,7 @@ def volume_render_fwd(rf, z, rd, noise, noise_std, white, m_thres, want_weights=
     rf, z = f32c(rf), f32c(z)
     n, s = z.shape
     dev = rf.device
-    rd = rd if (rd.dtype == torch.float32 and rd.dim() == 2 and rd.stride(1) == 1) else f32c(rd).reshape(-1, 3)
-    rd_ptr, rd_stride = _row_view(rd)
+    rd_ptr, rd_stride, rd = _dir_rows(rd)
     k = len(m_thres)
     rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
     disp = torch.empty((n,), dtype=torch.float32, device=dev)
@@ -650,8 +679,7 @@ def volume_render_fwd(rf, z, rd, noise, noise_std, white, m_thres, want_weights=
 def volume_render_bwd(rf, z, rd, noise, noise_std, white, g_rgb, g_depth, g_acc, g_disp, g_weights):
     rf, z = f32c(rf), f32c(z)
     n, s = z.shape
-    rd = rd if (rd.dtype == torch.float32 and rd.dim() == 2 and rd.stride(1) == 1) else f32c(rd).reshape(-1, 3)
-    rd_ptr, rd_stride = _row_view(rd)
+    rd_ptr, rd_stride, rd = _dir_rows(rd)
     g_rf = torch.empty((n, s, 4), dtype=torch.float32, device=rf.device)
     nz = None if (noise is None or noise_std <= 0.0) else f32c(noise)
     gs = [None if g is None else f32c(g) for g in (g_rgb, g_depth, g_acc, g_disp, g_weights)]
@@ -712,7 +740,30 @@ def fine_depths(z_coarse, weights, num_fine, u=None, want_samples=False):
     return (z_fine, zs) if want_samples else z_fine
 
 
-_ws_cache = {}
+_render_ws = {}   # current stream -> (cached workspace buffer, the bytes the latest render call on that stream asked for)
+
+
+def _stream_key():
+    # (the current device's current stream: the one the kernels are enqueued on, _hip.stream())
+    return torch.cuda.current_device(), torch.cuda.current_stream().cuda_stream
+
+
+def _render_workspace(dev, nbytes):
+    """Workspace of a no-grad render call on the current stream: one cached buffer per stream, grown when needed, and the record
+    of which bytes the LATEST call there used - its status block is their last 256 bytes (render_status_words)."""
+    key = _stream_key()
+    ws, _ = _render_ws.get(key, (None, 0))
+    if ws is None or ws.device != dev or ws.numel() < nbytes:
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    _render_ws[key] = (ws, nbytes)
+    return ws[:nbytes]
+
+
+def _latest_render_workspace():
+    if _stream_key() not in _render_ws:
+        raise RuntimeError("render_status_words / render_nonfinite_count: no render_rays / render_rays_depth call on this stream yet")
+    ws, nbytes = _render_ws[_stream_key()]
+    return ws[:nbytes]
 
 
 def render_rays(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, noise_std, white, m_thres, draws=None):
@@ -723,17 +774,10 @@ def render_rays(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, noise_s
     rays = f32c(rays)
     n = rays.shape[0]
     dev = rays.device
-    draws = draws or {}
     k = len(m_thres)
     fine = num_fine > 0 and packed_f is not None
     nf = num_fine if fine else 0
-    nbytes = lib().dn_render_workspace_bytes(n, num_coarse, nf)
-    key = (dev, torch.cuda.current_stream().cuda_stream)
-    ws = _ws_cache.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-        _ws_cache[key] = ws
-    ws = ws[:nbytes]   # (the status block is the last 256 bytes of what THIS call asked for)
+    ws = _render_workspace(dev, lib().dn_render_workspace_bytes(n, num_coarse, nf))
 
     def new(*shape):
         return torch.empty(shape, dtype=torch.float32, device=dev)
@@ -741,15 +785,14 @@ def render_rays(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, noise_s
     rgb_f, depth_f, acc_f = (new(n, 3), new(n), new(n)) if fine else (None, None, None)
     dex = new(k, n) if k else None
     prec = packed_c.precision
-    t = {name: (None if draws.get(name) is None else f32c(draws[name])) for name in ("t_rand", "noise_c", "u", "noise_f")}
+    t_rand, noise_c, u, noise_f = _draw_tensors(draws)
     check(lib().dn_render_rays(
         ctypes.byref(packed_c.desc), ptr(packed_c.buffer),
         ctypes.byref(packed_f.desc) if fine else None, ptr(packed_f.buffer) if fine else None, prec,
         ptr(rays), rays.shape[1], n, num_coarse, nf, int(bool(lindisp)), float(noise_std), int(bool(white)),
-        host_floats(m_thres), k, ptr(t["t_rand"]), ptr(t["noise_c"]), ptr(t["u"]), ptr(t["noise_f"]),
+        host_floats(m_thres), k, ptr(t_rand), ptr(noise_c), ptr(u), ptr(noise_f),
         ptr(rgb_c), ptr(depth_c), ptr(acc_c), ptr(rgb_f), ptr(depth_f), ptr(acc_f), ptr(dex), ptr(ws), stream()),
         "dn_render_rays")
-    render_rays.last_workspace = ws
     return rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f, dex
 
 
@@ -758,8 +801,7 @@ def composite_density(rf, z, rd, noise, noise_std, m_thres):
     rf, z = f32c(rf), f32c(z)
     n, s = z.shape
     dev = rf.device
-    rd = rd if (rd.dtype == torch.float32 and rd.dim() == 2 and rd.stride(1) == 1) else f32c(rd).reshape(-1, 3)
-    rd_ptr, rd_stride = _row_view(rd)
+    rd_ptr, rd_stride, rd = _dir_rows(rd)
     k = len(m_thres)
     depth = torch.empty((n,), dtype=torch.float32, device=dev)
     acc = torch.empty_like(depth)
@@ -776,8 +818,7 @@ def density_resample(rf, z, rd, num_fine, noise=None, noise_std=0.0, u=None):
     rf, z = f32c(rf), f32c(z)
     n, nc = z.shape
     dev = rf.device
-    rd = rd if (rd.dtype == torch.float32 and rd.dim() == 2 and rd.stride(1) == 1) else f32c(rd).reshape(-1, 3)
-    rd_ptr, rd_stride = _row_view(rd)
+    rd_ptr, rd_stride, rd = _dir_rows(rd)
     depth = torch.empty((n,), dtype=torch.float32, device=dev)
     acc = torch.empty_like(depth)
     z_fine = torch.empty((n, nc + num_fine), dtype=torch.float32, device=dev)
@@ -794,45 +835,37 @@ def render_rays_depth(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, n
     rays = f32c(rays)
     n = rays.shape[0]
     dev = rays.device
-    draws = draws or {}
     k = 0 if m_thres is None else int(m_thres.numel())
     fine = num_fine > 0 and packed_f is not None
     nf = num_fine if fine else 0
-    nbytes = lib().dn_render_depth_workspace_bytes(n, num_coarse, nf)
-    key = (dev, torch.cuda.current_stream().cuda_stream)
-    ws = _ws_cache.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-        _ws_cache[key] = ws
-    ws = ws[:nbytes]   # (the status block is the last 256 bytes of what THIS call asked for)
+    ws = _render_workspace(dev, lib().dn_render_depth_workspace_bytes(n, num_coarse, nf))
 
     def new(*shape):
         return torch.empty(shape, dtype=torch.float32, device=dev)
     depth_c, acc_c = new(n), new(n)
     depth_f, acc_f = (new(n), new(n)) if fine else (None, None)
     dex = new(k, n) if k else None
-    t = {name: (None if draws.get(name) is None else f32c(draws[name])) for name in ("t_rand", "noise_c", "u", "noise_f")}
+    t_rand, noise_c, u, noise_f = _draw_tensors(draws)
     check(lib().dn_render_rays_depth(
         ctypes.byref(packed_c.desc), ptr(packed_c.buffer),
         ctypes.byref(packed_f.desc) if fine else None, ptr(packed_f.buffer) if fine else None, packed_c.precision,
         ptr(rays), rays.shape[1], n, num_coarse, nf, int(bool(lindisp)), float(noise_std),
-        ptr(m_thres) if k else None, k, ptr(t["t_rand"]), ptr(t["noise_c"]), ptr(t["u"]), ptr(t["noise_f"]),
+        ptr(m_thres) if k else None, k, ptr(t_rand), ptr(noise_c), ptr(u), ptr(noise_f),
         ptr(depth_c), ptr(acc_c), ptr(depth_f), ptr(acc_f), ptr(dex), ptr(ws), stream()), "dn_render_rays_depth")
-    render_rays.last_workspace = ws
     return depth_c, acc_c, depth_f, acc_f, dex
 
 
 def render_status_words(ws=None):
-    """Device copy (no synchronisation) of the two status words of the last dn_render_rays call on this stream - see
-    render_nonfinite_count; the caller sums the copies of several chunks and reads them back once."""
-    ws = render_rays.last_workspace if ws is None else ws
+    """Device copy (no synchronisation) of the two status words of the last dn_render_rays / dn_render_rays_depth call on this
+    stream - see render_nonfinite_count; the caller sums the copies of several chunks and reads them back once."""
+    ws = _latest_render_workspace() if ws is None else ws
     return ws[ws.numel() - 256: ws.numel() - 248].view(torch.int32).clone()
 
 
 def render_nonfinite_count(ws=None):
-    """Status block of the last dn_render_rays call on this stream (synchronises): non-finite raw radiance-field samples met
-    by the compositing passes + waves of the fp16 network kernel that saw an activation leave fp16's range."""
-    ws = render_rays.last_workspace if ws is None else ws
+    """Status block of the last dn_render_rays / dn_render_rays_depth call on this stream (synchronises): non-finite raw
+    radiance-field samples met by the compositing passes + waves of the fp16 network kernel that saw an activation leave fp16's range."""
+    ws = _latest_render_workspace() if ws is None else ws
     words = ws[ws.numel() - 256: ws.numel() - 248].view(torch.int32).tolist()
     return int(words[0]) + int(words[1])
 
@@ -845,7 +878,6 @@ def render_rays_train(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, n
     rays = f32c(rays)
     n = rays.shape[0]
     dev = rays.device
-    draws = draws or {}
     k = len(m_thres)
     fine = num_fine > 0 and packed_f is not None
     nf = num_fine if fine else 0
@@ -864,16 +896,16 @@ def render_rays_train(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, n
     rgb_c, depth_c, acc_c = new(n, 3), new(n), new(n)
     rgb_f, depth_f, acc_f = (new(n, 3), new(n), new(n)) if fine else (None, None, None)
     dex = new(k, n) if k else None
-    t = {name: (None if draws.get(name) is None else f32c(draws[name])) for name in ("t_rand", "noise_c", "u", "noise_f")}
+    t_rand, noise_c, u, noise_f = _draw_tensors(draws)
     check(lib().dn_render_rays_train(
         ctypes.byref(packed_c.desc), ptr(packed_c.buffer),
         ctypes.byref(packed_f.desc) if fine else None, ptr(packed_f.buffer) if fine else None, prec,
         ptr(rays), rays.shape[1], n, num_coarse, nf, int(bool(lindisp)), float(noise_std), int(bool(white)),
-        host_floats(m_thres), k, ptr(t["t_rand"]), ptr(t["noise_c"]), ptr(t["u"]), ptr(t["noise_f"]),
+        host_floats(m_thres), k, ptr(t_rand), ptr(noise_c), ptr(u), ptr(noise_f),
         ptr(rgb_c), ptr(depth_c), ptr(acc_c), ptr(rgb_f), ptr(depth_f), ptr(acc_f), ptr(dex), ptr(ws),
         ptr(act_c), ptr(masks_c), ptr(act_f), ptr(masks_f), ptr(rng_state), int(bool(perturb)), stream()), "dn_render_rays_train")
-    saved = dict(rays=rays, ws=ws, act_c=act_c, masks_c=masks_c, act_f=act_f, masks_f=masks_f, noise_c=t["noise_c"],
-                 noise_f=t["noise_f"], n=n, nc=num_coarse, nf=nf, noise_std=float(noise_std), white=bool(white), prec=prec,
+    saved = dict(rays=rays, ws=ws, act_c=act_c, masks_c=masks_c, act_f=act_f, masks_f=masks_f, noise_c=noise_c,
+                 noise_f=noise_f, n=n, nc=num_coarse, nf=nf, noise_std=float(noise_std), white=bool(white), prec=prec,
                  rng_state=rng_state)
     return (rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f, dex), saved
 
@@ -893,19 +925,10 @@ def render_rays_backward(packed_c, packed_f, saved, g_c, g_f, views_c, views_f, 
     grads_c = grads_buf(packed_c, n * nc) if nets & 1 else None
     grads_f = grads_buf(packed_f, n * (nc + nf)) if (fine and nets & 2) else None
 
-    def arrays(views):
-        if views is None:
-            return None, None
-        return ((c_void_p * len(views))(*[w.data_ptr() for w, _ in views]), (c_void_p * len(views))(*[b.data_ptr() for _, b in views]))
-    wc, bc = arrays(views_c if nets & 1 else None)
-    wf, bf = arrays(views_f if (fine and nets & 2) else None)
+    wc, bc = _view_ptrs(views_c if nets & 1 else None)
+    wf, bf = _view_ptrs(views_f if (fine and nets & 2) else None)
     gs = [None if g is None else f32c(g) for g in tuple(g_c) + tuple(g_f)]
-    k_nets = 2 if (fine and nets == 3) else 1
-    scratch, scratch_bytes = _wgrad_scratch(packed_c, k_nets)
-    if fine:   # (two architectures: the larger need)
-        other = _wgrad_scratch(packed_f, k_nets)
-        if other[1] > scratch_bytes:
-            scratch, scratch_bytes = other
+    scratch, scratch_bytes = _wgrad_scratch(2 if (fine and nets == 3) else 1, packed_c, *([packed_f] if fine else []))
     check(lib().dn_render_rays_backward_ws(
         ctypes.byref(packed_c.desc), ptr(packed_c.buffers_bwd[prec]),
         ctypes.byref(packed_f.desc) if fine else None, ptr(packed_f.buffers_bwd[prec]) if fine else None, prec,

@@ -93,23 +93,14 @@ class FusedNetFn(torch.autograd.Function):
             _ops.mlp_weight_grad_all_into(pk, act, grads, n, views, prec=ctx.prec)
             ctx.sink.backward_done()
             return (None,) * (6 + 2 * len(mods))
-        res = _ops.mlp_weight_grad_all(pk, act, grads, n, [tuple(m.weight.shape) for m in mods], prec=ctx.prec)
-        flat = []
-        for d_w, d_b in res:
-            flat.extend((d_w, d_b))
-        return (None, None, None, None, None, None) + tuple(flat)
+        res = _ops.mlp_weight_grad_all(pk, act, grads, n, _weight_shapes(model), prec=ctx.prec)
+        return (None,) * 6 + tuple(t for pair in res for t in pair)
 
 
 def _packed_core(model, log_xyz, log_dir):
     """The packed network with its CORE stream fresh - what a 16-bit-saved training forward reads in every mode.  (In the default
     'bf16' mode `model.packed(train=True)` refreshes the 48-point stream instead; that stream and its key are left alone here.)"""
-    pk = model._packed_slot(log_xyz, log_dir)
-    key = model.param_key()
-    if pk.key != key or torch.cuda.is_current_stream_capturing():
-        mods = model.linear_modules()
-        pk.pack([m.weight for m in mods], [m.bias for m in mods], _hip.PACK_CORE)
-        pk.key = key
-    return pk
+    return model.packed(log_xyz, log_dir, parts=_hip.PACK_CORE)
 
 
 class FusedNetInputFn(torch.autograd.Function):
@@ -164,15 +155,17 @@ class FusedNetInputFn(torch.autograd.Function):
             _ops.mlp_weight_grad_all_into(pk, act, grads, n, views, prec=ctx.prec)
             ctx.sink.backward_done()
             return head + (None,) * (2 * len(mods))
-        res = _ops.mlp_weight_grad_all(pk, act, grads, n, [tuple(m.weight.shape) for m in mods], prec=ctx.prec)
+        res = _ops.mlp_weight_grad_all(pk, act, grads, n, _weight_shapes(model), prec=ctx.prec)
         return head + tuple(t for pair in res for t in pair)
 
 
-def _params_of(model):
-    params = []
-    for m in model.linear_modules():
-        params += [m.weight, m.bias]
-    return params
+def _params_of(*models):
+    """[weight, bias, ...] of the networks given (None skipped) in linear_modules() order: the autograd inputs of the Functions."""
+    return [p for model in models if model is not None for m in model.linear_modules() for p in (m.weight, m.bias)]
+
+
+def _weight_shapes(model):
+    return [tuple(m.weight.shape) for m in model.linear_modules()]
 
 
 class RenderRaysTrainFn(torch.autograd.Function):
@@ -219,7 +212,7 @@ class RenderRaysTrainFn(torch.autograd.Function):
         if views_c is not None and (views_f is not None or not fine):
             # gradients accumulate straight into the bucket's views; the fine half first so that its exchange is in flight
             # while the coarse half runs
-            keep = []
+            keep = []   # (the launches' saved gradients and scratch, until this function returns)
             if fine:
                 keep.append(_ops.render_rays_backward(pc, pf, saved, g_c, g_f, views_c, views_f, nets=2))
                 sink_f.backward_done()
@@ -227,16 +220,13 @@ class RenderRaysTrainFn(torch.autograd.Function):
             sink_c.backward_done()
             return (None,) * (7 + n_c + n_f)
 
-        def fresh(model):
-            shapes = [tuple(m.weight.shape) for m in model.linear_modules()]
-            flat = torch.zeros(sum(o * i + o for o, i in shapes), dtype=torch.float32, device=saved["rays"].device)
-            out, off = [], 0
-            for o, i in shapes:
-                out.append((flat[off:off + o * i].view(o, i), flat[off + o * i:off + o * i + o]))
-                off += o * i + o
-            return out
-        views_c = fresh(model_c)
-        views_f = fresh(model_f) if fine else None
+        dev = saved["rays"].device
+        views_c = _ops.zeroed_grad_views(_weight_shapes(model_c), dev)
+        views_f = _ops.zeroed_grad_views(_weight_shapes(model_f), dev) if fine else None
+        # The buffers this call returns (saved gradients, reduction scratch) are dropped while its kernels are still queued - as `keep`
+        # is above when this function returns.  Safe on one assumption: they were allocated on the stream the kernels were enqueued
+        # on, and PyTorch's caching allocator is stream-ordered - a freed block is handed out again only to work queued on that same
+        # stream, i.e. behind those kernels.
         _ops.render_rays_backward(pc, pf, saved, g_c, g_f, views_c, views_f, nets=3)
         grads = [t for pair in views_c for t in pair]
         if model_f is not None:
@@ -246,12 +236,7 @@ class RenderRaysTrainFn(torch.autograd.Function):
 
 def render_rays_train(model_c, model_f, rays, cfg, draws, thres, logs):
     """The fused training path of predict_and_render_radiance (both networks covered by the training kernels)."""
-    params = []
-    for model in (model_c, model_f):
-        if model is not None:
-            for m in model.linear_modules():
-                params += [m.weight, m.bias]
-    return RenderRaysTrainFn.apply(model_c, model_f, rays, cfg, draws, thres, logs, *params)
+    return RenderRaysTrainFn.apply(model_c, model_f, rays, cfg, draws, thres, logs, *_params_of(model_c, model_f))
 
 
 def mlp_encoded(model, x):
@@ -295,10 +280,7 @@ def run_network_fused_rays(model, rays, z_vals, log_xyz=True, log_dir=True):
         pts = ro[..., None, :] + rd[..., None, :] * z_vals[..., :, None]
         return _modules_on_points(model, pts, rays[..., -3:] if model.use_viewdirs else None, log_xyz, log_dir).reshape(n, s, 4)
     if needs_grad(model) and train_fused_ok(model):
-        params = []
-        for m in model.linear_modules():
-            params += [m.weight, m.bias]
-        return FusedNetFn.apply(model, rays, z_vals, None, log_xyz, log_dir, *params).reshape(n, s, 4)
+        return FusedNetFn.apply(model, rays, z_vals, None, log_xyz, log_dir, *_params_of(model)).reshape(n, s, 4)
     return _ops.run_network_rays(model.packed(log_xyz, log_dir), rays, z_vals)
 
 
@@ -311,8 +293,5 @@ def run_network_fused(model, pts, viewdirs, samples_per_ray, log_xyz=True, log_d
             return FusedNetInputFn.apply(model, pts, viewdirs, samples_per_ray, log_xyz, log_dir, *_params_of(model))
         return _modules_on_points(model, pts.reshape(-1, samples_per_ray, 3), viewdirs, log_xyz, log_dir)
     if needs_grad(model) and train_fused_ok(model):
-        params = []
-        for m in model.linear_modules():
-            params += [m.weight, m.bias]
-        return FusedNetFn.apply(model, pts, viewdirs, samples_per_ray, log_xyz, log_dir, *params)
+        return FusedNetFn.apply(model, pts, viewdirs, samples_per_ray, log_xyz, log_dir, *_params_of(model))
     return _ops.run_network_pts(model.packed(log_xyz, log_dir), pts, viewdirs, samples_per_ray)

@@ -85,34 +85,46 @@ class FlexibleNeRFModel(torch.nn.Module):
                     include_input_dir=self.include_input_dir, use_viewdirs=self.use_viewdirs,
                     log_sampling_xyz=log_sampling_xyz, log_sampling_dir=log_sampling_dir)
 
-    def packed(self, log_sampling_xyz=True, log_sampling_dir=True, train=False, precision=None):
-        """MFMA fragment streams for the current parameters (re-packed when any parameter changed).  `train=True` (the training
-        entry points) refreshes only the stream the training forward reads - the core one, or the 48-point kernel's in the
-        8-bit-saved-tensor mode - and leaves the other stale; the next caller without it - any render - brings both up to date.
-
-        "Changed" = a new storage, a bumped tensor version (every ordinary in-place op), or ANY optimizer step since the
-        last pack: fused optimizers (`Adam(fused=True)`) update parameters without bumping their versions."""
-        mods = self.linear_modules()
-        dev = mods[0].weight.device
+    def _pack_of(self, cache, cls, log_sampling_xyz, log_sampling_dir, precision):
+        """The pack object of (precision, sampling flags, device) in `cache`, created empty on first use."""
+        dev = self.layer1.weight.device
         prec = _ops._precision if precision is None else precision   # (a render may ask for fp16 beside the bf16 training pack)
+        slot = (prec, bool(log_sampling_xyz), bool(log_sampling_dir), dev)
+        pk = cache.get(slot)
+        if pk is None:
+            pk = cache[slot] = cls(self.desc_kwargs(log_sampling_xyz, log_sampling_dir), dev, prec)
+        return pk
+
+    def _stale(self, packed_from, key):
+        """True when a stream packed from parameter key `packed_from` has to be packed again for `key`: the parameters may have
+        changed - a new storage, a bumped tensor version (every ordinary in-place op), or ANY optimizer step since (fused
+        optimizers, `Adam(fused=True)`, update parameters without bumping their versions; mark_parameters_updated()) - and
+        ALWAYS under stream capture: a captured graph must contain the pack of the weights it runs on, whatever the host-side
+        cache believes at capture time."""
+        return packed_from != key or (self.layer1.weight.device.type == "cuda" and torch.cuda.is_current_stream_capturing())
+
+    def _weights_and_biases(self):
+        mods = self.linear_modules()
+        return [m.weight for m in mods], [m.bias for m in mods]
+
+    def packed(self, log_sampling_xyz=True, log_sampling_dir=True, train=False, precision=None, parts=None):
+        """MFMA fragment streams for the current parameters (re-packed when any parameter changed: _stale).  `train=True` (the
+        training entry points) refreshes only the stream the training forward reads - the 48-point kernel's in the
+        8-bit-saved-tensor mode (its forward is the 48-point kernel), the core one otherwise - and leaves the other stale; the
+        next caller without it - any render, which may read either - brings both up to date.  `parts` (_hip.PACK_CORE |
+        _hip.PACK_G48) restricts the refresh to these streams (still only where stale); the others and their keys are left alone."""
+        pk = self._pack_of(self._packed, _ops.PackedMLP, log_sampling_xyz, log_sampling_dir, precision)
+        if parts is None:
+            parts = _hip.PACK_ALL
+            if train:
+                parts = _hip.PACK_G48 if _ops.train_precision(pk) == _hip.PREC_BF16_S8 else _hip.PACK_CORE
         key = self.param_key()
-        pk = self._packed_slot(log_sampling_xyz, log_sampling_dir, prec)
-        # under stream capture always (re)pack: a captured graph must contain the pack of the weights it runs on, whatever
-        # the host-side cache believes at capture time
-        capturing = dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
-        # a training entry point reads ONE of the two streams: the 48-point one in the 8-bit-saved-tensor mode (its forward is the
-        # 48-point kernel), the core one otherwise; a render may read either
-        want_core = want_48 = True
-        if train:
-            want_48 = _ops.train_precision(pk) == _hip.PREC_BF16_S8
-            want_core = not want_48
-        parts = 0
-        if want_core and (pk.key != key or capturing):
-            parts |= _hip.PACK_CORE
-        if want_48 and (pk.key48 != key or capturing):
-            parts |= _hip.PACK_G48
+        if not self._stale(pk.key, key):
+            parts &= ~_hip.PACK_CORE
+        if not self._stale(pk.key48, key):
+            parts &= ~_hip.PACK_G48
         if parts:
-            pk.pack([m.weight for m in mods], [m.bias for m in mods], parts)
+            pk.pack(*self._weights_and_biases(), parts)
             if parts & _hip.PACK_CORE:
                 pk.key = key
             if parts & _hip.PACK_G48:
@@ -122,33 +134,17 @@ class FlexibleNeRFModel(torch.nn.Module):
     def packed_density(self, log_sampling_xyz=True, log_sampling_dir=True, precision=None):
         """MFMA fragment streams of the DENSITY sub-network - the trunk + fc_alpha, all that depth, accumulation and the Dex
         readout depend on (render_dex_depth) - for the current parameters.  A cache of its own beside packed()'s, with the same
-        staleness rule: re-packed when param_key() changed (storage, tensor version, any optimizer step or
-        mark_parameters_updated()) and always under stream capture.  A net without view directions is its own density net."""
-        mods = self.linear_modules()
-        dev = mods[0].weight.device
-        prec = _ops._precision if precision is None else precision
-        slot = (prec, bool(log_sampling_xyz), bool(log_sampling_dir), dev)
-        pk = self._packed_density.get(slot)
-        if pk is None:
-            pk = _ops.PackedDensityMLP(self.desc_kwargs(log_sampling_xyz, log_sampling_dir), dev, prec)
-            self._packed_density[slot] = pk
+        staleness rule (_stale).  A net without view directions is its own density net."""
+        pk = self._pack_of(self._packed_density, _ops.PackedDensityMLP, log_sampling_xyz, log_sampling_dir, precision)
         key = self.param_key()
-        capturing = dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
-        if pk.key != key or capturing:
-            pk.pack([m.weight for m in mods], [m.bias for m in mods])
+        if self._stale(pk.key, key):
+            pk.pack(*self._weights_and_biases())
             pk.key = key
         return pk
 
     def _packed_slot(self, log_sampling_xyz=True, log_sampling_dir=True, precision=None):
-        """The PackedMLP object of (precision, sampling flags, device), created empty on first use (packed() fills it)."""
-        dev = self.layer1.weight.device
-        prec = _ops._precision if precision is None else precision
-        slot = (prec, bool(log_sampling_xyz), bool(log_sampling_dir), dev)
-        pk = self._packed.get(slot)
-        if pk is None:
-            pk = _ops.PackedMLP(self.desc_kwargs(log_sampling_xyz, log_sampling_dir), dev, prec)
-            self._packed[slot] = pk
-        return pk
+        """The PackedMLP object of (precision, sampling flags, device), as it is (packed() brings it up to date)."""
+        return self._pack_of(self._packed, _ops.PackedMLP, log_sampling_xyz, log_sampling_dir, precision)
 
     def fused_ok(self):
         """True when the fused HIP kernel covers this configuration."""

@@ -89,19 +89,20 @@ def depth_error_img(D_est_tensor, D_gt_tensor, mask, abs_thres=1., dilate_radius
 
 
 # ---- hot path ------------------------------------------------------------------------------------------
-import os as _os
-_FP16_RENDER_DISABLED = [False]   # set once an fp16 render overflowed (see predict_and_render_radiance)
-_STAGEWISE_TRAINING = [bool(int(_os.environ.get("DEXNERF_STAGEWISE_TRAINING", "0")))]   # tests flip this to compare the two routes
+_FP16_RENDER_DISABLED = [False]   # set once an fp16 render overflowed (see _fp16_guard / _warn_fp16_range)
+_STAGEWISE_TRAINING = [bool(int(os.environ.get("DEXNERF_STAGEWISE_TRAINING", "0")))]   # tests flip this to compare the two routes
 
 
-def _fusable(network_fn, embed_fn, embeddirs_fn):
+def _fusable(network_fn, embed_fn, embeddirs_fn, density=False):
+    """True when the fused HIP kernels cover this network with these embedders; density=True asks for the position embedder
+    alone (render_dex_depth: the density sub-network reads no view direction)."""
     if not (isinstance(network_fn, FlexibleNeRFModel) and network_fn.fused_ok()):
         return False
     if not isinstance(embed_fn, Embedder):
         return False
     if embed_fn.num_encoding_functions != network_fn.num_encoding_fn_xyz or not embed_fn.include_input:
         return False
-    if network_fn.use_viewdirs:
+    if network_fn.use_viewdirs and not density:
         if not isinstance(embeddirs_fn, Embedder):
             return False
         if embeddirs_fn.num_encoding_functions != network_fn.num_encoding_fn_dir or not embeddirs_fn.include_input:
@@ -139,6 +140,71 @@ def _wants_grad(*models):
                for m in models)
 
 
+def _draws(n, nc, nf, fine, perturb, std, dev):
+    """The random numbers of one chunk of n rays, drawn in the reference's order (train_utils.py:92-202): rand, randn, rand, randn
+    -> t_rand (n, nc), noise_c (n, nc), u (n, nf), noise_f (n, nc + nf).  What the settings do not use is neither drawn nor
+    present.  A parity rule: every fused render path takes its draws from here."""
+    def rand(*shape):
+        return torch.rand(shape, dtype=torch.float32, device=dev)
+
+    def randn(*shape):
+        return torch.randn(shape, dtype=torch.float32, device=dev)
+    draws = {}
+    if perturb:
+        draws["t_rand"] = rand(n, nc)
+    if std > 0.0:
+        draws["noise_c"] = randn(n, nc)
+    if fine and perturb:
+        draws["u"] = rand(n, nf)
+    if fine and std > 0.0:
+        draws["noise_f"] = randn(n, nc + nf)
+    return draws
+
+
+def _fp16_guard(models, density=False):
+    """(precision code a no-grad render of `models` runs in, guarded?).  In the bf16 modes such a render runs the fp16 instances of
+    the kernels (_ops.set_render_policy), guarded against fp16's range by the status words the render leaves in its workspace.
+    Guarded = the render precision differs from the configured one, the stream is not capturing (a capture cannot read the
+    words back: no synchronisation inside it), no earlier fp16 render of this process overflowed, and every network's kernel
+    instance (density=True: its density sub-network's) carries the range tracker.  Otherwise: the configured precision."""
+    prec = _ops.render_precision()
+    guarded = (prec != _ops._precision and not torch.cuda.is_current_stream_capturing() and not _FP16_RENDER_DISABLED[0]
+               and all(_ops.fp16_range_guard(m, density=density) for m in models))
+    return (prec if guarded else _ops._precision), guarded
+
+
+def _warn_fp16_range():
+    import warnings
+    # stacklevel 4 = the caller of the public function: this <- _render_chunk / _render_chunks <- public function <- caller
+    warnings.warn("nerf: an fp16 render produced non-finite raw radiance-field values (a hidden activation beyond fp16's "
+                  "range, 65504); this render is repeated in bf16 and every later one in this process runs in bf16 "
+                  "(nerf.set_render_policy)", RuntimeWarning, stacklevel=4)
+    _FP16_RENDER_DISABLED[0] = True
+
+
+def _join_chunks(chunks):
+    """Per-chunk lists of maps -> one list, rows concatenated; a None column stays None.  A single chunk is returned as it is
+    (the very same tensors: cat would copy every map)."""
+    if len(chunks) == 1:
+        return list(chunks[0])
+    return [torch.cat(col, dim=0) if col[0] is not None else None for col in zip(*chunks)]
+
+
+def _render_chunks(rays, chunksize, render_chunk):
+    """The chunk loop of the image-level renders.  render_chunk(batch, status) -> maps renders one chunk: with a list as `status`
+    under the guarded-fp16 policy (a guarded chunk appends a device copy of the status words the guard reads), with None in the
+    configured precision.  The words of all chunks are summed and read back ONCE (one host synchronisation per image, not per
+    chunk); if some chunk left fp16's range: one warning and the whole call again in the configured precision."""
+    def run(status):
+        return [render_chunk(batch, status) for batch in get_minibatches(rays, chunksize=chunksize)]
+    status = []
+    chunks = run(status)
+    if status and int(torch.stack(status).sum().item()) > 0:
+        _warn_fp16_range()
+        chunks = run(None)   # (chunks that draw random numbers draw FRESH ones here, not those of the fp16 attempt)
+    return _join_chunks(chunks)
+
+
 def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, mode="train",
                                 encode_position_fn=None, encode_direction_fn=None, m_thres_cand=None):
     """One ray chunk through coarse sampling -> coarse net -> composite -> inverse-CDF resampling -> fine
@@ -148,7 +214,17 @@ def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, mo
     Supersets of the fork: m_thres_cand=None gives exactly six outputs (eval_nerf.py:175-187 unpacks six);
     num_fine == 0 / model_fine None returns None for the fine maps and the coarse Dex depths instead of the
     fork's NameError (:201).  RNG draw order matches the reference (rand, randn, rand, randn).
+    A no-grad render under the guarded-fp16 policy checks this chunk itself (one host read); if it left fp16's range it is
+    repeated in bf16 on the same draws.
     """
+    return _render_chunk(ray_batch, model_coarse, model_fine, options, mode, encode_position_fn, encode_direction_fn, m_thres_cand)
+
+
+def _render_chunk(ray_batch, model_coarse, model_fine, options, mode, encode_position_fn, encode_direction_fn, m_thres_cand,
+                  status=None, fp16_ok=True):
+    """predict_and_render_radiance.  status: a list - the image-level drivers' way to defer the fp16 guard: a guarded render
+    appends a copy of its status words (the workspace may be reused by the next chunk) instead of reading them; fp16_ok=False:
+    a no-grad render in the configured precision, unguarded."""
     _require_device(ray_batch, "predict_and_render_radiance")
     opt = getattr(options.nerf, mode)
     thres = _thresholds(m_thres_cand)
@@ -162,77 +238,47 @@ def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, mo
     dev = ray_batch.device
     use_viewdirs = ray_batch.shape[-1] > 8
 
-    def rand(*shape):
-        return torch.rand(shape, dtype=torch.float32, device=dev)
-
-    def randn(*shape):
-        return torch.randn(shape, dtype=torch.float32, device=dev)
+    def outputs(maps):
+        dex = maps[6]
+        return tuple(list(maps[:6]) + ([] if dex is None else [dex[k] for k in range(dex.shape[0])]))
 
     fused_models = (_fusable(model_coarse, encode_position_fn, encode_direction_fn)
                     and (not fine or _fusable(model_fine, encode_position_fn, encode_direction_fn))
                     and model_coarse.use_viewdirs == use_viewdirs)
     if fused_models and not _wants_grad(model_coarse, model_fine) and not inputs_need_grad(ray_batch):
-        # whole chunk in one C-ABI call (dn_render_rays); draws generated in the reference's order
-        draws = {}
-        if perturb:
-            draws["t_rand"] = rand(n, nc)
-        if std > 0.0:
-            draws["noise_c"] = randn(n, nc)
-        if fine and perturb:
-            draws["u"] = rand(n, nf)
-        if fine and std > 0.0:
-            draws["noise_f"] = randn(n, nc + nf)
+        # whole chunk in one C-ABI call (dn_render_rays)
+        draws = _draws(n, nc, nf, fine, perturb, std, dev)
         lx = encode_position_fn.log_sampling
         ld = encode_direction_fn.log_sampling if use_viewdirs else True
-        # bf16 modes: a no-grad render runs the fp16 instance of the kernel (_ops.set_render_policy), guarded against fp16's
-        # range by the non-finite count the compositing passes leave in the workspace; stream capture cannot read it back
-        # (no synchronisation inside a capture), so captured renders stay in the configured precision
-        prec = _ops.render_precision()
-        guarded = (prec != _ops._precision and not torch.cuda.is_current_stream_capturing() and not _FP16_RENDER_DISABLED[0]
-                   and _ops.fp16_range_guard(model_coarse) and (not fine or _ops.fp16_range_guard(model_fine)))
-        if not guarded:
-            prec = _ops._precision
-        pc = model_coarse.packed(lx, ld, precision=prec)
-        pf = model_fine.packed(lx, ld, precision=prec) if fine else None
-        maps = _ops.render_rays(pc, pf, ray_batch, nc, nf if fine else 0, lindisp, std, white, thres, draws)
-        if guarded and _DEFERRED_GUARD[0] is not None:
-            # called from run_one_iter_of_nerf: the status words of every chunk are read ONCE per image, there (no host
-            # synchronisation per chunk); a copy, because the workspace may be reused by the next chunk
-            _DEFERRED_GUARD[0].append(_ops.render_status_words())
+        models = [model_coarse] + ([model_fine] if fine else [])
+
+        def render(prec):
+            pc = model_coarse.packed(lx, ld, precision=prec)
+            pf = model_fine.packed(lx, ld, precision=prec) if fine else None
+            return _ops.render_rays(pc, pf, ray_batch, nc, nf if fine else 0, lindisp, std, white, thres, draws)
+        prec, guarded = _fp16_guard(models) if fp16_ok else (_ops._precision, False)
+        maps = render(prec)
+        if guarded and status is not None:
+            status.append(_ops.render_status_words())
         elif guarded and _ops.render_nonfinite_count() > 0:
             _warn_fp16_range()
-            pc = model_coarse.packed(lx, ld)
-            pf = model_fine.packed(lx, ld) if fine else None
-            maps = _ops.render_rays(pc, pf, ray_batch, nc, nf if fine else 0, lindisp, std, white, thres, draws)
-        rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f, dex = maps
-        dex_list = [] if dex is None else [dex[k] for k in range(dex.shape[0])]
-        return tuple([rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f] + dex_list)
+            maps = render(_ops._precision)
+        return outputs(maps)
 
     if (fused_models and train_fused_ok(model_coarse) and (not fine or train_fused_ok(model_fine))
             and not inputs_need_grad(ray_batch) and not _STAGEWISE_TRAINING[0]):
         # training: the whole chunk as one differentiable op - one C-ABI call forward (dn_render_rays_train), one backward
-        # (dn_render_rays_backward); draws in the reference's order
-        draws = {}
-        if perturb:
-            draws["t_rand"] = rand(n, nc)
-        if std > 0.0:
-            draws["noise_c"] = randn(n, nc)
-        if fine and perturb:
-            draws["u"] = rand(n, nf)
-        if fine and std > 0.0:
-            draws["noise_f"] = randn(n, nc + nf)
+        # (dn_render_rays_backward)
+        draws = _draws(n, nc, nf, fine, perturb, std, dev)
         logs = (encode_position_fn.log_sampling, encode_direction_fn.log_sampling if use_viewdirs else True)
-        rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f, dex = render_rays_train(
-            model_coarse, model_fine if fine else None, _ops.f32c(ray_batch), (nc, nf if fine else 0, lindisp, std, white), draws,
-            thres, logs)
-        dex_list = [] if dex is None else [dex[k] for k in range(dex.shape[0])]
-        return tuple([rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f] + dex_list)
+        return outputs(render_rays_train(model_coarse, model_fine if fine else None, _ops.f32c(ray_batch),
+                                         (nc, nf if fine else 0, lindisp, std, white), draws, thres, logs))
 
     # stage-by-stage composition (autograd through a network the fused training kernels do not cover, inputs that
-    # require grad, or DEXNERF_STAGEWISE_TRAINING=1)
+    # require grad, or DEXNERF_STAGEWISE_TRAINING=1); the compositing stages draw their own noise, in the same order
     rays = _ops.f32c(ray_batch)
     ro, rd = rays[..., :3], rays[..., 3:6]
-    z_vals = _ops.coarse_depths(rays, nc, lindisp, rand(n, nc) if perturb else None)
+    z_vals = _ops.coarse_depths(rays, nc, lindisp, torch.rand((n, nc), dtype=torch.float32, device=dev) if perturb else None)
 
     def network(model, z):
         if fused_models and (train_fused_ok(model) or not needs_grad(model)):
@@ -249,7 +295,7 @@ def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, mo
     rgb_c, acc_c, weights, depth_c = coarse[0], coarse[2], coarse[3], coarse[4]
     if not fine:
         return tuple([rgb_c, depth_c, acc_c, None, None, None] + list(coarse[5:]))
-    u = rand(n, nf) if perturb else None
+    u = torch.rand((n, nf), dtype=torch.float32, device=dev) if perturb else None
     z_fine = _ops.fine_depths(z_vals, weights.detach(), nf, u)
     rf = network(model_fine, z_fine)
     fine_out = volume_render_radiance_field(rf, z_fine, rd, radiance_field_noise_std=std, white_background=white,
@@ -257,15 +303,8 @@ def predict_and_render_radiance(ray_batch, model_coarse, model_fine, options, mo
     return tuple([rgb_c, depth_c, acc_c, fine_out[0], fine_out[4], fine_out[2]] + list(fine_out[5:]))
 
 
-_DEFERRED_GUARD = [None]   # a list while run_one_iter_of_nerf collects its chunks' fp16 status words, else None
-
-
-def _warn_fp16_range():
-    import warnings
-    warnings.warn("nerf: an fp16 render produced non-finite raw radiance-field values (a hidden activation beyond fp16's "
-                  "range, 65504); this render is repeated in bf16 and every later one in this process runs in bf16 "
-                  "(nerf.set_render_policy)", RuntimeWarning, stacklevel=3)
-    _FP16_RENDER_DISABLED[0] = True
+def _to_image(maps, shapes):
+    return tuple(m.reshape(shape) if m is not None else None for m, shape in zip(maps, shapes))
 
 
 def run_one_iter_of_nerf(height, width, focal_length, model_coarse, model_fine, ray_origins, ray_directions, options,
@@ -285,10 +324,6 @@ def run_one_iter_of_nerf(height, width, focal_length, model_coarse, model_fine, 
         viewdirs = ray_directions / ray_directions.norm(p=2, dim=-1).unsqueeze(-1)
         viewdirs = viewdirs.reshape((-1, 3))
     img_shape = ray_directions.shape
-    restore_shapes = [img_shape, img_shape[:-1], img_shape[:-1]]
-    if model_fine:
-        restore_shapes = restore_shapes + restore_shapes
-    restore_shapes = restore_shapes + [img_shape[:-1]] * len(thres)
     if options.dataset.no_ndc is False:
         ro, rd = ndc_rays(height, width, focal_length, 1.0, ray_origins, ray_directions)
     else:
@@ -302,38 +337,16 @@ def run_one_iter_of_nerf(height, width, focal_length, model_coarse, model_fine, 
         far = options.dataset.far * torch.ones_like(rd[..., :1])
         parts = [ro, rd, near, far] + ([viewdirs] if viewdirs is not None else [])
         rays = torch.cat(parts, dim=-1).float()
-    def render_chunks():
-        return [predict_and_render_radiance(batch, model_coarse, model_fine, options, mode=mode,
-                                            encode_position_fn=encode_position_fn,
-                                            encode_direction_fn=encode_direction_fn, m_thres_cand=thres)
-                for batch in get_minibatches(rays, chunksize=getattr(options.nerf, mode).chunksize)]
-    _DEFERRED_GUARD[0] = []
-    try:
-        chunks = render_chunks()
-        status = _DEFERRED_GUARD[0]
-    finally:
-        _DEFERRED_GUARD[0] = None
-    if status and int(torch.stack(status).sum().item()) > 0:
-        # some chunk's fp16 render left fp16's range: the whole call again in bf16 (one host read per image, not per chunk)
-        _warn_fp16_range()
-        chunks = render_chunks()
-    if len(chunks) == 1:
-        images = list(chunks[0])   # a single chunk: nothing to concatenate (cat would copy every map)
-    else:
-        images = [torch.cat(col, dim=0) if col[0] is not None else None for col in zip(*chunks)]
-    if mode == "validation":
-        if not model_fine:
-            # coarse-only: rgb, depth, acc, (None x3), dex...  -> reference returns the 3 maps + three Nones
-            shapes = restore_shapes[:3] + [None, None, None] + restore_shapes[3:]
-        else:
-            shapes = restore_shapes
-        images = [img.reshape(shape) if img is not None else None for img, shape in zip(images, shapes)]
-    return tuple(images)
 
-
-def _depth_fusable(model, embed_fn):
-    return (isinstance(model, FlexibleNeRFModel) and model.fused_ok() and isinstance(embed_fn, Embedder)
-            and embed_fn.num_encoding_functions == model.num_encoding_fn_xyz and embed_fn.include_input)
+    def render_chunk(batch, status):
+        return _render_chunk(batch, model_coarse, model_fine, options, mode, encode_position_fn, encode_direction_fn, thres,
+                             status=status, fp16_ok=status is not None)
+    images = _render_chunks(rays, getattr(options.nerf, mode).chunksize, render_chunk)
+    if mode != "validation":
+        return tuple(images)
+    # rgb, depth, acc per pass (coarse-only: the reference returns the 3 maps + three Nones), then the Dex depths
+    three = [img_shape, img_shape[:-1], img_shape[:-1]]
+    return _to_image(images, three + (three if model_fine else [None, None, None]) + [img_shape[:-1]] * len(thres))
 
 
 _THRESHOLDS_ON_DEVICE = {}   # (thresholds, device) -> device tensor: one host-to-device copy per threshold set, none per render
@@ -369,7 +382,7 @@ def render_dex_depth(height, width, focal_length, model_coarse, model_fine, ray_
     fine = nf > 0 and bool(model_fine)
     models = [model_coarse] + ([model_fine] if fine else [])
     for m in models:
-        if not _depth_fusable(m, encode_position_fn):
+        if not _fusable(m, encode_position_fn, None, density=True):
             raise RuntimeError("render_dex_depth: needs FlexibleNeRFModel networks the fused HIP kernels cover (fused_ok()) and this "
                                "package's position embedder with the network's encoding; there is no fallback")
         _require_device(m.layer1.weight, "render_dex_depth")
@@ -391,40 +404,23 @@ def render_dex_depth(height, width, focal_length, model_coarse, model_fine, ray_
     lindisp = bool(opt.lindisp)
     lx = encode_position_fn.log_sampling
     m_thres = _threshold_tensor(thres, dev)
-    prec = _ops.render_precision()
-    guarded = (prec != _ops._precision and not torch.cuda.is_current_stream_capturing() and not _FP16_RENDER_DISABLED[0]
-               and all(_ops.fp16_range_guard(m, density=True) for m in models))
+    guard = _fp16_guard(models, density=True)
+    # precision code -> the density packs: fetched once per pass over the chunks, not per chunk (a pass runs in one precision, and
+    # the re-render after a trip in another - the configured one is never the guarded one - so it fetches its own)
+    packs = {}
 
-    def render_chunks(prec):
-        pc = model_coarse.packed_density(lx, True, precision=prec)
-        pf = model_fine.packed_density(lx, True, precision=prec) if fine else None
-        chunks, status = [], []
-        for batch in get_minibatches(rays, chunksize=opt.chunksize):
-            n = batch.shape[0]
-            draws = {}   # the reference's order (train_utils.py:92-202), as in predict_and_render_radiance
-            if perturb:
-                draws["t_rand"] = torch.rand((n, nc), dtype=torch.float32, device=dev)
-            if std > 0.0:
-                draws["noise_c"] = torch.randn((n, nc), dtype=torch.float32, device=dev)
-            if fine and perturb:
-                draws["u"] = torch.rand((n, nf), dtype=torch.float32, device=dev)
-            if fine and std > 0.0:
-                draws["noise_f"] = torch.randn((n, nc + nf), dtype=torch.float32, device=dev)
-            depth_c, acc_c, depth_f, acc_f, dex = _ops.render_rays_depth(pc, pf, batch, nc, nf if fine else 0, lindisp, std, m_thres,
-                                                                        draws)
-            status.append(_ops.render_status_words())
-            chunks.append([depth_c, acc_c, depth_f, acc_f] + ([] if dex is None else [dex[k] for k in range(dex.shape[0])]))
-        return chunks, status
-
-    chunks, status = render_chunks(prec if guarded else _ops._precision)
-    if guarded and status and int(torch.stack(status).sum().item()) > 0:
-        # some chunk's fp16 render left fp16's range: the whole call again in bf16 (one host read per image, not per chunk)
-        _warn_fp16_range()
-        chunks, _ = render_chunks(_ops._precision)
-    if len(chunks) == 1:
-        maps = list(chunks[0])
-    else:
-        maps = [torch.cat(col, dim=0) if col[0] is not None else None for col in zip(*chunks)]
-    if mode == "validation":
-        maps = [m.reshape(img_shape[:-1]) if m is not None else None for m in maps]
-    return tuple(maps)
+    def render_chunk(batch, status):
+        prec, guarded = guard if status is not None else (_ops._precision, False)
+        if prec not in packs:
+            packs[prec] = (model_coarse.packed_density(lx, True, precision=prec),
+                           model_fine.packed_density(lx, True, precision=prec) if fine else None)
+        draws = _draws(batch.shape[0], nc, nf, fine, perturb, std, dev)
+        depth_c, acc_c, depth_f, acc_f, dex = _ops.render_rays_depth(*packs[prec], batch, nc, nf if fine else 0, lindisp, std, m_thres,
+                                                                    draws)
+        maps = [depth_c, acc_c, depth_f, acc_f] + ([] if dex is None else [dex[k] for k in range(dex.shape[0])])
+        words = _ops.render_status_words()   # (copied for unguarded chunks too, as it always was: same launches on every path)
+        if guarded:
+            status.append(words)
+        return maps
+    maps = _render_chunks(rays, opt.chunksize, render_chunk)
+    return _to_image(maps, [img_shape[:-1]] * len(maps)) if mode == "validation" else tuple(maps)

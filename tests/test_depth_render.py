@@ -619,7 +619,7 @@ def test_depth_render_is_hipgraph_capturable(golden, dev):
     rays = _ops.pack_ray_rows(G(g["ro"], dev), G(g["rd"], dev), None, 2.0, 6.0)
     pc, pf = mc.packed_density(), mf.packed_density()
     thres = torch.tensor([5.0, 10.0], device=dev)
-    eager = _ops.render_rays_depth(pc, pf, rays, 64, 64, False, 0.0, thres)   # also warms up (function attributes)
+    eager = _ops.render_rays_depth(pc, pf, rays, 64, 64, False, 0.0, thres)   # also warms up (the per-stream workspace record)
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
     side = torch.cuda.Stream()

@@ -633,7 +633,7 @@ def test_render_is_hipgraph_capturable(golden, dev):
     rays = oc.pack_rays(torch.from_numpy(g["ro"]), torch.from_numpy(g["rd"]), cfg).to(dev)
     pc, pf = mc.packed(), mf.packed()
     thres = [5.0, 10.0]
-    eager = _ops.render_rays(pc, pf, rays, 64, 64, False, 0.0, True, thres)   # also warms up (function attributes)
+    eager = _ops.render_rays(pc, pf, rays, 64, 64, False, 0.0, True, thres)   # also warms up (the per-stream workspace record)
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
     side = torch.cuda.Stream()

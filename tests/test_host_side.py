@@ -338,3 +338,43 @@ def test_run_reference_launcher_resolves_the_builds_package(tmp_path):
     (scripts / "which.py").write_text("import nerf\nprint(getattr(nerf, 'WHO', 'build'))\n")
     r2 = subprocess.run([sys.executable, str(scripts / "which.py")], capture_output=True, text=True, env=env, timeout=300)
     assert r2.stdout.strip() == "decoy"
+
+
+@pytest.mark.parametrize("perturb", [False, True])
+@pytest.mark.parametrize("std", [0.0, 0.2])
+@pytest.mark.parametrize("fine", [False, True])
+def test_draws_follow_the_reference_order(perturb, std, fine):
+    """train_utils._draws is the one place that knows the reference's draw order (train_utils.py:92-202): rand (n, nc), randn (n, nc),
+    rand (n, nf), randn (n, nc + nf) -> t_rand, noise_c, u, noise_f; what a setting does not use is neither drawn nor present."""
+    from nerf import train_utils
+    n, nc, nf, seed = 5, 4, 3, 11
+    cpu = torch.device("cpu")
+    torch.manual_seed(seed)
+    want = {}
+    if perturb:
+        want["t_rand"] = torch.rand((n, nc))
+    if std > 0.0:
+        want["noise_c"] = torch.randn((n, nc))
+    if fine and perturb:
+        want["u"] = torch.rand((n, nf))
+    if fine and std > 0.0:
+        want["noise_f"] = torch.randn((n, nc + nf))
+    state = torch.get_rng_state()
+    torch.manual_seed(seed)
+    got = train_utils._draws(n, nc, nf, fine, perturb, std, cpu)
+    assert sorted(got) == sorted(want)
+    for name, t in want.items():
+        assert got[name].dtype == torch.float32 and got[name].device == cpu and torch.equal(got[name], t), name
+    assert torch.equal(torch.get_rng_state(), state)
+
+
+def test_join_chunks_keeps_a_single_chunk_and_none_columns():
+    from nerf import train_utils
+    a, b = torch.arange(6.0).reshape(2, 3), torch.arange(2.0)
+    joined = train_utils._join_chunks([[a, None, b]])
+    assert len(joined) == 3 and joined[0] is a and joined[1] is None and joined[2] is b   # no torch.cat: the very same tensors
+    chunks = [[torch.full((k, 3), float(k)), None, torch.full((k,), float(-k))] for k in (2, 1, 3)]
+    joined = train_utils._join_chunks(chunks)
+    assert joined[1] is None
+    assert torch.equal(joined[0], torch.cat([c[0] for c in chunks], dim=0)) and joined[0].shape == (6, 3)
+    assert torch.equal(joined[2], torch.tensor([-2.0, -2.0, -1.0, -3.0, -3.0, -3.0]))
