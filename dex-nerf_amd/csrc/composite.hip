@@ -5,7 +5,7 @@
 // instruction reads one coalesced run of the (ray, sample) row; the transmittance product is a
 // wave-level fp64 scan with a carry between 64-sample chunks (ATen's CPU cumprod accumulates in double
 // and rounds each prefix to fp32), the Dex readout is a ballot + first-set-bit per threshold.
-// HBM-bound: 20 B/sample in (rf float4 + z), (10+K)*4 B/ray out.
+// HBM-bound: 20 B/sample in (rf float4 + z), (10+K)*4 B/ray out; backward 40 B/sample, its geometry form 44 B/sample + 12 B/ray.
 #include "composite_body.h"
 
 namespace dn {
@@ -29,12 +29,28 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(
 //   s_i = gC.c_i + gD z_i + gA + gW_i ;  R_i = sum_{k>i} s_k w_k ;  dL/dalpha_i = s_i T_i - R_i / o_i ;
 //   dL/dsigma_i = dL/dalpha_i * dist_i * exp(-sigma_i dist_i) ; dL/draw_sigma = [raw+noise > 0] * that ;
 //   dL/draw_rgb = w_i * gC * c (1 - c).
-template <int MAXC>
+//
+// GEOM: the geometry form (dn_volume_render_backward_geom) - the same wave, scan and sample_terms, and besides g_rf (now optional)
+// the gradients w.r.t. the depths and the direction the intervals dist_i = dz_i |rd| are made of (dz_i = z[i+1] - z[i]; the last
+// sample's interval is the constant 1e10):
+//   ddist_i = dL/dalpha_i * sigma_i * exp(-sigma_i dist_i)   (0 where raw+noise <= 0)
+//   g_z_i   = gD w_i + |rd| (ddist_{i-1} - ddist_i)          (ddist_{-1} = 0; the last sample has no -ddist term)
+//   g_rd    = (sum_i ddist_i dz_i) rd / |rd|                 (the last sample included, with dz = 1e10)
+// The second loop runs over the chunks in descending order and g_z needs the previous sample's ddist across the chunk boundary:
+// ddist is kept per chunk and a third, ascending pass hands lane 63's value on as a carry, as the forward scan does.  Plain stores;
+// g_rd is one lane-local sum in chunk order followed by the fixed butterfly of wave_sum: bit-reproducible.  GEOM = false compiles to
+// the kernel as it was.
+__device__ __forceinline__ float wave_shift_up1(float v, float first) {   // lane l - 1's value (lane 0: `first`)
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, first), __builtin_bit_cast(int, v), 0x138, 0xF, 0xF, false));   // wave_shr:1
+}
+
+template <int MAXC, bool GEOM>
 __global__ __launch_bounds__(256) void composite_bwd_kernel(
     const float4* __restrict__ rf, const float* __restrict__ z, const float* __restrict__ rd, int rd_stride,
     const float* __restrict__ noise, float noise_std, int white, int64_t n_rays, int S, const float* __restrict__ g_rgb,
     const float* __restrict__ g_depth, const float* __restrict__ g_acc, const float* __restrict__ g_disp,
-    const float* __restrict__ g_weights, float4* __restrict__ g_rf, RngRef rng, unsigned* __restrict__ absmax_part) {
+    const float* __restrict__ g_weights, float4* __restrict__ g_rf, RngRef rng, unsigned* __restrict__ absmax_part,
+    float* __restrict__ g_z, float* __restrict__ g_rd) {
   const int lane = lane_id();
   const int64_t ray_of_wave = static_cast<int64_t>(blockIdx.x) * kRaysPerBlock + (threadIdx.x >> 6);
   // absmax_part (the 8-bit-saved-tensor training path, api.cpp): this workgroup's largest finite |gradient it stores| goes to
@@ -56,6 +72,8 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
 
   float w_[MAXC], t_[MAXC], om_[MAXC], de_[MAXC], sw_[MAXC], s_[MAXC], c0_[MAXC], c1_[MAXC], c2_[MAXC];
   bool pos_[MAXC];
+  // GEOM: dz_i, and sigma_i exp(-sigma_i dist_i) = ddist_i / dalpha_i, which the second loop turns into ddist_i in place
+  float dzv_[GEOM ? MAXC : 1], dd_[GEOM ? MAXC : 1];
   double carry = 1.0;
   float sum_d = 0.f, sum_a = 0.f;
 #pragma unroll
@@ -80,6 +98,10 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
     c0_[c] = sigmoidf_(raw.x); c1_[c] = sigmoidf_(raw.y); c2_[c] = sigmoidf_(raw.z);
     w_[c] = w; t_[c] = trans; om_[c] = t.one_m_alpha;
     de_[c] = t.dist * expf(-t.sigma * t.dist);  // dalpha/dsigma
+    if constexpr (GEOM) {
+      dzv_[c] = (sc == S - 1) ? 1e10f : (z1 - z0);
+      dd_[c] = t.sigma * expf(-t.sigma * t.dist);   // dalpha/ddist
+    }
     pos_[c] = valid && (t.sigma > 0.0f);
     s_[c] = z0;  // z for now; turned into s_i below once gD is final
     sum_d += w * z0;
@@ -113,15 +135,19 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
     const float suffix_excl = (total - incl) + tail;     // sum_{k > i} within chunk + later chunks
     tail += total;
     const int s = c * 64 + lane;
+    if constexpr (GEOM) {
+      if (s >= S) dd_[c] = 0.0f;
+    }
     if (s < S) {
       const float dalpha = s_[c] * t_[c] - suffix_excl / om_[c];
       const float dsig = pos_[c] ? dalpha * de_[c] : 0.0f;
+      if constexpr (GEOM) dd_[c] = pos_[c] ? dalpha * dd_[c] : 0.0f;
       float4 g;
       g.x = w_[c] * gc0 * c0_[c] * (1.0f - c0_[c]);
       g.y = w_[c] * gc1 * c1_[c] * (1.0f - c1_[c]);
       g.z = w_[c] * gc2 * c2_[c] * (1.0f - c2_[c]);
       g.w = dsig;
-      if (live) {
+      if (live && (!GEOM || g_rf != nullptr)) {
         g_rf[ray * S + s] = g;
         const float a0 = fabsf(g.x), a1 = fabsf(g.y), a2 = fabsf(g.z), a3 = fabsf(g.w);
         gmax = (a0 < 3.0e38f) ? fmaxf(gmax, a0) : gmax;   // (a non-finite gradient does not set the scale: absmax_kernel's rule)
@@ -129,6 +155,25 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
         gmax = (a2 < 3.0e38f) ? fmaxf(gmax, a2) : gmax;
         gmax = (a3 < 3.0e38f) ? fmaxf(gmax, a3) : gmax;
       }
+    }
+  }
+  if constexpr (GEOM) {
+    // third pass, ascending: the previous sample's ddist (lane 63 of the chunk before as the carry)
+    float prev_last = 0.0f, rd_sum = 0.0f;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+      const int s = c * 64 + lane;
+      const float prev = wave_shift_up1(dd_[c], prev_last);
+      prev_last = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, dd_[c]), 63));
+      if (s < S) {
+        const float own = (s == S - 1) ? 0.0f : dd_[c];   // the last interval is a constant: no -ddist term
+        if (g_z != nullptr) g_z[ray * S + s] = gd * w_[c] + rd_norm * (prev - own);
+        rd_sum += dd_[c] * dzv_[c];
+      }
+    }
+    if (g_rd != nullptr) {
+      rd_sum = wave_sum(rd_sum);
+      if (lane < 3) g_rd[ray * 3 + lane] = rd_sum * (lane == 0 ? dx : (lane == 1 ? dy : dz)) / rd_norm;
     }
   }
   if (absmax_part != nullptr) {   // (workgroup-uniform)
@@ -188,6 +233,38 @@ extern "C" int dn_volume_render_backward(const float* rf, const float* z, const 
                                         g_disp, g_weights, g_rf, nullptr, 0u, stream, nullptr);
 }
 
+#define DN_LAUNCH_BWD(MC, GEOM, G_Z, G_RD)                                                                          \
+  hipLaunchKernelGGL((composite_bwd_kernel<MC, GEOM>), dim3(grid), dim3(256), 0, as_stream(stream),                 \
+                     reinterpret_cast<const float4*>(rf), z, rd, rd_stride, noise, noise_std, white_background,     \
+                     n_rays, n_samples, g_rgb, g_depth, g_acc, g_disp, g_weights, reinterpret_cast<float4*>(g_rf),  \
+                     RngRef{rng_state, rng_stream}, absmax_part, G_Z, G_RD)
+
+extern "C" int dn_volume_render_backward_geom(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise,
+                                              float noise_std, int white_background, int64_t n_rays, int n_samples,
+                                              const float* g_rgb, const float* g_depth, const float* g_acc, const float* g_disp,
+                                              const float* g_weights, float* g_rf, float* g_z, float* g_rd, dn_stream_t stream) {
+  if (n_rays == 0) return 0;
+  DN_REQUIRE(rf && z && rd && (g_rf || g_z || g_rd) && n_rays >= 0 && n_samples >= 1 && rd_stride >= 3,
+             "dn_volume_render_backward_geom: bad arguments");
+  DN_REQUIRE(n_samples <= 1024, "dn_volume_render_backward_geom: at most 1024 samples per ray");
+  DN_REQUIRE(((reinterpret_cast<uintptr_t>(rf) | reinterpret_cast<uintptr_t>(g_rf)) & 15) == 0,
+             "dn_volume_render_backward_geom: rf / g_rf must be 16-byte aligned");
+  if (g_z == nullptr && g_rd == nullptr)   // nothing of the geometry wanted: the plain kernel
+    return dn::volume_render_backward_rng(rf, z, rd, rd_stride, noise, noise_std, white_background, n_rays, n_samples, g_rgb, g_depth,
+                                          g_acc, g_disp, g_weights, g_rf, nullptr, 0u, stream, nullptr);
+  const unsigned grid = static_cast<unsigned>((n_rays + kRaysPerBlock - 1) / kRaysPerBlock);
+  const int chunks = (n_samples + 63) / 64;
+  const uint32_t* rng_state = nullptr;
+  const uint32_t rng_stream = 0u;
+  unsigned* absmax_part = nullptr;
+  if (chunks <= 1) DN_LAUNCH_BWD(1, true, g_z, g_rd);
+  else if (chunks <= 2) DN_LAUNCH_BWD(2, true, g_z, g_rd);
+  else if (chunks <= 4) DN_LAUNCH_BWD(4, true, g_z, g_rd);
+  else if (chunks <= 8) DN_LAUNCH_BWD(8, true, g_z, g_rd);
+  else DN_LAUNCH_BWD(16, true, g_z, g_rd);
+  return check_launch("dn_volume_render_backward_geom");
+}
+
 int dn::volume_render_backward_rng(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise, float noise_std,
                                    int white_background, int64_t n_rays, int n_samples, const float* g_rgb, const float* g_depth,
                                    const float* g_acc, const float* g_disp, const float* g_weights, float* g_rf,
@@ -201,15 +278,12 @@ int dn::volume_render_backward_rng(const float* rf, const float* z, const float*
   if (n_rays == 0) return 0;
   const unsigned grid = static_cast<unsigned>((n_rays + kRaysPerBlock - 1) / kRaysPerBlock);
   const int chunks = (n_samples + 63) / 64;
-#define DN_LAUNCH_BWD(MC)                                                                                          \
-  hipLaunchKernelGGL(composite_bwd_kernel<MC>, dim3(grid), dim3(256), 0, as_stream(stream),                        \
-                     reinterpret_cast<const float4*>(rf), z, rd, rd_stride, noise, noise_std, white_background,    \
-                     n_rays, n_samples, g_rgb, g_depth, g_acc, g_disp, g_weights, reinterpret_cast<float4*>(g_rf), RngRef{rng_state, rng_stream}, absmax_part)
-  if (chunks <= 1) DN_LAUNCH_BWD(1);
-  else if (chunks <= 2) DN_LAUNCH_BWD(2);
-  else if (chunks <= 4) DN_LAUNCH_BWD(4);
-  else if (chunks <= 8) DN_LAUNCH_BWD(8);
-  else DN_LAUNCH_BWD(16);
+  float* const no_g = nullptr;
+  if (chunks <= 1) DN_LAUNCH_BWD(1, false, no_g, no_g);
+  else if (chunks <= 2) DN_LAUNCH_BWD(2, false, no_g, no_g);
+  else if (chunks <= 4) DN_LAUNCH_BWD(4, false, no_g, no_g);
+  else if (chunks <= 8) DN_LAUNCH_BWD(8, false, no_g, no_g);
+  else DN_LAUNCH_BWD(16, false, no_g, no_g);
 #undef DN_LAUNCH_BWD
   return check_launch("dn_volume_render_backward");
 }

@@ -282,6 +282,92 @@ __global__ __launch_bounds__(256) void sampler_kernel(const float* __restrict__ 
   sampler_resample<MODE>(w, cdf, bins, sbuf, u, ray, live, B, nf, samples, inds, z_fine, sort_len, rng);
 }
 
+// Backward of coarse_depths_kernel w.r.t. the near / far columns of the ray rows: one wave per ray.  The stratified jitter
+// z'_i = lower_i + (upper_i - lower_i) t_i is linear in the unjittered depths, coupled to the neighbours through the midpoints:
+//   dL/dz_j = g_j ((1 - t_j) (j > 0 ? 1/2 : 1) + t_j (j < nc - 1 ? 1/2 : 1)) + g_{j+1} (1 - t_{j+1}) / 2 + g_{j-1} t_{j-1} / 2,
+// then dz_j/dnear = 1 - t, dz_j/dfar = t (linear) or z_j^2 (1 - t) / near^2, z_j^2 t / far^2 (lindisp), t = linspace(0, 1, nc)[j].
+// The two sums are lane-local in ascending j, then the fixed butterfly of wave_sum, in fp64: plain stores, bit-reproducible.
+__global__ __launch_bounds__(256) void coarse_depths_bwd_kernel(const float* __restrict__ rays, int ray_stride, int64_t n_rays, int nc,
+                                                                int lindisp, const float* __restrict__ t_rand,
+                                                                const float* __restrict__ g_z, float* __restrict__ g_near_far) {
+  const int lane = lane_id();
+  const int64_t ray = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  if (ray >= n_rays) return;   // wave-uniform; no block-level sync in this kernel
+  const float near = rays[ray * ray_stride + 6];
+  const float far = rays[ray * ray_stride + 7];
+  const float* g = g_z + ray * nc;
+  const float* tr = (t_rand != nullptr) ? t_rand + ray * nc : nullptr;
+  double s_near = 0.0, s_far = 0.0;
+  for (int j = lane; j < nc; j += 64) {
+    float gz = g[j];
+    if (tr != nullptr) {
+      const float tj = tr[j];
+      gz = gz * ((1.0f - tj) * (j > 0 ? 0.5f : 1.0f) + tj * (j < nc - 1 ? 0.5f : 1.0f));
+      if (j + 1 < nc) gz += g[j + 1] * (1.0f - tr[j + 1]) * 0.5f;
+      if (j > 0) gz += g[j - 1] * tr[j - 1] * 0.5f;
+    }
+    const float t = linspace_elem(0.0f, 1.0f, nc, j);
+    float dn_ = 1.0f - t, df_ = t;
+    if (lindisp) {
+      const float zj = coarse_z_at(near, far, nc, j, 1);
+      dn_ = zj * zj * (1.0f - t) / (near * near);
+      df_ = zj * zj * t / (far * far);
+    }
+    s_near += static_cast<double>(gz) * static_cast<double>(dn_);
+    s_far += static_cast<double>(gz) * static_cast<double>(df_);
+  }
+  s_near = wave_sum(s_near);
+  s_far = wave_sum(s_far);
+  if (lane == 0) {
+    g_near_far[ray * 2 + 0] = static_cast<float>(s_near);
+    g_near_far[ray * 2 + 1] = static_cast<float>(s_far);
+  }
+}
+
+// Backward of the coarse + fine merge z_fine = sort(cat(z_coarse, z_samples)) w.r.t. the coarse depths (the samples are detached, as in
+// the reference: train_utils.py:170): g_z_coarse[j] = g_z_fine[p(j)], p(j) = the slot coarse depth j takes in a stable ascending sort
+// of the concatenation = (coarse depths in front of it: smaller, or equal with a smaller index) + (samples strictly smaller) - coarse
+// entries come first on ties, as in the forward's merge, so z_fine[p(j)] == z_coarse[j] bitwise whichever arm the forward took.  One
+// wave per ray on its own LDS rows; a half that is ascending is counted by its index / a binary search, one that is not (a
+// non-ascending z_coarse, the samples of a random u) by comparing against every element.  A pure gather: plain stores.
+__global__ __launch_bounds__(256) void fine_depths_bwd_kernel(const float* __restrict__ z_coarse, const float* __restrict__ z_samples,
+                                                              const float* __restrict__ g_z_fine, int64_t n_rays, int nc, int nf,
+                                                              float* __restrict__ g_z_coarse) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int wave = threadIdx.x >> 6;
+  const int lane = lane_id();
+  const int64_t ray = static_cast<int64_t>(blockIdx.x) * kSamplerWaves + wave;
+  if (ray >= n_rays) return;   // wave-uniform; the waves share no LDS row and no barrier
+  float* zc = lds + wave * (nc + nf);
+  float* zs = zc + nc;
+  for (int i = lane; i < nc; i += 64) zc[i] = z_coarse[ray * nc + i];
+  for (int q = lane; q < nf; q += 64) zs[q] = z_samples[ray * nf + q];
+  wave_lds_sync();
+  bool c_ordered = true, s_ordered = true;
+  for (int i = lane; i + 1 < nc; i += 64)
+    if (zc[i] > zc[i + 1]) c_ordered = false;
+  for (int q = lane; q + 1 < nf; q += 64)
+    if (zs[q] > zs[q + 1]) s_ordered = false;
+  const bool c_asc = __all(c_ordered), s_asc = __all(s_ordered);
+  const int total = nc + nf;
+  for (int j = lane; j < nc; j += 64) {
+    const float v = zc[j];
+    int p = j;
+    if (!c_asc) {
+      p = 0;
+      for (int k = 0; k < nc; ++k) p += (zc[k] < v || (zc[k] == v && k < j)) ? 1 : 0;
+    }
+    if (s_asc) {
+      int lo = 0, hi = nf;
+      while (lo < hi) { const int mid = (lo + hi) >> 1; if (zs[mid] < v) lo = mid + 1; else hi = mid; }
+      p += lo;
+    } else {
+      for (int q = 0; q < nf; ++q) p += (zs[q] < v) ? 1 : 0;
+    }
+    g_z_coarse[ray * nc + j] = g_z_fine[ray * total + min(p, total - 1)];   // (p < nc + nf always; the clamp only keeps a NaN depth's read in bounds)
+  }
+}
+
 static int next_pow2(int v) {
   int p = 1;
   while (p < v) p <<= 1;
@@ -507,6 +593,16 @@ int dn::coarse_depths_rng(const float* rays, int ray_stride, int64_t n_rays, int
   return check_launch("dn_coarse_depths");
 }
 
+extern "C" int dn_coarse_depths_backward(const float* rays, int ray_stride, int64_t n_rays, int num_coarse, int lindisp,
+                                         const float* t_rand, const float* g_z, float* g_near_far, dn_stream_t stream) {
+  if (n_rays == 0) return 0;
+  DN_REQUIRE(rays && g_z && g_near_far && n_rays >= 0 && num_coarse >= 1 && ray_stride >= 8, "dn_coarse_depths_backward: bad arguments");
+  const unsigned grid = static_cast<unsigned>((n_rays + 3) / 4);
+  hipLaunchKernelGGL(coarse_depths_bwd_kernel, dim3(grid), dim3(256), 0, as_stream(stream), rays, ray_stride, n_rays, num_coarse, lindisp,
+                     t_rand, g_z, g_near_far);
+  return check_launch("dn_coarse_depths_backward");
+}
+
 namespace dn {
 // frequency bands as the reference builds them (nerf_helpers.py:134-149): 2**linspace(0, L-1, L) or
 // linspace(1, 2**(L-1), L), fp32.
@@ -571,4 +667,17 @@ int dn::fine_depths_rng(const float* z_coarse, const float* weights, const float
   hipLaunchKernelGGL(sampler_kernel<1>, dim3(grid), dim3(256), lds, as_stream(stream), z_coarse, weights, u, n_rays, B,
                      num_fine, z_samples, static_cast<int64_t*>(nullptr), z_fine, sort_len, RngRef{rng_state, kRngStreamU});
   return check_launch("dn_fine_depths");
+}
+
+extern "C" int dn_fine_depths_backward(const float* z_coarse, const float* z_samples, const float* g_z_fine, int64_t n_rays, int num_coarse,
+                                       int num_fine, float* g_z_coarse, dn_stream_t stream) {
+  if (n_rays == 0) return 0;
+  DN_REQUIRE(z_coarse && z_samples && g_z_fine && g_z_coarse && n_rays >= 0, "dn_fine_depths_backward: bad arguments");
+  DN_REQUIRE(num_coarse >= 1 && num_coarse <= 512 && num_fine >= 1 && num_coarse + num_fine <= 2048,
+             "dn_fine_depths_backward: need 1 <= num_coarse <= 512, num_fine >= 1 and num_coarse + num_fine <= 2048");
+  const size_t lds = static_cast<size_t>(kSamplerWaves) * (num_coarse + num_fine) * sizeof(float);   // <= 32 KiB
+  const unsigned grid = static_cast<unsigned>((n_rays + kSamplerWaves - 1) / kSamplerWaves);
+  hipLaunchKernelGGL(fine_depths_bwd_kernel, dim3(grid), dim3(256), lds, as_stream(stream), z_coarse, z_samples, g_z_fine, n_rays,
+                     num_coarse, num_fine, g_z_coarse);
+  return check_launch("dn_fine_depths_backward");
 }

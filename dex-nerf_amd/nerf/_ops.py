@@ -328,6 +328,37 @@ def coarse_depths(rays, num_coarse, lindisp, t_rand=None):
     return z
 
 
+def coarse_depths_bwd(rays, num_coarse, lindisp, t_rand, g_z):
+    """dn_coarse_depths_backward: (N,2) = [dL/dnear, dL/dfar] of the ray rows."""
+    rays, g_z = f32c(rays), f32c(g_z)
+    n = rays.shape[0]
+    out = torch.empty((n, 2), dtype=torch.float32, device=rays.device)
+    tr = None if t_rand is None else f32c(t_rand)
+    check(lib().dn_coarse_depths_backward(ptr(rays), rays.shape[1], n, num_coarse, int(bool(lindisp)), ptr(tr), ptr(g_z), ptr(out),
+                                          stream()), "dn_coarse_depths_backward")
+    return out
+
+
+class CoarseDepthsFn(torch.autograd.Function):
+    """coarse_depths, differentiable w.r.t. the near / far columns of the ray rows (pose / ray optimisation: the stage-by-stage route
+    of predict_and_render_radiance takes it when the rows require grad).  The jitter draws carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, rays, num_coarse, lindisp, t_rand):
+        rows = f32c(rays)
+        ctx.save_for_backward(rows, t_rand if t_rand is not None else torch.empty(0, device=rows.device))
+        ctx.cfg = (int(num_coarse), bool(lindisp), t_rand is not None, rays.dtype)
+        return coarse_depths(rows, num_coarse, lindisp, t_rand)
+
+    @staticmethod
+    def backward(ctx, g_z):
+        rows, t_rand = ctx.saved_tensors
+        nc, lindisp, jitter, dtype = ctx.cfg
+        g_rows = torch.zeros_like(rows)
+        g_rows[:, 6:8] = coarse_depths_bwd(rows, nc, lindisp, t_rand if jitter else None, g_z)
+        return g_rows.to(dtype), None, None, None
+
+
 def positional_encoding(x, num_fns, include_input=True, log_sampling=True):
     shape = x.shape
     dim = shape[-1]
@@ -689,9 +720,28 @@ def volume_render_bwd(rf, z, rd, noise, noise_std, white, g_rgb, g_depth, g_acc,
     return g_rf
 
 
+def volume_render_bwd_geom(rf, z, rd, noise, noise_std, white, g_rgb, g_depth, g_acc, g_disp, g_weights, want_rf=True, want_z=True,
+                           want_rd=True):
+    """dn_volume_render_backward_geom: (g_rf (N,S,4), g_z (N,S), g_rd (N,3)), None for what is not wanted."""
+    rf, z = f32c(rf), f32c(z)
+    n, s = z.shape
+    rd_ptr, rd_stride, rd = _dir_rows(rd)
+    dev = rf.device
+    g_rf = torch.empty((n, s, 4), dtype=torch.float32, device=dev) if want_rf else None
+    g_z = torch.empty((n, s), dtype=torch.float32, device=dev) if want_z else None
+    g_rd = torch.empty((n, 3), dtype=torch.float32, device=dev) if want_rd else None
+    nz = None if (noise is None or noise_std <= 0.0) else f32c(noise)
+    gs = [None if g is None else f32c(g) for g in (g_rgb, g_depth, g_acc, g_disp, g_weights)]
+    check(lib().dn_volume_render_backward_geom(ptr(rf), ptr(z), rd_ptr, rd_stride, ptr(nz), float(noise_std), int(bool(white)), n, s,
+                                               ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), ptr(gs[3]), ptr(gs[4]), ptr(g_rf), ptr(g_z),
+                                               ptr(g_rd), stream()), "dn_volume_render_backward_geom")
+    return g_rf, g_z, g_rd
+
+
 class VolumeRenderFn(torch.autograd.Function):
-    """Differentiable w.r.t. the radiance field only: depths and directions carry no gradient on this path
-    (the reference detaches z_samples, train_utils.py:170)."""
+    """Differentiable w.r.t. the radiance field, the depths and the ray directions (dists = dz |rd|, depth = sum w z).  The
+    geometry entry point runs only when z or rd ask for a gradient; otherwise the backward is dn_volume_render_backward as ever.
+    The Dex depth maps are not differentiable, and the reference detaches z_samples (train_utils.py:170)."""
 
     @staticmethod
     def forward(ctx, rf, z, rd, noise, noise_std, white, m_thres):
@@ -711,6 +761,15 @@ class VolumeRenderFn(torch.autograd.Function):
 
         def nz(g):
             return None if g is None else g.contiguous()
+        need_rf, need_z, need_rd = ctx.needs_input_grad[:3]
+        if need_z or need_rd:
+            g_rf, g_z, g_rd = volume_render_bwd_geom(rf, z, rd, noise if has_noise else None, noise_std, white, nz(g_rgb), nz(g_depth),
+                                                     nz(g_acc), nz(g_disp), nz(g_weights), need_rf, need_z, need_rd)
+            if g_z is not None:
+                g_z = g_z.to(z.dtype)
+            if g_rd is not None:
+                g_rd = g_rd.reshape(rd.shape).to(rd.dtype)
+            return g_rf, g_z, g_rd, None, None, None, None
         g_rf = volume_render_bwd(rf, z, rd, noise if has_noise else None, noise_std, white, nz(g_rgb), nz(g_depth),
                                  nz(g_acc), nz(g_disp), nz(g_weights))
         return g_rf, None, None, None, None, None, None
@@ -738,6 +797,34 @@ def fine_depths(z_coarse, weights, num_fine, u=None, want_samples=False):
     check(lib().dn_fine_depths(ptr(z_coarse), ptr(weights), ptr(uu), n, nc, num_fine, ptr(z_fine), ptr(zs), stream()),
           "dn_fine_depths")
     return (z_fine, zs) if want_samples else z_fine
+
+
+def fine_depths_bwd(z_coarse, z_samples, g_z_fine):
+    """dn_fine_depths_backward: g_z_coarse (N,Nc), the gather of g_z_fine at the slots the coarse depths took in the merge."""
+    z_coarse, z_samples, g_z_fine = f32c(z_coarse), f32c(z_samples), f32c(g_z_fine)
+    n, nc = z_coarse.shape
+    nf = z_samples.shape[1]
+    assert g_z_fine.shape == (n, nc + nf)
+    out = torch.empty((n, nc), dtype=torch.float32, device=z_coarse.device)
+    check(lib().dn_fine_depths_backward(ptr(z_coarse), ptr(z_samples), ptr(g_z_fine), n, nc, nf, ptr(out), stream()),
+          "dn_fine_depths_backward")
+    return out
+
+
+class FineDepthsFn(torch.autograd.Function):
+    """fine_depths, differentiable w.r.t. the coarse depths through the merge; the resamples are detached, as in the reference
+    (train_utils.py:170), so the weights and the draws get nothing.  Keeps z_samples for its backward."""
+
+    @staticmethod
+    def forward(ctx, z_coarse, weights, num_fine, u):
+        z_fine, zs = fine_depths(z_coarse, weights, num_fine, u, want_samples=True)
+        ctx.save_for_backward(z_coarse, zs)
+        return z_fine
+
+    @staticmethod
+    def backward(ctx, g_z_fine):
+        z_coarse, zs = ctx.saved_tensors
+        return fine_depths_bwd(z_coarse, zs, g_z_fine).to(z_coarse.dtype), None, None, None
 
 
 _render_ws = {}   # current stream -> (cached workspace buffer, the bytes the latest render call on that stream asked for)

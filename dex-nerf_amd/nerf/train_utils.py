@@ -278,7 +278,11 @@ def _render_chunk(ray_batch, model_coarse, model_fine, options, mode, encode_pos
     # require grad, or DEXNERF_STAGEWISE_TRAINING=1); the compositing stages draw their own noise, in the same order
     rays = _ops.f32c(ray_batch)
     ro, rd = rays[..., :3], rays[..., 3:6]
-    z_vals = _ops.coarse_depths(rays, nc, lindisp, torch.rand((n, nc), dtype=torch.float32, device=dev) if perturb else None)
+    # rows that require grad (pose / ray optimisation): the depths carry their gradient to near / far, through the merge and - in
+    # volume_render_radiance_field - through dists and depth; rows without grad take none of that
+    ray_grad = inputs_need_grad(ray_batch)
+    t_rand = torch.rand((n, nc), dtype=torch.float32, device=dev) if perturb else None
+    z_vals = _ops.CoarseDepthsFn.apply(rays, nc, lindisp, t_rand) if ray_grad else _ops.coarse_depths(rays, nc, lindisp, t_rand)
 
     def network(model, z):
         if fused_models and (train_fused_ok(model) or not needs_grad(model)):
@@ -296,7 +300,7 @@ def _render_chunk(ray_batch, model_coarse, model_fine, options, mode, encode_pos
     if not fine:
         return tuple([rgb_c, depth_c, acc_c, None, None, None] + list(coarse[5:]))
     u = torch.rand((n, nf), dtype=torch.float32, device=dev) if perturb else None
-    z_fine = _ops.fine_depths(z_vals, weights.detach(), nf, u)
+    z_fine = _ops.FineDepthsFn.apply(z_vals, weights.detach(), nf, u) if ray_grad else _ops.fine_depths(z_vals, weights.detach(), nf, u)
     rf = network(model_fine, z_fine)
     fine_out = volume_render_radiance_field(rf, z_fine, rd, radiance_field_noise_std=std, white_background=white,
                                             m_thres_cand=thres)

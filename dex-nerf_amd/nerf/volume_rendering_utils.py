@@ -17,7 +17,8 @@ def volume_render_radiance_field(radiance_field, depth_values, ray_directions, r
 
     radiance_field (..., S, 4) raw [r,g,b,sigma]; depth_values (..., S); ray_directions (..., 3).
     Train-time noise is drawn with torch.randn on the device (reference :31-39).  Differentiable w.r.t.
-    radiance_field (the Dex depths are gathers of grad-free depths, as in the reference).
+    radiance_field, depth_values and ray_directions (dists = dz |rd|, depth = sum w z); the Dex depths - gathers of the
+    depths at an argmax - are not.
     """
     _require_device(radiance_field, "volume_render_radiance_field")
     lead = depth_values.shape[:-1]
@@ -30,7 +31,7 @@ def volume_render_radiance_field(radiance_field, depth_values, ray_directions, r
     std = float(radiance_field_noise_std)
     if std > 0.0:
         noise = torch.randn(z.shape, dtype=torch.float32, device=z.device)
-    if torch.is_grad_enabled() and rf.requires_grad:
+    if torch.is_grad_enabled() and (rf.requires_grad or z.requires_grad or rd.requires_grad):
         outs = _ops.VolumeRenderFn.apply(rf, z, rd, noise, std, bool(white_background), thres)
         rgb, disp, acc, weights, depth = outs[:5]
         dex = outs[5] if len(outs) > 5 else None
