@@ -368,6 +368,133 @@ __global__ __launch_bounds__(256) void fine_depths_bwd_kernel(const float* __res
   }
 }
 
+// Backward of ray generation w.r.t. the camera: the 16-float record [rinv9, origin3, fx, cx, cy, ndc_focal] of ray_bundle_kernel /
+// select_rays*_kernel receives the gradient of the rays' origins, directions and unit view directions (NDC: of the warped origins /
+// directions of ndc_warp, the view directions those of the unwarped directions).  Per ray, in fp64 from the fp32 record and the integer
+// pixel: d = [(col - cx) / fx, (row - cy) / fx, 1], rd_j = sum_k d_k rinv[3j + k], v = rd / |rd|;
+//   NDC: (g_o', g_d') pulled back through the six expressions of ndc_warp and the shift o + t rd to (g_o, g_d); o'_{0,1}, d'_{0,1} are
+//        linear in the focal length, so g_focal = (g_o'_0 o'_0 + g_o'_1 o'_1 + g_d'_0 d'_0 + g_d'_1 d'_1) / focal;
+//   g_d += (g_v - v (v . g_v)) / |rd|;
+//   g_origin += g_o, g_rinv[3j + k] += g_d[j] d_k, e_k = sum_j g_d[j] rinv[3j + k], g_cx -= e_0 / fx, g_cy -= e_1 / fx,
+//   g_fx -= (e_0 d_0 + e_1 d_1) / fx.
+// The sums are formed in a fixed order: a lane adds its rays (thread index, then strides of the whole grid) in ascending order, the
+// lanes of a wave meet in wave_sum's butterfly, the waves of a workgroup through LDS in wave order, and each workgroup stores 16
+// doubles; camera_grad_finish_kernel adds those in workgroup order.  The grid is a function of n alone (camera_grad_blocks): plain
+// stores, bit-reproducible on any device.
+constexpr int kCamGradThreads = 256;
+constexpr int kCamGradMaxBlocks = 64;
+
+static int camera_grad_blocks(int64_t n) {
+  const int64_t blocks = (n + kCamGradThreads - 1) / kCamGradThreads;
+  return static_cast<int>(blocks < kCamGradMaxBlocks ? blocks : kCamGradMaxBlocks);
+}
+
+__global__ __launch_bounds__(kCamGradThreads) void camera_grad_kernel(const float* __restrict__ cam, int width, const int64_t* __restrict__ pix,
+                                                                      int64_t n, const float* __restrict__ g_ro, int ro_stride,
+                                                                      const float* __restrict__ g_rd, int rd_stride,
+                                                                      const float* __restrict__ g_vd, int vd_stride, double height_d,
+                                                                      double ndc_focal, double ndc_near, double* __restrict__ partials) {
+  __shared__ double part[kCamGradThreads / 64][16];
+  double rinv[9], origin[3];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) rinv[k] = static_cast<double>(cam[k]);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) origin[k] = static_cast<double>(cam[9 + k]);
+  const double fx = static_cast<double>(cam[12]), cx = static_cast<double>(cam[13]), cy = static_cast<double>(cam[14]);
+  const bool ndc = ndc_focal > 0.0;
+  const double sx = -1.0 / (static_cast<double>(width) / (2.0 * ndc_focal));
+  const double sy = -1.0 / (height_d / (2.0 * ndc_focal));
+  double acc[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) acc[k] = 0.0;
+  const int64_t step = static_cast<int64_t>(gridDim.x) * kCamGradThreads;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kCamGradThreads + threadIdx.x; i < n; i += step) {
+    const int64_t px = (pix != nullptr) ? pix[i] : i;
+    const int64_t row = px / width;
+    const int64_t col = px - row * width;
+    const double d[3] = {(static_cast<double>(col) - cx) / fx, (static_cast<double>(row) - cy) / fx, 1.0};
+    double rd[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) rd[j] = (d[0] * rinv[3 * j + 0] + d[1] * rinv[3 * j + 1]) + d[2] * rinv[3 * j + 2];
+    double go[3] = {0.0, 0.0, 0.0}, gd[3] = {0.0, 0.0, 0.0};
+    if (g_ro != nullptr) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) go[j] = static_cast<double>(g_ro[i * ro_stride + j]);
+    }
+    if (g_rd != nullptr) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) gd[j] = static_cast<double>(g_rd[i * rd_stride + j]);
+    }
+    if (ndc) {
+      // forward: t = -(near + o_z) / rd_z, p = o + t rd, o' = [sx p0 / p2, sy p1 / p2, 1 + 2 near / p2],
+      //          d' = [sx (rd0 / rd2 - p0 / p2), sy (rd1 / rd2 - p1 / p2), -2 near / p2]
+      const double t = -(ndc_near + origin[2]) / rd[2];
+      const double p[3] = {origin[0] + t * rd[0], origin[1] + t * rd[1], origin[2] + t * rd[2]};
+      const double ip = 1.0 / p[2], iz = 1.0 / rd[2];
+      const double o0 = sx * p[0] * ip, o1 = sy * p[1] * ip;
+      const double w0 = sx * (rd[0] * iz - p[0] * ip), w1 = sy * (rd[1] * iz - p[1] * ip);
+      acc[15] += (go[0] * o0 + go[1] * o1 + gd[0] * w0 + gd[1] * w1) / ndc_focal;
+      const double a0 = go[0] - gd[0], a1 = go[1] - gd[1];
+      double gp[3];
+      gp[0] = sx * ip * a0;
+      gp[1] = sy * ip * a1;
+      gp[2] = -(sx * p[0] * a0 + sy * p[1] * a1) * ip * ip + 2.0 * ndc_near * ip * ip * (gd[2] - go[2]);
+      double gr[3];
+      gr[0] = sx * iz * gd[0];
+      gr[1] = sy * iz * gd[1];
+      gr[2] = -(sx * rd[0] * gd[0] + sy * rd[1] * gd[1]) * iz * iz;
+      const double gt = gp[0] * rd[0] + gp[1] * rd[1] + gp[2] * rd[2];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        go[j] = gp[j];
+        gd[j] = gr[j] + t * gp[j];
+      }
+      go[2] -= gt * iz;
+      gd[2] -= gt * t * iz;
+    }
+    if (g_vd != nullptr) {
+      const double gv[3] = {static_cast<double>(g_vd[i * vd_stride + 0]), static_cast<double>(g_vd[i * vd_stride + 1]),
+                            static_cast<double>(g_vd[i * vd_stride + 2])};
+      const double inv_nrm = 1.0 / sqrt((rd[0] * rd[0] + rd[1] * rd[1]) + rd[2] * rd[2]);
+      const double v[3] = {rd[0] * inv_nrm, rd[1] * inv_nrm, rd[2] * inv_nrm};
+      const double vg = (v[0] * gv[0] + v[1] * gv[1]) + v[2] * gv[2];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) gd[j] += (gv[j] - v[j] * vg) * inv_nrm;
+    }
+    double e[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) e[k] = (gd[0] * rinv[k] + gd[1] * rinv[3 + k]) + gd[2] * rinv[6 + k];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      acc[9 + j] += go[j];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) acc[3 * j + k] += gd[j] * d[k];
+    }
+    acc[12] -= (e[0] * d[0] + e[1] * d[1]) / fx;
+    acc[13] -= e[0] / fx;
+    acc[14] -= e[1] / fx;
+  }
+  const int wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    const double s = wave_sum(acc[k]);
+    if (lane_id() == 0) part[wave][k] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < 16) {
+    double s = part[0][threadIdx.x];
+    for (int w = 1; w < kCamGradThreads / 64; ++w) s += part[w][threadIdx.x];
+    partials[static_cast<int64_t>(blockIdx.x) * 16 + threadIdx.x] = s;
+  }
+}
+
+__global__ __launch_bounds__(64) void camera_grad_finish_kernel(const double* __restrict__ partials, int n_blocks, float* __restrict__ g_cam) {
+  if (threadIdx.x >= 16) return;
+  double s = 0.0;
+  for (int b = 0; b < n_blocks; ++b) s += partials[b * 16 + threadIdx.x];
+  g_cam[threadIdx.x] = static_cast<float>(s);
+}
+
 static int next_pow2(int v) {
   int p = 1;
   while (p < v) p <<= 1;
@@ -422,6 +549,53 @@ extern "C" int dn_select_rays_indirect(int height, int width, const float* cams,
                      far, pixel_index, n_rays, images, channels, rays, target, static_cast<uint32_t*>(nullptr), static_cast<int64_t*>(nullptr),
                      0.0, 0.0);
   return check_launch("dn_select_rays_indirect");
+}
+
+extern "C" int dn_select_rays_indirect_ndc(int height, int width, const float* cams, const int32_t* view, float near, float far,
+                                           const int64_t* pixel_index, int64_t n_rays, const float* images, int channels, float* rays,
+                                           float* target, double focal, double ndc_near, dn_stream_t stream) {
+  if (n_rays == 0) return 0;
+  DN_REQUIRE(height > 0 && width > 0 && cams && view && pixel_index && rays && n_rays >= 0, "dn_select_rays_indirect_ndc: bad arguments");
+  DN_REQUIRE(target == nullptr || (images != nullptr && channels >= 3), "dn_select_rays_indirect_ndc: target requested without images of >= 3 channels");
+  DN_REQUIRE(std::isfinite(focal) && focal > 0.0 && std::isfinite(ndc_near), "dn_select_rays_indirect_ndc: focal must be positive and finite, the near plane finite");
+  const int block = 256;
+  const unsigned grid = static_cast<unsigned>((n_rays + block - 1) / block);
+  hipLaunchKernelGGL(select_rays_indirect_kernel<true>, dim3(grid), dim3(block), 0, as_stream(stream), cams, view, 0, height, width, near,
+                     far, pixel_index, n_rays, images, channels, rays, target, static_cast<uint32_t*>(nullptr), static_cast<int64_t*>(nullptr),
+                     focal, ndc_near);
+  return check_launch("dn_select_rays_indirect_ndc");
+}
+
+extern "C" size_t dn_camera_grad_scratch_bytes(int64_t n_rays) {
+  const int blocks = camera_grad_blocks(n_rays > 0 ? n_rays : 0);
+  return static_cast<size_t>(blocks > 0 ? blocks : 1) * 16 * sizeof(double);
+}
+
+extern "C" int dn_camera_grad(int height, int width, const float* cam16, const int64_t* pixel_index, int64_t n_rays, const float* g_ro,
+                              int ro_stride, const float* g_rd, int rd_stride, const float* g_viewdir, int vd_stride, double ndc_focal,
+                              double ndc_near, void* scratch, size_t scratch_bytes, float* g_cam16, dn_stream_t stream) {
+  DN_REQUIRE(height > 0 && width > 0 && n_rays >= 0, "dn_camera_grad: bad arguments (image size, ray count)");
+  DN_REQUIRE(cam16 != nullptr && g_cam16 != nullptr, "dn_camera_grad: the camera record and its gradient must be given");
+  DN_REQUIRE(g_ro != nullptr || g_rd != nullptr || g_viewdir != nullptr, "dn_camera_grad: no upstream gradient given");
+  DN_REQUIRE((g_ro == nullptr || ro_stride >= 3) && (g_rd == nullptr || rd_stride >= 3) && (g_viewdir == nullptr || vd_stride >= 3),
+             "dn_camera_grad: the row stride of an upstream gradient must be >= 3 floats");
+  DN_REQUIRE(static_cast<int64_t>(height) * width < (1LL << 31), "dn_camera_grad: image too large");
+  DN_REQUIRE(pixel_index != nullptr || n_rays <= static_cast<int64_t>(height) * width, "dn_camera_grad: more rays than pixels without a pixel index");
+  DN_REQUIRE(std::isfinite(ndc_focal) && ndc_focal >= 0.0 && std::isfinite(ndc_near),
+             "dn_camera_grad: ndc_focal must be finite and >= 0 (0: world-space rays), the near plane finite");
+  DN_REQUIRE(scratch != nullptr && scratch_bytes >= dn_camera_grad_scratch_bytes(n_rays),
+             "dn_camera_grad: scratch smaller than dn_camera_grad_scratch_bytes(n_rays)");
+  DN_REQUIRE(reinterpret_cast<uintptr_t>(scratch) % 8 == 0, "dn_camera_grad: scratch must be 8-byte aligned");
+  const int blocks = camera_grad_blocks(n_rays);
+  double* partials = static_cast<double*>(scratch);
+  if (blocks > 0) {
+    hipLaunchKernelGGL(camera_grad_kernel, dim3(blocks), dim3(kCamGradThreads), 0, as_stream(stream), cam16, width, pixel_index, n_rays, g_ro,
+                       ro_stride, g_rd, rd_stride, g_viewdir, vd_stride, static_cast<double>(height), ndc_focal, ndc_near, partials);
+    const int rc = check_launch("dn_camera_grad");
+    if (rc != 0) return rc;
+  }
+  hipLaunchKernelGGL(camera_grad_finish_kernel, dim3(1), dim3(64), 0, as_stream(stream), partials, blocks, g_cam16);   // (no rays: 16 zeros)
+  return check_launch("dn_camera_grad");
 }
 
 extern "C" int dn_select_rays_draw(int height, int width, const float* cams, const int32_t* view, int n_views, float near, float far,

@@ -228,6 +228,130 @@ def select_rays_indirect(height, width, cams, view, near, far, pixel_index, imag
     return rays, target
 
 
+def select_rays_indirect_ndc(height, width, cams, view, near, far, pixel_index, focal, ndc_near, images=None):
+    """select_rays_indirect with origin / direction of every row warped to NDC (dn_select_rays_indirect_ndc)."""
+    pix = pixel_index.contiguous()
+    assert pix.dtype == torch.int64 and view.dtype == torch.int32 and cams.dtype == torch.float32 and cams.is_contiguous()
+    n = pix.numel()
+    rays, target, img, channels = _ray_outputs(n, images, pix.device)
+    check(lib().dn_select_rays_indirect_ndc(height, width, ptr(cams), ptr(view), float(near), float(far), ptr(pix), n, ptr(img), channels,
+                                            ptr(rays), ptr(target), float(focal), float(ndc_near), stream()), "dn_select_rays_indirect_ndc")
+    return rays, target
+
+
+# ---- camera -> rays, differentiable in the camera -----------------------------------------------------------------------
+def camera_record(extrinsic, intrinsic, focal_length, height, width, ndc_focal=None):
+    """The 16-float camera record [rinv9, origin3, fx, cx, cy, ndc_focal | 0] of the ray kernels as differentiable torch ops on
+    the HOST: the two fp32 torch.inverse calls of get_ray_bundle (5-argument fork convention: world->camera `extrinsic`, 3x3
+    `intrinsic`), or - `intrinsic=None`, the 4-argument convention - the camera-to-world rotation with its y / z columns negated,
+    cx = W / 2, cy = H / 2, fx = focal_length.  `tensor.to("cpu")` is differentiable, so a gradient of the record reaches
+    `extrinsic` / `intrinsic` / `focal_length` / `ndc_focal` on whatever device they live on."""
+    host = extrinsic.to("cpu", torch.float32)
+    if intrinsic is not None:
+        k = intrinsic.to("cpu", torch.float32)
+        rinv = torch.inverse(host[:3, :3])
+        origin = torch.inverse(host)[:3, -1]
+        intr = torch.stack([k[0, 0], k[0, 2], k[1, 2]])
+    else:
+        rinv = host[:3, :3] * torch.tensor([1.0, -1.0, -1.0])
+        origin = host[:3, -1]
+        fx = (focal_length.to("cpu", torch.float32).reshape(()) if torch.is_tensor(focal_length)
+              else torch.tensor(float(focal_length), dtype=torch.float32))
+        intr = torch.stack([fx, torch.tensor(width * 0.5), torch.tensor(height * 0.5)])
+    if torch.is_tensor(ndc_focal):
+        last = ndc_focal.to("cpu", torch.float32).reshape(1)
+    else:
+        last = torch.tensor([0.0 if ndc_focal is None else float(ndc_focal)])
+    return torch.cat([rinv.reshape(-1), origin, intr, last])
+
+
+def camera_grad_scratch_bytes(n):
+    return int(lib().dn_camera_grad_scratch_bytes(int(n)))
+
+
+def camera_grad(height, width, cam16, pixel_index, n, g_ro, g_rd, g_viewdir, ndc_focal=0.0, ndc_near=1.0):
+    """dn_camera_grad: the (16,) device gradient of the camera record from upstream gradients of the rays' origins / directions /
+    view directions - (N, >= 3) fp32 views whose last dim is contiguous (column slices of packed rows go as they are), None = absent."""
+    assert cam16.is_cuda and cam16.dtype == torch.float32 and cam16.is_contiguous() and cam16.numel() == 16
+    keep, args = [], []
+    for g in (g_ro, g_rd, g_viewdir):
+        if g is None:
+            args += [None, 0]
+        else:
+            p, stride, t = _dir_rows(g)
+            keep.append(t)
+            args += [p, stride]
+    pix = None
+    if pixel_index is not None:
+        pix = pixel_index.contiguous()
+        assert pix.dtype == torch.int64 and pix.is_cuda and pix.numel() == n
+    nbytes = camera_grad_scratch_bytes(n)
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=cam16.device)
+    g_cam = torch.empty(16, dtype=torch.float32, device=cam16.device)
+    check(lib().dn_camera_grad(int(height), int(width), ptr(cam16), ptr(pix), int(n), *args, float(ndc_focal), float(ndc_near),
+                               ptr(scratch), nbytes, ptr(g_cam), stream()), "dn_camera_grad")
+    return g_cam
+
+
+def _camera_rays_forward(values, cams, height, width, pixel_index, near, far, image, ndc_focal, ndc_near):
+    """The existing forward op for a camera record: `values` = its 16 floats on the host (full-image bundle and world-space rows:
+    dn_ray_bundle / dn_select_rays, as get_ray_bundle / RaySelector.select call them), `cams` = the record on the device (NDC rows)."""
+    rinv, origin, (fx, cx, cy) = values[:9], values[9:12], values[12:15]
+    if pixel_index is None:
+        return ray_bundle(height, width, rinv, origin, fx, cx, cy, cams.device if cams is not None else None)
+    if ndc_focal:
+        view = torch.zeros((), dtype=torch.int32, device=cams.device)
+        images = None if image is None else image[None]
+        return select_rays_indirect_ndc(height, width, cams.reshape(1, 16), view, near, far, pixel_index, ndc_focal, ndc_near, images)
+    return select_rays(height, width, rinv, origin, fx, cx, cy, near, far, pixel_index, image)
+
+
+class CameraRaysFn(torch.autograd.Function):
+    """Rays of one camera, differentiable w.r.t. its record (camera_record): the full-image bundle (pixel_index None -> ro, rd
+    (H,W,3)) or the packed rows of chosen pixels (-> rows (N,11), target (N,3) | None; with `ndc_focal` origin / direction warped
+    to NDC).  The forward is the existing forward op on the record's values - outputs bit-identical to get_ray_bundle /
+    RaySelector.select / the NDC draw.  The backward is dn_camera_grad (fp64 Jacobian, fixed-order sums) into a (16,) device
+    tensor, returned as the gradient of the HOST record: one 64-byte device-to-host read per backward, which synchronises - so it
+    cannot run under stream capture, and raises there."""
+
+    @staticmethod
+    def forward(ctx, record, device, height, width, pixel_index, near, far, image, ndc_focal, ndc_near):
+        rec = record.detach().to(torch.float32).contiguous()
+        cams = rec.to(device)
+        ctx.save_for_backward(cams, pixel_index if pixel_index is not None else torch.empty(0, dtype=torch.int64, device=device))
+        ctx.cfg = (int(height), int(width), pixel_index is not None, float(ndc_focal or 0.0), float(ndc_near), record.dtype)
+        out = _camera_rays_forward(rec.tolist(), cams, int(height), int(width), pixel_index, near, far, image, ndc_focal, ndc_near)
+        if pixel_index is not None and out[1] is not None:
+            ctx.mark_non_differentiable(out[1])
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_a, g_b):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("CameraRaysFn.backward: the camera gradient is read back to the host (64 bytes), which cannot be "
+                               "captured into a HIP graph; run the camera's backward outside the capture")
+        cams, pix = ctx.saved_tensors
+        height, width, selected, ndc_focal, ndc_near, dtype = ctx.cfg
+        if selected:
+            n = pix.numel()
+            g = f32c(g_a) if g_a is not None else torch.zeros((n, 11), dtype=torch.float32, device=cams.device)
+            g_cam = camera_grad(height, width, cams, pix, n, g[:, 0:3], g[:, 3:6], g[:, 8:11], ndc_focal, ndc_near)
+        else:
+            n = height * width
+            if g_a is None and g_b is None:
+                g_a = torch.zeros((n, 3), dtype=torch.float32, device=cams.device)
+            g_ro = None if g_a is None else f32c(g_a).reshape(n, 3)
+            g_rd = None if g_b is None else f32c(g_b).reshape(n, 3)
+            g_cam = camera_grad(height, width, cams, None, n, g_ro, g_rd, None, 0.0, 1.0)
+        return (g_cam.cpu().to(dtype),) + (None,) * 9
+
+
+def camera_needs_grad(*values):
+    """True when grad is enabled and one of the camera quantities (tensors; floats and None are skipped) requires grad."""
+    return torch.is_grad_enabled() and any(torch.is_tensor(v) and v.requires_grad for v in values)
+
+
 def new_rng_state(seed, device, first_iteration=0):
     """Device record {seed_lo, seed_hi, cur, nxt} for the in-kernel draws of a training loop (csrc/dn_rng.h)."""
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF

@@ -49,8 +49,21 @@ def get_ray_bundle(height: int, width: int, focal_length, tform_cam2world: torch
     selects the upstream pinhole camera-to-world convention - an extension with no oracle in the fork.
     The two 4x4/3x3 inverses are taken on the host (LAPACK, like the reference on CPU); the per-pixel
     work runs in the HIP kernel for device poses.
+
+    A pose, intrinsic or tensor focal length that requires grad (with grad enabled) receives its gradient: device poses through
+    _ops.CameraRaysFn (the same forward kernel, dn_camera_grad backward), host poses through the torch composition below on the
+    undetached camera record.  The values are those of the call without grad.
     """
     pose = tform_cam2world
+    if _ops.camera_needs_grad(pose, intrinsic, focal_length):
+        record = _ops.camera_record(pose, intrinsic, focal_length, height, width)
+        if pose.is_cuda:
+            return _ops.CameraRaysFn.apply(record, pose.device, height, width, None, 0.0, 0.0, None, None, 1.0)
+        rinv, origin, fx, cx, cy = record[:9].reshape(3, 3), record[9:12], record[12], record[13], record[14]
+        ii, jj = meshgrid_xy(torch.arange(width, dtype=torch.float32), torch.arange(height, dtype=torch.float32))
+        directions = torch.stack([(ii - cx) / fx, (jj - cy) / fx, torch.ones_like(ii)], dim=-1)
+        ray_directions = torch.sum(directions[..., None, :] * rinv, dim=-1)
+        return origin.expand(ray_directions.shape), ray_directions
     host = pose.detach().to("cpu", torch.float32)
     if intrinsic is not None:
         k = intrinsic.detach().to("cpu", torch.float32)
@@ -172,6 +185,28 @@ class MultiViewRaySelector:
         """Rows + target pixels for the view held in `view` (default: self.view, set with `self.view.fill_(k)`)."""
         return _ops.select_rays_indirect(self.height, self.width, self.cams, self.view if view is None else view, self.near,
                                          self.far, pixel_index, self.images)
+
+
+def select_camera_rays(height, width, extrinsic, intrinsic, near, far, pixel_index, image=None, focal_length=None, ndc_focal=None,
+                       ndc_near=1.0):
+    """Packed (N,11) ray rows [ro, rd, near, far, viewdir] of the pixels `pixel_index` (device int64, row-major h*W + w) of ONE
+    camera - and their RGB from `image` (H,W,C) when given: (rows, target | None) - differentiable w.r.t. `extrinsic`, `intrinsic`,
+    a tensor `focal_length` and a tensor `ndc_focal` (camera pose / intrinsics refinement; `intrinsic=None` selects get_ray_bundle's
+    4-argument camera-to-world convention with `focal_length`).  The rows are bit-identical to RaySelector.select's; with `ndc_focal`
+    origin and direction are warped to NDC (near plane `ndc_near`), bit-identical to the NDC draw's rows for the same pixels, the view
+    directions those of the unwarped rays.  One kernel forward (the existing selection kernels), dn_camera_grad backward; a camera that
+    does not require grad, or a call under torch.no_grad(), launches the forward alone."""
+    _require_device(pixel_index, "select_camera_rays")
+    dev = pixel_index.device
+    img = None if image is None else image.to(dev)
+    focal = None if ndc_focal is None else float(ndc_focal.detach() if torch.is_tensor(ndc_focal) else ndc_focal)
+    if _ops.camera_needs_grad(extrinsic, intrinsic, focal_length, ndc_focal):
+        record = _ops.camera_record(extrinsic, intrinsic, focal_length, height, width, ndc_focal)
+        return _ops.CameraRaysFn.apply(record, dev, height, width, pixel_index, near, far, img, focal, ndc_near)
+    with torch.no_grad():
+        record = _ops.camera_record(extrinsic, intrinsic, focal_length, height, width, ndc_focal)
+    cams = record.to(dev) if focal else None
+    return _ops._camera_rays_forward(record.tolist(), cams, int(height), int(width), pixel_index, near, far, img, focal, ndc_near)
 
 
 def get_embedding_function(num_encoding_functions=6, include_input=True, log_sampling=True):
