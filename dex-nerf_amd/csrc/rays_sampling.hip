@@ -98,6 +98,49 @@ __global__ void select_rays_kernel(RayBundleArgs a, float near, float far, const
   }
 }
 
+// The row of ray i: pixel `px` of the camera record `cam`, target pixel from that view's image `img` (NULL target: none).  The body
+// of select_rays_indirect_kernel and select_rays_views_kernel - one sequence of fp32 operations (the unit is compiled with
+// -ffp-contract=off), so the rows of the two kernels are bit-identical for the same (view, pixel).
+template <bool NDC>
+__device__ __forceinline__ void select_ray_row(const float* __restrict__ cam, int height, int width, float near, float far, int64_t px,
+                                               const float* __restrict__ img, int channels, float* __restrict__ r, float* __restrict__ tgt,
+                                               double focal, double ndc_near) {
+  const float fx = cam[12], cx = cam[13], cy = cam[14];
+  const int row = static_cast<int>(px / width);
+  const int col = static_cast<int>(px - static_cast<int64_t>(row) * width);
+  const float d0 = (static_cast<float>(col) - cx) / fx;
+  const float d1 = (static_cast<float>(row) - cy) / fx;
+  const float d2 = 1.0f;
+  float rd[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const float p0 = d0 * cam[3 * j + 0];
+    const float p1 = d1 * cam[3 * j + 1];
+    const float p2 = d2 * cam[3 * j + 2];
+    rd[j] = (p0 + p1) + p2;
+  }
+  const float nrm = sqrtf((rd[0] * rd[0] + rd[1] * rd[1]) + rd[2] * rd[2]);
+  if constexpr (NDC) {
+    const float o[3] = {cam[9], cam[10], cam[11]};
+    ndc_warp(static_cast<double>(height), static_cast<double>(width), focal, ndc_near, o, rd, r, r + 3);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) r[8 + j] = rd[j] / nrm;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      r[j] = cam[9 + j];
+      r[3 + j] = rd[j];
+      r[8 + j] = rd[j] / nrm;
+    }
+  }
+  r[6] = near;
+  r[7] = far;
+  if (tgt != nullptr) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) tgt[c] = img[px * channels + c];
+  }
+}
+
 // The same with the camera chosen on the device: `cams` holds one 16-float record per training view
 // [rinv9, origin3, fx, cx, cy, -] and `view` is a device scalar, so a captured HIP graph of the whole training
 // iteration can be replayed for any view (host-side camera constants would be frozen into the graph).
@@ -126,49 +169,50 @@ __global__ void select_rays_indirect_kernel(const float* __restrict__ cams, cons
     rng_words(rng_state[0], rng_state[1], iteration, kRngStreamView, 0, w);
     v = static_cast<int>(w[0] % static_cast<uint32_t>(n_views));
   }
-  const float* cam = cams + static_cast<int64_t>(v) * 16;
-  const float fx = cam[12], cx = cam[13], cy = cam[14];
   int64_t px;
   if (pix != nullptr) px = pix[i];
   else {
     px = feistel_permute(static_cast<uint32_t>(i), static_cast<uint32_t>(height) * static_cast<uint32_t>(width), rng_state[0], rng_state[1], iteration);
     if (pix_out != nullptr) pix_out[i] = px;
   }
-  const int row = static_cast<int>(px / width);
-  const int col = static_cast<int>(px - static_cast<int64_t>(row) * width);
-  const float d0 = (static_cast<float>(col) - cx) / fx;
-  const float d1 = (static_cast<float>(row) - cy) / fx;
-  const float d2 = 1.0f;
-  float rd[3];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const float p0 = d0 * cam[3 * j + 0];
-    const float p1 = d1 * cam[3 * j + 1];
-    const float p2 = d2 * cam[3 * j + 2];
-    rd[j] = (p0 + p1) + p2;
+  select_ray_row<NDC>(cams + static_cast<int64_t>(v) * 16, height, width, near, far, px,
+                      target != nullptr ? images + static_cast<int64_t>(v) * height * width * channels : nullptr, channels, rays + i * 11,
+                      target != nullptr ? target + i * 3 : nullptr, focal, ndc_near);
+}
+
+// Mixed-camera batches: every ray carries its own view.  pix != NULL: ray i is pixel pix[i] of view view_index[i] (both the caller's
+// contract: 0 <= view_index[i] < n_views).  pix == NULL: the (view, pixel) pairs are DRAWN here - element i of the iteration's draw
+// is q = feistel_permute(i, V H W), the keyed permutation of select_rays_indirect_kernel over the pixels of ALL views, view = q / (H W),
+// pixel = q - view H W - so any prefix is a draw without replacement over (view, pixel) pairs, and with one view it is that kernel's
+// draw.  The first kernel of an iteration like it: thread 0 publishes the state's NEXT counter as the CURRENT one.
+template <bool NDC>
+__global__ void select_rays_views_kernel(const float* __restrict__ cams, const int* __restrict__ view_index, int n_views, int height, int width,
+                                         float near, float far, const int64_t* __restrict__ pix, int64_t n, const float* __restrict__ images,
+                                         int channels, float* __restrict__ rays, float* __restrict__ target, uint32_t* __restrict__ rng_state,
+                                         int64_t* __restrict__ pix_out, int* __restrict__ view_out, double focal, double ndc_near) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  uint32_t iteration = 0;
+  if (pix == nullptr) {
+    iteration = rng_state[3];
+    if (i == 0) rng_state[2] = iteration;   // (nobody in this launch reads word 2)
   }
-  const float nrm = sqrtf((rd[0] * rd[0] + rd[1] * rd[1]) + rd[2] * rd[2]);
-  float* r = rays + i * 11;
-  if constexpr (NDC) {
-    const float o[3] = {cam[9], cam[10], cam[11]};
-    ndc_warp(static_cast<double>(height), static_cast<double>(width), focal, ndc_near, o, rd, r, r + 3);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) r[8 + j] = rd[j] / nrm;
+  if (i >= n) return;
+  const uint32_t per_view = static_cast<uint32_t>(height) * static_cast<uint32_t>(width);
+  int v;
+  int64_t px;
+  if (pix != nullptr) {
+    v = view_index[i];
+    px = pix[i];
   } else {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      r[j] = cam[9 + j];
-      r[3 + j] = rd[j];
-      r[8 + j] = rd[j] / nrm;
-    }
+    const uint32_t q = feistel_permute(static_cast<uint32_t>(i), static_cast<uint32_t>(n_views) * per_view, rng_state[0], rng_state[1], iteration);
+    v = static_cast<int>(q / per_view);
+    px = q - static_cast<uint32_t>(v) * per_view;
+    if (pix_out != nullptr) pix_out[i] = px;
+    if (view_out != nullptr) view_out[i] = v;
   }
-  r[6] = near;
-  r[7] = far;
-  if (target != nullptr) {
-    const float* img = images + static_cast<int64_t>(v) * height * width * channels;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) target[i * 3 + c] = img[px * channels + c];
-  }
+  select_ray_row<NDC>(cams + static_cast<int64_t>(v) * 16, height, width, near, far, px,
+                      target != nullptr ? images + static_cast<int64_t>(v) * height * width * channels : nullptr, channels, rays + i * 11,
+                      target != nullptr ? target + i * 3 : nullptr, focal, ndc_near);
 }
 
 // Forward-facing NDC warp (reference nerf/nerf_helpers.py:172-199), op for op (compiled -ffp-contract=off).
@@ -389,91 +433,102 @@ static int camera_grad_blocks(int64_t n) {
   return static_cast<int>(blocks < kCamGradMaxBlocks ? blocks : kCamGradMaxBlocks);
 }
 
-__global__ __launch_bounds__(kCamGradThreads) void camera_grad_kernel(const float* __restrict__ cam, int width, const int64_t* __restrict__ pix,
-                                                                      int64_t n, const float* __restrict__ g_ro, int ro_stride,
-                                                                      const float* __restrict__ g_rd, int rd_stride,
-                                                                      const float* __restrict__ g_vd, int vd_stride, double height_d,
-                                                                      double ndc_focal, double ndc_near, double* __restrict__ partials) {
-  __shared__ double part[kCamGradThreads / 64][16];
-  double rinv[9], origin[3];
+// The camera record in fp64 and the two NDC scales: what every ray of one camera shares.
+struct CamGradCamera {
+  double rinv[9], origin[3], fx, cx, cy, sx, sy;
+};
+
+__device__ __forceinline__ CamGradCamera camera_grad_load(const float* __restrict__ cam, int width, double height_d, double ndc_focal) {
+  CamGradCamera c;
 #pragma unroll
-  for (int k = 0; k < 9; ++k) rinv[k] = static_cast<double>(cam[k]);
+  for (int k = 0; k < 9; ++k) c.rinv[k] = static_cast<double>(cam[k]);
 #pragma unroll
-  for (int k = 0; k < 3; ++k) origin[k] = static_cast<double>(cam[9 + k]);
-  const double fx = static_cast<double>(cam[12]), cx = static_cast<double>(cam[13]), cy = static_cast<double>(cam[14]);
-  const bool ndc = ndc_focal > 0.0;
-  const double sx = -1.0 / (static_cast<double>(width) / (2.0 * ndc_focal));
-  const double sy = -1.0 / (height_d / (2.0 * ndc_focal));
-  double acc[16];
+  for (int k = 0; k < 3; ++k) c.origin[k] = static_cast<double>(cam[9 + k]);
+  c.fx = static_cast<double>(cam[12]);
+  c.cx = static_cast<double>(cam[13]);
+  c.cy = static_cast<double>(cam[14]);
+  c.sx = -1.0 / (static_cast<double>(width) / (2.0 * ndc_focal));
+  c.sy = -1.0 / (height_d / (2.0 * ndc_focal));
+  return c;
+}
+
+// The Jacobian of ray i (pixel px of camera c) applied to its upstream gradients, added to the 16 sums of the record's gradient:
+// the one statement of the formulas above, shared by camera_grad_kernel and camera_grad_views_kernel.
+__device__ __forceinline__ void camera_grad_ray(const CamGradCamera& c, int width, int64_t px, int64_t i, const float* __restrict__ g_ro,
+                                                int ro_stride, const float* __restrict__ g_rd, int rd_stride, const float* __restrict__ g_vd,
+                                                int vd_stride, bool ndc, double ndc_focal, double ndc_near, double (&acc)[16]) {
+  const double* rinv = c.rinv;
+  const double* origin = c.origin;
+  const double fx = c.fx, cx = c.cx, cy = c.cy, sx = c.sx, sy = c.sy;
+  const int64_t row = px / width;
+  const int64_t col = px - row * width;
+  const double d[3] = {(static_cast<double>(col) - cx) / fx, (static_cast<double>(row) - cy) / fx, 1.0};
+  double rd[3];
 #pragma unroll
-  for (int k = 0; k < 16; ++k) acc[k] = 0.0;
-  const int64_t step = static_cast<int64_t>(gridDim.x) * kCamGradThreads;
-  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kCamGradThreads + threadIdx.x; i < n; i += step) {
-    const int64_t px = (pix != nullptr) ? pix[i] : i;
-    const int64_t row = px / width;
-    const int64_t col = px - row * width;
-    const double d[3] = {(static_cast<double>(col) - cx) / fx, (static_cast<double>(row) - cy) / fx, 1.0};
-    double rd[3];
+  for (int j = 0; j < 3; ++j) rd[j] = (d[0] * rinv[3 * j + 0] + d[1] * rinv[3 * j + 1]) + d[2] * rinv[3 * j + 2];
+  double go[3] = {0.0, 0.0, 0.0}, gd[3] = {0.0, 0.0, 0.0};
+  if (g_ro != nullptr) {
 #pragma unroll
-    for (int j = 0; j < 3; ++j) rd[j] = (d[0] * rinv[3 * j + 0] + d[1] * rinv[3 * j + 1]) + d[2] * rinv[3 * j + 2];
-    double go[3] = {0.0, 0.0, 0.0}, gd[3] = {0.0, 0.0, 0.0};
-    if (g_ro != nullptr) {
+    for (int j = 0; j < 3; ++j) go[j] = static_cast<double>(g_ro[i * ro_stride + j]);
+  }
+  if (g_rd != nullptr) {
 #pragma unroll
-      for (int j = 0; j < 3; ++j) go[j] = static_cast<double>(g_ro[i * ro_stride + j]);
-    }
-    if (g_rd != nullptr) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) gd[j] = static_cast<double>(g_rd[i * rd_stride + j]);
-    }
-    if (ndc) {
-      // forward: t = -(near + o_z) / rd_z, p = o + t rd, o' = [sx p0 / p2, sy p1 / p2, 1 + 2 near / p2],
-      //          d' = [sx (rd0 / rd2 - p0 / p2), sy (rd1 / rd2 - p1 / p2), -2 near / p2]
-      const double t = -(ndc_near + origin[2]) / rd[2];
-      const double p[3] = {origin[0] + t * rd[0], origin[1] + t * rd[1], origin[2] + t * rd[2]};
-      const double ip = 1.0 / p[2], iz = 1.0 / rd[2];
-      const double o0 = sx * p[0] * ip, o1 = sy * p[1] * ip;
-      const double w0 = sx * (rd[0] * iz - p[0] * ip), w1 = sy * (rd[1] * iz - p[1] * ip);
-      acc[15] += (go[0] * o0 + go[1] * o1 + gd[0] * w0 + gd[1] * w1) / ndc_focal;
-      const double a0 = go[0] - gd[0], a1 = go[1] - gd[1];
-      double gp[3];
-      gp[0] = sx * ip * a0;
-      gp[1] = sy * ip * a1;
-      gp[2] = -(sx * p[0] * a0 + sy * p[1] * a1) * ip * ip + 2.0 * ndc_near * ip * ip * (gd[2] - go[2]);
-      double gr[3];
-      gr[0] = sx * iz * gd[0];
-      gr[1] = sy * iz * gd[1];
-      gr[2] = -(sx * rd[0] * gd[0] + sy * rd[1] * gd[1]) * iz * iz;
-      const double gt = gp[0] * rd[0] + gp[1] * rd[1] + gp[2] * rd[2];
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        go[j] = gp[j];
-        gd[j] = gr[j] + t * gp[j];
-      }
-      go[2] -= gt * iz;
-      gd[2] -= gt * t * iz;
-    }
-    if (g_vd != nullptr) {
-      const double gv[3] = {static_cast<double>(g_vd[i * vd_stride + 0]), static_cast<double>(g_vd[i * vd_stride + 1]),
-                            static_cast<double>(g_vd[i * vd_stride + 2])};
-      const double inv_nrm = 1.0 / sqrt((rd[0] * rd[0] + rd[1] * rd[1]) + rd[2] * rd[2]);
-      const double v[3] = {rd[0] * inv_nrm, rd[1] * inv_nrm, rd[2] * inv_nrm};
-      const double vg = (v[0] * gv[0] + v[1] * gv[1]) + v[2] * gv[2];
-#pragma unroll
-      for (int j = 0; j < 3; ++j) gd[j] += (gv[j] - v[j] * vg) * inv_nrm;
-    }
-    double e[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) e[k] = (gd[0] * rinv[k] + gd[1] * rinv[3 + k]) + gd[2] * rinv[6 + k];
+    for (int j = 0; j < 3; ++j) gd[j] = static_cast<double>(g_rd[i * rd_stride + j]);
+  }
+  if (ndc) {
+    // forward: t = -(near + o_z) / rd_z, p = o + t rd, o' = [sx p0 / p2, sy p1 / p2, 1 + 2 near / p2],
+    //          d' = [sx (rd0 / rd2 - p0 / p2), sy (rd1 / rd2 - p1 / p2), -2 near / p2]
+    const double t = -(ndc_near + origin[2]) / rd[2];
+    const double p[3] = {origin[0] + t * rd[0], origin[1] + t * rd[1], origin[2] + t * rd[2]};
+    const double ip = 1.0 / p[2], iz = 1.0 / rd[2];
+    const double o0 = sx * p[0] * ip, o1 = sy * p[1] * ip;
+    const double w0 = sx * (rd[0] * iz - p[0] * ip), w1 = sy * (rd[1] * iz - p[1] * ip);
+    acc[15] += (go[0] * o0 + go[1] * o1 + gd[0] * w0 + gd[1] * w1) / ndc_focal;
+    const double a0 = go[0] - gd[0], a1 = go[1] - gd[1];
+    double gp[3];
+    gp[0] = sx * ip * a0;
+    gp[1] = sy * ip * a1;
+    gp[2] = -(sx * p[0] * a0 + sy * p[1] * a1) * ip * ip + 2.0 * ndc_near * ip * ip * (gd[2] - go[2]);
+    double gr[3];
+    gr[0] = sx * iz * gd[0];
+    gr[1] = sy * iz * gd[1];
+    gr[2] = -(sx * rd[0] * gd[0] + sy * rd[1] * gd[1]) * iz * iz;
+    const double gt = gp[0] * rd[0] + gp[1] * rd[1] + gp[2] * rd[2];
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-      acc[9 + j] += go[j];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) acc[3 * j + k] += gd[j] * d[k];
+      go[j] = gp[j];
+      gd[j] = gr[j] + t * gp[j];
     }
-    acc[12] -= (e[0] * d[0] + e[1] * d[1]) / fx;
-    acc[13] -= e[0] / fx;
-    acc[14] -= e[1] / fx;
+    go[2] -= gt * iz;
+    gd[2] -= gt * t * iz;
   }
+  if (g_vd != nullptr) {
+    const double gv[3] = {static_cast<double>(g_vd[i * vd_stride + 0]), static_cast<double>(g_vd[i * vd_stride + 1]),
+                          static_cast<double>(g_vd[i * vd_stride + 2])};
+    const double inv_nrm = 1.0 / sqrt((rd[0] * rd[0] + rd[1] * rd[1]) + rd[2] * rd[2]);
+    const double v[3] = {rd[0] * inv_nrm, rd[1] * inv_nrm, rd[2] * inv_nrm};
+    const double vg = (v[0] * gv[0] + v[1] * gv[1]) + v[2] * gv[2];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) gd[j] += (gv[j] - v[j] * vg) * inv_nrm;
+  }
+  double e[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) e[k] = (gd[0] * rinv[k] + gd[1] * rinv[3 + k]) + gd[2] * rinv[6 + k];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    acc[9 + j] += go[j];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) acc[3 * j + k] += gd[j] * d[k];
+  }
+  acc[12] -= (e[0] * d[0] + e[1] * d[1]) / fx;
+  acc[13] -= e[0] / fx;
+  acc[14] -= e[1] / fx;
+}
+
+// The 16 sums of a workgroup: wave_sum's butterfly, the waves through LDS in wave order, 16 doubles stored.  Every thread of the
+// workgroup calls it (it holds a barrier).
+__device__ __forceinline__ void camera_grad_block_store(const double (&acc)[16], double* __restrict__ out16) {
+  __shared__ double part[kCamGradThreads / 64][16];
   const int wave = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < 16; ++k) {
@@ -484,15 +539,59 @@ __global__ __launch_bounds__(kCamGradThreads) void camera_grad_kernel(const floa
   if (threadIdx.x < 16) {
     double s = part[0][threadIdx.x];
     for (int w = 1; w < kCamGradThreads / 64; ++w) s += part[w][threadIdx.x];
-    partials[static_cast<int64_t>(blockIdx.x) * 16 + threadIdx.x] = s;
+    out16[threadIdx.x] = s;
   }
 }
 
+__global__ __launch_bounds__(kCamGradThreads) void camera_grad_kernel(const float* __restrict__ cam, int width, const int64_t* __restrict__ pix,
+                                                                      int64_t n, const float* __restrict__ g_ro, int ro_stride,
+                                                                      const float* __restrict__ g_rd, int rd_stride,
+                                                                      const float* __restrict__ g_vd, int vd_stride, double height_d,
+                                                                      double ndc_focal, double ndc_near, double* __restrict__ partials) {
+  const CamGradCamera c = camera_grad_load(cam, width, height_d, ndc_focal);
+  const bool ndc = ndc_focal > 0.0;
+  double acc[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) acc[k] = 0.0;
+  const int64_t step = static_cast<int64_t>(gridDim.x) * kCamGradThreads;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kCamGradThreads + threadIdx.x; i < n; i += step) {
+    const int64_t px = (pix != nullptr) ? pix[i] : i;
+    camera_grad_ray(c, width, px, i, g_ro, ro_stride, g_rd, rd_stride, g_vd, vd_stride, ndc, ndc_focal, ndc_near, acc);
+  }
+  camera_grad_block_store(acc, partials + static_cast<int64_t>(blockIdx.x) * 16);
+}
+
+// Mixed-camera batches: workgroup (b, v) of a (camera_grad_blocks(n), V) grid walks the rays in camera_grad_kernel's order and adds
+// those of view v (the others are skipped: the 4-byte view index of every ray is read once per view), then stores its 16 sums at
+// partials[(v blocks + b) 16]; camera_grad_finish_kernel, one workgroup per view, adds a view's partials in workgroup order.  The
+// order of every sum is a function of (n, V) and the view indices alone: plain stores, bit-reproducible on any device.
+__global__ __launch_bounds__(kCamGradThreads) void camera_grad_views_kernel(const float* __restrict__ cams, int width, const int* __restrict__ view_index,
+                                                                            const int64_t* __restrict__ pix, int64_t n,
+                                                                            const float* __restrict__ g_ro, int ro_stride,
+                                                                            const float* __restrict__ g_rd, int rd_stride,
+                                                                            const float* __restrict__ g_vd, int vd_stride, double height_d,
+                                                                            double ndc_focal, double ndc_near, double* __restrict__ partials) {
+  const int view = static_cast<int>(blockIdx.y);
+  const CamGradCamera c = camera_grad_load(cams + static_cast<int64_t>(view) * 16, width, height_d, ndc_focal);
+  const bool ndc = ndc_focal > 0.0;
+  double acc[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) acc[k] = 0.0;
+  const int64_t step = static_cast<int64_t>(gridDim.x) * kCamGradThreads;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kCamGradThreads + threadIdx.x; i < n; i += step) {
+    if (view_index[i] != view) continue;
+    camera_grad_ray(c, width, pix[i], i, g_ro, ro_stride, g_rd, rd_stride, g_vd, vd_stride, ndc, ndc_focal, ndc_near, acc);
+  }
+  camera_grad_block_store(acc, partials + (static_cast<int64_t>(view) * gridDim.x + blockIdx.x) * 16);
+}
+
+// Workgroup v adds the n_blocks partials of record v in workgroup order (dn_camera_grad: one record, one workgroup).
 __global__ __launch_bounds__(64) void camera_grad_finish_kernel(const double* __restrict__ partials, int n_blocks, float* __restrict__ g_cam) {
   if (threadIdx.x >= 16) return;
+  const double* mine = partials + static_cast<int64_t>(blockIdx.x) * n_blocks * 16;
   double s = 0.0;
-  for (int b = 0; b < n_blocks; ++b) s += partials[b * 16 + threadIdx.x];
-  g_cam[threadIdx.x] = static_cast<float>(s);
+  for (int b = 0; b < n_blocks; ++b) s += mine[b * 16 + threadIdx.x];
+  g_cam[static_cast<int64_t>(blockIdx.x) * 16 + threadIdx.x] = static_cast<float>(s);
 }
 
 static int next_pow2(int v) {
@@ -626,6 +725,91 @@ extern "C" int dn_select_rays_draw_ndc(int height, int width, const float* cams,
                      far, static_cast<const int64_t*>(nullptr), n_rays, images, channels, rays, target, rng_state, pixel_index_out, focal,
                      ndc_near);
   return check_launch("dn_select_rays_draw_ndc");
+}
+
+extern "C" int dn_select_rays_views(int height, int width, const float* cams, int n_views, const int32_t* view_index, float near, float far,
+                                    const int64_t* pixel_index, int64_t n_rays, const float* images, int channels, float* rays, float* target,
+                                    double ndc_focal, double ndc_near, dn_stream_t stream) {
+  if (n_rays == 0) return 0;
+  DN_REQUIRE(height > 0 && width > 0 && rays && n_rays >= 0, "dn_select_rays_views: bad arguments (image size, ray count, rows)");
+  DN_REQUIRE(cams != nullptr && n_views >= 1, "dn_select_rays_views: the camera records (n_views >= 1) must be given");
+  DN_REQUIRE(view_index != nullptr && pixel_index != nullptr, "dn_select_rays_views: view_index and pixel_index must be given");
+  DN_REQUIRE(static_cast<int64_t>(n_views) * height * width < (1LL << 31), "dn_select_rays_views: n_views x image too large (V H W must be < 2^31)");
+  DN_REQUIRE(target == nullptr || (images != nullptr && channels >= 3), "dn_select_rays_views: target requested without images of >= 3 channels");
+  DN_REQUIRE(std::isfinite(ndc_focal) && ndc_focal >= 0.0 && std::isfinite(ndc_near),
+             "dn_select_rays_views: ndc_focal must be finite and >= 0 (0: world-space rays), the near plane finite");
+  const int block = 256;
+  const unsigned grid = static_cast<unsigned>((n_rays + block - 1) / block);
+  if (ndc_focal > 0.0) {
+    hipLaunchKernelGGL(select_rays_views_kernel<true>, dim3(grid), dim3(block), 0, as_stream(stream), cams, view_index, n_views, height, width, near,
+                       far, pixel_index, n_rays, images, channels, rays, target, static_cast<uint32_t*>(nullptr), static_cast<int64_t*>(nullptr),
+                       static_cast<int*>(nullptr), ndc_focal, ndc_near);
+  } else {
+    hipLaunchKernelGGL(select_rays_views_kernel<false>, dim3(grid), dim3(block), 0, as_stream(stream), cams, view_index, n_views, height, width, near,
+                       far, pixel_index, n_rays, images, channels, rays, target, static_cast<uint32_t*>(nullptr), static_cast<int64_t*>(nullptr),
+                       static_cast<int*>(nullptr), 0.0, 0.0);
+  }
+  return check_launch("dn_select_rays_views");
+}
+
+extern "C" int dn_select_rays_draw_views(int height, int width, const float* cams, int n_views, float near, float far, uint32_t* rng_state,
+                                         int64_t n_rays, const float* images, int channels, float* rays, float* target,
+                                         int64_t* pixel_index_out, int32_t* view_index_out, double ndc_focal, double ndc_near, dn_stream_t stream) {
+  DN_REQUIRE(height > 0 && width > 0 && rng_state && rays, "dn_select_rays_draw_views: bad arguments (image size, RNG state, rows)");
+  DN_REQUIRE(cams != nullptr && n_views >= 1, "dn_select_rays_draw_views: the camera records (n_views >= 1) must be given");
+  DN_REQUIRE(static_cast<int64_t>(n_views) * height * width < (1LL << 31), "dn_select_rays_draw_views: n_views x image too large (V H W must be < 2^31)");
+  DN_REQUIRE(n_rays >= 1 && n_rays <= static_cast<int64_t>(n_views) * height * width,
+             "dn_select_rays_draw_views: need 1 <= n_rays <= V H W (the draw is without replacement)");
+  DN_REQUIRE(target == nullptr || (images != nullptr && channels >= 3), "dn_select_rays_draw_views: target requested without images of >= 3 channels");
+  DN_REQUIRE(std::isfinite(ndc_focal) && ndc_focal >= 0.0 && std::isfinite(ndc_near),
+             "dn_select_rays_draw_views: ndc_focal must be finite and >= 0 (0: world-space rays), the near plane finite");
+  const int block = 256;
+  const unsigned grid = static_cast<unsigned>((n_rays + block - 1) / block);
+  if (ndc_focal > 0.0) {
+    hipLaunchKernelGGL(select_rays_views_kernel<true>, dim3(grid), dim3(block), 0, as_stream(stream), cams, static_cast<const int*>(nullptr), n_views,
+                       height, width, near, far, static_cast<const int64_t*>(nullptr), n_rays, images, channels, rays, target, rng_state,
+                       pixel_index_out, view_index_out, ndc_focal, ndc_near);
+  } else {
+    hipLaunchKernelGGL(select_rays_views_kernel<false>, dim3(grid), dim3(block), 0, as_stream(stream), cams, static_cast<const int*>(nullptr), n_views,
+                       height, width, near, far, static_cast<const int64_t*>(nullptr), n_rays, images, channels, rays, target, rng_state,
+                       pixel_index_out, view_index_out, 0.0, 0.0);
+  }
+  return check_launch("dn_select_rays_draw_views");
+}
+
+extern "C" size_t dn_camera_grad_views_scratch_bytes(int64_t n_rays, int n_views) {
+  const int blocks = camera_grad_blocks(n_rays > 0 ? n_rays : 0);
+  return static_cast<size_t>(blocks > 0 ? blocks : 1) * static_cast<size_t>(n_views > 0 ? n_views : 1) * 16 * sizeof(double);
+}
+
+extern "C" int dn_camera_grad_views(int height, int width, const float* cams, int n_views, const int32_t* view_index, const int64_t* pixel_index,
+                                    int64_t n_rays, const float* g_ro, int ro_stride, const float* g_rd, int rd_stride, const float* g_viewdir,
+                                    int vd_stride, double ndc_focal, double ndc_near, void* scratch, size_t scratch_bytes, float* g_cams,
+                                    dn_stream_t stream) {
+  DN_REQUIRE(height > 0 && width > 0 && n_rays >= 0, "dn_camera_grad_views: bad arguments (image size, ray count)");
+  DN_REQUIRE(cams != nullptr && g_cams != nullptr, "dn_camera_grad_views: the camera records and their gradient must be given");
+  DN_REQUIRE(n_views >= 1 && n_views <= 65535, "dn_camera_grad_views: n_views must be in [1, 65535]");
+  DN_REQUIRE(view_index != nullptr && pixel_index != nullptr, "dn_camera_grad_views: view_index and pixel_index must be given");
+  DN_REQUIRE(g_ro != nullptr || g_rd != nullptr || g_viewdir != nullptr, "dn_camera_grad_views: no upstream gradient given");
+  DN_REQUIRE((g_ro == nullptr || ro_stride >= 3) && (g_rd == nullptr || rd_stride >= 3) && (g_viewdir == nullptr || vd_stride >= 3),
+             "dn_camera_grad_views: the row stride of an upstream gradient must be >= 3 floats");
+  DN_REQUIRE(static_cast<int64_t>(n_views) * height * width < (1LL << 31), "dn_camera_grad_views: n_views x image too large (V H W must be < 2^31)");
+  DN_REQUIRE(std::isfinite(ndc_focal) && ndc_focal >= 0.0 && std::isfinite(ndc_near),
+             "dn_camera_grad_views: ndc_focal must be finite and >= 0 (0: world-space rays), the near plane finite");
+  DN_REQUIRE(scratch != nullptr && scratch_bytes >= dn_camera_grad_views_scratch_bytes(n_rays, n_views),
+             "dn_camera_grad_views: scratch smaller than dn_camera_grad_views_scratch_bytes(n_rays, n_views)");
+  DN_REQUIRE(reinterpret_cast<uintptr_t>(scratch) % 8 == 0, "dn_camera_grad_views: scratch must be 8-byte aligned");
+  const int blocks = camera_grad_blocks(n_rays);
+  double* partials = static_cast<double*>(scratch);
+  if (blocks > 0) {
+    hipLaunchKernelGGL(camera_grad_views_kernel, dim3(blocks, n_views), dim3(kCamGradThreads), 0, as_stream(stream), cams, width, view_index,
+                       pixel_index, n_rays, g_ro, ro_stride, g_rd, rd_stride, g_viewdir, vd_stride, static_cast<double>(height), ndc_focal,
+                       ndc_near, partials);
+    const int rc = check_launch("dn_camera_grad_views");
+    if (rc != 0) return rc;
+  }
+  hipLaunchKernelGGL(camera_grad_finish_kernel, dim3(n_views), dim3(64), 0, as_stream(stream), partials, blocks, g_cams);   // (no rays: V x 16 zeros)
+  return check_launch("dn_camera_grad_views");
 }
 
 // ---- S9 loss head on the device: mse(rgb_coarse, target) + mse(rgb_fine, target) (train_dexnerf_rgb.py:264-277; with

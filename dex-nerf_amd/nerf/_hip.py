@@ -36,6 +36,7 @@ EXPORTS = (
     "dn_render_depth_workspace_bytes", "dn_render_rays_depth",
     "dn_volume_render_backward_geom", "dn_coarse_depths_backward", "dn_fine_depths_backward",
     "dn_select_rays_indirect_ndc", "dn_camera_grad_scratch_bytes", "dn_camera_grad",
+    "dn_select_rays_views", "dn_select_rays_draw_views", "dn_camera_grad_views_scratch_bytes", "dn_camera_grad_views",
 )
 
 
@@ -144,10 +145,16 @@ def _declare(lib):
     lib.dn_camera_grad_scratch_bytes.argtypes = [c_int64]
     lib.dn_camera_grad_scratch_bytes.restype = c_size_t
     lib.dn_camera_grad.argtypes = [c_int, c_int, fp, vp, c_int64, fp, c_int, fp, c_int, fp, c_int, dbl, dbl, vp, c_size_t, fp, vp]
+    lib.dn_select_rays_views.argtypes = [c_int, c_int, fp, c_int, vp, c_float, c_float, vp, c_int64, fp, c_int, fp, fp, dbl, dbl, vp]
+    lib.dn_select_rays_draw_views.argtypes = [c_int, c_int, fp, c_int, c_float, c_float, vp, c_int64, fp, c_int, fp, fp, vp, vp, dbl, dbl, vp]
+    lib.dn_camera_grad_views_scratch_bytes.argtypes = [c_int64, c_int]
+    lib.dn_camera_grad_views_scratch_bytes.restype = c_size_t
+    lib.dn_camera_grad_views.argtypes = [c_int, c_int, fp, c_int, vp, vp, c_int64, fp, c_int, fp, c_int, fp, c_int, dbl, dbl, vp, c_size_t, fp, vp]
     for name in EXPORTS:
         if name not in ("dn_last_error", "dn_mlp_density_packed_bytes", "dn_render_depth_workspace_bytes", "dn_mlp_packed_bytes", "dn_render_workspace_bytes",
                         "dn_mlp_backward_packed_bytes", "dn_render_train_workspace_bytes",
-                        "dn_mlp_input_grad_packed_bytes", "dn_mlp_backward_input_workspace_bytes", "dn_camera_grad_scratch_bytes"):
+                        "dn_mlp_input_grad_packed_bytes", "dn_mlp_backward_input_workspace_bytes", "dn_camera_grad_scratch_bytes",
+                        "dn_camera_grad_views_scratch_bytes"):
             getattr(lib, name).restype = c_int
 
 

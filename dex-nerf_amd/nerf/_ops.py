@@ -347,6 +347,103 @@ class CameraRaysFn(torch.autograd.Function):
         return (g_cam.cpu().to(dtype),) + (None,) * 9
 
 
+# ---- mixed-camera batches: a view index per ray --------------------------------------------------------------------------
+def _view_index(view_index, n):
+    views = view_index.contiguous()
+    assert views.dtype == torch.int32 and views.is_cuda and views.dim() == 1 and views.numel() == n, "view_index: (N,) int32 on the device"
+    return views
+
+
+def select_rays_views(height, width, cams, view_index, near, far, pixel_index, images=None, ndc_focal=None, ndc_near=1.0):
+    """select_rays_indirect with a view per ray (dn_select_rays_views): row i is pixel `pixel_index[i]` of camera `view_index[i]`
+    ((N,) int32, device) out of `cams` (V,16), its target from `images` (V,H,W,C).  ndc_focal: NDC rows (select_rays_indirect_ndc's)."""
+    pix = pixel_index.contiguous()
+    assert pix.dtype == torch.int64 and cams.dtype == torch.float32 and cams.is_contiguous() and cams.dim() == 2
+    n = pix.numel()
+    views = _view_index(view_index, n)
+    rays, target, img, channels = _ray_outputs(n, images, pix.device)
+    check(lib().dn_select_rays_views(int(height), int(width), ptr(cams), int(cams.shape[0]), ptr(views), float(near), float(far), ptr(pix), n,
+                                     ptr(img), channels, ptr(rays), ptr(target), float(ndc_focal or 0.0), float(ndc_near), stream()),
+          "dn_select_rays_views")
+    return rays, target
+
+
+def select_rays_draw_views(height, width, cams, near, far, rng_state, n_rays, images=None, want_pixels=False, ndc_focal=None, ndc_near=1.0):
+    """select_rays_draw with the view of every ray drawn too (dn_select_rays_draw_views): `n_rays` distinct (view, pixel) pairs out of
+    the V H W pixels of all cameras in `cams`, from `rng_state`'s next iteration.  Returns (rows, target), with want_pixels also the
+    drawn pixels (int64) and views (int32)."""
+    assert cams.dtype == torch.float32 and cams.is_contiguous() and cams.dim() == 2 and rng_state.dtype == torch.int32
+    dev = cams.device
+    rays, target, img, channels = _ray_outputs(n_rays, images, dev)
+    pix = torch.empty((n_rays,), dtype=torch.int64, device=dev) if want_pixels else None
+    views = torch.empty((n_rays,), dtype=torch.int32, device=dev) if want_pixels else None
+    check(lib().dn_select_rays_draw_views(int(height), int(width), ptr(cams), int(cams.shape[0]), float(near), float(far), ptr(rng_state),
+                                          int(n_rays), ptr(img), channels, ptr(rays), ptr(target), ptr(pix), ptr(views),
+                                          float(ndc_focal or 0.0), float(ndc_near), stream()), "dn_select_rays_draw_views")
+    return (rays, target, pix, views) if want_pixels else (rays, target)
+
+
+def camera_grad_views_scratch_bytes(n, n_views):
+    return int(lib().dn_camera_grad_views_scratch_bytes(int(n), int(n_views)))
+
+
+def camera_grad_views(height, width, cams, view_index, pixel_index, n, g_ro, g_rd, g_viewdir, ndc_focal=0.0, ndc_near=1.0):
+    """dn_camera_grad_views: the (V,16) device gradient of the camera records `cams` from upstream gradients of a mixed batch's
+    origins / directions / view directions (as camera_grad takes them); row v sums the rays with view_index == v."""
+    assert cams.is_cuda and cams.dtype == torch.float32 and cams.is_contiguous() and cams.dim() == 2 and cams.shape[1] == 16
+    pix = pixel_index.contiguous()
+    assert pix.dtype == torch.int64 and pix.is_cuda and pix.numel() == n
+    views = _view_index(view_index, n)
+    if n == 0:   # empty tensors carry NULL data pointers, which the entry point refuses: one unread element each (V x 16 zeros are written)
+        pix, views = pix.new_zeros(1), views.new_zeros(1)
+        g_ro, g_rd, g_viewdir = torch.zeros((1, 3), dtype=torch.float32, device=cams.device), None, None
+    keep, args = [], []
+    for g in (g_ro, g_rd, g_viewdir):
+        if g is None:
+            args += [None, 0]
+        else:
+            p, stride, t = _dir_rows(g)
+            keep.append(t)
+            args += [p, stride]
+    n_views = int(cams.shape[0])
+    nbytes = camera_grad_views_scratch_bytes(n, n_views)
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=cams.device)
+    g_cams = torch.empty((n_views, 16), dtype=torch.float32, device=cams.device)
+    check(lib().dn_camera_grad_views(int(height), int(width), ptr(cams), n_views, ptr(views), ptr(pix), int(n), *args, float(ndc_focal),
+                                     float(ndc_near), ptr(scratch), nbytes, ptr(g_cams), stream()), "dn_camera_grad_views")
+    return g_cams
+
+
+class CameraRaysViewsFn(torch.autograd.Function):
+    """CameraRaysFn for a mixed batch: `records` (V,16) on the host (camera_record per view, stacked), `view_index` / `pixel_index`
+    (N) on the device -> rows (N,11), target (N,3) | None.  Forward dn_select_rays_views, backward dn_camera_grad_views into a (V,16)
+    device tensor returned as the gradient of the host records: ONE device-to-host read per backward (V x 64 bytes), which
+    synchronises - so it cannot run under stream capture, and raises there."""
+
+    @staticmethod
+    def forward(ctx, records, device, height, width, view_index, pixel_index, near, far, images, ndc_focal, ndc_near):
+        cams = records.detach().to(torch.float32).contiguous().to(device)
+        ctx.save_for_backward(cams, view_index, pixel_index)
+        ctx.cfg = (int(height), int(width), float(ndc_focal or 0.0), float(ndc_near), records.dtype)
+        out = select_rays_views(int(height), int(width), cams, view_index, near, far, pixel_index, images, ndc_focal, ndc_near)
+        if out[1] is not None:
+            ctx.mark_non_differentiable(out[1])
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_a, g_b):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("CameraRaysViewsFn.backward: the camera gradient is read back to the host (64 bytes per view), which cannot be "
+                               "captured into a HIP graph; run the camera's backward outside the capture")
+        cams, views, pix = ctx.saved_tensors
+        height, width, ndc_focal, ndc_near, dtype = ctx.cfg
+        n = pix.numel()
+        g = f32c(g_a) if g_a is not None else torch.zeros((n, 11), dtype=torch.float32, device=cams.device)
+        g_cams = camera_grad_views(height, width, cams, views, pix, n, g[:, 0:3], g[:, 3:6], g[:, 8:11], ndc_focal, ndc_near)
+        return (g_cams.cpu().to(dtype),) + (None,) * 10
+
+
 def camera_needs_grad(*values):
     """True when grad is enabled and one of the camera quantities (tensors; floats and None are skipped) requires grad."""
     return torch.is_grad_enabled() and any(torch.is_tensor(v) and v.requires_grad for v in values)

@@ -2,6 +2,8 @@
 fine render -> mse + mse -> backward -> Adam) with nothing in it but this library's kernels - 16 launches on the as-shipped nets:
 
     dn_select_rays_draw      view + pixels drawn without replacement on the device, packed ray rows, target pixels   (1 kernel)
+                             (draw_view="rays": dn_select_rays_draw_views - every ray's view drawn with its pixel, a batch
+                             across all training images)
                              (forward-facing captures, no_ndc: False: dn_select_rays_draw_ndc - the rows warped to NDC in the
                              same kernel, near plane 1, as run_one_iter_of_nerf does)
     dn_mlp_pack_train_pair   both weight streams of both networks                                                     (2 kernels)
@@ -28,6 +30,8 @@ from .train_utils import _fusable
 class FusedTrainStep:
     def __init__(self, model_coarse, model_fine, selector, options, bucket, encode_position_fn, encode_direction_fn, num_rays, seed=0,
                  luminance=False, first_iteration=0, draw_view=False, ndc_focal=None):
+        if not (isinstance(draw_view, bool) or draw_view == "rays"):
+            raise ValueError(f"FusedTrainStep: draw_view must be False, True or \"rays\" (got {draw_view!r})")
         opt = options.nerf.train
         self.ndc = getattr(options.dataset, "no_ndc", True) is False
         if self.ndc and ndc_focal is None:
@@ -46,7 +50,9 @@ class FusedTrainStep:
         dev = next(model_coarse.parameters()).device
         self.rng_state = _ops.new_rng_state(seed, dev, first_iteration)
         self.loss3 = None
-        self.draw_view = bool(draw_view)   # True: the iteration's training view is drawn in the kernel too (else: selector.view)
+        # True: the iteration's training view is drawn in the kernel too (else: selector.view); "rays": the view of EVERY ray is drawn
+        # with its pixel, a batch across all training images (dn_select_rays_draw_views)
+        self.draw_view = draw_view
         self.zero_in_step = True     # False: the optimizer leaves the gradient bucket cleared (FlatAdam(zero_grads=True))
 
     @staticmethod
@@ -85,8 +91,12 @@ class FusedTrainStep:
         of both networks in ONE launch (dn_mlp_weight_grad_pair); coarse_backward() must not follow."""
         mc, mf = self.models
         sel = self.selector
-        rays, target = _ops.select_rays_draw(sel.height, sel.width, sel.cams, None if self.draw_view else sel.view, sel.near, sel.far,
-                                             self.rng_state, self.num_rays, sel.images, ndc_focal=self.ndc_focal, ndc_near=1.0)
+        if self.draw_view == "rays":
+            rays, target = _ops.select_rays_draw_views(sel.height, sel.width, sel.cams, sel.near, sel.far, self.rng_state, self.num_rays,
+                                                       sel.images, ndc_focal=self.ndc_focal, ndc_near=1.0)
+        else:
+            rays, target = _ops.select_rays_draw(sel.height, sel.width, sel.cams, None if self.draw_view else sel.view, sel.near, sel.far,
+                                                 self.rng_state, self.num_rays, sel.images, ndc_focal=self.ndc_focal, ndc_near=1.0)
         pc, pf, prec = _ops.pack_train_pair(mc, mf, self.logs)
         maps, saved = _ops.render_rays_train(pc, pf, rays, self.nc, self.nf, self.lindisp, self.noise_std, self.white, [], None, prec=prec,
                                              rng_state=self.rng_state, perturb=self.perturb)

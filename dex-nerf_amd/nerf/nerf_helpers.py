@@ -154,6 +154,15 @@ class RaySelector:
                                 pixel_index, image)
 
 
+def random_view_pixel_pairs(n_views, pixels_per_view, n, device, generator=None):
+    """(view_index (n,) int32, pixel_index (n,) int64) of n distinct (view, pixel) pairs: the first n elements of a device randperm
+    over the n_views * pixels_per_view pixels of all views, q -> (q // pixels_per_view, q % pixels_per_view)."""
+    total = n_views * pixels_per_view
+    q = torch.randperm(total, device=device, generator=generator)[:min(n, total)]
+    view = torch.div(q, pixels_per_view, rounding_mode="floor")
+    return view.to(torch.int32), q - view * pixels_per_view
+
+
 class MultiViewRaySelector:
     """RaySelector for a set of training cameras whose index is a DEVICE scalar: the camera records (two host inverses per
     view, once) and the stacked images live on the device, so `select` contains no per-view host constant and a captured
@@ -181,21 +190,66 @@ class MultiViewRaySelector:
         total = self.height * self.width
         return torch.randperm(total, device=self.device, generator=generator)[:min(n, total)]
 
+    def random_pairs(self, n, generator=None):
+        """(view_index (n,) int32, pixel_index (n,) int64): n distinct (view, pixel) pairs out of the V H W pixels of all views,
+        drawn on the device."""
+        return random_view_pixel_pairs(int(self.cams.shape[0]), self.height * self.width, n, self.device, generator)
+
     def select(self, pixel_index, view=None):
-        """Rows + target pixels for the view held in `view` (default: self.view, set with `self.view.fill_(k)`)."""
+        """Rows + target pixels for the view held in `view` (default: self.view, set with `self.view.fill_(k)`); a 1-D int32 device
+        tensor with one element per pixel selects the view of every ray (a mixed-camera batch: dn_select_rays_views)."""
+        if view is not None and view.dim() == 1:
+            return _ops.select_rays_views(self.height, self.width, self.cams, view, self.near, self.far, pixel_index, self.images)
         return _ops.select_rays_indirect(self.height, self.width, self.cams, self.view if view is None else view, self.near,
                                          self.far, pixel_index, self.images)
 
 
+def _select_camera_rays_views(height, width, extrinsic, intrinsic, near, far, pixel_index, view_index, image, focal_length, ndc_focal, ndc_near):
+    """select_camera_rays for a mixed batch: one camera record per view (the existing _ops.camera_record), stacked to (V,16)."""
+    if extrinsic.dim() != 3:
+        raise ValueError("select_camera_rays: with view_index, extrinsic is (V,4,4)")
+    n_views = int(extrinsic.shape[0])
+    per_view_k = intrinsic is not None and intrinsic.dim() == 3
+    if per_view_k and int(intrinsic.shape[0]) != n_views:
+        raise ValueError(f"select_camera_rays: {n_views} extrinsics but {int(intrinsic.shape[0])} intrinsics")
+    if image is not None and (image.dim() != 4 or int(image.shape[0]) != n_views):
+        raise ValueError(f"select_camera_rays: {n_views} extrinsics but images of shape {tuple(image.shape)} (expected (V,H,W,C))")
+    if view_index.dim() != 1 or view_index.numel() != pixel_index.numel():
+        raise ValueError("select_camera_rays: view_index and pixel_index must both hold one element per ray")
+    _require_device(pixel_index, "select_camera_rays")
+    _require_device(view_index, "select_camera_rays")
+    dev = pixel_index.device
+    imgs = None if image is None else image.to(dev)
+    focal = None if ndc_focal is None else float(ndc_focal.detach() if torch.is_tensor(ndc_focal) else ndc_focal)
+    views = view_index.to(torch.int32)
+
+    def records():
+        return torch.stack([_ops.camera_record(extrinsic[v], intrinsic[v] if per_view_k else intrinsic, focal_length, height, width, ndc_focal)
+                            for v in range(n_views)])
+    if _ops.camera_needs_grad(extrinsic, intrinsic, focal_length, ndc_focal):
+        return _ops.CameraRaysViewsFn.apply(records(), dev, height, width, views, pixel_index, near, far, imgs, focal, ndc_near)
+    with torch.no_grad():
+        cams = records().to(dev)
+    return _ops.select_rays_views(int(height), int(width), cams, views, near, far, pixel_index, imgs, focal, ndc_near)
+
+
 def select_camera_rays(height, width, extrinsic, intrinsic, near, far, pixel_index, image=None, focal_length=None, ndc_focal=None,
-                       ndc_near=1.0):
+                       ndc_near=1.0, view_index=None):
     """Packed (N,11) ray rows [ro, rd, near, far, viewdir] of the pixels `pixel_index` (device int64, row-major h*W + w) of ONE
     camera - and their RGB from `image` (H,W,C) when given: (rows, target | None) - differentiable w.r.t. `extrinsic`, `intrinsic`,
     a tensor `focal_length` and a tensor `ndc_focal` (camera pose / intrinsics refinement; `intrinsic=None` selects get_ray_bundle's
     4-argument camera-to-world convention with `focal_length`).  The rows are bit-identical to RaySelector.select's; with `ndc_focal`
     origin and direction are warped to NDC (near plane `ndc_near`), bit-identical to the NDC draw's rows for the same pixels, the view
     directions those of the unwarped rays.  One kernel forward (the existing selection kernels), dn_camera_grad backward; a camera that
-    does not require grad, or a call under torch.no_grad(), launches the forward alone."""
+    does not require grad, or a call under torch.no_grad(), launches the forward alone.
+
+    `view_index` (N, device): a mixed batch of V cameras - ray i is pixel `pixel_index[i]` of camera `view_index[i]`; `extrinsic` is
+    (V,4,4), `intrinsic` (V,3,3) or (3,3) shared, `image` (V,H,W,C); a tensor `focal_length` / `ndc_focal` is shared by the views.  One
+    kernel forward (dn_select_rays_views, rows bit-identical to the one-camera call's), dn_camera_grad_views backward with one (V,16)
+    read-back for all cameras."""
+    if view_index is not None:
+        return _select_camera_rays_views(height, width, extrinsic, intrinsic, near, far, pixel_index, view_index, image, focal_length,
+                                         ndc_focal, ndc_near)
     _require_device(pixel_index, "select_camera_rays")
     dev = pixel_index.device
     img = None if image is None else image.to(dev)

@@ -171,6 +171,9 @@ def main(argv=None):
     ap.add_argument("--no-hip-graph", action="store_true",
                     help="launch every kernel of an iteration from Python instead of replaying one captured HIP graph "
                          "(single-GPU runs capture by default: the as-shipped 4x128 nets at 1024 rays are launch-bound)")
+    ap.add_argument("--mix-views", action="store_true",
+                    help="draw every ray's training view together with its pixel (a batch across all training images, upstream NeRF's "
+                         "default; nerf.FusedTrainStep(draw_view=\"rays\")) instead of one view per iteration")
     args = ap.parse_args(argv)
     user_bounds = args.near is not None or args.far is not None
     args.ndc = bool(args.llff) and not args.no_ndc
@@ -261,14 +264,19 @@ def main(argv=None):
     fused = None
     if fused_ok:
         fused = nerf.FusedTrainStep(student[0], student[1], selector, cfg, bucket, ex, ed, args.num_random_rays, seed=args.seed + 7919 * rank,
-                                    luminance=args.ir, first_iteration=start, draw_view=True, ndc_focal=ndc_focal)
+                                    luminance=args.ir, first_iteration=start, draw_view="rays" if args.mix_views else True,
+                                    ndc_focal=ndc_focal)
     graphed = nerf.GraphedTrainStep(fused, opt, eager_iterations=3, use_graphs=use_graph) if fused is not None else None
     use_graph = use_graph and world == 1      # (the autograd step's single graph below: one rank only)
 
     def iteration():
         """The torch composition (--autograd-step, configurations outside nerf.FusedTrainStep): select rays -> coarse +
         fine render -> loss -> backward -> (all-reduce) -> Adam; device-side state only."""
-        rays, target = selector.select(selector.random_pixels(args.num_random_rays))
+        if args.mix_views:
+            view_index, pixel_index = selector.random_pairs(args.num_random_rays)
+            rays, target = selector.select(pixel_index, view=view_index)
+        else:
+            rays, target = selector.select(selector.random_pixels(args.num_random_rays))
         if args.ndc:
             # run_one_iter_of_nerf's NDC branch (reference train_utils.py:240-262) on the selected rows: origins / directions
             # through dn_ndc_rays (near plane at 1), bounds 0 .. 1, view directions stay those of the unwarped rays
