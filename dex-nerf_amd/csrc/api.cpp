@@ -236,10 +236,26 @@ extern "C" int dn_render_rays_train(const dn_mlp_desc* desc_coarse, const void* 
                                     float* depth_c, float* acc_c, float* rgb_f, float* depth_f, float* acc_f, float* dex_f,
                                     void* workspace, void* act_c, void* masks_c, void* act_f, void* masks_f,
                                     const uint32_t* rng_state, int perturb, dn_stream_t stream) {
-  if (n_rays == 0) return 0;
+  if (n_rays == 0) return 0;   // (before any check, as ever: empty tensors carry NULL data pointers)
+  return dn_render_rays_train_geom(desc_coarse, packed_coarse, desc_fine, packed_fine, precision, rays, ray_stride, n_rays, num_coarse, num_fine,
+                                   lindisp, noise_std, white_background, h_m_thres, n_thres, t_rand, noise_c, u, noise_f, rgb_c, depth_c, acc_c,
+                                   rgb_f, depth_f, acc_f, dex_f, workspace, act_c, masks_c, act_f, masks_f, rng_state, perturb, nullptr, stream);
+}
+
+// dn_render_rays_train + z_samples (N, num_fine): the resamples the merge backward needs (dn_fine_depths_backward), caller-owned, may
+// be NULL.  Outputs and workspace layout are dn_render_rays_train's.
+extern "C" int dn_render_rays_train_geom(const dn_mlp_desc* desc_coarse, const void* packed_coarse, const dn_mlp_desc* desc_fine,
+                                         const void* packed_fine, int precision, const float* rays, int ray_stride,
+                                         int64_t n_rays, int num_coarse, int num_fine, int lindisp, float noise_std,
+                                         int white_background, const float* h_m_thres, int n_thres, const float* t_rand,
+                                         const float* noise_c, const float* u, const float* noise_f, float* rgb_c,
+                                         float* depth_c, float* acc_c, float* rgb_f, float* depth_f, float* acc_f, float* dex_f,
+                                         void* workspace, void* act_c, void* masks_c, void* act_f, void* masks_f,
+                                         const uint32_t* rng_state, int perturb, float* z_samples, dn_stream_t stream) {
   DN_REQUIRE(desc_coarse && packed_coarse && rays && workspace && act_c && masks_c && n_rays >= 0, "dn_render_rays_train: bad arguments");
   DN_REQUIRE(num_fine == 0 || (desc_fine && packed_fine && act_f && masks_f), "dn_render_rays_train: fine pass requested without a fine net / its buffers");
   DN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "dn_render_rays_train: workspace must be 256-byte aligned");
+  if (n_rays == 0) return 0;
   Workspace w = carve(workspace, n_rays, num_coarse, num_fine, true);
   int rc;
   // a NULL draw with an RNG state: drawn in the kernels (dn_rng.h) - jitter / resampling u only when `perturb`, density noise
@@ -255,7 +271,7 @@ extern "C" int dn_render_rays_train(const dn_mlp_desc* desc_coarse, const void* 
                                    fine ? nullptr : dex_f, nullptr, stream, rng_state, kRngStreamNoiseCoarse)))
     return rc;
   if (!fine) return 0;
-  if ((rc = fine_depths_rng(w.z_c, w.w_c, u, n_rays, num_coarse, num_fine, w.z_f, nullptr, rng_perturb, stream))) return rc;
+  if ((rc = fine_depths_rng(w.z_c, w.w_c, u, n_rays, num_coarse, num_fine, w.z_f, z_samples, rng_perturb, stream))) return rc;
   if ((rc = dn_run_network_train(desc_fine, precision, packed_fine, nullptr, nullptr, rays, ray_stride, w.z_f, n_rays,
                                  num_coarse + num_fine, w.rf_f, act_f, masks_f, stream)))
     return rc;
@@ -336,4 +352,124 @@ extern "C" int dn_render_rays_backward(const dn_mlp_desc* desc_coarse, const voi
                                     num_fine, noise_std, white_background, noise_c, noise_f, g_rgb_c, g_depth_c, g_acc_c, g_rgb_f, g_depth_f,
                                     g_acc_f, workspace, act_c, masks_c, grads_c, act_f, masks_f, grads_f, h_dW_c, h_db_c, h_dW_f, h_db_f, nets,
                                     rng_state, nullptr, 0, stream);
+}
+
+// ---- the backward of dn_render_rays_train_geom with the ray gradient (pose / ray optimisation on the fused step) -----------------
+namespace dn {
+struct GeomWorkspace {
+  float *g_z_f, *g_rd_f, *d_rays_f, *d_z_f;   // fine pass: compositing geometry, network input gradients
+  float *g_z_c, *g_rd_c, *d_rays_c, *d_z_c;   // coarse pass
+  float *gathered, *g_near_far;               // the merge's gather into the coarse depths; the near / far columns
+  void* input_grad;                           // dn_mlp_backward_input's workspace, one network at a time
+  size_t input_grad_bytes, bytes;
+};
+
+static GeomWorkspace carve_geom(void* base, const dn_mlp_desc* desc_c, const dn_mlp_desc* desc_f, int64_t n, int stride, int nc, int nf) {
+  GeomWorkspace w{};
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    void* p = base ? static_cast<void*>(static_cast<char*>(base) + off) : nullptr;
+    off += align256(bytes);
+    return p;
+  };
+  auto floats = [&](size_t count) { return static_cast<float*>(take(count * sizeof(float))); };
+  const size_t rays = static_cast<size_t>(n);
+  if (nf > 0) {
+    w.g_z_f = floats(rays * (nc + nf)); w.g_rd_f = floats(rays * 3); w.d_rays_f = floats(rays * stride); w.d_z_f = floats(rays * (nc + nf));
+    w.gathered = floats(rays * nc);
+  }
+  w.g_z_c = floats(rays * nc); w.g_rd_c = floats(rays * 3); w.d_rays_c = floats(rays * stride); w.d_z_c = floats(rays * nc);
+  w.g_near_far = floats(rays * 2);
+  w.input_grad_bytes = dn_mlp_backward_input_workspace_bytes(desc_c, n * nc, 1);
+  if (nf > 0) {
+    const size_t fine = dn_mlp_backward_input_workspace_bytes(desc_f, n * (nc + nf), 1);
+    if (fine > w.input_grad_bytes) w.input_grad_bytes = fine;
+  }
+  w.input_grad = take(w.input_grad_bytes);
+  w.bytes = off;
+  return w;
+}
+}  // namespace dn
+
+extern "C" size_t dn_render_backward_geom_workspace_bytes(const dn_mlp_desc* desc_coarse, const dn_mlp_desc* desc_fine, int64_t n_rays,
+                                                          int ray_stride, int num_coarse, int num_fine) {
+  if (!desc_coarse || n_rays < 0 || ray_stride < 8 || num_coarse < 1 || num_fine < 0 || (num_fine > 0 && !desc_fine)) return 0;
+  return carve_geom(nullptr, desc_coarse, desc_fine, n_rays, ray_stride, num_coarse, num_fine).bytes;
+}
+
+extern "C" int dn_render_rays_backward_geom(const dn_mlp_desc* desc_coarse, const void* packed_bwd_coarse, const void* packed_ig_coarse,
+                                            const dn_mlp_desc* desc_fine, const void* packed_bwd_fine, const void* packed_ig_fine,
+                                            int precision, const float* rays, int ray_stride, int64_t n_rays, int num_coarse, int num_fine,
+                                            int lindisp, int perturb, float noise_std, int white_background, const float* t_rand,
+                                            const float* noise_c, const float* noise_f, const float* z_samples, const float* g_rgb_c,
+                                            const float* g_depth_c, const float* g_acc_c, const float* g_rgb_f, const float* g_depth_f,
+                                            const float* g_acc_f, void* workspace, const void* act_c, const void* masks_c, void* grads_c,
+                                            const void* act_f, const void* masks_f, void* grads_f, float* const* h_dW_c, float* const* h_db_c,
+                                            float* const* h_dW_f, float* const* h_db_f, const uint32_t* rng_state, void* wg_scratch,
+                                            size_t wg_scratch_bytes, void* geom_workspace, size_t geom_workspace_bytes, float* d_rays,
+                                            dn_stream_t stream) {
+  const bool fine = num_fine > 0;
+  DN_REQUIRE(n_rays >= 0 && num_coarse >= 1 && num_fine >= 0 && ray_stride >= 8, "dn_render_rays_backward_geom: bad sizes");
+  DN_REQUIRE(desc_coarse && packed_bwd_coarse && packed_ig_coarse && rays && workspace && masks_c && grads_c && d_rays && geom_workspace,
+             "dn_render_rays_backward_geom: bad arguments");
+  DN_REQUIRE(!fine || (desc_fine && packed_bwd_fine && packed_ig_fine && masks_f && grads_f && z_samples),
+             "dn_render_rays_backward_geom: fine pass without the fine net's buffers / z_samples");
+  DN_REQUIRE(((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(geom_workspace)) & 255) == 0,
+             "dn_render_rays_backward_geom: workspaces must be 256-byte aligned");
+  DN_REQUIRE(wg_scratch != nullptr || wg_scratch_bytes == 0, "dn_render_rays_backward_geom: wg_scratch_bytes without wg_scratch");
+  // weight gradients: all four arrays of the networks in use, or none (frozen networks: the weight-gradient launch is skipped)
+  const bool wgrad = h_dW_c != nullptr;
+  DN_REQUIRE(wgrad == (h_db_c != nullptr) && (!fine || (wgrad == (h_dW_f != nullptr) && wgrad == (h_db_f != nullptr))),
+             "dn_render_rays_backward_geom: weight-gradient outputs are given for every network in use, or for none");
+  DN_REQUIRE(!wgrad || (act_c && (!fine || act_f)), "dn_render_rays_backward_geom: weight gradients need the saved activations");
+  if (precision == DN_PREC_F16 || precision == DN_PREC_BF16_S8) {
+    set_error("dn_render_rays_backward_geom: DN_PREC_F32, or DN_PREC_BF16 with 16-bit saved tensors (as dn_mlp_backward_input)");
+    return DN_E_UNSUPPORTED;
+  }
+  DN_REQUIRE(precision == DN_PREC_F32 || precision == DN_PREC_BF16, "dn_render_rays_backward_geom: unknown precision %d", precision);
+  const size_t need = dn_render_backward_geom_workspace_bytes(desc_coarse, desc_fine, n_rays, ray_stride, num_coarse, num_fine);
+  DN_REQUIRE(geom_workspace_bytes >= need, "dn_render_rays_backward_geom: geom_workspace too small (%zu bytes needed)", need);
+  DN_REQUIRE(ray_stride >= (desc_coarse->use_viewdirs || (fine && desc_fine->use_viewdirs) ? 11 : 8),
+             "dn_render_rays_backward_geom: ray_stride too small for view directions");
+  if (n_rays == 0) return 0;
+  Workspace w = carve(workspace, n_rays, num_coarse, num_fine, true);
+  GeomWorkspace g = carve_geom(geom_workspace, desc_coarse, desc_fine, n_rays, ray_stride, num_coarse, num_fine);
+  int rc;
+  // the weight gradients exactly as dn_render_rays_backward_ws (nets == 3) forms them
+  const bool pair_wgrad = wgrad && fine && std::memcmp(desc_coarse, desc_fine, sizeof(dn_mlp_desc)) == 0 && weight_grad_pair_fits(*desc_fine);
+  auto half = [&](const dn_mlp_desc* desc, const void* packed_bwd, const void* packed_ig, const float* rf, const float* z, int samples,
+                  const float* noise, const float* g_rgb, const float* g_depth, const float* g_acc, const void* act, const void* masks,
+                  void* grads, float* const* h_dW, float* const* h_db, uint32_t noise_stream, float* g_z, float* g_rd, float* d_rays_net,
+                  float* d_z) -> int {
+    if ((rc = volume_render_backward_geom_rng(rf, z, rays + 3, ray_stride, noise, noise_std, white_background, n_rays, samples, g_rgb,
+                                              g_depth, g_acc, nullptr, nullptr, w.g_rf, g_z, g_rd, rng_state, noise_stream, stream)))
+      return rc;
+    const int64_t n_points = n_rays * samples;
+    if ((rc = mlp_backward_data_partials(desc, precision, packed_bwd, w.g_rf, masks, n_points, grads, nullptr, 0, stream))) return rc;
+    if ((rc = dn_mlp_backward_input(desc, precision, packed_ig, grads, nullptr, nullptr, rays, ray_stride, z, n_rays, samples, nullptr,
+                                    nullptr, d_rays_net, d_z, g.input_grad, g.input_grad_bytes, stream)))
+      return rc;
+    if (!wgrad || pair_wgrad) return 0;
+    return dn_mlp_weight_grad_all_ws(desc, precision, act, grads, n_points, h_dW, h_db, wg_scratch, wg_scratch_bytes, stream);
+  };
+  // the fine network first, as dn_render_rays_backward; its depth gradient feeds the coarse depths through the merge
+  if (fine) {
+    if ((rc = half(desc_fine, packed_bwd_fine, packed_ig_fine, w.rf_f, w.z_f, num_coarse + num_fine, noise_f, g_rgb_f, g_depth_f, g_acc_f, act_f,
+                   masks_f, grads_f, h_dW_f, h_db_f, kRngStreamNoiseFine, g.g_z_f, g.g_rd_f, g.d_rays_f, g.d_z_f)))
+      return rc;
+  }
+  if ((rc = half(desc_coarse, packed_bwd_coarse, packed_ig_coarse, w.rf_c, w.z_c, num_coarse, noise_c, g_rgb_c, g_depth_c, g_acc_c, act_c, masks_c,
+                 grads_c, h_dW_c, h_db_c, kRngStreamNoiseCoarse, g.g_z_c, g.g_rd_c, g.d_rays_c, g.d_z_c)))
+    return rc;
+  if (pair_wgrad &&
+      (rc = dn_mlp_weight_grad_pair_ws(desc_fine, precision, act_f, grads_f, n_rays * (num_coarse + num_fine), h_dW_f, h_db_f, act_c, grads_c,
+                                       n_rays * num_coarse, h_dW_c, h_db_c, wg_scratch, wg_scratch_bytes, stream)))
+    return rc;
+  // g_z_fine = g_z + d_z, gathered into the coarse depths; g_z_coarse = (g_z + d_z) + gathered -> near / far; then the rows
+  if (fine && (rc = fine_depths_backward_sum(w.z_c, z_samples, g.g_z_f, g.d_z_f, n_rays, num_coarse, num_fine, g.gathered, stream))) return rc;
+  if ((rc = coarse_depths_backward_rng(rays, ray_stride, n_rays, num_coarse, lindisp, t_rand, g.g_z_c, g.d_z_c, fine ? g.gathered : nullptr,
+                                       g.g_near_far, perturb ? rng_state : nullptr, stream)))
+    return rc;
+  return combine_ray_grads(g.d_rays_c, fine ? g.d_rays_f : nullptr, g.g_rd_c, fine ? g.g_rd_f : nullptr, g.g_near_far, n_rays, ray_stride, d_rays,
+                           stream);
 }

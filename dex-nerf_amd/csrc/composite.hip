@@ -243,6 +243,16 @@ extern "C" int dn_volume_render_backward_geom(const float* rf, const float* z, c
                                               float noise_std, int white_background, int64_t n_rays, int n_samples,
                                               const float* g_rgb, const float* g_depth, const float* g_acc, const float* g_disp,
                                               const float* g_weights, float* g_rf, float* g_z, float* g_rd, dn_stream_t stream) {
+  return dn::volume_render_backward_geom_rng(rf, z, rd, rd_stride, noise, noise_std, white_background, n_rays, n_samples, g_rgb, g_depth,
+                                             g_acc, g_disp, g_weights, g_rf, g_z, g_rd, nullptr, 0u, stream);
+}
+
+// dn_volume_render_backward_geom; noise == NULL with an RNG state: the forward's density noise regenerated in the kernel, as
+// volume_render_backward_rng does for the plain form
+int dn::volume_render_backward_geom_rng(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise, float noise_std,
+                                        int white_background, int64_t n_rays, int n_samples, const float* g_rgb, const float* g_depth,
+                                        const float* g_acc, const float* g_disp, const float* g_weights, float* g_rf, float* g_z,
+                                        float* g_rd, const uint32_t* rng_state, uint32_t rng_stream, dn_stream_t stream) {
   if (n_rays == 0) return 0;
   DN_REQUIRE(rf && z && rd && (g_rf || g_z || g_rd) && n_rays >= 0 && n_samples >= 1 && rd_stride >= 3,
              "dn_volume_render_backward_geom: bad arguments");
@@ -251,11 +261,9 @@ extern "C" int dn_volume_render_backward_geom(const float* rf, const float* z, c
              "dn_volume_render_backward_geom: rf / g_rf must be 16-byte aligned");
   if (g_z == nullptr && g_rd == nullptr)   // nothing of the geometry wanted: the plain kernel
     return dn::volume_render_backward_rng(rf, z, rd, rd_stride, noise, noise_std, white_background, n_rays, n_samples, g_rgb, g_depth,
-                                          g_acc, g_disp, g_weights, g_rf, nullptr, 0u, stream, nullptr);
+                                          g_acc, g_disp, g_weights, g_rf, rng_state, rng_stream, stream, nullptr);
   const unsigned grid = static_cast<unsigned>((n_rays + kRaysPerBlock - 1) / kRaysPerBlock);
   const int chunks = (n_samples + 63) / 64;
-  const uint32_t* rng_state = nullptr;
-  const uint32_t rng_stream = 0u;
   unsigned* absmax_part = nullptr;
   if (chunks <= 1) DN_LAUNCH_BWD(1, true, g_z, g_rd);
   else if (chunks <= 2) DN_LAUNCH_BWD(2, true, g_z, g_rd);

@@ -65,6 +65,19 @@ int volume_render_backward_rng(const float* rf, const float* z, const float* rd,
                                int white_background, int64_t n_rays, int n_samples, const float* g_rgb, const float* g_depth,
                                const float* g_acc, const float* g_disp, const float* g_weights, float* g_rf,
                                const uint32_t* rng_state, uint32_t rng_stream, dn_stream_t stream, unsigned* absmax_part = nullptr);
+// the geometry backwards with an RNG state / with the upstream gradient handed over as the terms of a sum (dn_render_rays_backward_geom)
+int volume_render_backward_geom_rng(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise, float noise_std,
+                                    int white_background, int64_t n_rays, int n_samples, const float* g_rgb, const float* g_depth,
+                                    const float* g_acc, const float* g_disp, const float* g_weights, float* g_rf, float* g_z, float* g_rd,
+                                    const uint32_t* rng_state, uint32_t rng_stream, dn_stream_t stream);
+int coarse_depths_backward_rng(const float* rays, int ray_stride, int64_t n_rays, int num_coarse, int lindisp, const float* t_rand,
+                               const float* g_z, const float* g_z_b, const float* g_z_c, float* g_near_far, const uint32_t* rng_state,
+                               dn_stream_t stream);
+int fine_depths_backward_sum(const float* z_coarse, const float* z_samples, const float* g_z_fine, const float* g_z_fine_b, int64_t n_rays,
+                             int num_coarse, int num_fine, float* g_z_coarse, dn_stream_t stream);
+// pose.hip: d_rays = d_rays_c + d_rays_f, + g_rd_c + g_rd_f on columns 3:6, the near / far gradient on columns 6:8
+int combine_ray_grads(const float* d_rays_c, const float* d_rays_f, const float* g_rd_c, const float* g_rd_f, const float* g_near_far,
+                      int64_t n_rays, int ray_stride, float* d_rays, dn_stream_t stream);
 // mlp_train.hip: dn_mlp_backward_data with the largest |g_out| already formed by the caller's previous kernel (DN_PREC_BF16_S8 with the
 // per-launch gradient scale): n_partials words whose maximum it is (composite.hip composite_bwd_kernel) - NULL: a launch of its own finds it
 int mlp_backward_data_partials(const dn_mlp_desc* desc, int precision, const void* packed_bwd, const float* g_out, const void* masks,

@@ -333,22 +333,35 @@ __global__ __launch_bounds__(256) void sampler_kernel(const float* __restrict__ 
 // The two sums are lane-local in ascending j, then the fixed butterfly of wave_sum, in fp64: plain stores, bit-reproducible.
 __global__ __launch_bounds__(256) void coarse_depths_bwd_kernel(const float* __restrict__ rays, int ray_stride, int64_t n_rays, int nc,
                                                                 int lindisp, const float* __restrict__ t_rand,
-                                                                const float* __restrict__ g_z, float* __restrict__ g_near_far) {
+                                                                const float* __restrict__ g_z, float* __restrict__ g_near_far,
+                                                                const float* __restrict__ g_z_b, const float* __restrict__ g_z_c,
+                                                                RngRef rng) {
   const int lane = lane_id();
   const int64_t ray = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
   if (ray >= n_rays) return;   // wave-uniform; no block-level sync in this kernel
   const float near = rays[ray * ray_stride + 6];
   const float far = rays[ray * ray_stride + 7];
-  const float* g = g_z + ray * nc;
   const float* tr = (t_rand != nullptr) ? t_rand + ray * nc : nullptr;
+  // the upstream gradient of depth i: g_z alone, or (g_z + g_z_b) + g_z_c when the caller hands the terms of a sum separately
+  // (dn_render_rays_backward_geom: compositing + network + merge); the jitter as given, or regenerated as coarse_depths_kernel drew it
+  auto g = [&](int i) {
+    float v = g_z[ray * nc + i];
+    if (g_z_b != nullptr) v += g_z_b[ray * nc + i];
+    if (g_z_c != nullptr) v += g_z_c[ray * nc + i];
+    return v;
+  };
+  // (a lane forms the terms of depths j - 1, j, j + 1: up to three reads per pointer and, in the RNG form, three Philox draws per
+  // depth instead of one - a few hundred multiplies per ray at nc = 64, beside a kernel that is launch-bound; not cached per lane)
+  const bool jitter = tr != nullptr || rng.state != nullptr;
+  auto t_of = [&](int i) { return tr != nullptr ? tr[i] : rng_uniform(rng, static_cast<uint64_t>(ray) * nc + i); };
   double s_near = 0.0, s_far = 0.0;
   for (int j = lane; j < nc; j += 64) {
-    float gz = g[j];
-    if (tr != nullptr) {
-      const float tj = tr[j];
+    float gz = g(j);
+    if (jitter) {
+      const float tj = t_of(j);
       gz = gz * ((1.0f - tj) * (j > 0 ? 0.5f : 1.0f) + tj * (j < nc - 1 ? 0.5f : 1.0f));
-      if (j + 1 < nc) gz += g[j + 1] * (1.0f - tr[j + 1]) * 0.5f;
-      if (j > 0) gz += g[j - 1] * tr[j - 1] * 0.5f;
+      if (j + 1 < nc) gz += g(j + 1) * (1.0f - t_of(j + 1)) * 0.5f;
+      if (j > 0) gz += g(j - 1) * t_of(j - 1) * 0.5f;
     }
     const float t = linspace_elem(0.0f, 1.0f, nc, j);
     float dn_ = 1.0f - t, df_ = t;
@@ -376,7 +389,7 @@ __global__ __launch_bounds__(256) void coarse_depths_bwd_kernel(const float* __r
 // non-ascending z_coarse, the samples of a random u) by comparing against every element.  A pure gather: plain stores.
 __global__ __launch_bounds__(256) void fine_depths_bwd_kernel(const float* __restrict__ z_coarse, const float* __restrict__ z_samples,
                                                               const float* __restrict__ g_z_fine, int64_t n_rays, int nc, int nf,
-                                                              float* __restrict__ g_z_coarse) {
+                                                              float* __restrict__ g_z_coarse, const float* __restrict__ g_z_fine_b) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int wave = threadIdx.x >> 6;
   const int lane = lane_id();
@@ -408,7 +421,8 @@ __global__ __launch_bounds__(256) void fine_depths_bwd_kernel(const float* __res
     } else {
       for (int q = 0; q < nf; ++q) p += (zs[q] < v) ? 1 : 0;
     }
-    g_z_coarse[ray * nc + j] = g_z_fine[ray * total + min(p, total - 1)];   // (p < nc + nf always; the clamp only keeps a NaN depth's read in bounds)
+    const int64_t at = ray * total + min(p, total - 1);   // (p < nc + nf always; the clamp only keeps a NaN depth's read in bounds)
+    g_z_coarse[ray * nc + j] = (g_z_fine_b != nullptr) ? g_z_fine[at] + g_z_fine_b[at] : g_z_fine[at];   // (g_z_fine_b: the second term of a sum)
   }
 }
 
@@ -953,11 +967,19 @@ int dn::coarse_depths_rng(const float* rays, int ray_stride, int64_t n_rays, int
 
 extern "C" int dn_coarse_depths_backward(const float* rays, int ray_stride, int64_t n_rays, int num_coarse, int lindisp,
                                          const float* t_rand, const float* g_z, float* g_near_far, dn_stream_t stream) {
+  return dn::coarse_depths_backward_rng(rays, ray_stride, n_rays, num_coarse, lindisp, t_rand, g_z, nullptr, nullptr, g_near_far, nullptr, stream);
+}
+
+// dn_coarse_depths_backward; the upstream gradient as up to three terms, (g_z + g_z_b) + g_z_c; t_rand == NULL with an RNG state: the
+// jitter coarse_depths_rng drew for this iteration, regenerated in the kernel
+int dn::coarse_depths_backward_rng(const float* rays, int ray_stride, int64_t n_rays, int num_coarse, int lindisp, const float* t_rand,
+                                   const float* g_z, const float* g_z_b, const float* g_z_c, float* g_near_far, const uint32_t* rng_state,
+                                   dn_stream_t stream) {
   if (n_rays == 0) return 0;
   DN_REQUIRE(rays && g_z && g_near_far && n_rays >= 0 && num_coarse >= 1 && ray_stride >= 8, "dn_coarse_depths_backward: bad arguments");
   const unsigned grid = static_cast<unsigned>((n_rays + 3) / 4);
   hipLaunchKernelGGL(coarse_depths_bwd_kernel, dim3(grid), dim3(256), 0, as_stream(stream), rays, ray_stride, n_rays, num_coarse, lindisp,
-                     t_rand, g_z, g_near_far);
+                     t_rand, g_z, g_near_far, g_z_b, g_z_c, RngRef{rng_state, kRngStreamJitter});
   return check_launch("dn_coarse_depths_backward");
 }
 
@@ -1029,6 +1051,12 @@ int dn::fine_depths_rng(const float* z_coarse, const float* weights, const float
 
 extern "C" int dn_fine_depths_backward(const float* z_coarse, const float* z_samples, const float* g_z_fine, int64_t n_rays, int num_coarse,
                                        int num_fine, float* g_z_coarse, dn_stream_t stream) {
+  return dn::fine_depths_backward_sum(z_coarse, z_samples, g_z_fine, nullptr, n_rays, num_coarse, num_fine, g_z_coarse, stream);
+}
+
+// dn_fine_depths_backward; the upstream gradient as g_z_fine + g_z_fine_b (the second term may be NULL)
+int dn::fine_depths_backward_sum(const float* z_coarse, const float* z_samples, const float* g_z_fine, const float* g_z_fine_b, int64_t n_rays,
+                                 int num_coarse, int num_fine, float* g_z_coarse, dn_stream_t stream) {
   if (n_rays == 0) return 0;
   DN_REQUIRE(z_coarse && z_samples && g_z_fine && g_z_coarse && n_rays >= 0, "dn_fine_depths_backward: bad arguments");
   DN_REQUIRE(num_coarse >= 1 && num_coarse <= 512 && num_fine >= 1 && num_coarse + num_fine <= 2048,
@@ -1036,6 +1064,6 @@ extern "C" int dn_fine_depths_backward(const float* z_coarse, const float* z_sam
   const size_t lds = static_cast<size_t>(kSamplerWaves) * (num_coarse + num_fine) * sizeof(float);   // <= 32 KiB
   const unsigned grid = static_cast<unsigned>((n_rays + kSamplerWaves - 1) / kSamplerWaves);
   hipLaunchKernelGGL(fine_depths_bwd_kernel, dim3(grid), dim3(256), lds, as_stream(stream), z_coarse, z_samples, g_z_fine, n_rays,
-                     num_coarse, num_fine, g_z_coarse);
+                     num_coarse, num_fine, g_z_coarse, g_z_fine_b);
   return check_launch("dn_fine_depths_backward");
 }

@@ -37,6 +37,8 @@ EXPORTS = (
     "dn_volume_render_backward_geom", "dn_coarse_depths_backward", "dn_fine_depths_backward",
     "dn_select_rays_indirect_ndc", "dn_camera_grad_scratch_bytes", "dn_camera_grad",
     "dn_select_rays_views", "dn_select_rays_draw_views", "dn_camera_grad_views_scratch_bytes", "dn_camera_grad_views",
+    "dn_pose_records", "dn_pose_records_backward", "dn_render_rays_train_geom", "dn_render_backward_geom_workspace_bytes",
+    "dn_render_rays_backward_geom",
 )
 
 
@@ -150,8 +152,17 @@ def _declare(lib):
     lib.dn_camera_grad_views_scratch_bytes.argtypes = [c_int64, c_int]
     lib.dn_camera_grad_views_scratch_bytes.restype = c_size_t
     lib.dn_camera_grad_views.argtypes = [c_int, c_int, fp, c_int, vp, vp, c_int64, fp, c_int, fp, c_int, fp, c_int, dbl, dbl, vp, c_size_t, fp, vp]
+    lib.dn_pose_records.argtypes = [fp, fp, fp, c_int, dbl, c_int, fp, fp, vp]
+    lib.dn_pose_records_backward.argtypes = [fp, fp, fp, c_int, fp, fp, vp]
+    lib.dn_render_rays_train_geom.argtypes = lib.dn_render_rays_train.argtypes[:-1] + [fp, vp]
+    lib.dn_render_backward_geom_workspace_bytes.argtypes = [POINTER(MlpDesc), POINTER(MlpDesc), c_int64, c_int, c_int, c_int]
+    lib.dn_render_backward_geom_workspace_bytes.restype = c_size_t
+    lib.dn_render_rays_backward_geom.argtypes = [POINTER(MlpDesc), vp, vp, POINTER(MlpDesc), vp, vp, c_int, fp, c_int, c_int64, c_int, c_int,
+                                                 c_int, c_int, c_float, c_int, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, vp, vp, vp, vp, vp, vp, vp,
+                                                 POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), vp, vp, c_size_t,
+                                                 vp, c_size_t, fp, vp]
     for name in EXPORTS:
-        if name not in ("dn_last_error", "dn_mlp_density_packed_bytes", "dn_render_depth_workspace_bytes", "dn_mlp_packed_bytes", "dn_render_workspace_bytes",
+        if name not in ("dn_render_backward_geom_workspace_bytes", "dn_last_error", "dn_mlp_density_packed_bytes", "dn_render_depth_workspace_bytes", "dn_mlp_packed_bytes", "dn_render_workspace_bytes",
                         "dn_mlp_backward_packed_bytes", "dn_render_train_workspace_bytes",
                         "dn_mlp_input_grad_packed_bytes", "dn_mlp_backward_input_workspace_bytes", "dn_camera_grad_scratch_bytes",
                         "dn_camera_grad_views_scratch_bytes"):

@@ -1180,9 +1180,10 @@ def render_nonfinite_count(ws=None):
 
 # ---- predict_and_render_radiance under autograd: one C call forward, one (or two halves) backward ----------------------
 def render_rays_train(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, noise_std, white, m_thres, draws=None, prec=None,
-                      rng_state=None, perturb=False):
+                      rng_state=None, perturb=False, geom=False):
     """dn_render_rays_train: the training forward of a whole ray chunk.  Returns (maps, saved): maps = (rgb_c, depth_c, acc_c,
-    rgb_f, depth_f, acc_f, dex), saved = what dn_render_rays_backward needs (workspace, per-network act / masks, the draws)."""
+    rgb_f, depth_f, acc_f, dex), saved = what dn_render_rays_backward needs (workspace, per-network act / masks, the draws).
+    geom=True: dn_render_rays_train_geom - saved also holds the fine pass's resamples and what render_rays_backward_geom needs."""
     rays = f32c(rays)
     n = rays.shape[0]
     dev = rays.device
@@ -1205,16 +1206,21 @@ def render_rays_train(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, n
     rgb_f, depth_f, acc_f = (new(n, 3), new(n), new(n)) if fine else (None, None, None)
     dex = new(k, n) if k else None
     t_rand, noise_c, u, noise_f = _draw_tensors(draws)
-    check(lib().dn_render_rays_train(
-        ctypes.byref(packed_c.desc), ptr(packed_c.buffer),
-        ctypes.byref(packed_f.desc) if fine else None, ptr(packed_f.buffer) if fine else None, prec,
-        ptr(rays), rays.shape[1], n, num_coarse, nf, int(bool(lindisp)), float(noise_std), int(bool(white)),
-        host_floats(m_thres), k, ptr(t_rand), ptr(noise_c), ptr(u), ptr(noise_f),
-        ptr(rgb_c), ptr(depth_c), ptr(acc_c), ptr(rgb_f), ptr(depth_f), ptr(acc_f), ptr(dex), ptr(ws),
-        ptr(act_c), ptr(masks_c), ptr(act_f), ptr(masks_f), ptr(rng_state), int(bool(perturb)), stream()), "dn_render_rays_train")
+    args = [ctypes.byref(packed_c.desc), ptr(packed_c.buffer),
+            ctypes.byref(packed_f.desc) if fine else None, ptr(packed_f.buffer) if fine else None, prec,
+            ptr(rays), rays.shape[1], n, num_coarse, nf, int(bool(lindisp)), float(noise_std), int(bool(white)),
+            host_floats(m_thres), k, ptr(t_rand), ptr(noise_c), ptr(u), ptr(noise_f),
+            ptr(rgb_c), ptr(depth_c), ptr(acc_c), ptr(rgb_f), ptr(depth_f), ptr(acc_f), ptr(dex), ptr(ws),
+            ptr(act_c), ptr(masks_c), ptr(act_f), ptr(masks_f), ptr(rng_state), int(bool(perturb))]
     saved = dict(rays=rays, ws=ws, act_c=act_c, masks_c=masks_c, act_f=act_f, masks_f=masks_f, noise_c=noise_c,
                  noise_f=noise_f, n=n, nc=num_coarse, nf=nf, noise_std=float(noise_std), white=bool(white), prec=prec,
                  rng_state=rng_state)
+    if geom:
+        z_samples = new(n, nf) if fine else None
+        check(lib().dn_render_rays_train_geom(*args, ptr(z_samples), stream()), "dn_render_rays_train_geom")
+        saved.update(t_rand=t_rand, z_samples=z_samples, lindisp=bool(lindisp), perturb=bool(perturb))
+    else:
+        check(lib().dn_render_rays_train(*args, stream()), "dn_render_rays_train")
     return (rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f, dex), saved
 
 
@@ -1246,3 +1252,83 @@ def render_rays_backward(packed_c, packed_f, saved, g_c, g_f, views_c, views_f, 
         ptr(grads_f), wc, bc, wf, bf, int(nets), ptr(saved.get("rng_state")), ptr(scratch), scratch_bytes, stream()), "dn_render_rays_backward")
     _note_s8_record(grads_c, prec); _note_s8_record(grads_f, prec)
     return grads_c, grads_f, scratch   # (kept alive by the caller until the stream has consumed them: PyTorch's caching allocator is stream-ordered)
+
+
+# ---- the render with its ray gradient, and camera records from twists: the pieces of nerf.FusedPoseStep ----------------------------
+def render_rays_train_geom(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, noise_std, white, m_thres, draws=None, prec=None,
+                           rng_state=None, perturb=False):
+    """dn_render_rays_train_geom: render_rays_train that also keeps the fine pass's resamples (saved["z_samples"]) and the settings the
+    geometry backward needs - what render_rays_backward_geom takes.  prec: PREC_F32, or PREC_BF16 with 16-bit saves (the default:
+    the packed network's own precision, never the 8-bit-saved code)."""
+    return render_rays_train(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, noise_std, white, m_thres, draws,
+                             packed_c.precision if prec is None else prec, rng_state, perturb, geom=True)
+
+
+def render_rays_backward_geom(packed_c, packed_f, saved, g_c, g_f, views_c=None, views_f=None):
+    """dn_render_rays_backward_geom on what render_rays_train_geom saved: returns (d_rays (N, stride), the buffers to keep alive until
+    the stream has consumed them).  g_c / g_f = (g_rgb, g_depth, g_acc) upstream gradients (None = zero).  views_* = [(dW, db)] in
+    linear_modules() order to ACCUMULATE the weight gradients into, as render_rays_backward does; None (both): frozen networks, no
+    weight-gradient launch.  The packs need their backward and input-gradient streams (ensure_backward_stream /
+    ensure_input_grad_stream)."""
+    rays = saved["rays"]
+    dev = rays.device
+    n, nc, nf, prec = saved["n"], saved["nc"], saved["nf"], saved["prec"]
+    fine = nf > 0 and packed_f is not None
+
+    def grads_buf(packed, n_points):
+        return torch.empty(train_sizes(packed, n_points, prec=prec)[2], dtype=torch.uint8, device=dev)
+    grads_c = grads_buf(packed_c, n * nc)
+    grads_f = grads_buf(packed_f, n * (nc + nf)) if fine else None
+    wc, bc = _view_ptrs(views_c)
+    wf, bf = _view_ptrs(views_f if fine else None)
+    scratch, scratch_bytes = (None, 0)
+    if views_c is not None:
+        scratch, scratch_bytes = _wgrad_scratch(2 if fine else 1, packed_c, *([packed_f] if fine else []))
+    gs = [None if g is None else f32c(g) for g in tuple(g_c) + tuple(g_f)]
+    desc_f = ctypes.byref(packed_f.desc) if fine else None
+    nbytes = int(lib().dn_render_backward_geom_workspace_bytes(ctypes.byref(packed_c.desc), desc_f, n, rays.shape[1], nc, nf))
+    geom_ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    d_rays = torch.empty_like(rays)
+    check(lib().dn_render_rays_backward_geom(
+        ctypes.byref(packed_c.desc), ptr(packed_c.buffers_bwd[prec]), ptr(packed_c.buffer_ig),
+        desc_f, ptr(packed_f.buffers_bwd[prec]) if fine else None, ptr(packed_f.buffer_ig) if fine else None, prec,
+        ptr(rays), rays.shape[1], n, nc, nf, int(saved["lindisp"]), int(saved["perturb"]), saved["noise_std"], int(saved["white"]),
+        ptr(saved["t_rand"]), ptr(saved["noise_c"]), ptr(saved["noise_f"]), ptr(saved["z_samples"]),
+        ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), ptr(gs[3]), ptr(gs[4]), ptr(gs[5]),
+        ptr(saved["ws"]), ptr(saved["act_c"]), ptr(saved["masks_c"]), ptr(grads_c), ptr(saved["act_f"]), ptr(saved["masks_f"]), ptr(grads_f),
+        wc, bc, wf, bf, ptr(saved.get("rng_state")), ptr(scratch), scratch_bytes, ptr(geom_ws), nbytes, ptr(d_rays), stream()),
+        "dn_render_rays_backward_geom")
+    return d_rays, (grads_c, grads_f, scratch, geom_ws, gs)
+
+
+def _pose_inputs(xi, e0):
+    assert xi.is_cuda and xi.dtype == torch.float32 and xi.is_contiguous() and xi.dim() == 2 and xi.shape[1] == 6, "xi: (V,6) fp32 on the device"
+    n_views = int(xi.shape[0])
+    assert e0.is_cuda and e0.dtype == torch.float32 and e0.is_contiguous() and e0.numel() == 16 * n_views, "e0: (V,4,4) fp32 on the device"
+    return n_views
+
+
+def pose_records(xi, e0, k, ndc_focal=None, cams=None, extrinsics=None, want_extrinsics=False):
+    """dn_pose_records: the camera records (V,16) of E_v = se3_exp(xi[v]) @ e0[v] - xi (V,6) fp32 (omega, t), e0 (V,4,4) fp32
+    world->camera, k (3,3) shared or (V,3,3), all on the device.  `cams` / `extrinsics`: buffers to write into (else allocated).
+    Returns cams, or (cams, extrinsics (V,4,4)) with want_extrinsics / an extrinsics buffer."""
+    n_views = _pose_inputs(xi, e0)
+    assert k.is_cuda and k.dtype == torch.float32 and k.is_contiguous() and k.numel() in (9, 9 * n_views), "k: (3,3) or (V,3,3) fp32 on the device"
+    if cams is None:
+        cams = torch.empty((n_views, 16), dtype=torch.float32, device=xi.device)
+    if extrinsics is None and want_extrinsics:
+        extrinsics = torch.empty((n_views, 4, 4), dtype=torch.float32, device=xi.device)
+    check(lib().dn_pose_records(ptr(xi), ptr(e0), ptr(k), int(k.dim() == 3), float(ndc_focal or 0.0), n_views, ptr(cams), ptr(extrinsics),
+                                stream()), "dn_pose_records")
+    return cams if extrinsics is None else (cams, extrinsics)
+
+
+def pose_records_backward(g_cams, xi, e0, out=None, keep=None):
+    """dn_pose_records_backward: g_xi (V,6) from g_cams (V,16) (camera_grad_views' output) at the given xi / e0.  `out`: the tensor to
+    write (else allocated); `keep`: a second tensor that receives the same values."""
+    n_views = _pose_inputs(xi, e0)
+    assert g_cams.is_cuda and g_cams.dtype == torch.float32 and g_cams.is_contiguous() and g_cams.shape == (n_views, 16)
+    if out is None:
+        out = torch.empty((n_views, 6), dtype=torch.float32, device=xi.device)
+    check(lib().dn_pose_records_backward(ptr(g_cams), ptr(xi), ptr(e0), n_views, ptr(out), ptr(keep), stream()), "dn_pose_records_backward")
+    return out

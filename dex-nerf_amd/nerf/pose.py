@@ -1,8 +1,11 @@
 """Camera pose refinement against a trained NeRF (iNeRF-style): the chain pose -> rays -> render -> loss -> pose gradient on the
 library's kernels (select_camera_rays forward / dn_camera_grad backward, predict_and_render_radiance with rows that require grad);
-MultiPoseRefiner: all cameras of a capture together, on mixed-camera batches (dn_select_rays_views / dn_camera_grad_views)."""
+MultiPoseRefiner: all cameras of a capture together, on mixed-camera batches (dn_select_rays_views / dn_camera_grad_views);
+FusedPoseStep: the same iteration as library launches only - twists, records, draw, render, loss, ray gradient, camera gradient,
+twist gradient and Adam all on the device, replayed as one HIP graph."""
 import torch
 
+from . import _hip, _ops
 from .nerf_helpers import _require_device, img2mse, random_view_pixel_pairs, select_camera_rays
 from .train_utils import predict_and_render_radiance
 
@@ -152,3 +155,155 @@ class MultiPoseRefiner:
         """The current estimates se3_exp(xi[v]) @ extrinsics0[v], (V,4,4), detached (fp32, on the refiner's device)."""
         with torch.no_grad():
             return self._extrinsics().to(self.device, torch.float32)
+
+
+class FusedPoseStep:
+    """The refinement iteration of MultiPoseRefiner with the networks frozen and nothing on the host: E_v = se3_exp(xi[v]) @
+    extrinsics0[v] with xi (V,6) fp32 ON THE DEVICE under dn_adam_step.  One `step()` enqueues, on the current stream and without a
+    host read,
+
+        dn_pose_records              xi -> camera records (and the extrinsics)
+        dn_select_rays_draw_views    `num_rays` distinct (view, pixel) pairs, their rows and targets (NDC rows with `ndc_focal`)
+        dn_render_rays_train_geom    coarse + fine render on the cached packs; jitter, resampling u and density noise drawn in the kernels
+        dn_mse2_loss                 loss3 = [loss, mse_coarse, mse_fine] and the upstream gradients
+        dn_render_rays_backward_geom the gradient of the rows, no weight gradients
+        dn_camera_grad_views         -> the gradient of the records
+        dn_pose_records_backward     -> the gradient of xi
+        dn_adam_step                 constant `lr`, gradients cleared in the same pass
+
+    Under nerf.set_precision('bf16' | 'bf16-s8' | 'bf16-s16') the step runs bf16 with 16-bit saved tensors (FusedNetInputFn's rule),
+    under 'fp32' fp32.  The networks' parameters, their requires_grad flags and their .grad are never touched.  The first
+    `eager_iterations` steps run eagerly and bring the packed streams up to date; the next one is captured into one HIP graph and
+    replayed from then on (use_graphs=False: eager throughout).  If capture fails the loop goes on eagerly and `fallback_reason` says
+    why.  Networks with view directions only (the selection kernels write 11-column rows), like FusedTrainStep.  `extrinsics0` (V,4,4) or (4,4), `intrinsic` (3,3) or (V,3,3), `images` (V,H,W,C), all on the device.
+
+    loss3, xi, last_grad ((V,6): the gradient the latest step used) and rng_state are device tensors; PoseRefiner / MultiPoseRefiner
+    (float64 xi on the host, explicit pixels) stay the parity reference."""
+
+    def __init__(self, model_coarse, model_fine, options, height, width, intrinsic, extrinsics0, images, encode_position_fn,
+                 encode_direction_fn, num_rays, lr, seed=0, first_iteration=0, ndc_focal=None, use_graphs=True, eager_iterations=3):
+        if extrinsics0.dim() == 2:
+            extrinsics0 = extrinsics0[None]
+        if extrinsics0.dim() != 3 or tuple(extrinsics0.shape[1:]) != (4, 4):
+            raise ValueError("FusedPoseStep: extrinsics0 is (V,4,4) or (4,4)")
+        self.n_views = int(extrinsics0.shape[0])
+        if intrinsic.dim() == 3 and int(intrinsic.shape[0]) != self.n_views:
+            raise ValueError(f"FusedPoseStep: {self.n_views} extrinsics but {int(intrinsic.shape[0])} intrinsics")
+        if images.dim() != 4 or int(images.shape[0]) != self.n_views:
+            raise ValueError(f"FusedPoseStep: {self.n_views} extrinsics but images of shape {tuple(images.shape)} (expected (V,H,W,C))")
+        self.height, self.width = int(height), int(width)
+        if tuple(images.shape[1:3]) != (self.height, self.width):
+            raise ValueError(f"FusedPoseStep: images of shape {tuple(images.shape)} for {self.height} x {self.width} cameras")
+        for t in (extrinsics0, intrinsic, images):
+            _require_device(t, "FusedPoseStep")
+        opt = options.nerf.train
+        self.models = (model_coarse, model_fine)
+        self.nc = int(opt.num_coarse)
+        self.nf = int(opt.num_fine) if model_fine is not None else 0
+        self.lindisp, self.perturb = bool(opt.lindisp), bool(opt.perturb)
+        self.noise_std, self.white = float(opt.radiance_field_noise_std), bool(opt.white_background)
+        self.near, self.far = float(options.dataset.near), float(options.dataset.far)
+        from ._train import train_fused_ok
+        from .train_utils import _fusable
+        nets = [m for m in self.models if m is not None]
+        if model_coarse is None or not all(_fusable(m, encode_position_fn, encode_direction_fn) and train_fused_ok(m) and m.use_viewdirs
+                                           for m in nets):
+            raise ValueError("FusedPoseStep: a network outside the fused training kernels (W in {128, 256}, L_xyz in {6, 10}, view "
+                             "directions, precision fp32 / bf16); MultiPoseRefiner differentiates those")
+        self.logs = (encode_position_fn.log_sampling, encode_direction_fn.log_sampling)
+        dev = self.device = extrinsics0.device
+        self.num_rays = min(int(num_rays), self.n_views * self.height * self.width)
+        self.ndc_focal = None if ndc_focal is None else float(ndc_focal)
+        self.lr = float(lr)
+        self.e0 = extrinsics0.detach().to(torch.float32).contiguous()
+        self.k = intrinsic.detach().to(torch.float32).contiguous()
+        self.images = _hip.f32c(images.detach())
+        n = 6 * self.n_views
+        padded = (n + 3) // 4 * 4                 # dn_adam_step works on multiples of four elements
+        self._flat = torch.zeros(4, padded, dtype=torch.float32, device=dev)    # rows: xi, gradient, exp_avg, exp_avg_sq
+        self.xi = self._flat[0, :n].view(self.n_views, 6)
+        self._grad = self._flat[1, :n].view(self.n_views, 6)
+        self.last_grad = torch.zeros(self.n_views, 6, dtype=torch.float32, device=dev)
+        # dn_adam_step's state record (parallel.FlatAdam): float [steps taken, ticket, last lr, -], then double [beta1^t, beta2^t, decay^t]
+        self._adam_state = torch.zeros(12, dtype=torch.float32, device=dev)[:10]
+        self._adam_state[4:10].view(torch.float64).fill_(1.0)
+        self.rng_state = _ops.new_rng_state(seed, dev, first_iteration)
+        self.cams = torch.zeros(self.n_views, 16, dtype=torch.float32, device=dev)
+        self.loss3 = None
+        self.use_graphs, self.eager_left = bool(use_graphs), int(eager_iterations)
+        self.graph = None
+        self.fallback_reason = None
+        self._keep = None
+
+    def _packs(self):
+        """The packed networks (core stream) with their backward and input-gradient streams; brought up to date outside a capture
+        only - the networks are frozen, a captured step reads the streams the eager steps left."""
+        packs = []
+        capturing = torch.cuda.is_current_stream_capturing()
+        for m in self.models:
+            if m is None:
+                packs.append(None)
+                continue
+            if capturing:
+                pk = m._packed_slot(*self.logs)
+                if pk.buffers_bwd.get(pk.precision) is None or pk.buffer_ig is None:
+                    raise RuntimeError("FusedPoseStep: a step was captured before an eager one had packed the networks")
+            else:
+                pk = m.packed(*self.logs, parts=_hip.PACK_CORE)
+                _ops.ensure_backward_stream(m, pk, pk.precision)
+                _ops.ensure_input_grad_stream(m, pk)
+            packs.append(pk)
+        return packs
+
+    def _enqueue(self):
+        pc, pf = self._packs()
+        _ops.pose_records(self.xi, self.e0, self.k, self.ndc_focal, cams=self.cams)
+        rays, target, pix, views = _ops.select_rays_draw_views(self.height, self.width, self.cams, self.near, self.far, self.rng_state,
+                                                               self.num_rays, self.images, want_pixels=True, ndc_focal=self.ndc_focal,
+                                                               ndc_near=1.0)
+        maps, saved = _ops.render_rays_train_geom(pc, pf, rays, self.nc, self.nf, self.lindisp, self.noise_std, self.white, [], None,
+                                                  prec=pc.precision, rng_state=self.rng_state, perturb=self.perturb)
+        self.loss3, g_c, g_f = _ops.mse2_loss(maps[0], maps[3], target, False, self.rng_state)
+        d_rays, keep = _ops.render_rays_backward_geom(pc, pf, saved, (g_c, None, None), (g_f, None, None))
+        g_cams = _ops.camera_grad_views(self.height, self.width, self.cams, views, pix, self.num_rays, d_rays[:, 0:3], d_rays[:, 3:6],
+                                        d_rays[:, 8:11], self.ndc_focal or 0.0, 1.0)
+        _ops.pose_records_backward(g_cams, self.xi, self.e0, out=self._grad, keep=self.last_grad)
+        _ops.adam_step(self._flat[0], self._flat[1], self._flat[2], self._flat[3], self._adam_state, self.lr, 1.0, (0.9, 0.999), 1e-8, True)
+        # alive until the next call (stream-ordered allocator; under capture they belong to the graph's pool)
+        self._keep = (views, pix, rays, target, maps, saved, d_rays, g_cams, keep, g_c, g_f)
+
+    def step(self):
+        """One refinement iteration.  Returns loss3 (device, [loss, mse_coarse, mse_fine]); nothing is read back."""
+        if torch.cuda.is_current_stream_capturing():      # inside the caller's own capture: the launches go into that graph
+            self._enqueue()
+            return self.loss3
+        if self.graph is not None:
+            self.graph.replay()
+            return self.loss3
+        if self.eager_left > 0 or not self.use_graphs:
+            self.eager_left -= 1
+            self._enqueue()
+            return self.loss3
+        try:
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, capture_error_mode="thread_local"):    # a capture only records ...
+                self._enqueue()
+            self.graph = graph
+        except Exception as exc:  # noqa: BLE001
+            self.graph, self.use_graphs = None, False
+            self.fallback_reason = f"{type(exc).__name__}: {exc}"
+            torch.cuda.synchronize()
+            self._enqueue()
+            return self.loss3
+        self.graph.replay()                                                     # ... this iteration's step runs here
+        return self.loss3
+
+    def latest_draw(self):
+        """(view_index (N) int32, pixel_index (N) int64, rows (N,11), target (N,3)) of the latest step, device tensors kept alive until the
+        next eager step (a replayed graph rewrites them in place) - for tests."""
+        return self._keep[:4]
+
+    def extrinsics(self):
+        """The current estimates se3_exp(xi[v]) @ extrinsics0[v], (V,4,4) fp32 on the device (dn_pose_records at the current xi)."""
+        return _ops.pose_records(self.xi, self.e0, self.k, self.ndc_focal, want_extrinsics=True)[1]
