@@ -39,6 +39,7 @@ EXPORTS = (
     "dn_select_rays_views", "dn_select_rays_draw_views", "dn_camera_grad_views_scratch_bytes", "dn_camera_grad_views",
     "dn_pose_records", "dn_pose_records_backward", "dn_render_rays_train_geom", "dn_render_backward_geom_workspace_bytes",
     "dn_render_rays_backward_geom",
+    "dn_render_loss",
 )
 
 
@@ -117,6 +118,8 @@ def _declare(lib):
     lib.dn_select_rays_draw_ndc.argtypes = [c_int, c_int, fp, vp, c_int, c_float, c_float, vp, c_int64, fp, c_int, fp, fp, vp,
                                             ctypes.c_double, ctypes.c_double, vp]
     lib.dn_mse2_loss.argtypes = [fp, fp, fp, c_int64, c_int, fp, fp, fp, vp, vp]
+    lib.dn_render_loss.argtypes = [fp, fp, fp, fp, fp, fp, vp, vp, vp, c_int64, c_int64, c_int, c_float, c_float, c_float, c_float, c_float, c_float,
+                                   fp, fp, fp, fp, fp, vp, vp]
     lib.dn_rng_fill.argtypes = [vp, ctypes.c_uint32, c_int64, c_int, fp, vp]
     lib.dn_pack_ray_rows.argtypes = [fp, fp, fp, c_float, c_float, c_int64, fp, vp]
     dbl = ctypes.c_double

@@ -509,6 +509,55 @@ def mse2_loss(rgb_c, rgb_f, target, luminance=False, rng_state=None):
     return loss3, g_c, g_f
 
 
+def render_loss(rgb_c, rgb_f, target, depth_c=None, depth_f=None, depth_src=None, pixel_index=None, view_index=None, view=None,
+                weights=(1.0, 1.0), depth_weights=(0.0, 0.0), depth_range=(0.0, float("inf")), luminance=False, rng_state=None):
+    """(loss6 = [loss, mse_coarse, mse_fine, D_coarse, D_fine, M] on the device, g_rgb_coarse, g_rgb_fine, g_depth_coarse, g_depth_fine):
+    the general loss head + its upstream gradients in one launch (dn_render_loss); advances `rng_state`'s iteration counter.
+    depth_src: (N) target depths, or with pixel_index (N) int64 the (V, H W) / (V,H,W) depth maps they are gathered from - the view of
+    ray i is view_index[i] ((N) int32), else `view` (device int32 scalar), else 0.  None: no depth term (both depth gradients None)."""
+    rgb_c, target = f32c(rgb_c), f32c(target)
+    n = rgb_c.shape[0]
+    dev = rgb_c.device
+    loss6 = torch.empty(6, dtype=torch.float32, device=dev)
+    g_c = torch.empty_like(rgb_c)
+    g_f = None
+    if rgb_f is not None:
+        rgb_f = f32c(rgb_f)
+        g_f = torch.empty_like(rgb_f)
+    gd_c = gd_f = pix = views = None
+    hw = 0
+    if depth_src is not None:
+        if depth_c is None:
+            raise ValueError("render_loss: a depth target needs depth_c")
+        depth_src, depth_c = f32c(depth_src), f32c(depth_c)
+        assert depth_c.numel() == n and depth_src.is_cuda
+        gd_c = torch.empty_like(depth_c)
+        if depth_f is not None:
+            depth_f = f32c(depth_f)
+            assert depth_f.numel() == n
+            gd_f = torch.empty_like(depth_f)
+        if pixel_index is None:
+            assert depth_src.numel() == n and view_index is None and view is None, "render_loss: direct depth targets are (N)"
+        else:
+            pix = pixel_index.contiguous()
+            assert pix.dtype == torch.int64 and pix.is_cuda and pix.numel() == n and depth_src.dim() >= 2
+            hw = depth_src[0].numel()
+            if view_index is not None:
+                views = _view_index(view_index, n)
+            elif view is not None:
+                assert view.dtype == torch.int32 and view.is_cuda and view.numel() == 1
+            else:
+                assert depth_src.shape[0] >= 1
+    else:
+        depth_c = depth_f = view = None
+    check(lib().dn_render_loss(ptr(rgb_c), ptr(rgb_f), ptr(target), ptr(depth_c), ptr(depth_f), ptr(depth_src), ptr(pix), ptr(views),
+                               ptr(view) if (pix is not None and views is None) else None, hw, n, int(bool(luminance)),
+                               float(weights[0]), float(weights[1]), float(depth_weights[0]), float(depth_weights[1]),
+                               float(depth_range[0]), float(depth_range[1]), ptr(loss6), ptr(g_c), ptr(g_f), ptr(gd_c), ptr(gd_f),
+                               ptr(rng_state), stream()), "dn_render_loss")
+    return loss6, g_c, g_f, gd_c, gd_f
+
+
 def ndc_rays(height, width, focal, near, rays_o, rays_d):
     ro, rd = f32c(rays_o), f32c(rays_d)
     n = ro.numel() // 3

@@ -10,6 +10,9 @@ fine render -> mse + mse -> backward -> Adam) with nothing in it but this librar
     dn_render_rays_train     coarse depths / net / composite, resampling, fine net / composite; the jitter, the resampling u and
                              the density noise drawn inside the kernels that consume them                             (6 kernels)
     dn_mse2_loss             loss, both MSEs and the two upstream gradients                                            (1 kernel)
+                             (depth_images / loss_weights / depth_weights given: dn_render_loss in its place - weighted colour terms
+                             plus a masked depth term whose targets it gathers from the depth maps at the drawn (view, pixel)
+                             pairs, and the upstream gradients of the depth maps as well)
     dn_render_rays_backward  composite backward + backward-data chain per network, then ONE weight-gradient launch for the
                              layers of both (one rank; with several ranks the networks are done one at a time so that the
                              fine network's all-reduce overlaps the coarse half)                                       (5 kernels)
@@ -24,16 +27,26 @@ import torch
 
 from . import _ops
 from ._train import train_fused_ok
+from .loss import loss_head_settings
 from .train_utils import _fusable
 
 
 class FusedTrainStep:
     def __init__(self, model_coarse, model_fine, selector, options, bucket, encode_position_fn, encode_direction_fn, num_rays, seed=0,
-                 luminance=False, first_iteration=0, draw_view=False, ndc_focal=None):
+                 luminance=False, first_iteration=0, draw_view=False, ndc_focal=None, depth_images=None, loss_weights=(1.0, 1.0),
+                 depth_weights=(0.0, 0.0), depth_range=(0.0, float("inf"))):
         if not (isinstance(draw_view, bool) or draw_view == "rays"):
             raise ValueError(f"FusedTrainStep: draw_view must be False, True or \"rays\" (got {draw_view!r})")
         opt = options.nerf.train
         self.ndc = getattr(options.dataset, "no_ndc", True) is False
+        if depth_images is not None and draw_view is True:
+            raise ValueError("FusedTrainStep: depth_images need the view of every ray (draw_view=False or \"rays\"); with "
+                             "draw_view=True the view is drawn inside the selection kernel and not returned")
+        shape = None if depth_images is None else (selector.cams.shape[0], selector.height, selector.width)
+        # None: the reference's head (dn_mse2_loss); else the settings of dn_render_loss.  Both colour weights must be > 0 here: the
+        # default 8-bit mode scales its saved gradients per launch from the largest upstream gradient
+        self.head = loss_head_settings("FusedTrainStep", depth_images, loss_weights, depth_weights, depth_range, shape=shape, ndc=self.ndc,
+                                       colour_weights_positive=True)
         if self.ndc and ndc_focal is None:
             raise ValueError("FusedTrainStep: NDC rays (dataset.no_ndc: False) need the capture's focal length (ndc_focal)")
         self.ndc_focal = float(ndc_focal) if self.ndc else None
@@ -49,7 +62,7 @@ class FusedTrainStep:
             raise ValueError("FusedTrainStep: configuration outside the fused training kernels (see FusedTrainStep.applicable)")
         dev = next(model_coarse.parameters()).device
         self.rng_state = _ops.new_rng_state(seed, dev, first_iteration)
-        self.loss3 = None
+        self.loss3 = self.loss6 = None       # loss6 (general head only) = [loss, mse_c, mse_f, D_c, D_f, valid rays]; loss3 its first three
         # True: the iteration's training view is drawn in the kernel too (else: selector.view); "rays": the view of EVERY ray is drawn
         # with its pixel, a batch across all training images (dn_select_rays_draw_views)
         self.draw_view = draw_view
@@ -91,7 +104,17 @@ class FusedTrainStep:
         of both networks in ONE launch (dn_mlp_weight_grad_pair); coarse_backward() must not follow."""
         mc, mf = self.models
         sel = self.selector
-        if self.draw_view == "rays":
+        head = self.head
+        gather = head is not None and head["depth_images"] is not None
+        pix = views = None
+        if gather and self.draw_view == "rays":
+            rays, target, pix, views = _ops.select_rays_draw_views(sel.height, sel.width, sel.cams, sel.near, sel.far, self.rng_state,
+                                                                   self.num_rays, sel.images, want_pixels=True, ndc_focal=self.ndc_focal,
+                                                                   ndc_near=1.0)
+        elif gather:
+            rays, target, pix = _ops.select_rays_draw(sel.height, sel.width, sel.cams, sel.view, sel.near, sel.far, self.rng_state,
+                                                      self.num_rays, sel.images, want_pixels=True, ndc_focal=self.ndc_focal, ndc_near=1.0)
+        elif self.draw_view == "rays":
             rays, target = _ops.select_rays_draw_views(sel.height, sel.width, sel.cams, sel.near, sel.far, self.rng_state, self.num_rays,
                                                        sel.images, ndc_focal=self.ndc_focal, ndc_near=1.0)
         else:
@@ -100,7 +123,16 @@ class FusedTrainStep:
         pc, pf, prec = _ops.pack_train_pair(mc, mf, self.logs)
         maps, saved = _ops.render_rays_train(pc, pf, rays, self.nc, self.nf, self.lindisp, self.noise_std, self.white, [], None, prec=prec,
                                              rng_state=self.rng_state, perturb=self.perturb)
-        self.loss3, g_c, g_f = _ops.mse2_loss(maps[0], maps[3], target, self.luminance, self.rng_state)
+        gd_c = gd_f = None
+        if head is None:
+            self.loss3, g_c, g_f = _ops.mse2_loss(maps[0], maps[3], target, self.luminance, self.rng_state)
+        else:
+            self.loss6, g_c, g_f, gd_c, gd_f = _ops.render_loss(
+                maps[0], maps[3], target, maps[1], maps[4], head["depth_images"], pix, views, sel.view if (gather and views is None) else None,
+                head["weights"], head["depth_weights"], head["depth_range"], self.luminance, self.rng_state)
+            self.loss3 = self.loss6[:3]
+            gd_c = gd_c if head["depth_weights"][0] != 0.0 else None      # (weight 0: the backward of a photometric step)
+            gd_f = gd_f if head["depth_weights"][1] != 0.0 else None
         if _zero and self.zero_in_step:
             self.bucket.flat.zero_()
         views_c, views_f = mc._grad_sink.views(mc), mf._grad_sink.views(mf)
@@ -108,16 +140,22 @@ class FusedTrainStep:
             raise RuntimeError("FusedTrainStep: a parameter's .grad is no longer the FlatGradBucket's view")
         none3 = (None, None, None)
         if both:
-            keep = [_ops.render_rays_backward(pc, pf, saved, (g_c, None, None), (g_f, None, None), views_c, views_f, nets=3)]
+            keep = [_ops.render_rays_backward(pc, pf, saved, (g_c, gd_c, None), (g_f, gd_f, None), views_c, views_f, nets=3)]
         else:
-            keep = [_ops.render_rays_backward(pc, pf, saved, none3, (g_f, None, None), views_c, views_f, nets=2)]
-        self._half = (pc, pf, saved, g_c, views_c, views_f)
-        self._keep = (keep, saved, maps, rays, target, g_c, g_f)   # alive until the next call (stream-ordered allocator)
+            keep = [_ops.render_rays_backward(pc, pf, saved, none3, (g_f, gd_f, None), views_c, views_f, nets=2)]
+        self._half = (pc, pf, saved, g_c, gd_c, views_c, views_f)
+        self._keep = (keep, saved, maps, rays, target, g_c, g_f, pix, views, gd_c, gd_f)   # alive until the next call (stream-ordered allocator)
 
     def coarse_backward(self):
-        pc, pf, saved, g_c, views_c, views_f = self._half
+        pc, pf, saved, g_c, gd_c, views_c, views_f = self._half
         none3 = (None, None, None)
-        self._keep[0].append(_ops.render_rays_backward(pc, pf, saved, (g_c, None, None), none3, views_c, views_f, nets=1))
+        self._keep[0].append(_ops.render_rays_backward(pc, pf, saved, (g_c, gd_c, None), none3, views_c, views_f, nets=1))
+
+    def latest_draw(self):
+        """(view_index (N) int32 | None, pixel_index (N) int64 | None, rows, target) of the latest step - the pairs only with
+        depth_images (the default head never asks the draw for them) - device tensors kept alive until the next eager step (a replayed
+        graph rewrites them in place); for tests."""
+        return self._keep[8], self._keep[7], self._keep[3], self._keep[4]
 
 
 class GraphedTrainStep:

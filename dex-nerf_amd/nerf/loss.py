@@ -1,0 +1,90 @@
+"""The loss head of the training loop under autograd: weighted mse(rgb_coarse) + mse(rgb_fine) plus a masked depth term, value and
+gradients from ONE kernel launch (dn_render_loss).  FusedTrainStep / FusedPoseStep call the same head without an autograd graph."""
+import torch
+
+from . import _hip, _ops
+from .nerf_helpers import _require_device
+
+
+def loss_head_settings(who, depth_images, loss_weights, depth_weights, depth_range, shape=None, ndc=False, colour_weights_positive=False):
+    """The loss-head arguments of a fused step (FusedTrainStep / FusedPoseStep), validated.  None when they are all at their defaults:
+    the step then keeps the reference's head, dn_mse2_loss.  `shape`: the (V,H,W) the depth maps must have.  Else a dict(depth_images (V,H,W) fp32 on the device | None, weights,
+    depth_weights, depth_range) for _ops.render_loss.  Raises ValueError on settings the step cannot honour."""
+    weights, d_weights = tuple(float(w) for w in loss_weights), tuple(float(w) for w in depth_weights)
+    d_range = tuple(float(x) for x in depth_range)
+    if len(weights) != 2 or len(d_weights) != 2 or len(d_range) != 2:
+        raise ValueError(f"{who}: loss_weights, depth_weights and depth_range are pairs (coarse, fine) / (lo, hi)")
+    if depth_images is None and weights == (1.0, 1.0) and d_weights == (0.0, 0.0):
+        return None
+    finite = all(w == w and abs(w) != float("inf") for w in weights + d_weights)
+    if not finite or min(weights + d_weights) < 0.0:
+        raise ValueError(f"{who}: loss_weights / depth_weights must be finite and >= 0 (got {weights}, {d_weights})")
+    if colour_weights_positive and min(weights) <= 0.0:
+        raise ValueError(f"{who}: both loss_weights must be > 0 on the training step (got {weights}): its default 8-bit mode scales the "
+                         "saved gradients per launch from the largest upstream gradient")
+    if weights == (0.0, 0.0) and d_weights == (0.0, 0.0):
+        raise ValueError(f"{who}: every loss weight is zero")
+    if max(d_weights) > 0.0:
+        if depth_images is None:
+            raise ValueError(f"{who}: depth_weights {d_weights} need depth_images")
+        if ndc:
+            raise ValueError(f"{who}: no depth term on NDC rows - an NDC depth is not metric (depth_weights {d_weights})")
+    if d_range[0] != d_range[0] or d_range[1] != d_range[1]:
+        raise ValueError(f"{who}: depth_range must not hold NaN")
+    if depth_images is not None:
+        if depth_images.dim() != 3:
+            raise ValueError(f"{who}: depth_images is (V,H,W) (got {tuple(depth_images.shape)})")
+        if shape is not None and tuple(depth_images.shape) != tuple(int(x) for x in shape):
+            raise ValueError(f"{who}: depth_images of shape {tuple(depth_images.shape)} for {shape[0]} views of {shape[1]} x {shape[2]}")
+        _require_device(depth_images, who)
+        depth_images = _hip.f32c(depth_images.detach())
+    return dict(depth_images=depth_images, weights=weights, depth_weights=d_weights, depth_range=d_range)
+
+
+class RenderLossFn(torch.autograd.Function):
+    """(rgb_c, rgb_f | None, depth_c | None, depth_f | None) -> (loss (), loss6 (6)).  The forward runs dn_render_loss and keeps the
+    gradients it wrote; the backward multiplies them by grad_output."""
+
+    @staticmethod
+    def forward(ctx, rgb_c, rgb_f, depth_c, depth_f, target, target_depth, weights, depth_weights, depth_range, luminance):
+        loss6, *grads = _ops.render_loss(rgb_c.detach(), None if rgb_f is None else rgb_f.detach(), target,
+                                         None if depth_c is None else depth_c.detach(), None if depth_f is None else depth_f.detach(),
+                                         target_depth, weights=weights, depth_weights=depth_weights, depth_range=depth_range,
+                                         luminance=luminance)
+        ctx.present = [g is not None for g in grads]
+        ctx.save_for_backward(*[g for g in grads if g is not None])
+        ctx.mark_non_differentiable(loss6)
+        return loss6[0].clone(), loss6
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss, _g_terms):
+        saved = iter(ctx.saved_tensors)
+        out = []
+        for present, needs in zip(ctx.present, ctx.needs_input_grad[:4]):
+            g = next(saved) if present else None
+            out.append(g * g_loss if (g is not None and needs) else None)
+        return tuple(out) + (None,) * 6
+
+
+def render_loss(rgb_c, rgb_f, target, depth_c=None, depth_f=None, target_depth=None, weights=(1.0, 1.0), depth_weights=(0.0, 0.0),
+                depth_range=(0.0, float("inf")), luminance=False):
+    """weights[0] mse(rgb_c, target) + weights[1] mse(rgb_f, target) + depth_weights[0] D(depth_c) + depth_weights[1] D(depth_f), with
+    D(depth) the mean of (depth - target_depth)^2 over the rays whose target depth lies inside depth_range (exclusive; NaN: outside).
+    `luminance`: the IR head (both colour sides through 0.299 r + 0.587 g + 0.114 b).  rgb_f / depth_f may be None (coarse only);
+    target_depth None: no depth term.  Returns the scalar loss, differentiable in the four maps; its `.terms` is the device tensor
+    [loss, mse_coarse, mse_fine, D_coarse, D_fine, number of valid rays].  Device tensors only."""
+    for t in (rgb_c, rgb_f, target, depth_c, depth_f, target_depth):
+        if t is not None:
+            _require_device(t, "render_loss")
+    if target_depth is None:
+        depth_c = depth_f = None
+    elif depth_c is None:
+        raise ValueError("render_loss: target_depth needs depth_c")
+    n = rgb_c.reshape(-1, 3).shape[0]
+    flat = [rgb_c.reshape(n, 3), None if rgb_f is None else rgb_f.reshape(n, 3), None if depth_c is None else depth_c.reshape(n),
+            None if depth_f is None else depth_f.reshape(n)]
+    loss, terms = RenderLossFn.apply(*flat, target.detach().reshape(n, -1)[:, :3], None if target_depth is None else target_depth.detach().reshape(n),
+                                     tuple(weights), tuple(depth_weights), tuple(depth_range), bool(luminance))
+    loss.terms = terms
+    return loss

@@ -166,6 +166,10 @@ class FusedPoseStep:
         dn_select_rays_draw_views    `num_rays` distinct (view, pixel) pairs, their rows and targets (NDC rows with `ndc_focal`)
         dn_render_rays_train_geom    coarse + fine render on the cached packs; jitter, resampling u and density noise drawn in the kernels
         dn_mse2_loss                 loss3 = [loss, mse_coarse, mse_fine] and the upstream gradients
+                                     (depth_images / loss_weights / depth_weights given: dn_render_loss in its place - weighted
+                                     colour terms, e.g. loss_weights=(0, 1) for a fine-only refinement, plus a masked depth term
+                                     on `depth_images` (V,H,W) gathered at the drawn pairs; loss6 = [loss, mse_coarse, mse_fine,
+                                     D_coarse, D_fine, valid rays], loss3 its first three words)
         dn_render_rays_backward_geom the gradient of the rows, no weight gradients
         dn_camera_grad_views         -> the gradient of the records
         dn_pose_records_backward     -> the gradient of xi
@@ -181,7 +185,9 @@ class FusedPoseStep:
     (float64 xi on the host, explicit pixels) stay the parity reference."""
 
     def __init__(self, model_coarse, model_fine, options, height, width, intrinsic, extrinsics0, images, encode_position_fn,
-                 encode_direction_fn, num_rays, lr, seed=0, first_iteration=0, ndc_focal=None, use_graphs=True, eager_iterations=3):
+                 encode_direction_fn, num_rays, lr, seed=0, first_iteration=0, ndc_focal=None, use_graphs=True, eager_iterations=3,
+                 depth_images=None, loss_weights=(1.0, 1.0), depth_weights=(0.0, 0.0), depth_range=(0.0, float("inf"))):
+        from .loss import loss_head_settings
         if extrinsics0.dim() == 2:
             extrinsics0 = extrinsics0[None]
         if extrinsics0.dim() != 3 or tuple(extrinsics0.shape[1:]) != (4, 4):
@@ -194,6 +200,10 @@ class FusedPoseStep:
         self.height, self.width = int(height), int(width)
         if tuple(images.shape[1:3]) != (self.height, self.width):
             raise ValueError(f"FusedPoseStep: images of shape {tuple(images.shape)} for {self.height} x {self.width} cameras")
+        # None: the reference's head (dn_mse2_loss); else the settings of dn_render_loss (a zero colour weight is allowed here: fp32 or
+        # 16-bit saves, no per-launch 8-bit gradient scale)
+        self.head = loss_head_settings("FusedPoseStep", depth_images, loss_weights, depth_weights, depth_range,
+                                       shape=tuple(images.shape[:3]), ndc=ndc_focal is not None)
         for t in (extrinsics0, intrinsic, images):
             _require_device(t, "FusedPoseStep")
         opt = options.nerf.train
@@ -229,7 +239,7 @@ class FusedPoseStep:
         self._adam_state[4:10].view(torch.float64).fill_(1.0)
         self.rng_state = _ops.new_rng_state(seed, dev, first_iteration)
         self.cams = torch.zeros(self.n_views, 16, dtype=torch.float32, device=dev)
-        self.loss3 = None
+        self.loss3 = self.loss6 = None
         self.use_graphs, self.eager_left = bool(use_graphs), int(eager_iterations)
         self.graph = None
         self.fallback_reason = None
@@ -263,14 +273,25 @@ class FusedPoseStep:
                                                                ndc_near=1.0)
         maps, saved = _ops.render_rays_train_geom(pc, pf, rays, self.nc, self.nf, self.lindisp, self.noise_std, self.white, [], None,
                                                   prec=pc.precision, rng_state=self.rng_state, perturb=self.perturb)
-        self.loss3, g_c, g_f = _ops.mse2_loss(maps[0], maps[3], target, False, self.rng_state)
-        d_rays, keep = _ops.render_rays_backward_geom(pc, pf, saved, (g_c, None, None), (g_f, None, None))
+        gd_c = gd_f = None
+        if self.head is None:
+            self.loss3, g_c, g_f = _ops.mse2_loss(maps[0], maps[3], target, False, self.rng_state)
+        else:
+            head = self.head
+            gather = head["depth_images"] is not None
+            self.loss6, g_c, g_f, gd_c, gd_f = _ops.render_loss(
+                maps[0], maps[3], target, maps[1], maps[4], head["depth_images"], pix if gather else None, views if gather else None, None,
+                head["weights"], head["depth_weights"], head["depth_range"], False, self.rng_state)
+            self.loss3 = self.loss6[:3]
+            gd_c = gd_c if head["depth_weights"][0] != 0.0 else None      # (weight 0: the backward of a photometric step)
+            gd_f = gd_f if head["depth_weights"][1] != 0.0 else None
+        d_rays, keep = _ops.render_rays_backward_geom(pc, pf, saved, (g_c, gd_c, None), (g_f, gd_f, None))
         g_cams = _ops.camera_grad_views(self.height, self.width, self.cams, views, pix, self.num_rays, d_rays[:, 0:3], d_rays[:, 3:6],
                                         d_rays[:, 8:11], self.ndc_focal or 0.0, 1.0)
         _ops.pose_records_backward(g_cams, self.xi, self.e0, out=self._grad, keep=self.last_grad)
         _ops.adam_step(self._flat[0], self._flat[1], self._flat[2], self._flat[3], self._adam_state, self.lr, 1.0, (0.9, 0.999), 1e-8, True)
         # alive until the next call (stream-ordered allocator; under capture they belong to the graph's pool)
-        self._keep = (views, pix, rays, target, maps, saved, d_rays, g_cams, keep, g_c, g_f)
+        self._keep = (views, pix, rays, target, maps, saved, d_rays, g_cams, keep, g_c, g_f, gd_c, gd_f)
 
     def step(self):
         """One refinement iteration.  Returns loss3 (device, [loss, mse_coarse, mse_fine]); nothing is read back."""

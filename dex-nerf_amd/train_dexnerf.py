@@ -174,7 +174,22 @@ def main(argv=None):
     ap.add_argument("--mix-views", action="store_true",
                     help="draw every ray's training view together with its pixel (a batch across all training images, upstream NeRF's "
                          "default; nerf.FusedTrainStep(draw_view=\"rays\")) instead of one view per iteration")
+    ap.add_argument("--depth-weight", type=float, default=0.0,
+                    help="weight of the depth term of the loss, coarse and fine alike: the mean squared error of the expected depth against "
+                         "the dataset's depth maps over the pixels inside --depth-range (nerf.FusedTrainStep(depth_images=...)); needs a "
+                         "dataset with depths (the synthetic scene, --messytable) and implies --mix-views")
+    ap.add_argument("--depth-range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="pixels whose depth lies strictly inside (LO, HI) are supervised; default: the Dex validation mask, 0 to the "
+                         "dataset's mask_hi")
     args = ap.parse_args(argv)
+    if args.depth_weight < 0.0:
+        ap.error("--depth-weight must be >= 0")
+    if args.depth_weight > 0.0:
+        if args.llff:
+            ap.error("--depth-weight needs a dataset with depth maps; LLFF captures carry none (and an NDC depth is not metric)")
+        if args.autograd_step:
+            ap.error("--depth-weight runs on the fused step (nerf.FusedTrainStep), not with --autograd-step")
+        args.mix_views = True
     user_bounds = args.near is not None or args.far is not None
     args.ndc = bool(args.llff) and not args.no_ndc
     if args.ndc:
@@ -262,10 +277,17 @@ def main(argv=None):
                                          images=torch.stack([images[v].reshape(hw[0], hw[1], 3) for v in train_ids]), device=dev)
     loss_t = torch.zeros((), dtype=torch.float32, device=dev)
     fused = None
+    head = {}
+    if args.depth_weight > 0.0:
+        if not fused_ok:
+            raise SystemExit("--depth-weight: this configuration is outside nerf.FusedTrainStep (see FusedTrainStep.applicable)")
+        head = dict(depth_images=torch.stack([depths[v].reshape(hw).to(torch.float32) for v in train_ids]),
+                    depth_weights=(args.depth_weight, args.depth_weight),
+                    depth_range=tuple(args.depth_range) if args.depth_range else (0.0, float(data["mask_hi"])))
     if fused_ok:
         fused = nerf.FusedTrainStep(student[0], student[1], selector, cfg, bucket, ex, ed, args.num_random_rays, seed=args.seed + 7919 * rank,
                                     luminance=args.ir, first_iteration=start, draw_view="rays" if args.mix_views else True,
-                                    ndc_focal=ndc_focal)
+                                    ndc_focal=ndc_focal, **head)
     graphed = nerf.GraphedTrainStep(fused, opt, eager_iterations=3, use_graphs=use_graph) if fused is not None else None
     use_graph = use_graph and world == 1      # (the autograd step's single graph below: one rank only)
 
@@ -380,6 +402,9 @@ def main(argv=None):
         if depths[held_out] is not None:
             m_best, err = dex_sweep(out, depths[held_out], thres, data["mask_hi"])
             result["dex_best_threshold"], result["dex_abs_err_mm"] = int(m_best), err["depth_abs_err"]
+            # the expected depth sum(w z) of the fine pass - what --depth-weight supervises - under the same mask and metric
+            _, expected = nerf.dex_error_sweep(depths[held_out], [out[4]], gt_lo=0.0, gt_hi=data["mask_hi"])
+            result["expected_depth_abs_err_mm"] = expected[0]["depth_abs_err"]
         if args.save:
             opt_state = opt.state_dict()
             for group in opt_state["param_groups"]:   # the reference stores a Python float (train_dexnerf_rgb.py:443-456), not the
