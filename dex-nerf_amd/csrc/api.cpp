@@ -127,7 +127,6 @@ extern "C" int dn_render_rays(const dn_mlp_desc* desc_coarse, const void* packed
   DN_REQUIRE(desc_coarse && packed_coarse && rays && workspace && n_rays >= 0, "dn_render_rays: bad arguments");
   DN_REQUIRE(num_fine == 0 || (desc_fine && packed_fine), "dn_render_rays: fine pass requested without a fine net");
   DN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "dn_render_rays: workspace must be 256-byte aligned");
-  if (n_rays == 0) return 0;
   Workspace w = carve(workspace, n_rays, num_coarse, num_fine);
   int rc;
   {
@@ -280,80 +279,6 @@ extern "C" int dn_render_rays_train_geom(const dn_mlp_desc* desc_coarse, const v
                                 rng_state, kRngStreamNoiseFine);
 }
 
-extern "C" int dn_render_rays_backward_ws(const dn_mlp_desc* desc_coarse, const void* packed_bwd_coarse,
-                                          const dn_mlp_desc* desc_fine, const void* packed_bwd_fine, int precision,
-                                          const float* rays, int ray_stride, int64_t n_rays, int num_coarse, int num_fine,
-                                          float noise_std, int white_background, const float* noise_c, const float* noise_f,
-                                          const float* g_rgb_c, const float* g_depth_c, const float* g_acc_c,
-                                          const float* g_rgb_f, const float* g_depth_f, const float* g_acc_f, void* workspace,
-                                          const void* act_c, const void* masks_c, void* grads_c, const void* act_f,
-                                          const void* masks_f, void* grads_f, float* const* h_dW_c, float* const* h_db_c,
-                                          float* const* h_dW_f, float* const* h_db_f, int nets, const uint32_t* rng_state,
-                                          void* wg_scratch, size_t wg_scratch_bytes, dn_stream_t stream) {
-  if (n_rays == 0) return 0;
-  DN_REQUIRE(rays && workspace && n_rays >= 0 && (nets & ~3) == 0 && (wg_scratch != nullptr || wg_scratch_bytes == 0), "dn_render_rays_backward: bad arguments");
-  DN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "dn_render_rays_backward: workspace must be 256-byte aligned");
-  Workspace w = carve(workspace, n_rays, num_coarse, num_fine, true);
-  int rc;
-  // both networks, one architecture: the two backward-data chains first, then ONE weight-gradient launch for the layers of both
-  // (dn_mlp_weight_grad_pair) - a caller that wants the fine half finished early (its all-reduce under the coarse half) asks for
-  // the networks one at a time
-  const bool pair_wgrad = nets == 3 && num_fine > 0 && desc_coarse && desc_fine && std::memcmp(desc_coarse, desc_fine, sizeof(dn_mlp_desc)) == 0 &&
-                          weight_grad_pair_fits(*desc_fine);   // (both networks' layers in one batch: two D <= 12 networks)
-  auto half = [&](const dn_mlp_desc* desc, const void* packed_bwd, const float* rf, const float* z, int samples,
-                  const float* noise, const float* g_rgb, const float* g_depth, const float* g_acc, const void* act,
-                  const void* masks, void* grads, float* const* h_dW, float* const* h_db, uint32_t noise_stream) -> int {
-    DN_REQUIRE(desc && packed_bwd && act && masks && grads && h_dW && h_db, "dn_render_rays_backward: a network's buffers are missing");
-    // 8-bit saved tensors with the per-launch gradient scale: the compositing backward leaves the largest |gradient| of each of its
-    // workgroups behind, and the network backward reduces those words itself - no pass over g_rf in between (a few thousand words at
-    // most: beyond that the separate reduction kernel is the cheaper one)
-    const int64_t n_parts = (n_rays + 3) / 4;
-    // (DEXNERF_S8_ABSMAX_KERNEL=1, read per call: the separate reduction kernel regardless - the A/B of tests/test_hip_parity.py)
-    unsigned* parts = (precision == DN_PREC_BF16_S8 && s8_scale_is_per_launch() && n_parts <= 4096 && std::getenv("DEXNERF_S8_ABSMAX_KERNEL") == nullptr)
-                          ? w.absmax_part : nullptr;
-    if ((rc = volume_render_backward_rng(rf, z, rays + 3, ray_stride, noise, noise_std, white_background, n_rays, samples,
-                                         g_rgb, g_depth, g_acc, nullptr, nullptr, w.g_rf, rng_state, noise_stream, stream, parts)))
-      return rc;
-    const int64_t n_points = n_rays * samples;
-    if ((rc = mlp_backward_data_partials(desc, precision, packed_bwd, w.g_rf, masks, n_points, grads, parts, static_cast<int>(parts ? n_parts : 0), stream))) return rc;
-    if (pair_wgrad) return 0;   // both networks' weight gradients follow in one launch
-    // (one network at a time: the launches are stream-ordered, so the scratch is free again when the second one starts)
-    return dn_mlp_weight_grad_all_ws(desc, precision, act, grads, n_points, h_dW, h_db, wg_scratch, wg_scratch_bytes, stream);
-  };
-  // the fine network first: autograd's order too (its graph node is the younger one), and the half a data-parallel caller
-  // wants finished first so that its all-reduce overlaps the coarse half
-  if ((nets & 2) && num_fine > 0) {
-    if ((rc = half(desc_fine, packed_bwd_fine, w.rf_f, w.z_f, num_coarse + num_fine, noise_f, g_rgb_f, g_depth_f, g_acc_f,
-                   act_f, masks_f, grads_f, h_dW_f, h_db_f, kRngStreamNoiseFine)))
-      return rc;
-  }
-  if (nets & 1) {
-    if ((rc = half(desc_coarse, packed_bwd_coarse, w.rf_c, w.z_c, num_coarse, noise_c, g_rgb_c, g_depth_c, g_acc_c, act_c,
-                   masks_c, grads_c, h_dW_c, h_db_c, kRngStreamNoiseCoarse)))
-      return rc;
-  }
-  if (pair_wgrad)
-    return dn_mlp_weight_grad_pair_ws(desc_fine, precision, act_f, grads_f, n_rays * (num_coarse + num_fine), h_dW_f, h_db_f, act_c, grads_c,
-                                      n_rays * num_coarse, h_dW_c, h_db_c, wg_scratch, wg_scratch_bytes, stream);
-  return 0;
-}
-
-extern "C" int dn_render_rays_backward(const dn_mlp_desc* desc_coarse, const void* packed_bwd_coarse,
-                                       const dn_mlp_desc* desc_fine, const void* packed_bwd_fine, int precision,
-                                       const float* rays, int ray_stride, int64_t n_rays, int num_coarse, int num_fine,
-                                       float noise_std, int white_background, const float* noise_c, const float* noise_f,
-                                       const float* g_rgb_c, const float* g_depth_c, const float* g_acc_c,
-                                       const float* g_rgb_f, const float* g_depth_f, const float* g_acc_f, void* workspace,
-                                       const void* act_c, const void* masks_c, void* grads_c, const void* act_f,
-                                       const void* masks_f, void* grads_f, float* const* h_dW_c, float* const* h_db_c,
-                                       float* const* h_dW_f, float* const* h_db_f, int nets, const uint32_t* rng_state,
-                                       dn_stream_t stream) {
-  return dn_render_rays_backward_ws(desc_coarse, packed_bwd_coarse, desc_fine, packed_bwd_fine, precision, rays, ray_stride, n_rays, num_coarse,
-                                    num_fine, noise_std, white_background, noise_c, noise_f, g_rgb_c, g_depth_c, g_acc_c, g_rgb_f, g_depth_f,
-                                    g_acc_f, workspace, act_c, masks_c, grads_c, act_f, masks_f, grads_f, h_dW_c, h_db_c, h_dW_f, h_db_f, nets,
-                                    rng_state, nullptr, 0, stream);
-}
-
 // ---- the backward of dn_render_rays_train_geom with the ray gradient (pose / ray optimisation on the fused step) -----------------
 namespace dn {
 struct GeomWorkspace {
@@ -389,7 +314,136 @@ static GeomWorkspace carve_geom(void* base, const dn_mlp_desc* desc_c, const dn_
   w.bytes = off;
   return w;
 }
+
+// The one backward of dn_render_rays_train / dn_render_rays_train_geom: the body of dn_render_rays_backward_ws, dn_render_rays_backward
+// and dn_render_rays_backward_geom, which judge their own arguments, fill this struct and call it (n_rays > 0).
+struct BackwardNet {   // what one network brings
+  const dn_mlp_desc* desc;
+  const void *packed_bwd, *packed_ig;   // packed_ig: the input-gradient stream, geometry only
+  const float *noise, *g_rgb, *g_depth, *g_acc;
+  const void *act, *masks;
+  void* grads;
+  float* const *h_dW, *const *h_db;
+};
+
+struct RenderBackwardArgs {
+  BackwardNet coarse, fine;
+  int precision, ray_stride, num_coarse, num_fine, white_background;
+  const float* rays;
+  int64_t n_rays;
+  float noise_std;
+  void *workspace, *wg_scratch;
+  size_t wg_scratch_bytes;
+  int nets;     // bit 0 coarse, bit 1 fine; the geometry route: 3
+  bool wgrad;   // weight gradients wanted (the geometry route with frozen networks: not)
+  const uint32_t* rng_state;
+  dn_stream_t stream;
+  // the ray gradient, when d_rays is given: geom_workspace as carve_geom lays it out
+  float* d_rays;
+  void* geom_workspace;
+  int lindisp, perturb;
+  const float *t_rand, *z_samples;
+};
+
+static int render_rays_backward(const RenderBackwardArgs& a) {
+  const bool geom = a.d_rays != nullptr, fine = a.num_fine > 0;
+  const int64_t n_rays = a.n_rays;
+  const int nc = a.num_coarse, nf = a.num_fine;
+  const Workspace w = carve(a.workspace, n_rays, nc, nf, true);
+  const GeomWorkspace g = geom ? carve_geom(a.geom_workspace, a.coarse.desc, a.fine.desc, n_rays, a.ray_stride, nc, nf) : GeomWorkspace{};
+  int rc;
+  // both networks, one architecture: the two backward-data chains first, then ONE weight-gradient launch for the layers of both
+  // (dn_mlp_weight_grad_pair) - a caller that wants the fine half finished early (its all-reduce under the coarse half) asks for
+  // the networks one at a time
+  const bool pair_wgrad = a.wgrad && a.nets == 3 && fine && a.coarse.desc && a.fine.desc &&
+                          std::memcmp(a.coarse.desc, a.fine.desc, sizeof(dn_mlp_desc)) == 0 &&
+                          weight_grad_pair_fits(*a.fine.desc);   // (both networks' layers in one batch: two D <= 12 networks)
+  auto half = [&](const BackwardNet& net, const float* rf, const float* z, int samples, uint32_t noise_stream, float* g_z, float* g_rd,
+                  float* d_rays_net, float* d_z) -> int {
+    // 8-bit saved tensors with the per-launch gradient scale: the compositing backward leaves the largest |gradient| of each of its
+    // workgroups behind, and the network backward reduces those words itself - no pass over g_rf in between (a few thousand words at
+    // most: beyond that the separate reduction kernel is the cheaper one)
+    const int64_t n_parts = (n_rays + 3) / 4;
+    // (DEXNERF_S8_ABSMAX_KERNEL=1, read per call: the separate reduction kernel regardless - the A/B of tests/test_hip_parity.py)
+    unsigned* parts = (a.precision == DN_PREC_BF16_S8 && s8_scale_is_per_launch() && n_parts <= 4096 && std::getenv("DEXNERF_S8_ABSMAX_KERNEL") == nullptr)
+                          ? w.absmax_part : nullptr;
+    if ((rc = volume_render_backward_rng(geom ? "dn_volume_render_backward_geom" : "dn_volume_render_backward", rf, z, a.rays + 3, a.ray_stride,
+                                         net.noise, a.noise_std, a.white_background, n_rays, samples, net.g_rgb, net.g_depth, net.g_acc, nullptr,
+                                         nullptr, w.g_rf, g_z, g_rd, a.rng_state, noise_stream, parts, a.stream)))
+      return rc;
+    const int64_t n_points = n_rays * samples;
+    if ((rc = mlp_backward_data_partials(net.desc, a.precision, net.packed_bwd, w.g_rf, net.masks, n_points, net.grads, parts,
+                                         static_cast<int>(parts ? n_parts : 0), a.stream)))
+      return rc;
+    if (geom && (rc = dn_mlp_backward_input(net.desc, a.precision, net.packed_ig, net.grads, nullptr, nullptr, a.rays, a.ray_stride, z, n_rays,
+                                            samples, nullptr, nullptr, d_rays_net, d_z, g.input_grad, g.input_grad_bytes, a.stream)))
+      return rc;
+    if (!a.wgrad || pair_wgrad) return 0;   // none wanted, or both networks' weight gradients follow in one launch
+    // (one network at a time: the launches are stream-ordered, so the scratch is free again when the second one starts)
+    return dn_mlp_weight_grad_all_ws(net.desc, a.precision, net.act, net.grads, n_points, net.h_dW, net.h_db, a.wg_scratch, a.wg_scratch_bytes,
+                                     a.stream);
+  };
+  // the fine network first: autograd's order too (its graph node is the younger one), and the half a data-parallel caller
+  // wants finished first so that its all-reduce overlaps the coarse half; its depth gradient feeds the coarse depths through the merge
+  if ((a.nets & 2) && fine && (rc = half(a.fine, w.rf_f, w.z_f, nc + nf, kRngStreamNoiseFine, g.g_z_f, g.g_rd_f, g.d_rays_f, g.d_z_f))) return rc;
+  if ((a.nets & 1) && (rc = half(a.coarse, w.rf_c, w.z_c, nc, kRngStreamNoiseCoarse, g.g_z_c, g.g_rd_c, g.d_rays_c, g.d_z_c))) return rc;
+  if (pair_wgrad &&
+      (rc = dn_mlp_weight_grad_pair_ws(a.fine.desc, a.precision, a.fine.act, a.fine.grads, n_rays * (nc + nf), a.fine.h_dW, a.fine.h_db,
+                                       a.coarse.act, a.coarse.grads, n_rays * nc, a.coarse.h_dW, a.coarse.h_db, a.wg_scratch,
+                                       a.wg_scratch_bytes, a.stream)))
+    return rc;
+  if (!geom) return 0;
+  // g_z_fine = g_z + d_z, gathered into the coarse depths; g_z_coarse = (g_z + d_z) + gathered -> near / far; then the rows
+  if (fine && (rc = fine_depths_backward_sum(w.z_c, a.z_samples, g.g_z_f, g.d_z_f, n_rays, nc, nf, g.gathered, a.stream))) return rc;
+  if ((rc = coarse_depths_backward_rng(a.rays, a.ray_stride, n_rays, nc, a.lindisp, a.t_rand, g.g_z_c, g.d_z_c, fine ? g.gathered : nullptr,
+                                       g.g_near_far, a.perturb ? a.rng_state : nullptr, a.stream)))
+    return rc;
+  return combine_ray_grads(g.d_rays_c, fine ? g.d_rays_f : nullptr, g.g_rd_c, fine ? g.g_rd_f : nullptr, g.g_near_far, n_rays, a.ray_stride,
+                           a.d_rays, a.stream);
+}
 }  // namespace dn
+
+extern "C" int dn_render_rays_backward_ws(const dn_mlp_desc* desc_coarse, const void* packed_bwd_coarse,
+                                          const dn_mlp_desc* desc_fine, const void* packed_bwd_fine, int precision,
+                                          const float* rays, int ray_stride, int64_t n_rays, int num_coarse, int num_fine,
+                                          float noise_std, int white_background, const float* noise_c, const float* noise_f,
+                                          const float* g_rgb_c, const float* g_depth_c, const float* g_acc_c,
+                                          const float* g_rgb_f, const float* g_depth_f, const float* g_acc_f, void* workspace,
+                                          const void* act_c, const void* masks_c, void* grads_c, const void* act_f,
+                                          const void* masks_f, void* grads_f, float* const* h_dW_c, float* const* h_db_c,
+                                          float* const* h_dW_f, float* const* h_db_f, int nets, const uint32_t* rng_state,
+                                          void* wg_scratch, size_t wg_scratch_bytes, dn_stream_t stream) {
+  if (n_rays == 0) return 0;
+  // every argument is judged before any GPU work
+  DN_REQUIRE(rays && workspace && n_rays >= 0 && (nets & ~3) == 0 && (wg_scratch != nullptr || wg_scratch_bytes == 0), "dn_render_rays_backward: bad arguments");
+  DN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "dn_render_rays_backward: workspace must be 256-byte aligned");
+  RenderBackwardArgs a{};
+  a.coarse = BackwardNet{desc_coarse, packed_bwd_coarse, nullptr, noise_c, g_rgb_c, g_depth_c, g_acc_c, act_c, masks_c, grads_c, h_dW_c, h_db_c};
+  a.fine = BackwardNet{desc_fine, packed_bwd_fine, nullptr, noise_f, g_rgb_f, g_depth_f, g_acc_f, act_f, masks_f, grads_f, h_dW_f, h_db_f};
+  auto complete = [](const BackwardNet& n) { return n.desc && n.packed_bwd && n.act && n.masks && n.grads && n.h_dW && n.h_db; };
+  DN_REQUIRE((!((nets & 2) && num_fine > 0) || complete(a.fine)) && (!(nets & 1) || complete(a.coarse)),
+             "dn_render_rays_backward: a network's buffers are missing");
+  a.precision = precision; a.rays = rays; a.ray_stride = ray_stride; a.n_rays = n_rays;
+  a.num_coarse = num_coarse; a.num_fine = num_fine; a.noise_std = noise_std; a.white_background = white_background; a.workspace = workspace;
+  a.nets = nets; a.wgrad = true; a.rng_state = rng_state; a.wg_scratch = wg_scratch; a.wg_scratch_bytes = wg_scratch_bytes; a.stream = stream;
+  return render_rays_backward(a);
+}
+
+extern "C" int dn_render_rays_backward(const dn_mlp_desc* desc_coarse, const void* packed_bwd_coarse,
+                                       const dn_mlp_desc* desc_fine, const void* packed_bwd_fine, int precision,
+                                       const float* rays, int ray_stride, int64_t n_rays, int num_coarse, int num_fine,
+                                       float noise_std, int white_background, const float* noise_c, const float* noise_f,
+                                       const float* g_rgb_c, const float* g_depth_c, const float* g_acc_c,
+                                       const float* g_rgb_f, const float* g_depth_f, const float* g_acc_f, void* workspace,
+                                       const void* act_c, const void* masks_c, void* grads_c, const void* act_f,
+                                       const void* masks_f, void* grads_f, float* const* h_dW_c, float* const* h_db_c,
+                                       float* const* h_dW_f, float* const* h_db_f, int nets, const uint32_t* rng_state,
+                                       dn_stream_t stream) {
+  return dn_render_rays_backward_ws(desc_coarse, packed_bwd_coarse, desc_fine, packed_bwd_fine, precision, rays, ray_stride, n_rays, num_coarse,
+                                    num_fine, noise_std, white_background, noise_c, noise_f, g_rgb_c, g_depth_c, g_acc_c, g_rgb_f, g_depth_f,
+                                    g_acc_f, workspace, act_c, masks_c, grads_c, act_f, masks_f, grads_f, h_dW_c, h_db_c, h_dW_f, h_db_f, nets,
+                                    rng_state, nullptr, 0, stream);
+}
 
 extern "C" size_t dn_render_backward_geom_workspace_bytes(const dn_mlp_desc* desc_coarse, const dn_mlp_desc* desc_fine, int64_t n_rays,
                                                           int ray_stride, int num_coarse, int num_fine) {
@@ -408,6 +462,7 @@ extern "C" int dn_render_rays_backward_geom(const dn_mlp_desc* desc_coarse, cons
                                             float* const* h_dW_f, float* const* h_db_f, const uint32_t* rng_state, void* wg_scratch,
                                             size_t wg_scratch_bytes, void* geom_workspace, size_t geom_workspace_bytes, float* d_rays,
                                             dn_stream_t stream) {
+  // every argument is judged before any GPU work
   const bool fine = num_fine > 0;
   DN_REQUIRE(n_rays >= 0 && num_coarse >= 1 && num_fine >= 0 && ray_stride >= 8, "dn_render_rays_backward_geom: bad sizes");
   DN_REQUIRE(desc_coarse && packed_bwd_coarse && packed_ig_coarse && rays && workspace && masks_c && grads_c && d_rays && geom_workspace,
@@ -432,44 +487,14 @@ extern "C" int dn_render_rays_backward_geom(const dn_mlp_desc* desc_coarse, cons
   DN_REQUIRE(ray_stride >= (desc_coarse->use_viewdirs || (fine && desc_fine->use_viewdirs) ? 11 : 8),
              "dn_render_rays_backward_geom: ray_stride too small for view directions");
   if (n_rays == 0) return 0;
-  Workspace w = carve(workspace, n_rays, num_coarse, num_fine, true);
-  GeomWorkspace g = carve_geom(geom_workspace, desc_coarse, desc_fine, n_rays, ray_stride, num_coarse, num_fine);
-  int rc;
-  // the weight gradients exactly as dn_render_rays_backward_ws (nets == 3) forms them
-  const bool pair_wgrad = wgrad && fine && std::memcmp(desc_coarse, desc_fine, sizeof(dn_mlp_desc)) == 0 && weight_grad_pair_fits(*desc_fine);
-  auto half = [&](const dn_mlp_desc* desc, const void* packed_bwd, const void* packed_ig, const float* rf, const float* z, int samples,
-                  const float* noise, const float* g_rgb, const float* g_depth, const float* g_acc, const void* act, const void* masks,
-                  void* grads, float* const* h_dW, float* const* h_db, uint32_t noise_stream, float* g_z, float* g_rd, float* d_rays_net,
-                  float* d_z) -> int {
-    if ((rc = volume_render_backward_geom_rng(rf, z, rays + 3, ray_stride, noise, noise_std, white_background, n_rays, samples, g_rgb,
-                                              g_depth, g_acc, nullptr, nullptr, w.g_rf, g_z, g_rd, rng_state, noise_stream, stream)))
-      return rc;
-    const int64_t n_points = n_rays * samples;
-    if ((rc = mlp_backward_data_partials(desc, precision, packed_bwd, w.g_rf, masks, n_points, grads, nullptr, 0, stream))) return rc;
-    if ((rc = dn_mlp_backward_input(desc, precision, packed_ig, grads, nullptr, nullptr, rays, ray_stride, z, n_rays, samples, nullptr,
-                                    nullptr, d_rays_net, d_z, g.input_grad, g.input_grad_bytes, stream)))
-      return rc;
-    if (!wgrad || pair_wgrad) return 0;
-    return dn_mlp_weight_grad_all_ws(desc, precision, act, grads, n_points, h_dW, h_db, wg_scratch, wg_scratch_bytes, stream);
-  };
-  // the fine network first, as dn_render_rays_backward; its depth gradient feeds the coarse depths through the merge
-  if (fine) {
-    if ((rc = half(desc_fine, packed_bwd_fine, packed_ig_fine, w.rf_f, w.z_f, num_coarse + num_fine, noise_f, g_rgb_f, g_depth_f, g_acc_f, act_f,
-                   masks_f, grads_f, h_dW_f, h_db_f, kRngStreamNoiseFine, g.g_z_f, g.g_rd_f, g.d_rays_f, g.d_z_f)))
-      return rc;
-  }
-  if ((rc = half(desc_coarse, packed_bwd_coarse, packed_ig_coarse, w.rf_c, w.z_c, num_coarse, noise_c, g_rgb_c, g_depth_c, g_acc_c, act_c, masks_c,
-                 grads_c, h_dW_c, h_db_c, kRngStreamNoiseCoarse, g.g_z_c, g.g_rd_c, g.d_rays_c, g.d_z_c)))
-    return rc;
-  if (pair_wgrad &&
-      (rc = dn_mlp_weight_grad_pair_ws(desc_fine, precision, act_f, grads_f, n_rays * (num_coarse + num_fine), h_dW_f, h_db_f, act_c, grads_c,
-                                       n_rays * num_coarse, h_dW_c, h_db_c, wg_scratch, wg_scratch_bytes, stream)))
-    return rc;
-  // g_z_fine = g_z + d_z, gathered into the coarse depths; g_z_coarse = (g_z + d_z) + gathered -> near / far; then the rows
-  if (fine && (rc = fine_depths_backward_sum(w.z_c, z_samples, g.g_z_f, g.d_z_f, n_rays, num_coarse, num_fine, g.gathered, stream))) return rc;
-  if ((rc = coarse_depths_backward_rng(rays, ray_stride, n_rays, num_coarse, lindisp, t_rand, g.g_z_c, g.d_z_c, fine ? g.gathered : nullptr,
-                                       g.g_near_far, perturb ? rng_state : nullptr, stream)))
-    return rc;
-  return combine_ray_grads(g.d_rays_c, fine ? g.d_rays_f : nullptr, g.g_rd_c, fine ? g.g_rd_f : nullptr, g.g_near_far, n_rays, ray_stride, d_rays,
-                           stream);
+  RenderBackwardArgs a{};
+  a.coarse = BackwardNet{desc_coarse, packed_bwd_coarse, packed_ig_coarse, noise_c, g_rgb_c, g_depth_c, g_acc_c, act_c, masks_c, grads_c, h_dW_c, h_db_c};
+  a.fine = BackwardNet{desc_fine, packed_bwd_fine, packed_ig_fine, noise_f, g_rgb_f, g_depth_f, g_acc_f, act_f, masks_f, grads_f, h_dW_f, h_db_f};
+  a.precision = precision; a.rays = rays; a.ray_stride = ray_stride; a.n_rays = n_rays; a.num_coarse = num_coarse; a.num_fine = num_fine;
+  a.noise_std = noise_std; a.white_background = white_background; a.workspace = workspace;
+  a.nets = 3; a.wgrad = wgrad;   // always both chains; the weight gradients all or none
+  a.rng_state = rng_state; a.wg_scratch = wg_scratch; a.wg_scratch_bytes = wg_scratch_bytes;
+  a.d_rays = d_rays; a.geom_workspace = geom_workspace; a.lindisp = lindisp; a.perturb = perturb; a.t_rand = t_rand; a.z_samples = z_samples;
+  a.stream = stream;
+  return render_rays_backward(a);
 }

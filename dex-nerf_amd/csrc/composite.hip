@@ -214,7 +214,6 @@ int dn::volume_render_counting(const float* rf, const float* z, const float* rd,
   DN_REQUIRE(n_thres >= 0 && n_thres <= kMaxThres, "dn_volume_render: at most %d Dex thresholds", kMaxThres);
   DN_REQUIRE(n_thres == 0 || (h_m_thres && dex), "dn_volume_render: thresholds given without dex output");
   DN_REQUIRE((reinterpret_cast<uintptr_t>(rf) & 15) == 0, "dn_volume_render: rf must be 16-byte aligned");
-  if (n_rays == 0) return 0;
   ThresArgs th;
   for (int k = 0; k < kMaxThres; ++k) th.m[k] = (k < n_thres) ? h_m_thres[k] : 0.0f;
   const unsigned grid = static_cast<unsigned>((n_rays + kRaysPerBlock - 1) / kRaysPerBlock);
@@ -224,74 +223,50 @@ int dn::volume_render_counting(const float* rf, const float* z, const float* rd,
   return check_launch("dn_volume_render");
 }
 
+// The one launcher of composite_bwd_kernel (dn_volume_render_backward, dn_volume_render_backward_geom and the backward driver of
+// api.cpp; `name`: the entry point, for messages).  g_z / g_rd (the geometry outputs) and absmax_part are optional; GEOM is chosen by
+// whether a geometry output is wanted - none: the plain kernel, which needs g_rf.  noise == NULL with an RNG state: the forward's
+// density noise regenerated in the kernel.
+using CompositeBwdKernel = decltype(&composite_bwd_kernel<1, false>);
+
+static CompositeBwdKernel composite_bwd_instance(int chunks, bool geom) {
+  if (chunks <= 1) return geom ? composite_bwd_kernel<1, true> : composite_bwd_kernel<1, false>;
+  if (chunks <= 2) return geom ? composite_bwd_kernel<2, true> : composite_bwd_kernel<2, false>;
+  if (chunks <= 4) return geom ? composite_bwd_kernel<4, true> : composite_bwd_kernel<4, false>;
+  if (chunks <= 8) return geom ? composite_bwd_kernel<8, true> : composite_bwd_kernel<8, false>;
+  return geom ? composite_bwd_kernel<16, true> : composite_bwd_kernel<16, false>;
+}
+
+int dn::volume_render_backward_rng(const char* name, const float* rf, const float* z, const float* rd, int rd_stride, const float* noise,
+                                   float noise_std, int white_background, int64_t n_rays, int n_samples, const float* g_rgb,
+                                   const float* g_depth, const float* g_acc, const float* g_disp, const float* g_weights, float* g_rf,
+                                   float* g_z, float* g_rd, const uint32_t* rng_state, uint32_t rng_stream, unsigned* absmax_part,
+                                   dn_stream_t stream) {
+  if (n_rays == 0) return 0;
+  DN_REQUIRE(rf && z && rd && (g_rf || g_z || g_rd) && n_rays >= 0 && n_samples >= 1 && rd_stride >= 3, "%s: bad arguments", name);
+  DN_REQUIRE(n_samples <= 1024, "%s: at most 1024 samples per ray", name);
+  DN_REQUIRE(((reinterpret_cast<uintptr_t>(rf) | reinterpret_cast<uintptr_t>(g_rf)) & 15) == 0, "%s: rf / g_rf must be 16-byte aligned", name);
+  const unsigned grid = static_cast<unsigned>((n_rays + kRaysPerBlock - 1) / kRaysPerBlock);
+  hipLaunchKernelGGL(composite_bwd_instance((n_samples + 63) / 64, g_z != nullptr || g_rd != nullptr), dim3(grid), dim3(256), 0,
+                     as_stream(stream), reinterpret_cast<const float4*>(rf), z, rd, rd_stride, noise, noise_std, white_background, n_rays,
+                     n_samples, g_rgb, g_depth, g_acc, g_disp, g_weights, reinterpret_cast<float4*>(g_rf), RngRef{rng_state, rng_stream},
+                     absmax_part, g_z, g_rd);
+  return check_launch(name);
+}
+
 extern "C" int dn_volume_render_backward(const float* rf, const float* z, const float* rd, int rd_stride,
                                          const float* noise, float noise_std, int white_background, int64_t n_rays,
                                          int n_samples, const float* g_rgb, const float* g_depth, const float* g_acc,
                                          const float* g_disp, const float* g_weights, float* g_rf,
                                          dn_stream_t stream) {
-  return dn::volume_render_backward_rng(rf, z, rd, rd_stride, noise, noise_std, white_background, n_rays, n_samples, g_rgb, g_depth, g_acc,
-                                        g_disp, g_weights, g_rf, nullptr, 0u, stream, nullptr);
+  return dn::volume_render_backward_rng("dn_volume_render_backward", rf, z, rd, rd_stride, noise, noise_std, white_background, n_rays, n_samples,
+                                        g_rgb, g_depth, g_acc, g_disp, g_weights, g_rf, nullptr, nullptr, nullptr, 0u, nullptr, stream);
 }
-
-#define DN_LAUNCH_BWD(MC, GEOM, G_Z, G_RD)                                                                          \
-  hipLaunchKernelGGL((composite_bwd_kernel<MC, GEOM>), dim3(grid), dim3(256), 0, as_stream(stream),                 \
-                     reinterpret_cast<const float4*>(rf), z, rd, rd_stride, noise, noise_std, white_background,     \
-                     n_rays, n_samples, g_rgb, g_depth, g_acc, g_disp, g_weights, reinterpret_cast<float4*>(g_rf),  \
-                     RngRef{rng_state, rng_stream}, absmax_part, G_Z, G_RD)
 
 extern "C" int dn_volume_render_backward_geom(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise,
                                               float noise_std, int white_background, int64_t n_rays, int n_samples,
                                               const float* g_rgb, const float* g_depth, const float* g_acc, const float* g_disp,
                                               const float* g_weights, float* g_rf, float* g_z, float* g_rd, dn_stream_t stream) {
-  return dn::volume_render_backward_geom_rng(rf, z, rd, rd_stride, noise, noise_std, white_background, n_rays, n_samples, g_rgb, g_depth,
-                                             g_acc, g_disp, g_weights, g_rf, g_z, g_rd, nullptr, 0u, stream);
-}
-
-// dn_volume_render_backward_geom; noise == NULL with an RNG state: the forward's density noise regenerated in the kernel, as
-// volume_render_backward_rng does for the plain form
-int dn::volume_render_backward_geom_rng(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise, float noise_std,
-                                        int white_background, int64_t n_rays, int n_samples, const float* g_rgb, const float* g_depth,
-                                        const float* g_acc, const float* g_disp, const float* g_weights, float* g_rf, float* g_z,
-                                        float* g_rd, const uint32_t* rng_state, uint32_t rng_stream, dn_stream_t stream) {
-  if (n_rays == 0) return 0;
-  DN_REQUIRE(rf && z && rd && (g_rf || g_z || g_rd) && n_rays >= 0 && n_samples >= 1 && rd_stride >= 3,
-             "dn_volume_render_backward_geom: bad arguments");
-  DN_REQUIRE(n_samples <= 1024, "dn_volume_render_backward_geom: at most 1024 samples per ray");
-  DN_REQUIRE(((reinterpret_cast<uintptr_t>(rf) | reinterpret_cast<uintptr_t>(g_rf)) & 15) == 0,
-             "dn_volume_render_backward_geom: rf / g_rf must be 16-byte aligned");
-  if (g_z == nullptr && g_rd == nullptr)   // nothing of the geometry wanted: the plain kernel
-    return dn::volume_render_backward_rng(rf, z, rd, rd_stride, noise, noise_std, white_background, n_rays, n_samples, g_rgb, g_depth,
-                                          g_acc, g_disp, g_weights, g_rf, rng_state, rng_stream, stream, nullptr);
-  const unsigned grid = static_cast<unsigned>((n_rays + kRaysPerBlock - 1) / kRaysPerBlock);
-  const int chunks = (n_samples + 63) / 64;
-  unsigned* absmax_part = nullptr;
-  if (chunks <= 1) DN_LAUNCH_BWD(1, true, g_z, g_rd);
-  else if (chunks <= 2) DN_LAUNCH_BWD(2, true, g_z, g_rd);
-  else if (chunks <= 4) DN_LAUNCH_BWD(4, true, g_z, g_rd);
-  else if (chunks <= 8) DN_LAUNCH_BWD(8, true, g_z, g_rd);
-  else DN_LAUNCH_BWD(16, true, g_z, g_rd);
-  return check_launch("dn_volume_render_backward_geom");
-}
-
-int dn::volume_render_backward_rng(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise, float noise_std,
-                                   int white_background, int64_t n_rays, int n_samples, const float* g_rgb, const float* g_depth,
-                                   const float* g_acc, const float* g_disp, const float* g_weights, float* g_rf,
-                                   const uint32_t* rng_state, uint32_t rng_stream, dn_stream_t stream, unsigned* absmax_part) {
-  if (n_rays == 0) return 0;
-  DN_REQUIRE(rf && z && rd && g_rf && n_rays >= 0 && n_samples >= 1 && rd_stride >= 3,
-             "dn_volume_render_backward: bad arguments");
-  DN_REQUIRE(n_samples <= 1024, "dn_volume_render_backward: at most 1024 samples per ray");
-  DN_REQUIRE(((reinterpret_cast<uintptr_t>(rf) | reinterpret_cast<uintptr_t>(g_rf)) & 15) == 0,
-             "dn_volume_render_backward: rf / g_rf must be 16-byte aligned");
-  if (n_rays == 0) return 0;
-  const unsigned grid = static_cast<unsigned>((n_rays + kRaysPerBlock - 1) / kRaysPerBlock);
-  const int chunks = (n_samples + 63) / 64;
-  float* const no_g = nullptr;
-  if (chunks <= 1) DN_LAUNCH_BWD(1, false, no_g, no_g);
-  else if (chunks <= 2) DN_LAUNCH_BWD(2, false, no_g, no_g);
-  else if (chunks <= 4) DN_LAUNCH_BWD(4, false, no_g, no_g);
-  else if (chunks <= 8) DN_LAUNCH_BWD(8, false, no_g, no_g);
-  else DN_LAUNCH_BWD(16, false, no_g, no_g);
-#undef DN_LAUNCH_BWD
-  return check_launch("dn_volume_render_backward");
+  return dn::volume_render_backward_rng("dn_volume_render_backward_geom", rf, z, rd, rd_stride, noise, noise_std, white_background, n_rays,
+                                        n_samples, g_rgb, g_depth, g_acc, g_disp, g_weights, g_rf, g_z, g_rd, nullptr, 0u, nullptr, stream);
 }

@@ -61,15 +61,14 @@ int coarse_depths_rng(const float* rays, int ray_stride, int64_t n_rays, int num
                       float* z_vals, const uint32_t* rng_state, dn_stream_t stream);
 int fine_depths_rng(const float* z_coarse, const float* weights, const float* u, int64_t n_rays, int num_coarse, int num_fine,
                     float* z_fine, float* z_samples, const uint32_t* rng_state, dn_stream_t stream);
-int volume_render_backward_rng(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise, float noise_std,
-                               int white_background, int64_t n_rays, int n_samples, const float* g_rgb, const float* g_depth,
-                               const float* g_acc, const float* g_disp, const float* g_weights, float* g_rf,
-                               const uint32_t* rng_state, uint32_t rng_stream, dn_stream_t stream, unsigned* absmax_part = nullptr);
-// the geometry backwards with an RNG state / with the upstream gradient handed over as the terms of a sum (dn_render_rays_backward_geom)
-int volume_render_backward_geom_rng(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise, float noise_std,
-                                    int white_background, int64_t n_rays, int n_samples, const float* g_rgb, const float* g_depth,
-                                    const float* g_acc, const float* g_disp, const float* g_weights, float* g_rf, float* g_z, float* g_rd,
-                                    const uint32_t* rng_state, uint32_t rng_stream, dn_stream_t stream);
+// the one launcher of composite_bwd_kernel (`name`: the entry point, for messages): g_z / g_rd - the geometry form - and absmax_part
+// are optional
+int volume_render_backward_rng(const char* name, const float* rf, const float* z, const float* rd, int rd_stride, const float* noise,
+                               float noise_std, int white_background, int64_t n_rays, int n_samples, const float* g_rgb,
+                               const float* g_depth, const float* g_acc, const float* g_disp, const float* g_weights, float* g_rf,
+                               float* g_z, float* g_rd, const uint32_t* rng_state, uint32_t rng_stream, unsigned* absmax_part,
+                               dn_stream_t stream);
+// the geometry backwards with the upstream gradient handed over as the terms of a sum (the backward driver of api.cpp)
 int coarse_depths_backward_rng(const float* rays, int ray_stride, int64_t n_rays, int num_coarse, int lindisp, const float* t_rand,
                                const float* g_z, const float* g_z_b, const float* g_z_c, float* g_near_far, const uint32_t* rng_state,
                                dn_stream_t stream);

@@ -178,6 +178,14 @@ def _draw_tensors(draws):
     return [None if given.get(name) is None else f32c(given[name]) for name in ("t_rand", "noise_c", "u", "noise_f")]
 
 
+def _empty(dev, *shape):
+    return torch.empty(shape, dtype=torch.float32, device=dev)
+
+
+def _grads_buf(packed, n_points, prec, dev):
+    return torch.empty(train_sizes(packed, n_points, prec=prec)[2], dtype=torch.uint8, device=dev)
+
+
 def _ray_outputs(n, image, dev):
     """(rays (n,11), target (n,3) | None, fp32-contiguous image | None, its channel count) of the select_rays* wrappers."""
     rays = torch.empty((n, 11), dtype=torch.float32, device=dev)
@@ -1135,12 +1143,9 @@ def render_rays(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, noise_s
     fine = num_fine > 0 and packed_f is not None
     nf = num_fine if fine else 0
     ws = _render_workspace(dev, lib().dn_render_workspace_bytes(n, num_coarse, nf))
-
-    def new(*shape):
-        return torch.empty(shape, dtype=torch.float32, device=dev)
-    rgb_c, depth_c, acc_c = new(n, 3), new(n), new(n)
-    rgb_f, depth_f, acc_f = (new(n, 3), new(n), new(n)) if fine else (None, None, None)
-    dex = new(k, n) if k else None
+    rgb_c, depth_c, acc_c = _empty(dev, n, 3), _empty(dev, n), _empty(dev, n)
+    rgb_f, depth_f, acc_f = (_empty(dev, n, 3), _empty(dev, n), _empty(dev, n)) if fine else (None, None, None)
+    dex = _empty(dev, k, n) if k else None
     prec = packed_c.precision
     t_rand, noise_c, u, noise_f = _draw_tensors(draws)
     check(lib().dn_render_rays(
@@ -1196,12 +1201,9 @@ def render_rays_depth(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, n
     fine = num_fine > 0 and packed_f is not None
     nf = num_fine if fine else 0
     ws = _render_workspace(dev, lib().dn_render_depth_workspace_bytes(n, num_coarse, nf))
-
-    def new(*shape):
-        return torch.empty(shape, dtype=torch.float32, device=dev)
-    depth_c, acc_c = new(n), new(n)
-    depth_f, acc_f = (new(n), new(n)) if fine else (None, None)
-    dex = new(k, n) if k else None
+    depth_c, acc_c = _empty(dev, n), _empty(dev, n)
+    depth_f, acc_f = (_empty(dev, n), _empty(dev, n)) if fine else (None, None)
+    dex = _empty(dev, k, n) if k else None
     t_rand, noise_c, u, noise_f = _draw_tensors(draws)
     check(lib().dn_render_rays_depth(
         ctypes.byref(packed_c.desc), ptr(packed_c.buffer),
@@ -1240,10 +1242,6 @@ def render_rays_train(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, n
     fine = num_fine > 0 and packed_f is not None
     nf = num_fine if fine else 0
     ws = torch.empty(max(lib().dn_render_train_workspace_bytes(n, num_coarse, nf), 1), dtype=torch.uint8, device=dev)
-
-    def new(*shape):
-        return torch.empty(shape, dtype=torch.float32, device=dev)
-
     prec = train_precision(packed_c) if prec is None else prec
 
     def bufs(packed, n_points):
@@ -1251,9 +1249,9 @@ def render_rays_train(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, n
         return torch.empty(a, dtype=torch.uint8, device=dev), torch.empty(m, dtype=torch.uint8, device=dev)
     act_c, masks_c = bufs(packed_c, n * num_coarse)
     act_f, masks_f = bufs(packed_f, n * (num_coarse + nf)) if fine else (None, None)
-    rgb_c, depth_c, acc_c = new(n, 3), new(n), new(n)
-    rgb_f, depth_f, acc_f = (new(n, 3), new(n), new(n)) if fine else (None, None, None)
-    dex = new(k, n) if k else None
+    rgb_c, depth_c, acc_c = _empty(dev, n, 3), _empty(dev, n), _empty(dev, n)
+    rgb_f, depth_f, acc_f = (_empty(dev, n, 3), _empty(dev, n), _empty(dev, n)) if fine else (None, None, None)
+    dex = _empty(dev, k, n) if k else None
     t_rand, noise_c, u, noise_f = _draw_tensors(draws)
     args = [ctypes.byref(packed_c.desc), ptr(packed_c.buffer),
             ctypes.byref(packed_f.desc) if fine else None, ptr(packed_f.buffer) if fine else None, prec,
@@ -1265,7 +1263,7 @@ def render_rays_train(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, n
                  noise_f=noise_f, n=n, nc=num_coarse, nf=nf, noise_std=float(noise_std), white=bool(white), prec=prec,
                  rng_state=rng_state)
     if geom:
-        z_samples = new(n, nf) if fine else None
+        z_samples = _empty(dev, n, nf) if fine else None
         check(lib().dn_render_rays_train_geom(*args, ptr(z_samples), stream()), "dn_render_rays_train_geom")
         saved.update(t_rand=t_rand, z_samples=z_samples, lindisp=bool(lindisp), perturb=bool(perturb))
     else:
@@ -1273,32 +1271,34 @@ def render_rays_train(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, n
     return (rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f, dex), saved
 
 
+def _backward_args(packed_c, packed_f, saved, g_c, g_f, views_c, views_f, nets, wgrad):
+    """What both render backwards hand to the library for the networks in `nets`: (fine, grads_c, grads_f, the four (dW | db) pointer
+    arrays, the six upstream gradients fp32-contiguous, the weight-gradient scratch and its size - (None, 0) without `wgrad`)."""
+    dev = saved["rays"].device
+    n, nc, nf, prec = saved["n"], saved["nc"], saved["nf"], saved["prec"]
+    fine = nf > 0 and packed_f is not None
+    use_c, use_f = bool(nets & 1), bool(fine and nets & 2)
+    grads_c = _grads_buf(packed_c, n * nc, prec, dev) if use_c else None
+    grads_f = _grads_buf(packed_f, n * (nc + nf), prec, dev) if use_f else None
+    ptrs = _view_ptrs(views_c if use_c else None) + _view_ptrs(views_f if use_f else None)
+    gs = [None if g is None else f32c(g) for g in tuple(g_c) + tuple(g_f)]
+    scratch = _wgrad_scratch(2 if (fine and nets == 3) else 1, packed_c, *([packed_f] if fine else [])) if wgrad else (None, 0)
+    return fine, grads_c, grads_f, ptrs, gs, scratch
+
+
 def render_rays_backward(packed_c, packed_f, saved, g_c, g_f, views_c, views_f, nets=3):
     """dn_render_rays_backward: composite backward -> backward-data chain -> weight gradients for the networks selected by
     `nets` (bit 0 coarse, bit 1 fine), ACCUMULATING into views_* = [(dW, db)] in linear_modules() order.
     g_c / g_f = (g_rgb, g_depth, g_acc) upstream gradients (None = zero)."""
-    dev = saved["rays"].device
-    n, nc, nf = saved["n"], saved["nc"], saved["nf"]
-    fine = nf > 0 and packed_f is not None
-
-    prec = saved["prec"]
-
-    def grads_buf(packed, n_points):
-        return torch.empty(train_sizes(packed, n_points, prec=prec)[2], dtype=torch.uint8, device=dev)
-    grads_c = grads_buf(packed_c, n * nc) if nets & 1 else None
-    grads_f = grads_buf(packed_f, n * (nc + nf)) if (fine and nets & 2) else None
-
-    wc, bc = _view_ptrs(views_c if nets & 1 else None)
-    wf, bf = _view_ptrs(views_f if (fine and nets & 2) else None)
-    gs = [None if g is None else f32c(g) for g in tuple(g_c) + tuple(g_f)]
-    scratch, scratch_bytes = _wgrad_scratch(2 if (fine and nets == 3) else 1, packed_c, *([packed_f] if fine else []))
+    n, nc, nf, prec = saved["n"], saved["nc"], saved["nf"], saved["prec"]
+    fine, grads_c, grads_f, ptrs, gs, (scratch, scratch_bytes) = _backward_args(packed_c, packed_f, saved, g_c, g_f, views_c, views_f, nets, True)
     check(lib().dn_render_rays_backward_ws(
         ctypes.byref(packed_c.desc), ptr(packed_c.buffers_bwd[prec]),
         ctypes.byref(packed_f.desc) if fine else None, ptr(packed_f.buffers_bwd[prec]) if fine else None, prec,
         ptr(saved["rays"]), saved["rays"].shape[1], n, nc, nf, saved["noise_std"], int(saved["white"]),
-        ptr(saved["noise_c"]), ptr(saved["noise_f"]), ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), ptr(gs[3]), ptr(gs[4]), ptr(gs[5]),
+        ptr(saved["noise_c"]), ptr(saved["noise_f"]), *[ptr(g) for g in gs],
         ptr(saved["ws"]), ptr(saved["act_c"]), ptr(saved["masks_c"]), ptr(grads_c), ptr(saved["act_f"]), ptr(saved["masks_f"]),
-        ptr(grads_f), wc, bc, wf, bf, int(nets), ptr(saved.get("rng_state")), ptr(scratch), scratch_bytes, stream()), "dn_render_rays_backward")
+        ptr(grads_f), *ptrs, int(nets), ptr(saved.get("rng_state")), ptr(scratch), scratch_bytes, stream()), "dn_render_rays_backward")
     _note_s8_record(grads_c, prec); _note_s8_record(grads_f, prec)
     return grads_c, grads_f, scratch   # (kept alive by the caller until the stream has consumed them: PyTorch's caching allocator is stream-ordered)
 
@@ -1320,32 +1320,20 @@ def render_rays_backward_geom(packed_c, packed_f, saved, g_c, g_f, views_c=None,
     weight-gradient launch.  The packs need their backward and input-gradient streams (ensure_backward_stream /
     ensure_input_grad_stream)."""
     rays = saved["rays"]
-    dev = rays.device
     n, nc, nf, prec = saved["n"], saved["nc"], saved["nf"], saved["prec"]
-    fine = nf > 0 and packed_f is not None
-
-    def grads_buf(packed, n_points):
-        return torch.empty(train_sizes(packed, n_points, prec=prec)[2], dtype=torch.uint8, device=dev)
-    grads_c = grads_buf(packed_c, n * nc)
-    grads_f = grads_buf(packed_f, n * (nc + nf)) if fine else None
-    wc, bc = _view_ptrs(views_c)
-    wf, bf = _view_ptrs(views_f if fine else None)
-    scratch, scratch_bytes = (None, 0)
-    if views_c is not None:
-        scratch, scratch_bytes = _wgrad_scratch(2 if fine else 1, packed_c, *([packed_f] if fine else []))
-    gs = [None if g is None else f32c(g) for g in tuple(g_c) + tuple(g_f)]
+    fine, grads_c, grads_f, ptrs, gs, (scratch, scratch_bytes) = _backward_args(packed_c, packed_f, saved, g_c, g_f, views_c, views_f, 3,
+                                                                                  views_c is not None)
     desc_f = ctypes.byref(packed_f.desc) if fine else None
     nbytes = int(lib().dn_render_backward_geom_workspace_bytes(ctypes.byref(packed_c.desc), desc_f, n, rays.shape[1], nc, nf))
-    geom_ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    geom_ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=rays.device)
     d_rays = torch.empty_like(rays)
     check(lib().dn_render_rays_backward_geom(
         ctypes.byref(packed_c.desc), ptr(packed_c.buffers_bwd[prec]), ptr(packed_c.buffer_ig),
         desc_f, ptr(packed_f.buffers_bwd[prec]) if fine else None, ptr(packed_f.buffer_ig) if fine else None, prec,
         ptr(rays), rays.shape[1], n, nc, nf, int(saved["lindisp"]), int(saved["perturb"]), saved["noise_std"], int(saved["white"]),
-        ptr(saved["t_rand"]), ptr(saved["noise_c"]), ptr(saved["noise_f"]), ptr(saved["z_samples"]),
-        ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), ptr(gs[3]), ptr(gs[4]), ptr(gs[5]),
+        ptr(saved["t_rand"]), ptr(saved["noise_c"]), ptr(saved["noise_f"]), ptr(saved["z_samples"]), *[ptr(g) for g in gs],
         ptr(saved["ws"]), ptr(saved["act_c"]), ptr(saved["masks_c"]), ptr(grads_c), ptr(saved["act_f"]), ptr(saved["masks_f"]), ptr(grads_f),
-        wc, bc, wf, bf, ptr(saved.get("rng_state")), ptr(scratch), scratch_bytes, ptr(geom_ws), nbytes, ptr(d_rays), stream()),
+        *ptrs, ptr(saved.get("rng_state")), ptr(scratch), scratch_bytes, ptr(geom_ws), nbytes, ptr(d_rays), stream()),
         "dn_render_rays_backward_geom")
     return d_rays, (grads_c, grads_f, scratch, geom_ws, gs)
 

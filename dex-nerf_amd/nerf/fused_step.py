@@ -27,7 +27,7 @@ import torch
 
 from . import _ops
 from ._train import train_fused_ok
-from .loss import loss_head_settings
+from .loss import fused_loss_head, loss_head_settings
 from .train_utils import _fusable
 
 
@@ -104,52 +104,31 @@ class FusedTrainStep:
         of both networks in ONE launch (dn_mlp_weight_grad_pair); coarse_backward() must not follow."""
         mc, mf = self.models
         sel = self.selector
-        head = self.head
-        gather = head is not None and head["depth_images"] is not None
-        pix = views = None
-        if gather and self.draw_view == "rays":
-            rays, target, pix, views = _ops.select_rays_draw_views(sel.height, sel.width, sel.cams, sel.near, sel.far, self.rng_state,
-                                                                   self.num_rays, sel.images, want_pixels=True, ndc_focal=self.ndc_focal,
-                                                                   ndc_near=1.0)
-        elif gather:
-            rays, target, pix = _ops.select_rays_draw(sel.height, sel.width, sel.cams, sel.view, sel.near, sel.far, self.rng_state,
-                                                      self.num_rays, sel.images, want_pixels=True, ndc_focal=self.ndc_focal, ndc_near=1.0)
-        elif self.draw_view == "rays":
-            rays, target = _ops.select_rays_draw_views(sel.height, sel.width, sel.cams, sel.near, sel.far, self.rng_state, self.num_rays,
-                                                       sel.images, ndc_focal=self.ndc_focal, ndc_near=1.0)
-        else:
-            rays, target = _ops.select_rays_draw(sel.height, sel.width, sel.cams, None if self.draw_view else sel.view, sel.near, sel.far,
-                                                 self.rng_state, self.num_rays, sel.images, ndc_focal=self.ndc_focal, ndc_near=1.0)
+        gather = self.head is not None and self.head["depth_images"] is not None
+        # the draw: every ray's view with its pixel ("rays"), or pixels of one view - the selector's, or one drawn in the kernel;
+        # the drawn (pixel, view) come back only when the depth targets are gathered at them
+        by_ray = self.draw_view == "rays"
+        draw = _ops.select_rays_draw_views if by_ray else _ops.select_rays_draw
+        view = () if by_ray else (None if self.draw_view else sel.view,)
+        rays, target, *drawn = draw(sel.height, sel.width, sel.cams, *view, sel.near, sel.far, self.rng_state, self.num_rays, sel.images,
+                                    want_pixels=gather, ndc_focal=self.ndc_focal, ndc_near=1.0)
+        pix, views = (drawn + [None, None])[:2]
         pc, pf, prec = _ops.pack_train_pair(mc, mf, self.logs)
         maps, saved = _ops.render_rays_train(pc, pf, rays, self.nc, self.nf, self.lindisp, self.noise_std, self.white, [], None, prec=prec,
                                              rng_state=self.rng_state, perturb=self.perturb)
-        gd_c = gd_f = None
-        if head is None:
-            self.loss3, g_c, g_f = _ops.mse2_loss(maps[0], maps[3], target, self.luminance, self.rng_state)
-        else:
-            self.loss6, g_c, g_f, gd_c, gd_f = _ops.render_loss(
-                maps[0], maps[3], target, maps[1], maps[4], head["depth_images"], pix, views, sel.view if (gather and views is None) else None,
-                head["weights"], head["depth_weights"], head["depth_range"], self.luminance, self.rng_state)
-            self.loss3 = self.loss6[:3]
-            gd_c = gd_c if head["depth_weights"][0] != 0.0 else None      # (weight 0: the backward of a photometric step)
-            gd_f = gd_f if head["depth_weights"][1] != 0.0 else None
+        self.loss3, self.loss6, g_c, g_f = fused_loss_head(self.head, maps, target, self.rng_state, self.luminance, pix, views, sel.view)
         if _zero and self.zero_in_step:
             self.bucket.flat.zero_()
         views_c, views_f = mc._grad_sink.views(mc), mf._grad_sink.views(mf)
         if views_c is None or views_f is None:
             raise RuntimeError("FusedTrainStep: a parameter's .grad is no longer the FlatGradBucket's view")
-        none3 = (None, None, None)
-        if both:
-            keep = [_ops.render_rays_backward(pc, pf, saved, (g_c, gd_c, None), (g_f, gd_f, None), views_c, views_f, nets=3)]
-        else:
-            keep = [_ops.render_rays_backward(pc, pf, saved, none3, (g_f, gd_f, None), views_c, views_f, nets=2)]
-        self._half = (pc, pf, saved, g_c, gd_c, views_c, views_f)
-        self._keep = (keep, saved, maps, rays, target, g_c, g_f, pix, views, gd_c, gd_f)   # alive until the next call (stream-ordered allocator)
+        keep = [_ops.render_rays_backward(pc, pf, saved, g_c if both else (None, None, None), g_f, views_c, views_f, nets=3 if both else 2)]
+        self._half = (pc, pf, saved, g_c, views_c, views_f)
+        self._keep = (keep, saved, maps, rays, target, g_c[0], g_f[0], pix, views, g_c[1], g_f[1])   # alive until the next call (stream-ordered allocator)
 
     def coarse_backward(self):
-        pc, pf, saved, g_c, gd_c, views_c, views_f = self._half
-        none3 = (None, None, None)
-        self._keep[0].append(_ops.render_rays_backward(pc, pf, saved, (g_c, gd_c, None), none3, views_c, views_f, nets=1))
+        pc, pf, saved, g_c, views_c, views_f = self._half
+        self._keep[0].append(_ops.render_rays_backward(pc, pf, saved, g_c, (None, None, None), views_c, views_f, nets=1))
 
     def latest_draw(self):
         """(view_index (N) int32 | None, pixel_index (N) int64 | None, rows, target) of the latest step - the pairs only with

@@ -41,6 +41,22 @@ def loss_head_settings(who, depth_images, loss_weights, depth_weights, depth_ran
     return dict(depth_images=depth_images, weights=weights, depth_weights=d_weights, depth_range=d_range)
 
 
+def fused_loss_head(head, maps, target, rng_state, luminance=False, pixel_index=None, view_index=None, view=None):
+    """The loss head of a fused step on the maps of render_rays_train: dn_mse2_loss for head None (loss_head_settings), else
+    dn_render_loss with the depth targets gathered from head["depth_images"] at (view_index | view, pixel_index).  Returns (loss3,
+    loss6 | None, g_c, g_f): loss6 = [loss, mse_c, mse_f, D_c, D_f, valid rays], loss3 its first three words; g_c / g_f the upstream
+    (g_rgb, g_depth, g_acc) of the coarse / fine maps - no depth gradient where its weight is 0 (the backward of a photometric step)."""
+    if head is None:
+        loss3, g_c, g_f = _ops.mse2_loss(maps[0], maps[3], target, luminance, rng_state)
+        return loss3, None, (g_c, None, None), (g_f, None, None)
+    gather = head["depth_images"] is not None
+    loss6, g_c, g_f, gd_c, gd_f = _ops.render_loss(
+        maps[0], maps[3], target, maps[1], maps[4], head["depth_images"], pixel_index if gather else None, view_index if gather else None,
+        view if (gather and view_index is None) else None, head["weights"], head["depth_weights"], head["depth_range"], luminance, rng_state)
+    w_c, w_f = head["depth_weights"]
+    return loss6[:3], loss6, (g_c, gd_c if w_c != 0.0 else None, None), (g_f, gd_f if w_f != 0.0 else None, None)
+
+
 class RenderLossFn(torch.autograd.Function):
     """(rgb_c, rgb_f | None, depth_c | None, depth_f | None) -> (loss (), loss6 (6)).  The forward runs dn_render_loss and keeps the
     gradients it wrote; the backward multiplies them by grad_output."""

@@ -6,6 +6,7 @@ twist gradient and Adam all on the device, replayed as one HIP graph."""
 import torch
 
 from . import _hip, _ops
+from .loss import fused_loss_head, loss_head_settings
 from .nerf_helpers import _require_device, img2mse, random_view_pixel_pairs, select_camera_rays
 from .train_utils import predict_and_render_radiance
 
@@ -187,7 +188,6 @@ class FusedPoseStep:
     def __init__(self, model_coarse, model_fine, options, height, width, intrinsic, extrinsics0, images, encode_position_fn,
                  encode_direction_fn, num_rays, lr, seed=0, first_iteration=0, ndc_focal=None, use_graphs=True, eager_iterations=3,
                  depth_images=None, loss_weights=(1.0, 1.0), depth_weights=(0.0, 0.0), depth_range=(0.0, float("inf"))):
-        from .loss import loss_head_settings
         if extrinsics0.dim() == 2:
             extrinsics0 = extrinsics0[None]
         if extrinsics0.dim() != 3 or tuple(extrinsics0.shape[1:]) != (4, 4):
@@ -273,25 +273,14 @@ class FusedPoseStep:
                                                                ndc_near=1.0)
         maps, saved = _ops.render_rays_train_geom(pc, pf, rays, self.nc, self.nf, self.lindisp, self.noise_std, self.white, [], None,
                                                   prec=pc.precision, rng_state=self.rng_state, perturb=self.perturb)
-        gd_c = gd_f = None
-        if self.head is None:
-            self.loss3, g_c, g_f = _ops.mse2_loss(maps[0], maps[3], target, False, self.rng_state)
-        else:
-            head = self.head
-            gather = head["depth_images"] is not None
-            self.loss6, g_c, g_f, gd_c, gd_f = _ops.render_loss(
-                maps[0], maps[3], target, maps[1], maps[4], head["depth_images"], pix if gather else None, views if gather else None, None,
-                head["weights"], head["depth_weights"], head["depth_range"], False, self.rng_state)
-            self.loss3 = self.loss6[:3]
-            gd_c = gd_c if head["depth_weights"][0] != 0.0 else None      # (weight 0: the backward of a photometric step)
-            gd_f = gd_f if head["depth_weights"][1] != 0.0 else None
-        d_rays, keep = _ops.render_rays_backward_geom(pc, pf, saved, (g_c, gd_c, None), (g_f, gd_f, None))
+        self.loss3, self.loss6, g_c, g_f = fused_loss_head(self.head, maps, target, self.rng_state, False, pix, views)
+        d_rays, keep = _ops.render_rays_backward_geom(pc, pf, saved, g_c, g_f)
         g_cams = _ops.camera_grad_views(self.height, self.width, self.cams, views, pix, self.num_rays, d_rays[:, 0:3], d_rays[:, 3:6],
                                         d_rays[:, 8:11], self.ndc_focal or 0.0, 1.0)
         _ops.pose_records_backward(g_cams, self.xi, self.e0, out=self._grad, keep=self.last_grad)
         _ops.adam_step(self._flat[0], self._flat[1], self._flat[2], self._flat[3], self._adam_state, self.lr, 1.0, (0.9, 0.999), 1e-8, True)
         # alive until the next call (stream-ordered allocator; under capture they belong to the graph's pool)
-        self._keep = (views, pix, rays, target, maps, saved, d_rays, g_cams, keep, g_c, g_f, gd_c, gd_f)
+        self._keep = (views, pix, rays, target, maps, saved, d_rays, g_cams, keep, g_c[0], g_f[0], g_c[1], g_f[1])
 
     def step(self):
         """One refinement iteration.  Returns loss3 (device, [loss, mse_coarse, mse_fine]); nothing is read back."""
