@@ -15,28 +15,16 @@ DN_FWD32_INSTANCES(DN_FWD32_EXTERN)
 template <int BF16, int DENS = 0>
 __global__ void pack_kernel(NetLayout L, PackPtrs ptrs, char* __restrict__ packed) {
   using P = Prec<BF16>;
-  const int KX = kXyzPanel, KD = round_up(3 + 6 * L.LD, 16);
-  (void)KX; (void)KD;   // unused, kept: removing them changes the instructions of all three instances (HISTORY.md section 11)
   // bias tiles
   const int n_bias = L.total_bias_tiles * 32;
   float* bias_out = reinterpret_cast<float*>(packed);
   for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < L.bias_bytes / 4; idx += gridDim.x * blockDim.x) {
     float v = 0.0f;
     if (idx < n_bias) {
-      const int tile = idx / 32, hh = (idx % 32) / 16, r = idx % 16;
-      int s = 0;
-      while (s + 1 < L.n_stages && L.st[s + 1].bias0 <= tile) ++s;
-      const StageDesc& st = L.st[s];
-      int ts = tile - st.bias0;
-      const int row_in_tile = acc_row(r, hh);
-      if (st.src2 >= 0) {
-        if (ts == 0) v = (row_in_tile == 0) ? ptrs.b[st.src2][0] : 0.0f;
-        else { const int n = (ts - 1) * 32 + row_in_tile; v = (n < st.n_real) ? ptrs.b[st.src][n] : 0.0f; }
-      } else {
-        const int n = ts * 32 + row_in_tile;
-        if (DENS && s == L.n_stages - 1) v = (n == 3) ? ptrs.b[st.src][0] : 0.0f;
-        else v = (n < st.n_real) ? ptrs.b[st.src][n] : 0.0f;
-      }
+      const int tile = idx / 32, hh = (idx % 32) / 16, r = idx % 16, s = pack_stage_of_bias_tile(L, tile);
+      int src;
+      const int n = pack_src_row<32>(L.st[s], tile - L.st[s].bias0, acc_row(r, hh), DENS && s == L.n_stages - 1, &src);
+      if (n >= 0) v = ptrs.b[src][n];
     }
     bias_out[idx] = v;
   }
@@ -50,8 +38,7 @@ __global__ void pack_kernel(NetLayout L, PackPtrs ptrs, char* __restrict__ packe
     const int piece = static_cast<int>(idx / (P::EPP * 64));
     const int i = lane & 31, hh = lane >> 5;
     float v = 0.0f;
-    int s = 0;
-    while (s + 1 < L.n_stages && L.st[s + 1].piece0 <= piece) ++s;
+    const int s = pack_stage_of_piece(L, piece);
     const StageDesc& st = L.st[s];
     const int rel = piece - st.piece0;
     if (st.transposed) {
@@ -89,16 +76,9 @@ __global__ void pack_kernel(NetLayout L, PackPtrs ptrs, char* __restrict__ packe
         const int pc = pe_slot_col(st.pe_kind == 1 ? L.LX : L.LD, hh, u);
         col = (pc >= 0) ? st.col_pe0 + pc : -1;
       }
-      if (col >= 0) {
-        if (st.src2 >= 0) {
-          if (ts == 0) v = (i == 0) ? ptrs.w[st.src2][col] : 0.0f;
-          else { const int n = (ts - 1) * 32 + i; v = (n < st.n_real) ? ptrs.w[st.src][static_cast<long long>(n) * st.ld + col] : 0.0f; }
-        } else {
-          const int n = ts * 32 + i;
-          if (DENS && s == L.n_stages - 1) v = (n == 3) ? ptrs.w[st.src][col] : 0.0f;
-          else v = (n < st.n_real) ? ptrs.w[st.src][static_cast<long long>(n) * st.ld + col] : 0.0f;
-        }
-      }
+      int src;
+      const int n = pack_src_row<32>(st, ts, i, DENS && s == L.n_stages - 1, &src);
+      if (col >= 0 && n >= 0) v = ptrs.w[src][static_cast<long long>(n) * st.ld + col];
     }
     reinterpret_cast<typename P::Elem*>(wout)[idx] = static_cast<typename P::Elem>(v);
   }
@@ -114,9 +94,7 @@ static int launch_forward(FwdParams p, hipStream_t stream) {
   constexpr int KDP = round_up(3 + 6 * LD, 16) / (2 * Prec<BF16>::EPP);
   const size_t lds = kRingBytes + p.bias_bytes + WAVES * (kInRows * 32 * PT * sizeof(float) + PT * (KXP + KDP) * kPieceBytes);
   if (int rc = ensure_big_lds(reinterpret_cast<const void*>(kern))) return rc;
-  const int cus = device_cus();
-  const long long grid = p.n_tiles < cus ? p.n_tiles : cus;
-  hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(WAVES * 64), lds, stream, p);
+  hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(persistent_grid(p.n_tiles))), dim3(WAVES * 64), lds, stream, p);
   return check_launch("mlp_forward");
 }
 
@@ -127,17 +105,16 @@ int dispatch_forward(const dn_mlp_desc& d, int precision, FwdParams& p, hipStrea
   // PT=2 = 4 waves x 64 points, one wave per SIMD)
   // bf16 / fp16 inference from rays / points: the 48-points-per-wave geometry (mlp_fused48.hip) when the net fits it;
   // DEXNERF_BF16_GEOM=32 keeps the 32-point kernels (same results up to bf16 accumulation order and the cosine's phase form)
-  const char* geom_env = getenv("DEXNERF_BF16_GEOM");   // read per call: tests and probes switch it within one process
-  const bool geom48 = !(geom_env && atoi(geom_env) == 32);
-  if ((bf || hf) && geom48 && p.act == nullptr && p.mode != 2 && p.n_points < (1LL << 31) - 1024 && g48_supported(d, precision))
-    return launch_forward48(d, precision, p, p.packed + p.bias_bytes + static_cast<size_t>(p.total_pieces) * kPieceBytes, stream, comp, composited);
+  const char* region48 = p.packed + core_stream_bytes(p.bias_bytes, p.total_pieces);
+  if ((bf || hf) && !read_switches().geom32 && p.act == nullptr && p.mode != 2 && p.n_points < (1LL << 31) - 1024 && g48_supported(d, precision))
+    return launch_forward48(d, precision, p, region48, stream, comp, composited);
   if (p.act != nullptr && hf) { set_error("mlp_forward(train): fp16 is a render-only mode"); return DN_E_UNSUPPORTED; }
   if (p.act != nullptr && p.save8) {   // training forward with 8-bit saved units: a kernel of the 48-point geometry (mlp_fused48.hip)
     if (!bf || p.mode == 2 || !g48_train_supported(d) || p.n_points >= (1LL << 31) - 1024) {
       set_error("mlp_forward(train, 8-bit saved tensors): bf16 arithmetic, rays / points input, W in {128, 256}, L_xyz in {6, 10}, a depth the 48-point kernel holds in LDS");
       return DN_E_UNSUPPORTED;
     }
-    return launch_forward48(d, precision, p, p.packed + p.bias_bytes + static_cast<size_t>(p.total_pieces) * kPieceBytes, stream);
+    return launch_forward48(d, precision, p, region48, stream);
   }
   // one instance per row of DN_FWD32_INSTANCES (mlp_fused_kernel.h): training forward (bf16 / fp32) of the L_xyz in {10, 6} nets
   // (L_xyz = 6: the forward-facing nets of the reference's LLFF configs; the saved xyz panel's slots past 3 + 6 L are zeros), fp16
@@ -161,8 +138,6 @@ int dispatch_forward(const dn_mlp_desc& d, int precision, FwdParams& p, hipStrea
   return DN_E_UNSUPPORTED;
 }
 
-void fill_freqs(float* f, int num_fns, int log_sampling);  // rays_sampling.hip
-
 int setup_params(const dn_mlp_desc* desc, int precision, const void* packed, FwdParams* p) {
   int rc = validate_desc(desc, precision);
   if (rc) return rc;
@@ -181,22 +156,12 @@ int setup_params(const dn_mlp_desc* desc, int precision, const void* packed, Fwd
 }
 
 int launch_pack(const NetLayout& L, const PackPtrs& ptrs, void* packed, int precision, hipStream_t stream, bool density) {
-  if (density) {
-    if (precision == DN_PREC_BF16)
-      hipLaunchKernelGGL((pack_kernel<1, 1>), dim3(512), dim3(256), 0, stream, L, ptrs, static_cast<char*>(packed));
-    else if (precision == DN_PREC_F16)
-      hipLaunchKernelGGL((pack_kernel<2, 1>), dim3(512), dim3(256), 0, stream, L, ptrs, static_cast<char*>(packed));
-    else
-      hipLaunchKernelGGL((pack_kernel<0, 1>), dim3(512), dim3(256), 0, stream, L, ptrs, static_cast<char*>(packed));
-    return check_launch("mlp_pack_density");
-  }
-  if (precision == DN_PREC_BF16)
-    hipLaunchKernelGGL(pack_kernel<1>, dim3(512), dim3(256), 0, stream, L, ptrs, static_cast<char*>(packed));
-  else if (precision == DN_PREC_F16)
-    hipLaunchKernelGGL(pack_kernel<2>, dim3(512), dim3(256), 0, stream, L, ptrs, static_cast<char*>(packed));
-  else
-    hipLaunchKernelGGL(pack_kernel<0>, dim3(512), dim3(256), 0, stream, L, ptrs, static_cast<char*>(packed));
-  return check_launch("mlp_pack");
+  with_prec<true>(precision, [&](auto f) {
+    constexpr int F = decltype(f)::value;
+    auto kern = density ? pack_kernel<F, 1> : pack_kernel<F, 0>;
+    hipLaunchKernelGGL(kern, dim3(512), dim3(256), 0, stream, L, ptrs, static_cast<char*>(packed));
+  });
+  return check_launch(density ? "mlp_pack_density" : "mlp_pack");
 }
 
 }  // namespace dn
@@ -207,13 +172,15 @@ extern "C" size_t dn_mlp_packed_bytes(const dn_mlp_desc* desc, int precision) {
   if (validate_desc(desc, precision)) return 0;
   NetLayout L;
   build_layout(*desc, precision, &L);
-  return static_cast<size_t>(L.bias_bytes) + static_cast<size_t>(L.total_pieces) * kPieceBytes +
-         (g48_supported(*desc, precision) ? g48_region_bytes(*desc) : 0);
+  return core_stream_bytes(L.bias_bytes, L.total_pieces) + (g48_supported(*desc, precision) ? g48_region_bytes(*desc) : 0);
 }
 
 extern "C" int dn_fp16_range_guard(const dn_mlp_desc* desc) {
   if (validate_desc(desc, DN_PREC_F16)) return 0;
-  return (std::getenv("DEXNERF_G48_RUNTIME_SHAPE") == nullptr && std::getenv("DEXNERF_BF16_GEOM") == nullptr && g48_range_guard_complete(*desc)) ? 1 : 0;
+  // 1 when an fp16 launch of this network reports EVERY hidden activation that leaves fp16's range (FwdParams::range_flag).
+  // DEXNERF_BF16_GEOM in its wider reading: set to ANYTHING answers 0, although only 32 moves the dispatch (Switches)
+  const Switches sw = read_switches();
+  return (!sw.runtime_shape && !sw.geom_set && g48_supported(*desc, DN_PREC_F16) && g48_shape(*desc).range_guard_complete()) ? 1 : 0;
 }
 
 extern "C" int dn_mlp_pack(const dn_mlp_desc* desc, int precision, const float* const* h_weights,
@@ -230,17 +197,11 @@ extern "C" int dn_mlp_pack_parts(const dn_mlp_desc* desc, int precision, const f
   DN_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 15) == 0, "dn_mlp_pack: packed buffer must be 16-byte aligned");
   NetLayout L;
   build_layout(*desc, precision, &L);
-  const int n_params = desc->num_layers + (desc->use_viewdirs ? 4 : 1);
-  PackPtrs ptrs{};
-  for (int i = 0; i < n_params; ++i) {
-    DN_REQUIRE(h_weights[i] && h_biases[i], "dn_mlp_pack: parameter %d is NULL", i);
-    ptrs.w[i] = h_weights[i];
-    ptrs.b[i] = h_biases[i];
-  }
+  PackPtrs ptrs;
+  if ((rc = collect_pack_ptrs("dn_mlp_pack", *desc, h_weights, h_biases, &ptrs))) return rc;
   if (parts & DN_PACK_CORE) rc = launch_pack(L, ptrs, packed, precision, as_stream(stream));
   if (rc == 0 && (parts & DN_PACK_G48) && g48_supported(*desc, precision))
-    rc = launch_pack48(*desc, precision, ptrs, static_cast<char*>(packed) + L.bias_bytes + static_cast<size_t>(L.total_pieces) * kPieceBytes,
-                       as_stream(stream));
+    rc = launch_pack48(*desc, precision, ptrs, static_cast<char*>(packed) + core_stream_bytes(L.bias_bytes, L.total_pieces), as_stream(stream));
   return rc;
 }
 
@@ -270,19 +231,14 @@ extern "C" int dn_mlp_pack_density(const dn_mlp_desc* full, int precision, const
   NetLayout L;
   build_layout(d, precision, &L);
   const int D = full->num_layers;
-  PackPtrs ptrs{};
-  for (int i = 0; i < D; ++i) {   // layer1 + the trunk
-    DN_REQUIRE(h_weights[i] && h_biases[i], "dn_mlp_pack_density: parameter %d is NULL", i);
-    ptrs.w[i] = h_weights[i];
-    ptrs.b[i] = h_biases[i];
-  }
+  PackPtrs ptrs;
+  if ((rc = collect_pack_ptrs("dn_mlp_pack_density", *full, h_weights, h_biases, &ptrs, D))) return rc;   // layer1 + the trunk
   DN_REQUIRE(h_weights[D + 1] && h_biases[D + 1], "dn_mlp_pack_density: fc_alpha is NULL");
   ptrs.w[D] = h_weights[D + 1];   // the head stage's source: fc_alpha (pack_kernel, DENS)
   ptrs.b[D] = h_biases[D + 1];
   rc = launch_pack(L, ptrs, packed, precision, as_stream(stream), true);
   if (rc == 0 && g48_supported(d, precision))
-    rc = launch_pack48(d, precision, ptrs, static_cast<char*>(packed) + L.bias_bytes + static_cast<size_t>(L.total_pieces) * kPieceBytes,
-                       as_stream(stream), true);
+    rc = launch_pack48(d, precision, ptrs, static_cast<char*>(packed) + core_stream_bytes(L.bias_bytes, L.total_pieces), as_stream(stream), true);
   return rc;
 }
 
@@ -305,16 +261,7 @@ int dn::run_network_flagged(const dn_mlp_desc* desc, int precision, const void* 
   if (n_rays == 0) return 0;
   DN_REQUIRE(packed && out && n_rays >= 0 && samples_per_ray >= 1, "dn_run_network: bad arguments");
   DN_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0, "dn_run_network: out must be 16-byte aligned");
-  if (pts != nullptr) {
-    DN_REQUIRE(!desc->use_viewdirs || viewdirs, "dn_run_network: viewdirs required with use_viewdirs");
-    p.mode = 1; p.pts = pts; p.viewdirs = viewdirs;
-  } else {
-    DN_REQUIRE(rays && z_vals, "dn_run_network: need pts, or rays + z_vals");
-    DN_REQUIRE(ray_stride >= (desc->use_viewdirs ? 11 : 8), "dn_run_network: ray_stride too small");
-    p.mode = 0; p.rays = rays; p.ray_stride = ray_stride; p.z = z_vals;
-  }
-  p.n_points = n_rays * samples_per_ray;
-  p.S = samples_per_ray;
+  if ((rc = set_point_inputs("dn_run_network", *desc, pts, viewdirs, rays, ray_stride, z_vals, n_rays, samples_per_ray, &p))) return rc;
   p.out = out;
   p.range_flag = range_flag;
   if (p.n_points == 0) return 0;

@@ -3,9 +3,4 @@
 // Same template, compiled here under a name of its own.
 #define mlp_forward48_kernel mlp_forward_density48_kernel
 #include "mlp_fused48_kernel.h"
-
-namespace dn {
-
-DN_FWD48_DENSITY(DN_FWD48_INSTANTIATE)
-
-}  // namespace dn
+namespace dn { DN_FWD48_DENSITY(DN_FWD48_INSTANTIATE) }

@@ -804,7 +804,7 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
 }
 
 // ---- the instances: one row each, X(W, F, DC, MASKC, VIEWC, SAVE, OVLP, COMP), all eight template arguments --------------------
-// One sub-list per translation unit; DN_FWD48_INSTANCES is the whole family.  mlp_fused48.hip launch_forward48 picks among them.
+// One sub-list per translation unit; DN_FWD48_INSTANCES is the whole family.  mlp_geo48.h g48_pick picks among them.
 #define DN_FWD48_PAPER_BF16(X) /* mlp_fused48_paper_bf16.hip: the explicit-schedule bf16 instances of the paper network */ \
   X(256, 1, 8, 0x10u, 1, 0, 2, 0) X(256, 1, 8, 0x10u, 1, 0, 0, 0)
 #define DN_FWD48_PAPER_FP16(X) /* mlp_fused48_paper_fp16.hip: the same in fp16 */ \
@@ -815,11 +815,14 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
   X(128, 1, 4, 0u, 1, 0, 1, 0) X(128, 2, 4, 0u, 1, 0, 1, 0) /* ... encoding tile t + 1 inside tile t */ \
   X(128, 1, 4, 0u, 1, 0, 0, 1) X(128, 2, 4, 0u, 1, 0, 0, 1) /* ... compositing in the kernel */ \
   X(128, 1, 4, 0u, 1, 2, 0, 0) X(128, 1, 4, 0u, 1, 3, 0, 0) X(128, 1, 0, 0u, 0, 2, 0, 0) /* training forward */
-#define DN_FWD48_HOST_UNIT(X) /* mlp_fused48.hip: the remaining W = 256 instances */ \
-  X(256, 1, 0, 0u, 0, 0, 0, 0) X(256, 2, 0, 0u, 0, 0, 0, 0)       /* run-time shape */ \
-  X(256, 1, 8, 0x10u, 1, 0, 0, 1) X(256, 2, 8, 0x10u, 1, 0, 0, 1) /* paper network, compositing in the kernel */ \
-  X(256, 1, 8, 0x10u, 1, 2, 0, 0) X(256, 1, 8, 0x10u, 1, 3, 0, 0) X(256, 1, 0, 0u, 0, 2, 0, 0) /* training forward */
-#define DN_FWD48_INSTANCES(X) DN_FWD48_PAPER_BF16(X) DN_FWD48_PAPER_FP16(X) DN_FWD48_W128(X) DN_FWD48_HOST_UNIT(X)
+#define DN_FWD48_W256_RT(X) /* mlp_fused48_w256_rt.hip: the run-time-shape W = 256 instances, inference and training forward */ \
+  X(256, 1, 0, 0u, 0, 0, 0, 0) X(256, 2, 0, 0u, 0, 0, 0, 0) X(256, 1, 0, 0u, 0, 2, 0, 0)
+#define DN_FWD48_PAPER_COMP(X) /* mlp_fused48_paper_comp.hip: the paper network, compositing in the kernel */ \
+  X(256, 1, 8, 0x10u, 1, 0, 0, 1) X(256, 2, 8, 0x10u, 1, 0, 0, 1)
+#define DN_FWD48_PAPER_TRAIN(X) /* mlp_fused48_paper_train.hip: the paper network's training forward on three / two point groups */ \
+  X(256, 1, 8, 0x10u, 1, 2, 0, 0) X(256, 1, 8, 0x10u, 1, 3, 0, 0)
+#define DN_FWD48_INSTANCES(X) \
+  DN_FWD48_PAPER_BF16(X) DN_FWD48_PAPER_FP16(X) DN_FWD48_W128(X) DN_FWD48_W256_RT(X) DN_FWD48_PAPER_COMP(X) DN_FWD48_PAPER_TRAIN(X)
 // mlp_fused48_density.hip: the fixed-shape NO-view-direction instances - trunk + 4-row head, what dn_mlp_pack_density packs (the
 // density sub-network of the paper and the as-shipped nets) and any plain no-view-direction net of those two shapes.  That unit
 // compiles this template under the name mlp_forward_density48_kernel: tests/test_asm_hazards.py pins the number of kernels named

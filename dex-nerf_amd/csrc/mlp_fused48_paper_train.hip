@@ -1,0 +1,3 @@
+// The training-forward instances of the paper network of the 48-point forward kernel (mlp_fused48_kernel.h: DN_FWD48_PAPER_TRAIN).
+#include "mlp_fused48_kernel.h"
+namespace dn { DN_FWD48_PAPER_TRAIN(DN_FWD48_INSTANTIATE) }

@@ -119,10 +119,59 @@ inline unsigned pack48_blocks(const NetLayout& L) {
 inline size_t g48_region_bytes(const dn_mlp_desc& d) {
   NetLayout L;
   build_layout48(d, &L);
-  return static_cast<size_t>(L.bias_bytes) + kG48TableBytes + static_cast<size_t>(L.total_pieces) * kPieceBytes;
+  return core_stream_bytes(L.bias_bytes, L.total_pieces) + kG48TableBytes;
 }
 
-bool g48_range_guard_complete(const dn_mlp_desc& d);
+// ---- the developer switches of the network host layer, read per call (tests and probes flip them inside one process) ---------
+// The one place that names them.  Each keeps its own comparison rule; DEXNERF_BF16_GEOM has two readings, both kept.
+struct Switches {
+  bool geom32;            // DEXNERF_BF16_GEOM, atoi == 32: dispatch_forward keeps the 32-point kernels
+  bool geom_set;          // DEXNERF_BF16_GEOM set to anything: dn_fp16_range_guard then answers 0 (its second, wider reading)
+  bool runtime_shape;     // DEXNERF_G48_RUNTIME_SHAPE set: no fixed-shape instance
+  bool no_overlap;        // DEXNERF_G48_NO_OVERLAP set: no instance that encodes tile t + 1 inside tile t
+  int train_groups;       // DEXNERF_G48_TRAIN_GROUPS = 2 | 3: point groups per wave of the training launches; anything else: 0 = by size
+  bool fused_composite;   // DEXNERF_FUSED_COMPOSITE, atoi == 1: in-kernel compositing (off by default: launch_forward48)
+  bool s8_absmax_kernel;  // DEXNERF_S8_ABSMAX_KERNEL set: the absmax launch of its own (api.cpp reads this one itself)
+};
+inline Switches read_switches() {
+  auto set = [](const char* name) { return std::getenv(name) != nullptr; };
+  auto num = [](const char* name) { const char* e = std::getenv(name); return e ? std::atoi(e) : 0; };
+  const int groups = num("DEXNERF_G48_TRAIN_GROUPS");
+  return Switches{num("DEXNERF_BF16_GEOM") == 32, set("DEXNERF_BF16_GEOM"), set("DEXNERF_G48_RUNTIME_SHAPE"), set("DEXNERF_G48_NO_OVERLAP"),
+                  (groups == 2 || groups == 3) ? groups : 0, num("DEXNERF_FUSED_COMPOSITE") == 1, set("DEXNERF_S8_ABSMAX_KERNEL")};
+}
+
+// ---- which fixed shape a network is: the one classification; each consumer's rule is one named expression on it ----------------
+struct G48Shape {
+  int W, D;
+  bool paper_trunk;     // W 256, D 8, skip mask 0x10 (BASELINE configs 2, 4, 5)
+  bool shipped_trunk;   // W 128, D 4, no skip (the fork's as-shipped nets, config 3)
+  bool viewdirs;
+  // forward: the fixed-shape instances are built with the view-direction head ...
+  bool fwd_paper() const { return paper_trunk && viewdirs; }
+  bool fwd_shipped() const { return shipped_trunk && viewdirs; }
+  // ... and the density instances (mlp_forward_density48_kernel) are the same two trunks with the 4-row head instead
+  bool density_fixed() const { return (paper_trunk || shipped_trunk) && !viewdirs; }
+  // training on two point groups per wave: only the fixed forward shapes have such instances (SAVE = 3, PTC = 2)
+  bool two_group(const Switches& sw) const { return (fwd_paper() || fwd_shipped()) && !sw.runtime_shape; }
+  // fp16 range flag covers every hidden activation: in both paper instances (view directions or not) and in EVERY W = 128
+  // instance, the run-time-shape one included; the run-time-shape W = 256 instance tracks only the head stages
+  bool range_guard_complete() const { return paper_trunk || W == 128; }
+  // backward-data chain: no skip mask in the rule - the chain reads only the W-wide hidden block of a wide layer, so one fixed
+  // instance serves every skip pattern of its (W, D)
+  bool bwd_paper() const { return W == 256 && D == 8 && viewdirs; }
+  bool bwd_shipped() const { return W == 128 && D == 4 && viewdirs; }
+};
+inline G48Shape g48_shape(const dn_mlp_desc& d) {
+  NetLayout L;
+  build_layout48(d, &L);
+  G48Shape sh{};
+  sh.W = d.hidden_size; sh.D = d.num_layers; sh.viewdirs = d.use_viewdirs != 0;
+  sh.paper_trunk = sh.W == 256 && sh.D == 8 && L.skip_mask == 0x10u;
+  sh.shipped_trunk = sh.W == 128 && sh.D == 4 && L.skip_mask == 0u;
+  return sh;
+}
+
 // ---- training in the 48-point geometry: the 8-bit saved tensors of DN_PREC_BF16_S8 ("s8-48" layout) ------------------------
 // A wave's 48 points are three 16-point groups; groups are numbered along the point sequence (group G = point / 16) and two
 // consecutive groups form one 32-point record T = G / 2 - the unit of the weight-gradient kernel's K = 64 contraction.
@@ -200,19 +249,8 @@ inline long long g48_mask_wave_tiles(long long n_points) {
 // tile-rounds x points: launches of a few hundred tiles, where 384-point tiles leave units idle or make a short last round (a 1024-ray
 // step of the as-shipped nets: 171 and 342 tiles on 256 units -> 256 and 512 tiles of two thirds the work).  Forward and backward
 // of a launch must agree (the mask words are per wave tile): both call this.  DEXNERF_G48_TRAIN_GROUPS=2|3 (read per call) forces one.
-// (only the two fixed shapes have two-group instances: the paper network and the as-shipped 4 x 128 nets, as mlp_fused48.hip knows them)
-inline bool g48_two_group_shape(const dn_mlp_desc& d) {
-  NetLayout L;
-  build_layout48(d, &L);
-  const bool paper = d.hidden_size == 256 && d.num_layers == 8 && L.skip_mask == 0x10u && d.use_viewdirs;
-  const bool shipped = d.hidden_size == 128 && d.num_layers == 4 && L.skip_mask == 0u && d.use_viewdirs;
-  return (paper || shipped) && std::getenv("DEXNERF_G48_RUNTIME_SHAPE") == nullptr;
-}
-inline int g48_train_groups(long long n_points, int cus) {
-  if (const char* e = std::getenv("DEXNERF_G48_TRAIN_GROUPS")) {
-    const int v = std::atoi(e);
-    if (v == 2 || v == 3) return v;
-  }
+inline int g48_train_groups(long long n_points, int cus, const Switches& sw) {
+  if (sw.train_groups) return sw.train_groups;
   if (cus < 1) cus = 1;
   const long long t3 = (n_points + 383) / 384, t2 = (n_points + 255) / 256;
   const long long c3 = (t3 + cus - 1) / cus * 3, c2 = (t2 + cus - 1) / cus * 2;
@@ -267,7 +305,54 @@ inline int build_backward_layout48(const dn_mlp_desc& d, NetLayout* out) {
   return 0;
 }
 
-int launch_pack48(const dn_mlp_desc& d, int precision, const PackPtrs& ptrs, char* region, hipStream_t stream, bool density = false);
+// ---- instance selection of the 48-point forward: a row of DN_FWD48_INSTANCES / DN_FWD48_DENSITY (mlp_fused48_kernel.h) ----------
+struct G48Key {   // the eight template arguments of mlp_forward48_kernel
+  int W, F, DC;
+  unsigned MASKC;
+  int VIEWC, SAVE, OVLP, COMP;
+  bool operator==(const G48Key& o) const {
+    return W == o.W && F == o.F && DC == o.DC && MASKC == o.MASKC && VIEWC == o.VIEWC && SAVE == o.SAVE && OVLP == o.OVLP && COMP == o.COMP;
+  }
+};
+struct G48Pick {
+  G48Key key;
+  bool density;          // a row of DN_FWD48_DENSITY (mlp_forward_density48_kernel)
+  const char* refusal;   // not NULL: no instance (DN_E_UNSUPPORTED), with this text
+};
+// Pure: no launch, no device query.  Order of precedence: training, the density pair, self-compositing, overlapped encoding, plain
+// fixed shape, run-time shape.  What the launch derives from the key: SAVE = 3 runs 256-point tiles, OVLP = 1 takes a third set of
+// view-direction rows in LDS, COMP = 1 composites its rays (*composited).
+inline G48Pick g48_pick(const dn_mlp_desc& d, int precision, const FwdParams& p, const CompParams* comp, int cus, const Switches& sw) {
+  const G48Shape sh = g48_shape(d);
+  const bool paper = sh.fwd_paper() && !sw.runtime_shape, shipped = sh.fwd_shipped() && !sw.runtime_shape;
+  const int F = precision == DN_PREC_F16 ? 2 : 1;
+  auto fixed = [&](int save, int ovlp, int cmp) {
+    return G48Pick{paper ? G48Key{256, F, 8, 0x10u, 1, save, ovlp, cmp} : G48Key{128, F, 4, 0u, 1, save, ovlp, cmp}, false, nullptr};
+  };
+  auto run_time = [&](int save) { return G48Pick{G48Key{sh.W == 256 ? 256 : 128, F, 0, 0u, 0, save, 0, 0}, false, nullptr}; };
+  if (p.act != nullptr) {   // training forward (DN_PREC_BF16_S8): saved units + mask words
+    if (precision != DN_PREC_BF16 || !p.save8)
+      return G48Pick{G48Key{}, false, "mlp_forward48(train): the 48-point training forward is the bf16 / 8-bit-saved-tensor mode"};
+    // small launch: 256-point tiles (the backward asks the same question: launch_backward48)
+    if (sh.two_group(sw) && g48_train_groups(p.n_points, cus, sw) == 2) return fixed(3, 0, 0);
+    return (paper || shipped) ? fixed(2, 0, 0) : run_time(2);
+  }
+  // the same two trunks without view directions - the density sub-network (dn_mlp_pack_density): straight-line trunk + fc_out head
+  if (sh.density_fixed() && !sw.runtime_shape)
+    return G48Pick{sh.paper_trunk ? G48Key{256, F, 8, 0x10u, 0, 0, 0, 0} : G48Key{128, F, 4, 0u, 0, 0, 0, 0}, true, nullptr};
+  // a render that asked for its rays to be composited by the launch itself (dn_render_rays): whole rays per 384-point tile
+  if (comp != nullptr && comp->rgb != nullptr && (paper || shipped) && p.mode == 0 && p.S >= 1 && kG48PointsPerWg % p.S == 0 &&
+      comp->n_rays * p.S == p.n_points && sw.fused_composite)
+    return fixed(0, 0, 1);
+  // rays + depths (the render path): the as-shipped nets encode tile t + 1 inside tile t (OVLP = 1), the paper network tile t + 1's
+  // xyz encoding inside tile t's view-direction stage (OVLP = 2)
+  if ((paper || shipped) && p.mode == 0 && !sw.no_overlap) return fixed(0, shipped ? 1 : 2, 0);
+  return (paper || shipped) ? fixed(0, 0, 0) : run_time(0);
+}
+
+// b != NULL: two networks of one architecture (bf16; the coarse and the fine net of a training step) in one launch
+int launch_pack48(const dn_mlp_desc& d, int precision, const PackPtrs& a, char* region_a, hipStream_t stream, bool density = false,
+                  const PackPtrs* b = nullptr, char* region_b = nullptr);
 // comp != NULL: the caller would like the launch to composite its rays itself (rays + depths input, no density noise); *composited
 // says whether it did (the fixed-shape instances, samples per ray dividing the 384-point workgroup tile) - if not, `out` holds the
 // raw radiance field as always and the caller runs the compositing kernel
@@ -277,8 +362,7 @@ int backward48_entry(const dn_mlp_desc* desc, const void* packed_bwd, const floa
                      void* grads, float grad_scale, hipStream_t stream, const unsigned* partials = nullptr, int n_partials = 0);   // mlp_train48.hip
 int unpack48_entry(const dn_mlp_desc* desc, int which, const void* native, int64_t n_points, int slot, int width, int kind, float* out,
                    int ld_out, int col0, hipStream_t stream);                             // mlp_train48.hip
-int launch_pack48_pair(const dn_mlp_desc& d, const PackPtrs& a, const PackPtrs& b, char* region_a, char* region_b, hipStream_t stream);
-int launch_pack48_backward_pair(const dn_mlp_desc& d, const PackPtrs& a, const PackPtrs& b, char* packed_a, char* packed_b, hipStream_t stream);
-int launch_pack48_backward(const dn_mlp_desc& d, const PackPtrs& ptrs, char* packed, hipStream_t stream);   // mlp_train48.hip
+int launch_pack48_backward(const dn_mlp_desc& d, const PackPtrs& a, char* packed_a, hipStream_t stream, const PackPtrs* b = nullptr,
+                           char* packed_b = nullptr);   // mlp_train48.hip; b != NULL: the pair launch
 
 }  // namespace dn

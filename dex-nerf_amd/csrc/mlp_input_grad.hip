@@ -303,9 +303,7 @@ static int launch_input_grad(IgParams p, hipStream_t stream) {
   if (lds > 64 * 1024) {
     if (int rc = ensure_big_lds(reinterpret_cast<const void*>(kern))) return rc;
   }
-  const int cus = device_cus();
-  const long long grid = p.n_wg_tiles < cus ? p.n_wg_tiles : cus;
-  hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(kIgWaves * 64), lds, stream, p);
+  hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(persistent_grid(p.n_wg_tiles))), dim3(kIgWaves * 64), lds, stream, p);
   return check_launch("mlp_input_grad");
 }
 
@@ -347,13 +345,8 @@ extern "C" int dn_mlp_pack_input_grad(const dn_mlp_desc* desc, int precision, co
   int rc = validate_input_grad(desc, precision, "dn_mlp_pack_input_grad");
   if (rc) return rc;
   DN_REQUIRE(h_weights && packed, "dn_mlp_pack_input_grad: NULL pointer");
-  const int n_params = desc->num_layers + (desc->use_viewdirs ? 4 : 1);
-  PackPtrs ptrs{};
-  for (int i = 0; i < n_params; ++i) {
-    DN_REQUIRE(h_weights[i], "dn_mlp_pack_input_grad: parameter %d is NULL", i);
-    ptrs.w[i] = h_weights[i];
-    ptrs.b[i] = h_weights[i];   // unused (no bias in this stream)
-  }
+  PackPtrs ptrs;
+  if ((rc = collect_pack_ptrs("dn_mlp_pack_input_grad", *desc, h_weights, nullptr, &ptrs))) return rc;
   IgLayout g;
   build_input_grad_layout(*desc, precision, &g);
   if (precision == DN_PREC_BF16)

@@ -273,9 +273,7 @@ static int launch_backward(BwdParams p, hipStream_t stream) {
   constexpr int WAVES = waves_of<BF16, 1>();
   p.n_tiles = (p.n_points + WAVES * 32 - 1) / (WAVES * 32);
   if (int rc = ensure_big_lds(reinterpret_cast<const void*>(kern))) return rc;
-  const int cus = device_cus();
-  const long long grid = p.n_tiles < cus ? p.n_tiles : cus;
-  hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(WAVES * 64), kRingBytes + WAVES * kBwdWaveLds, stream, p);
+  hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(persistent_grid(p.n_tiles))), dim3(WAVES * 64), kRingBytes + WAVES * kBwdWaveLds, stream, p);
   return check_launch("mlp_backward");
 }
 
@@ -291,8 +289,7 @@ using namespace dn;
 
 extern "C" int dn_mlp_train_sizes(const dn_mlp_desc* desc, int precision, int64_t n_points, size_t* act_bytes,
                                   size_t* mask_bytes, size_t* grad_bytes) {
-  const bool s8 = precision == DN_PREC_BF16_S8;
-  if (s8) precision = DN_PREC_BF16;
+  const bool s8 = split_precision(&precision);
   int rc = validate_desc(desc, precision);
   if (rc) return rc;
   DN_REQUIRE(precision != DN_PREC_F16, "training kernels exist for fp32 and bf16 (fp16 is a render-only mode)");
@@ -338,18 +335,12 @@ extern "C" size_t dn_mlp_backward_packed_bytes(const dn_mlp_desc* desc, int prec
 
 extern "C" int dn_mlp_pack_backward(const dn_mlp_desc* desc, int precision, const float* const* h_weights, void* packed,
                                     dn_stream_t stream) {
-  const bool s8 = precision == DN_PREC_BF16_S8;
-  if (s8) precision = DN_PREC_BF16;
+  const bool s8 = split_precision(&precision);
   int rc = validate_desc(desc, precision);
   if (rc) return rc;
   DN_REQUIRE(h_weights && packed, "dn_mlp_pack_backward: NULL pointer");
-  const int n_params = desc->num_layers + (desc->use_viewdirs ? 4 : 1);
-  PackPtrs ptrs{};
-  for (int i = 0; i < n_params; ++i) {
-    DN_REQUIRE(h_weights[i], "dn_mlp_pack_backward: parameter %d is NULL", i);
-    ptrs.w[i] = h_weights[i];
-    ptrs.b[i] = h_weights[i];  // unused (no bias tiles in the backward stream)
-  }
+  PackPtrs ptrs;
+  if ((rc = collect_pack_ptrs("dn_mlp_pack_backward", *desc, h_weights, nullptr, &ptrs))) return rc;
   if (s8) {
     DN_REQUIRE(g48_train_supported(*desc), "dn_mlp_pack_backward: no 8-bit-saved-tensor training kernels for this network");
     return launch_pack48_backward(*desc, ptrs, static_cast<char*>(packed), as_stream(stream));
@@ -369,42 +360,28 @@ extern "C" int dn_mlp_pack_train_pair(const dn_mlp_desc* desc, const float* cons
   DN_REQUIRE(g48_train_supported(*desc), "dn_mlp_pack_train_pair: no 8-bit-saved-tensor training kernels for this network");
   DN_REQUIRE(h_weights_a && h_biases_a && packed_a && packed_bwd_a && h_weights_b && h_biases_b && packed_b && packed_bwd_b,
              "dn_mlp_pack_train_pair: NULL pointer");
-  const int n_params = desc->num_layers + (desc->use_viewdirs ? 4 : 1);
-  PackPtrs a{}, b{};
-  for (int i = 0; i < n_params; ++i) {
-    DN_REQUIRE(h_weights_a[i] && h_biases_a[i] && h_weights_b[i] && h_biases_b[i], "dn_mlp_pack_train_pair: parameter %d is NULL", i);
-    a.w[i] = h_weights_a[i]; a.b[i] = h_biases_a[i];
-    b.w[i] = h_weights_b[i]; b.b[i] = h_biases_b[i];
-  }
+  PackPtrs a, b;
+  if ((rc = collect_pack_ptrs("dn_mlp_pack_train_pair", *desc, h_weights_a, h_biases_a, &a))) return rc;
+  if ((rc = collect_pack_ptrs("dn_mlp_pack_train_pair", *desc, h_weights_b, h_biases_b, &b))) return rc;
   NetLayout L;
   build_layout(*desc, DN_PREC_BF16, &L);   // the 48-point region starts behind the core stream
-  const size_t core = static_cast<size_t>(L.bias_bytes) + static_cast<size_t>(L.total_pieces) * kPieceBytes;
-  if ((rc = launch_pack48_pair(*desc, a, b, static_cast<char*>(packed_a) + core, static_cast<char*>(packed_b) + core, as_stream(stream)))) return rc;
-  return launch_pack48_backward_pair(*desc, a, b, static_cast<char*>(packed_bwd_a), static_cast<char*>(packed_bwd_b), as_stream(stream));
+  const size_t core = core_stream_bytes(L.bias_bytes, L.total_pieces);
+  if ((rc = launch_pack48(*desc, DN_PREC_BF16, a, static_cast<char*>(packed_a) + core, as_stream(stream), false, &b, static_cast<char*>(packed_b) + core))) return rc;
+  return launch_pack48_backward(*desc, a, static_cast<char*>(packed_bwd_a), as_stream(stream), &b, static_cast<char*>(packed_bwd_b));
 }
 
 extern "C" int dn_run_network_train(const dn_mlp_desc* desc, int precision, const void* packed, const float* pts,
                                     const float* viewdirs, const float* rays, int ray_stride, const float* z_vals,
                                     int64_t n_rays, int samples_per_ray, float* out, void* act, void* masks,
                                     dn_stream_t stream) {
-  const bool s8 = precision == DN_PREC_BF16_S8;
-  if (s8) precision = DN_PREC_BF16;
+  const bool s8 = split_precision(&precision);
   FwdParams p;
   int rc = setup_params(desc, precision, packed, &p);
   if (rc) return rc;
   DN_REQUIRE(packed && out && act && masks && n_rays >= 0 && samples_per_ray >= 1, "dn_run_network_train: bad arguments");
   DN_REQUIRE(((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(act) | reinterpret_cast<uintptr_t>(masks)) & 15) == 0,
              "dn_run_network_train: buffers must be 16-byte aligned");
-  if (pts != nullptr) {
-    DN_REQUIRE(!desc->use_viewdirs || viewdirs, "dn_run_network_train: viewdirs required with use_viewdirs");
-    p.mode = 1; p.pts = pts; p.viewdirs = viewdirs;
-  } else {
-    DN_REQUIRE(rays && z_vals, "dn_run_network_train: need pts, or rays + z_vals");
-    DN_REQUIRE(ray_stride >= (desc->use_viewdirs ? 11 : 8), "dn_run_network_train: ray_stride too small");
-    p.mode = 0; p.rays = rays; p.ray_stride = ray_stride; p.z = z_vals;
-  }
-  p.n_points = n_rays * samples_per_ray;
-  p.S = samples_per_ray;
+  if ((rc = set_point_inputs("dn_run_network_train", *desc, pts, viewdirs, rays, ray_stride, z_vals, n_rays, samples_per_ray, &p))) return rc;
   p.out = out;
   p.act = static_cast<char*>(act);
   p.masks = static_cast<char*>(masks);
@@ -413,15 +390,13 @@ extern "C" int dn_run_network_train(const dn_mlp_desc* desc, int precision, cons
     TrainLayout48 t8;
     build_train_layout48(*desc, &t8);
     p.act_pieces = t8.act_units; p.mask_words = t8.mask_stages;
-    p.slot_xyz = t8.slot_xyz; p.slot_dir = t8.slot_dir; p.slot_layer1 = t8.slot_layer1; p.slot_trunk0 = t8.slot_trunk0;
-    p.slot_feat = t8.slot_feat; p.slot_dirout = t8.slot_dirout;
+    copy_act_slots(t8, &p);
     p.save8 = 1;
   } else {
     TrainLayout t;
     build_train_layout(*desc, precision, &t);
     p.act_pieces = t.act_pieces; p.mask_words = t.mask_words;
-    p.slot_xyz = t.slot_xyz; p.slot_dir = t.slot_dir; p.slot_layer1 = t.slot_layer1; p.slot_trunk0 = t.slot_trunk0;
-    p.slot_feat = t.slot_feat; p.slot_dirout = t.slot_dirout;
+    copy_act_slots(t, &p);
   }
   if (p.n_points == 0) return 0;
   return dispatch_forward(*desc, precision, p, as_stream(stream));
@@ -436,8 +411,7 @@ bool dn::s8_scale_is_per_launch() { return g_s8_grad_scale.load() == 0.0f; }
 
 int dn::mlp_backward_data_partials(const dn_mlp_desc* desc, int precision, const void* packed_bwd, const float* g_out, const void* masks,
                                    int64_t n_points, void* grads, const unsigned* partials, int n_partials, dn_stream_t stream) {
-  const bool s8 = precision == DN_PREC_BF16_S8;
-  if (s8) precision = DN_PREC_BF16;
+  const bool s8 = split_precision(&precision);
   int rc = validate_desc(desc, precision);
   if (rc) return rc;
   DN_REQUIRE(precision != DN_PREC_F16, "dn_mlp_backward_data: fp16 is a render-only mode");
@@ -464,8 +438,7 @@ int dn::mlp_backward_data_partials(const dn_mlp_desc* desc, int precision, const
   p.n_points = n_points;
   p.grads = static_cast<char*>(grads);
   p.grad_pieces = t.grad_pieces;
-  p.gslot_dirout = t.gslot_dirout; p.gslot_feat = t.gslot_feat; p.gslot_trunk0 = t.gslot_trunk0; p.gslot_layer1 = t.gslot_layer1;
-  p.gslot_out = t.gslot_out;
+  copy_grad_slots(t, &p);
   const bool bf = precision == DN_PREC_BF16;
   if (desc->hidden_size == 256) return bf ? launch_backward<256, true>(p, as_stream(stream)) : launch_backward<256, false>(p, as_stream(stream));
   if (desc->hidden_size == 128) return bf ? launch_backward<128, true>(p, as_stream(stream)) : launch_backward<128, false>(p, as_stream(stream));

@@ -376,9 +376,7 @@ __device__ __forceinline__ void pack48_backward_body(const NetLayout& L, const P
     const int piece = static_cast<int>(idx / 512);
     const int i = lane & 15, g = lane >> 4;
     float v = 0.0f;
-    int s = 0;
-    while (s + 1 < L.n_stages && L.st[s + 1].piece0 <= piece) ++s;
-    const StageDesc& st = L.st[s];
+    const StageDesc& st = L.st[pack_stage_of_piece(L, piece)];
     const int rel = piece - st.piece0;
     if (rel < st.n_tiles * st.pieces_per_tile) {
       // A[row][k] = W[k][row]: k runs over the forward layer's outputs in accumulator order (hidden pieces), then over one
@@ -449,46 +447,41 @@ int unpack48_entry(const dn_mlp_desc* desc, int which, const void* native, int64
   return check_launch("dn_mlp_unpack");
 }
 
-int launch_pack48_backward(const dn_mlp_desc& d, const PackPtrs& ptrs, char* packed, hipStream_t stream) {
+int launch_pack48_backward(const dn_mlp_desc& d, const PackPtrs& a, char* packed_a, hipStream_t stream, const PackPtrs* b, char* packed_b) {
   NetLayout L;
   build_backward_layout48(d, &L);
-  hipLaunchKernelGGL(pack48_backward_kernel, dim3(pack48_blocks(L)), dim3(256), 0, stream, L, ptrs, packed);
-  return check_launch("mlp_pack48_backward");
+  const dim3 blocks(pack48_blocks(L), b ? 2 : 1);
+  if (b) hipLaunchKernelGGL(pack48_backward_pair_kernel, blocks, dim3(256), 0, stream, L, a, *b, packed_a, packed_b);
+  else hipLaunchKernelGGL(pack48_backward_kernel, blocks, dim3(256), 0, stream, L, a, packed_a);
+  return check_launch(b ? "mlp_pack48_backward_pair" : "mlp_pack48_backward");
 }
 
-int launch_pack48_backward_pair(const dn_mlp_desc& d, const PackPtrs& a, const PackPtrs& b, char* packed_a, char* packed_b, hipStream_t stream) {
-  NetLayout L;
-  build_backward_layout48(d, &L);
-  hipLaunchKernelGGL(pack48_backward_pair_kernel, dim3(pack48_blocks(L), 2), dim3(256), 0, stream, L, a, b, packed_a, packed_b);
-  return check_launch("mlp_pack48_backward_pair");
-}
-
+// the instances, X(W, DC, VIEWC, PTC): fixed shapes on two / three point groups, run-time shape.  The forward of the launch made the
+// same choice of point groups (mlp_geo48.h g48_pick)
+#define DN_BWD48_INSTANCES(X) X(256, 8, 1, 2) X(128, 4, 1, 2) X(256, 8, 1, 3) X(128, 4, 1, 3) X(256, 0, 0, 3) X(128, 0, 0, 3)
 int launch_backward48(const dn_mlp_desc& d, Bwd48Params p, hipStream_t stream) {
   NetLayout L;
   build_backward_layout48(d, &L);
   p.total_pieces = L.total_pieces;
-  p.n_tiles = static_cast<int>((p.n_points + kG48PointsPerWg - 1) / kG48PointsPerWg);
   const size_t lds = static_cast<size_t>(kRingBytes) + kG48Waves * kBwd48WaveLds;
   const int cus = device_cus();
-  int grid = p.n_tiles < cus ? p.n_tiles : cus;
+  const Switches sw = read_switches();
+  const G48Shape sh = g48_shape(d);
+  // a small launch whose forward ran on 256-point tiles (two point groups per wave), else 384-point tiles
+  const int groups = (sh.two_group(sw) && g48_train_groups(p.n_points, cus, sw) == 2) ? 2 : 3;
+  const bool fixed = groups == 2 || ((sh.bwd_paper() || sh.bwd_shipped()) && !sw.runtime_shape);
+  const int W = sh.W == 256 ? 256 : 128, DC = fixed ? (W == 256 ? 8 : 4) : 0;
+  p.n_tiles = static_cast<int>((p.n_points + groups * 128 - 1) / (groups * 128));
   auto launch = [&](auto kern) -> int {
     if (int rc = ensure_big_lds(reinterpret_cast<const void*>(kern))) return rc;
-    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(kG48Waves * 64), lds, stream, p);
+    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(persistent_grid(p.n_tiles, cus))), dim3(kG48Waves * 64), lds, stream, p);
     return check_launch("mlp_backward48");
   };
-  // a small launch whose forward ran on 256-point tiles (two point groups per wave: mlp_geo48.h - the same question, the same answer)
-  if (g48_two_group_shape(d) && g48_train_groups(p.n_points, cus) == 2) {
-    p.n_tiles = static_cast<int>((p.n_points + 255) / 256);
-    grid = p.n_tiles < cus ? p.n_tiles : cus;
-    if (d.hidden_size == 256) return launch(mlp_backward48_kernel<256, 8, 1, 2>);
-    return launch(mlp_backward48_kernel<128, 4, 1, 2>);
-  }
-  const bool paper = d.hidden_size == 256 && d.num_layers == 8 && d.use_viewdirs;
-  const bool shipped = d.hidden_size == 128 && d.num_layers == 4 && d.use_viewdirs;
-  const bool fixed_ok = std::getenv("DEXNERF_G48_RUNTIME_SHAPE") == nullptr;
-  if (paper && fixed_ok) return launch(mlp_backward48_kernel<256, 8, 1>);
-  if (shipped && fixed_ok) return launch(mlp_backward48_kernel<128, 4, 1>);
-  return d.hidden_size == 256 ? launch(mlp_backward48_kernel<256>) : launch(mlp_backward48_kernel<128>);
+#define DN_CASE(W_, DC_, VIEWC_, PTC_) if (W == W_ && DC == DC_ && groups == PTC_) return launch(mlp_backward48_kernel<W_, DC_, VIEWC_, PTC_>);
+  DN_BWD48_INSTANCES(DN_CASE)
+#undef DN_CASE
+  set_error("mlp_backward48: the picked instance is not in the list");
+  return DN_E_UNSUPPORTED;
 }
 
 }  // namespace dn
@@ -511,8 +504,7 @@ int dn::backward48_entry(const dn_mlp_desc* desc, const void* packed_bwd, const 
   p.n_points = n_points;
   p.grads = static_cast<char*>(grads);
   p.grad_units = t.grad_units;
-  p.gslot_dirout = t.gslot_dirout; p.gslot_feat = t.gslot_feat; p.gslot_trunk0 = t.gslot_trunk0; p.gslot_layer1 = t.gslot_layer1;
-  p.gslot_out = t.gslot_out;
+  copy_grad_slots(t, &p);
   // the 256-byte record behind the units (mlp_geo48.h): the largest |upstream gradient| first when the scale is to follow it
   p.block = reinterpret_cast<unsigned*>(static_cast<char*>(grads) + g48_padded_records(n_points) * 2 * t.grad_units * kPieceBytes);
   p.auto_scale = grad_scale == 0.0f ? 1 : 0;
