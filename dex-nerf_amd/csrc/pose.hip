@@ -8,6 +8,17 @@
 //   M = R R0, p = R t0 + W t, rinv = adj(M) / det(M) (no rigidity assumed, as camera_record's torch.inverse), origin = -rinv p.
 // A, B, C and their derivatives in s are entire functions of s: below s = 1e-2 they are summed as series (nine terms: the first
 // neglected one is < 1e-24), where the closed forms cancel; above, the closed forms are accurate to a few ulp.
+//
+// Intrinsics (dn_camera_records and its backward; dn_pose_records copies K0's three entries): per refined camera phi = (a, b, c) fp32,
+// K0 the given matrix, s > 0 the caller's intrinsics_scale,
+//   fx = fx0 exp(s a),  cx = cx0 + s fx0 b,  cy = cy0 + s fx0 c   (fx0 = K0[0,0], cx0 = K0[0,2], cy0 = K0[1,2]),
+// one focal length (fx also divides the y term of the ray kernels), all three components dimensionless and of a rotation's size: a
+// principal-point shift of fx0 delta pixels looks like a rotation by delta, so one Adam with one lr drives twists and phi.  fp64 from
+// the fp32 inputs, rounded once: at phi = 0 the record is dn_pose_records' bit for bit.  One phi (3) shared by all views or phi (V,3).
+//   g_a = s fx g_fx,  g_b = s fx0 g_cx,  g_c = s fx0 g_cy  per view in fp64; a shared phi's gradient is their sum over the views added
+// in view order v = 0 .. V-1 in fp64 by one thread per component - plain stores, no atomics, the order a function of V alone (never
+// of the grid or the CU count).  The NDC warp's focal length is a constant of the scene's parameterisation (the selection and gradient
+// kernels take it as a host scalar, the networks were trained in that warped space): slot 15 of g_cams stays ignored.
 #include "dn_common.h"
 
 namespace dn {
@@ -127,13 +138,9 @@ __global__ __launch_bounds__(64) void pose_records_kernel(const float* __restric
 //   R, W in K and (A, B, C)(s):  g_K = A g_R + B (g_R K^T + K^T g_R) + B g_W + C (g_W K^T + K^T g_W),
 //                                g_s = <g_R, K> A' + (<g_R, K^2> + <g_W, K>) B' + <g_W, K^2> C'
 //   g_omega = vee(g_K - g_K^T) + 2 omega g_s.
-__global__ __launch_bounds__(64) void pose_records_bwd_kernel(const float* __restrict__ g_cams, const float* __restrict__ xi,
-                                                              const float* __restrict__ e0, int n_views, float* __restrict__ g_xi,
-                                                              float* __restrict__ g_xi_keep) {
-  const int v = blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= n_views) return;
-  const float* g = g_cams + 16 * v;
-  double out[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+// out[6] = the twist gradient of view v (zeros when its slots 0:12 are zero); g = g_cams + 16 v.
+__device__ inline void pose_grad(const float* __restrict__ g, const float* __restrict__ xi, const float* __restrict__ e0, int v, double (&out)[6]) {
+  for (int i = 0; i < 6; ++i) out[i] = 0.0;
   bool any = false;
   for (int i = 0; i < 12; ++i) any = any || (g[i] != 0.0f);
   if (any) {
@@ -178,10 +185,104 @@ __global__ __launch_bounds__(64) void pose_records_bwd_kernel(const float* __res
     out[1] = (gK[0][2] - gK[2][0]) + 2.0 * static_cast<double>(xi[6 * v + 1]) * gs;
     out[2] = (gK[1][0] - gK[0][1]) + 2.0 * static_cast<double>(xi[6 * v + 2]) * gs;
   }
+}
+
+__global__ __launch_bounds__(64) void pose_records_bwd_kernel(const float* __restrict__ g_cams, const float* __restrict__ xi,
+                                                              const float* __restrict__ e0, int n_views, float* __restrict__ g_xi,
+                                                              float* __restrict__ g_xi_keep) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n_views) return;
+  double out[6];
+  pose_grad(g_cams + 16 * v, xi, e0, v, out);
   for (int i = 0; i < 6; ++i) {
     const float r = static_cast<float>(out[i]);
     g_xi[6 * v + i] = r;
     if (g_xi_keep != nullptr) g_xi_keep[6 * v + i] = r;
+  }
+}
+
+// fx, cx, cy of one view from K0 and phi = (a, b, c) (NULL: zeros), scale s - the parameterisation of the header comment.
+struct Intrinsics {
+  double fx0, fx, cx, cy;
+};
+
+__device__ inline Intrinsics intrinsics_terms(const float* __restrict__ kv, const float* __restrict__ phi, double s) {
+  Intrinsics in;
+  const double a = phi ? phi[0] : 0.0, b = phi ? phi[1] : 0.0, c = phi ? phi[2] : 0.0;
+  in.fx0 = kv[0];
+  in.fx = in.fx0 * exp(s * a);
+  in.cx = static_cast<double>(kv[2]) + s * in.fx0 * b;
+  in.cy = static_cast<double>(kv[5]) + s * in.fx0 * c;
+  return in;
+}
+
+// pose_records_kernel with slots 12:15 from phi.
+__global__ __launch_bounds__(64) void camera_records_kernel(const float* __restrict__ xi, const float* __restrict__ phi, int phi_per_view,
+                                                            double scale, const float* __restrict__ e0, const float* __restrict__ k,
+                                                            int k_per_view, float ndc_focal, int n_views, float* __restrict__ cams,
+                                                            float* __restrict__ extrinsics) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n_views) return;
+  PoseTerms t;
+  pose_terms(xi + 6 * v, e0 + 16 * v, t);
+  float* c = cams + 16 * v;
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) c[3 * i + j] = static_cast<float>(t.rinv[i][j]);
+    c[9 + i] = static_cast<float>(-(t.rinv[i][0] * t.p[0] + t.rinv[i][1] * t.p[1] + t.rinv[i][2] * t.p[2]));
+  }
+  const Intrinsics in = intrinsics_terms(k + (k_per_view ? 9 * v : 0), phi ? phi + (phi_per_view ? 3 * v : 0) : nullptr, scale);
+  c[12] = static_cast<float>(in.fx); c[13] = static_cast<float>(in.cx); c[14] = static_cast<float>(in.cy); c[15] = ndc_focal;
+  if (extrinsics != nullptr) {
+    float* e = extrinsics + 16 * v;
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 3; ++j) e[4 * i + j] = static_cast<float>(t.M[i][j]);
+      e[4 * i + 3] = static_cast<float>(t.p[i]);
+    }
+    e[12] = 0.0f; e[13] = 0.0f; e[14] = 0.0f; e[15] = 1.0f;
+  }
+}
+
+// pose_records_bwd_kernel with a pose mask and the gradient of phi.  Per view: g_xi (zeros under pose_mask[v] == 0) and the three
+// contributions (s fx g_fx, s fx0 g_cx, s fx0 g_cy) in fp64.  phi_per_view: rounded and stored, grid ceil(V / 64).  Shared phi: ONE
+// workgroup walks the views (thread i: i, i + 64, ...), leaves the contributions in `contrib` (V,3) fp64, and after the barrier
+// threads 0..2 add them v = 0, 1, ..., V - 1 - plain stores, the order a function of V alone.
+__global__ __launch_bounds__(64) void camera_records_bwd_kernel(const float* __restrict__ g_cams, const float* __restrict__ xi,
+                                                                const float* __restrict__ phi, int phi_per_view, double scale,
+                                                                const float* __restrict__ e0, const float* __restrict__ k, int k_per_view,
+                                                                const int32_t* __restrict__ pose_mask, int n_views, float* __restrict__ g_xi,
+                                                                float* __restrict__ g_xi_keep, float* __restrict__ g_phi,
+                                                                float* __restrict__ g_phi_keep, double* contrib) {
+  const bool reduce = g_phi != nullptr && !phi_per_view;
+  for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < n_views; v += gridDim.x * blockDim.x) {
+    const float* g = g_cams + 16 * v;
+    double out[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (pose_mask == nullptr || pose_mask[v] != 0) pose_grad(g, xi, e0, v, out);
+    for (int i = 0; i < 6; ++i) {
+      const float r = static_cast<float>(out[i]);
+      g_xi[6 * v + i] = r;
+      if (g_xi_keep != nullptr) g_xi_keep[6 * v + i] = r;
+    }
+    if (g_phi == nullptr) continue;
+    const Intrinsics in = intrinsics_terms(k + (k_per_view ? 9 * v : 0), phi ? phi + (phi_per_view ? 3 * v : 0) : nullptr, scale);
+    const double gp[3] = {scale * in.fx * g[12], scale * in.fx0 * g[13], scale * in.fx0 * g[14]};
+    for (int i = 0; i < 3; ++i) {
+      if (reduce) {
+        contrib[3 * v + i] = gp[i];
+      } else {
+        const float r = static_cast<float>(gp[i]);
+        g_phi[3 * v + i] = r;
+        if (g_phi_keep != nullptr) g_phi_keep[3 * v + i] = r;
+      }
+    }
+  }
+  if (!reduce) return;
+  __syncthreads();     // (with its workgroup-scope fence: the contributions written above are visible to threads 0..2)
+  if (threadIdx.x < 3) {
+    double sum = 0.0;
+    for (int v = 0; v < n_views; ++v) sum += contrib[3 * v + threadIdx.x];
+    const float r = static_cast<float>(sum);
+    g_phi[threadIdx.x] = r;
+    if (g_phi_keep != nullptr) g_phi_keep[threadIdx.x] = r;
   }
 }
 
@@ -249,4 +350,50 @@ extern "C" int dn_pose_records_backward(const float* g_cams, const float* xi, co
   const unsigned grid = static_cast<unsigned>((n_views + 63) / 64);
   hipLaunchKernelGGL(pose_records_bwd_kernel, dim3(grid), dim3(64), 0, as_stream(stream), g_cams, xi, e0, n_views, g_xi, g_xi_keep);
   return check_launch("dn_pose_records_backward");
+}
+
+static bool scale_ok(double s) { return s > 0.0 && s < 3.0e38; }
+
+extern "C" int dn_camera_records(const float* xi, const float* phi, int phi_per_view, double intrinsics_scale, const float* e0, const float* k,
+                                 int k_per_view, double ndc_focal, int n_views, float* cams, float* extrinsics, dn_stream_t stream) {
+  DN_REQUIRE(n_views >= 0, "dn_camera_records: negative view count");
+  DN_REQUIRE(xi && e0 && k && cams, "dn_camera_records: NULL pointer");
+  DN_REQUIRE(aligned4(xi) && aligned4(phi) && aligned4(e0) && aligned4(k) && aligned4(cams) && aligned4(extrinsics),
+             "dn_camera_records: pointers must be 4-byte aligned");
+  DN_REQUIRE(ndc_focal >= 0.0 && ndc_focal < 3.0e38, "dn_camera_records: ndc_focal must be finite and >= 0 (0: world-space rays)");
+  DN_REQUIRE(scale_ok(intrinsics_scale), "dn_camera_records: intrinsics_scale must be finite and > 0");
+  if (n_views == 0) return 0;
+  const unsigned grid = static_cast<unsigned>((n_views + 63) / 64);
+  hipLaunchKernelGGL(camera_records_kernel, dim3(grid), dim3(64), 0, as_stream(stream), xi, phi, phi_per_view ? 1 : 0, intrinsics_scale, e0, k,
+                     k_per_view ? 1 : 0, static_cast<float>(ndc_focal), n_views, cams, extrinsics);
+  return check_launch("dn_camera_records");
+}
+
+extern "C" size_t dn_camera_records_scratch_bytes(int n_views) {
+  if (n_views <= 0) return 0;
+  return (static_cast<size_t>(n_views) * 3 * sizeof(double) + 255) / 256 * 256;
+}
+
+extern "C" int dn_camera_records_backward(const float* g_cams, const float* xi, const float* phi, int phi_per_view, double intrinsics_scale,
+                                          const float* e0, const float* k, int k_per_view, const int32_t* pose_mask, int n_views, float* g_xi,
+                                          float* g_xi_keep, float* g_phi, float* g_phi_keep, void* scratch, size_t scratch_bytes,
+                                          dn_stream_t stream) {
+  DN_REQUIRE(n_views >= 0, "dn_camera_records_backward: negative view count");
+  DN_REQUIRE(g_cams && xi && e0 && k && g_xi, "dn_camera_records_backward: NULL pointer");
+  DN_REQUIRE(g_phi || !g_phi_keep, "dn_camera_records_backward: g_phi_keep without g_phi");
+  DN_REQUIRE(aligned4(g_cams) && aligned4(xi) && aligned4(phi) && aligned4(e0) && aligned4(k) && aligned4(pose_mask) && aligned4(g_xi) &&
+                 aligned4(g_xi_keep) && aligned4(g_phi) && aligned4(g_phi_keep),
+             "dn_camera_records_backward: pointers must be 4-byte aligned");
+  DN_REQUIRE(scale_ok(intrinsics_scale), "dn_camera_records_backward: intrinsics_scale must be finite and > 0");
+  const bool reduce = g_phi != nullptr && !phi_per_view;
+  const size_t need = reduce ? dn_camera_records_scratch_bytes(n_views) : 0;
+  DN_REQUIRE(need == 0 || (scratch && (reinterpret_cast<uintptr_t>(scratch) & 7) == 0 && scratch_bytes >= need),
+             "dn_camera_records_backward: a shared g_phi needs dn_camera_records_scratch_bytes(n_views) bytes of 8-byte aligned scratch");
+  if (n_views == 0 && !reduce) return 0;
+  // a shared g_phi: one workgroup, so that its sum needs no second launch (n_views == 0: it stores the three zeros)
+  const unsigned grid = reduce ? 1u : static_cast<unsigned>((n_views + 63) / 64);
+  hipLaunchKernelGGL(camera_records_bwd_kernel, dim3(grid), dim3(64), 0, as_stream(stream), g_cams, xi, phi, phi_per_view ? 1 : 0,
+                     intrinsics_scale, e0, k, k_per_view ? 1 : 0, pose_mask, n_views, g_xi, g_xi_keep, g_phi, g_phi_keep,
+                     static_cast<double*>(scratch));
+  return check_launch("dn_camera_records_backward");
 }

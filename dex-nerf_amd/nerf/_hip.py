@@ -40,6 +40,7 @@ EXPORTS = (
     "dn_pose_records", "dn_pose_records_backward", "dn_render_rays_train_geom", "dn_render_backward_geom_workspace_bytes",
     "dn_render_rays_backward_geom",
     "dn_render_loss",
+    "dn_camera_records", "dn_camera_records_scratch_bytes", "dn_camera_records_backward",
 )
 
 
@@ -157,6 +158,10 @@ def _declare(lib):
     lib.dn_camera_grad_views.argtypes = [c_int, c_int, fp, c_int, vp, vp, c_int64, fp, c_int, fp, c_int, fp, c_int, dbl, dbl, vp, c_size_t, fp, vp]
     lib.dn_pose_records.argtypes = [fp, fp, fp, c_int, dbl, c_int, fp, fp, vp]
     lib.dn_pose_records_backward.argtypes = [fp, fp, fp, c_int, fp, fp, vp]
+    lib.dn_camera_records.argtypes = [fp, fp, c_int, dbl, fp, fp, c_int, dbl, c_int, fp, fp, vp]
+    lib.dn_camera_records_scratch_bytes.argtypes = [c_int]
+    lib.dn_camera_records_scratch_bytes.restype = c_size_t
+    lib.dn_camera_records_backward.argtypes = [fp, fp, fp, c_int, dbl, fp, fp, c_int, vp, c_int, fp, fp, fp, fp, vp, c_size_t, vp]
     lib.dn_render_rays_train_geom.argtypes = lib.dn_render_rays_train.argtypes[:-1] + [fp, vp]
     lib.dn_render_backward_geom_workspace_bytes.argtypes = [POINTER(MlpDesc), POINTER(MlpDesc), c_int64, c_int, c_int, c_int]
     lib.dn_render_backward_geom_workspace_bytes.restype = c_size_t

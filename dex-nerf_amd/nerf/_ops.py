@@ -1369,3 +1369,71 @@ def pose_records_backward(g_cams, xi, e0, out=None, keep=None):
         out = torch.empty((n_views, 6), dtype=torch.float32, device=xi.device)
     check(lib().dn_pose_records_backward(ptr(g_cams), ptr(xi), ptr(e0), n_views, ptr(out), ptr(keep), stream()), "dn_pose_records_backward")
     return out
+
+
+def _intrinsics_inputs(phi, k, scale, n_views):
+    """(phi_per_view, k_per_view) for phi None | (3,) shared | (V,3) per view and k (3,3) | (V,3,3), fp32 on the device."""
+    assert k.is_cuda and k.dtype == torch.float32 and k.is_contiguous() and k.dim() in (2, 3) and k.numel() in (9, 9 * n_views), \
+        "k: (3,3) or (V,3,3) fp32 on the device"
+    assert float(scale) > 0.0, "intrinsics_scale: a positive number"
+    if phi is None:
+        return 0, int(k.dim() == 3)
+    assert phi.is_cuda and phi.dtype == torch.float32 and phi.is_contiguous() and (phi.shape == (3,) or phi.shape == (n_views, 3)), \
+        "phi: (3,) shared or (V,3) per view, fp32 on the device"
+    return int(phi.dim() == 2), int(k.dim() == 3)
+
+
+def camera_records(xi, phi, e0, k, intrinsics_scale=1.0, ndc_focal=None, cams=None, extrinsics=None, want_extrinsics=False):
+    """dn_camera_records: pose_records with slots 12:15 from phi - fx = fx0 exp(s a), cx = cx0 + s fx0 b, cy = cy0 + s fx0 c, s =
+    `intrinsics_scale`; phi (3,) shared by the views, (V,3) per view, or None (zeros: pose_records' bits)."""
+    n_views = _pose_inputs(xi, e0)
+    phi_per_view, k_per_view = _intrinsics_inputs(phi, k, intrinsics_scale, n_views)
+    if cams is None:
+        cams = torch.empty((n_views, 16), dtype=torch.float32, device=xi.device)
+    if extrinsics is None and want_extrinsics:
+        extrinsics = torch.empty((n_views, 4, 4), dtype=torch.float32, device=xi.device)
+    check(lib().dn_camera_records(ptr(xi), ptr(phi), phi_per_view, float(intrinsics_scale), ptr(e0), ptr(k), k_per_view, float(ndc_focal or 0.0),
+                                  n_views, ptr(cams), ptr(extrinsics), stream()), "dn_camera_records")
+    return cams if extrinsics is None else (cams, extrinsics)
+
+
+def camera_records_scratch_bytes(n_views):
+    return int(lib().dn_camera_records_scratch_bytes(int(n_views)))
+
+
+def camera_records_backward(g_cams, xi, phi, e0, k, intrinsics_scale=1.0, pose_mask=None, shared=None, out=None, keep=None, out_phi=None,
+                            keep_phi=None, want_phi=True):
+    """dn_camera_records_backward: (g_xi (V,6), g_phi (3,) | (V,3) | None) from g_cams (V,16) at the given xi / phi.  `pose_mask` (V)
+    int32: views with 0 get exact zeros in g_xi.  phi None: `shared` says which gradient is wanted (True (3,), False (V,3)).  `out` /
+    `out_phi`: the tensors to write (else allocated); `keep` / `keep_phi`: second tensors that receive the same values;
+    want_phi=False: g_xi alone.  A shared g_phi is summed in view order over a scratch allocated here."""
+    n_views = _pose_inputs(xi, e0)
+    phi_per_view, k_per_view = _intrinsics_inputs(phi, k, intrinsics_scale, n_views)
+    if phi is None:
+        phi_per_view = int(shared is False)
+    assert g_cams.is_cuda and g_cams.dtype == torch.float32 and g_cams.is_contiguous() and g_cams.shape == (n_views, 16)
+    if pose_mask is not None:
+        assert pose_mask.is_cuda and pose_mask.dtype == torch.int32 and pose_mask.is_contiguous() and pose_mask.shape == (n_views,), \
+            "pose_mask: (V) int32 on the device"
+    if out is None:
+        out = torch.empty((n_views, 6), dtype=torch.float32, device=xi.device)
+    scratch, nbytes = None, 0
+    if want_phi:
+        shape = (n_views, 3) if phi_per_view else (3,)
+        if out_phi is None:
+            out_phi = torch.empty(shape, dtype=torch.float32, device=xi.device)
+        for t in (out_phi, keep_phi):
+            assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == shape), f"g_phi: {shape} fp32"
+        if not phi_per_view:
+            nbytes = camera_records_scratch_bytes(n_views)
+            scratch = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=xi.device)
+    else:
+        assert out_phi is None and keep_phi is None
+    g_in, xi_in, e0_in, g_out = g_cams, xi, e0, out
+    if n_views == 0:   # empty tensors carry NULL data pointers, which the entry point refuses: one unread element each
+        g_in = xi_in = e0_in = g_out = torch.zeros(1, dtype=torch.float32, device=k.device)
+        pose_mask = keep = None
+    check(lib().dn_camera_records_backward(ptr(g_in), ptr(xi_in), ptr(phi), phi_per_view, float(intrinsics_scale), ptr(e0_in), ptr(k), k_per_view,
+                                           ptr(pose_mask), n_views, ptr(g_out), ptr(keep), ptr(out_phi), ptr(keep_phi), ptr(scratch), nbytes,
+                                           stream()), "dn_camera_records_backward")
+    return out, out_phi

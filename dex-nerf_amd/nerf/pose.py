@@ -21,6 +21,37 @@ def se3_exp(xi):
     return torch.linalg.matrix_exp(twist)
 
 
+INTRINSICS_MODES = (None, "shared", "per_view")
+
+
+def _refinement_settings(who, n_views, refine_intrinsics, intrinsics_scale, fixed_views, refine_pose=True):
+    """The checked (mode, scale, pose mask as a list of V 0 / 1) of FusedPoseStep / MultiPoseRefiner."""
+    if refine_intrinsics not in INTRINSICS_MODES:
+        raise ValueError(f"{who}: refine_intrinsics is None, 'shared' or 'per_view' (got {refine_intrinsics!r})")
+    scale = float(intrinsics_scale)
+    if not 0.0 < scale < float("inf"):
+        raise ValueError(f"{who}: intrinsics_scale must be a positive finite number (got {intrinsics_scale!r})")
+    fixed = [int(v) for v in fixed_views]
+    if any(v < 0 or v >= n_views for v in fixed):
+        raise ValueError(f"{who}: fixed_views {fixed} out of range for {n_views} views")
+    if not refine_pose and refine_intrinsics is None:
+        raise ValueError(f"{who}: refine_pose=False with refine_intrinsics=None leaves nothing to refine")
+    mask = [0 if (not refine_pose or v in fixed) else 1 for v in range(n_views)]
+    return refine_intrinsics, scale, mask
+
+
+def refined_intrinsics(k0, phi, scale):
+    """K of the intrinsics parameterisation: fx = fx0 exp(s a), cx = cx0 + s fx0 b, cy = cy0 + s fx0 c with phi = (a, b, c) (3,) or
+    (V,3) and k0 (3,3) or (V,3,3); every other entry as given.  Differentiable in phi; (V,3,3) when either is per view."""
+    if phi.dim() == 2 and k0.dim() == 2:
+        k0 = k0.expand(phi.shape[0], 3, 3)
+    k0 = k0.to(phi.dtype)
+    fx0 = k0[..., 0, 0]
+    fx, cx, cy = fx0 * torch.exp(scale * phi[..., 0]), k0[..., 0, 2] + scale * fx0 * phi[..., 1], k0[..., 1, 2] + scale * fx0 * phi[..., 2]
+    rows = [torch.stack([fx, k0[..., 0, 1], cx], -1), torch.stack([k0[..., 1, 0], k0[..., 1, 1], cy], -1), k0[..., 2, :].expand(fx.shape + (3,))]
+    return torch.stack(rows, -2)
+
+
 class PoseRefiner:
     """Refines one camera's world->camera extrinsic against an image, the networks frozen: E = se3_exp(xi) @ extrinsic0 with the
     6-vector xi (float64, on the host) under torch.optim.Adam.  Every `step` draws `num_rays` distinct pixels from the refiner's own
@@ -90,13 +121,19 @@ class MultiPoseRefiner:
     """PoseRefiner for the V cameras of a capture refined together: E_v = se3_exp(xi[v]) @ extrinsics0[v], xi (V,6) float64 on the
     host under ONE torch.optim.Adam.  Every `step` draws `num_rays` distinct (view, pixel) pairs over all V H W pixels from the
     refiner's own seeded device generator, builds the mixed batch with one selection kernel (select_camera_rays with view_index) and
-    reads all V camera gradients back at once.  `intrinsic`: (3,3) shared or (V,3,3).  All state lives in the object."""
+    reads all V camera gradients back at once.  `intrinsic`: (3,3) shared or (V,3,3).  All state lives in the object.
+
+    `refine_intrinsics` "shared" | "per_view": phi (3,) | (V,3) float64 on the host under the same Adam, K = refined_intrinsics(intrinsic,
+    phi, intrinsics_scale) handed to select_camera_rays (FusedPoseStep's parameterisation; its parity reference).  `fixed_views`: views
+    whose xi gets a zero gradient."""
 
     def __init__(self, model_coarse, model_fine, options, height, width, intrinsic, extrinsics0, encode_position_fn, encode_direction_fn,
-                 num_rays, lr, seed=0, ndc_focal=None):
-        _require_device(extrinsics0, "MultiPoseRefiner")
+                 num_rays, lr, seed=0, ndc_focal=None, refine_intrinsics=None, intrinsics_scale=1.0, fixed_views=()):
         if extrinsics0.dim() != 3:
             raise ValueError("MultiPoseRefiner: extrinsics0 is (V,4,4)")
+        self.mode, self.intrinsics_scale, mask = _refinement_settings("MultiPoseRefiner", int(extrinsics0.shape[0]), refine_intrinsics,
+                                                                      intrinsics_scale, fixed_views)
+        _require_device(extrinsics0, "MultiPoseRefiner")
         self.models = (model_coarse, model_fine)
         self.options = options
         self.height, self.width = int(height), int(width)
@@ -108,8 +145,13 @@ class MultiPoseRefiner:
         self.num_rays = min(int(num_rays), self.n_views * self.height * self.width)
         self.ndc_focal = ndc_focal
         self.xi = torch.zeros(self.n_views, 6, dtype=torch.float64, requires_grad=True)
-        self.optimizer = torch.optim.Adam([self.xi], lr=lr)
+        self.pose_mask = None if all(mask) else torch.tensor(mask, dtype=torch.float64)[:, None]
+        self.phi = None
+        if self.mode is not None:
+            self.phi = torch.zeros((3,) if self.mode == "shared" else (self.n_views, 3), dtype=torch.float64, requires_grad=True)
+        self.optimizer = torch.optim.Adam([self.xi] if self.phi is None else [self.xi, self.phi], lr=lr)
         self.last_grad = None   # dL/dxi (V,6) of the latest step
+        self.last_grad_phi = None   # dL/dphi of the latest step
         self.generator = torch.Generator(device=self.device).manual_seed(int(seed))
 
     def draw_pairs(self):
@@ -119,10 +161,13 @@ class MultiPoseRefiner:
     def _extrinsics(self):
         return torch.stack([se3_exp(self.xi[v]) @ self.extrinsics0[v] for v in range(self.n_views)])
 
+    def _intrinsic(self):
+        return self.intrinsic if self.phi is None else refined_intrinsics(self.intrinsic.double(), self.phi, self.intrinsics_scale)
+
     def loss(self, images, view_index, pixel_index):
-        """mse(rgb_coarse, target) + mse(rgb_fine, target) on the given pairs at the current xi (differentiable in xi)."""
+        """mse(rgb_coarse, target) + mse(rgb_fine, target) on the given pairs at the current xi (differentiable in xi and phi)."""
         near, far = float(self.options.dataset.near), float(self.options.dataset.far)
-        rows, target = select_camera_rays(self.height, self.width, self._extrinsics(), self.intrinsic, near, far, pixel_index, image=images,
+        rows, target = select_camera_rays(self.height, self.width, self._extrinsics(), self._intrinsic(), near, far, pixel_index, image=images,
                                           ndc_focal=self.ndc_focal, view_index=view_index)
         out = predict_and_render_radiance(rows, self.models[0], self.models[1], self.options, mode="train",
                                           encode_position_fn=self.encoders[0], encode_direction_fn=self.encoders[1])
@@ -145,7 +190,11 @@ class MultiPoseRefiner:
             self.optimizer.zero_grad(set_to_none=True)
             loss = self.loss(images, view_index, pixel_index)
             loss.backward()
+            if self.pose_mask is not None:
+                self.xi.grad.mul_(self.pose_mask)
             self.last_grad = self.xi.grad.detach().clone()
+            if self.phi is not None:
+                self.last_grad_phi = self.phi.grad.detach().clone()
             self.optimizer.step()
         finally:
             for p, flag in zip(params, flags):
@@ -156,6 +205,11 @@ class MultiPoseRefiner:
         """The current estimates se3_exp(xi[v]) @ extrinsics0[v], (V,4,4), detached (fp32, on the refiner's device)."""
         with torch.no_grad():
             return self._extrinsics().to(self.device, torch.float32)
+
+    def intrinsics(self):
+        """The current K, (3,3) or (V,3,3) (per view when `intrinsic` or phi is), detached (fp32, on the refiner's device)."""
+        with torch.no_grad():
+            return self._intrinsic().to(self.device, torch.float32)
 
 
 class FusedPoseStep:
@@ -183,11 +237,23 @@ class FusedPoseStep:
     why.  Networks with view directions only (the selection kernels write 11-column rows), like FusedTrainStep.  `extrinsics0` (V,4,4) or (4,4), `intrinsic` (3,3) or (V,3,3), `images` (V,H,W,C), all on the device.
 
     loss3, xi, last_grad ((V,6): the gradient the latest step used) and rng_state are device tensors; PoseRefiner / MultiPoseRefiner
-    (float64 xi on the host, explicit pixels) stay the parity reference."""
+    (float64 xi on the host, explicit pixels) stay the parity reference.
+
+    `refine_intrinsics` "shared" | "per_view": the intrinsics are refined with the poses - phi = (a, b, c) per refined camera (one for
+    all views | (V,3)), fx = fx0 exp(s a), cx = cx0 + s fx0 b, cy = cy0 + s fx0 c with s = `intrinsics_scale` (the handle on phi's step
+    relative to the twists': all of phi is dimensionless and of a rotation's size, so ONE dn_adam_step with one lr drives the flat
+    buffer [xi (6V) | phi (3 | 3V) | pad to 4]).  dn_camera_records / dn_camera_records_backward then stand in the places of
+    dn_pose_records / dn_pose_records_backward, one kernel launch each like the pair they replace: the step stays at the eight library
+    calls above and its launch count does not grow in either mode (a shared phi's gradient is summed in view order inside the
+    backward's one launch).  `fixed_views` (view indices) and `refine_pose=False` (every view) hold poses fixed:
+    those views' twist gradients are exact zeros, which leaves their xi untouched bit for bit; either also puts the step on the new
+    pair.  With all four at their defaults the step is the launches above.  phi (a device view into the flat buffer, None when the
+    intrinsics are not refined), last_grad_phi, intrinsics()."""
 
     def __init__(self, model_coarse, model_fine, options, height, width, intrinsic, extrinsics0, images, encode_position_fn,
                  encode_direction_fn, num_rays, lr, seed=0, first_iteration=0, ndc_focal=None, use_graphs=True, eager_iterations=3,
-                 depth_images=None, loss_weights=(1.0, 1.0), depth_weights=(0.0, 0.0), depth_range=(0.0, float("inf"))):
+                 depth_images=None, loss_weights=(1.0, 1.0), depth_weights=(0.0, 0.0), depth_range=(0.0, float("inf")),
+                 refine_intrinsics=None, intrinsics_scale=1.0, fixed_views=(), refine_pose=True):
         if extrinsics0.dim() == 2:
             extrinsics0 = extrinsics0[None]
         if extrinsics0.dim() != 3 or tuple(extrinsics0.shape[1:]) != (4, 4):
@@ -200,6 +266,8 @@ class FusedPoseStep:
         self.height, self.width = int(height), int(width)
         if tuple(images.shape[1:3]) != (self.height, self.width):
             raise ValueError(f"FusedPoseStep: images of shape {tuple(images.shape)} for {self.height} x {self.width} cameras")
+        self.mode, self.intrinsics_scale, mask = _refinement_settings("FusedPoseStep", self.n_views, refine_intrinsics, intrinsics_scale,
+                                                                      fixed_views, refine_pose)
         # None: the reference's head (dn_mse2_loss); else the settings of dn_render_loss (a zero colour weight is allowed here: fp32 or
         # 16-bit saves, no per-launch 8-bit gradient scale)
         self.head = loss_head_settings("FusedPoseStep", depth_images, loss_weights, depth_weights, depth_range,
@@ -229,11 +297,21 @@ class FusedPoseStep:
         self.k = intrinsic.detach().to(torch.float32).contiguous()
         self.images = _hip.f32c(images.detach())
         n = 6 * self.n_views
-        padded = (n + 3) // 4 * 4                 # dn_adam_step works on multiples of four elements
+        n_phi = {None: 0, "shared": 3, "per_view": 3 * self.n_views}[self.mode]
+        padded = (n + n_phi + 3) // 4 * 4         # dn_adam_step works on multiples of four elements
         self._flat = torch.zeros(4, padded, dtype=torch.float32, device=dev)    # rows: xi, gradient, exp_avg, exp_avg_sq
         self.xi = self._flat[0, :n].view(self.n_views, 6)
         self._grad = self._flat[1, :n].view(self.n_views, 6)
         self.last_grad = torch.zeros(self.n_views, 6, dtype=torch.float32, device=dev)
+        self.phi = self._grad_phi = self.last_grad_phi = None
+        if self.mode is not None:
+            shape = (3,) if self.mode == "shared" else (self.n_views, 3)
+            self.phi = self._flat[0, n:n + n_phi].view(shape)
+            self._grad_phi = self._flat[1, n:n + n_phi].view(shape)
+            self.last_grad_phi = torch.zeros(shape, dtype=torch.float32, device=dev)
+        # dn_pose_records and its backward unless something of the new pair is asked for
+        self.camera_pair = self.mode is not None or not all(mask)
+        self.pose_mask = None if all(mask) else torch.tensor(mask, dtype=torch.int32, device=dev)
         # dn_adam_step's state record (parallel.FlatAdam): float [steps taken, ticket, last lr, -], then double [beta1^t, beta2^t, decay^t]
         self._adam_state = torch.zeros(12, dtype=torch.float32, device=dev)[:10]
         self._adam_state[4:10].view(torch.float64).fill_(1.0)
@@ -265,9 +343,14 @@ class FusedPoseStep:
             packs.append(pk)
         return packs
 
+    def _records(self, **kw):
+        if self.camera_pair:
+            return _ops.camera_records(self.xi, self.phi, self.e0, self.k, self.intrinsics_scale, self.ndc_focal, **kw)
+        return _ops.pose_records(self.xi, self.e0, self.k, self.ndc_focal, **kw)
+
     def _enqueue(self):
         pc, pf = self._packs()
-        _ops.pose_records(self.xi, self.e0, self.k, self.ndc_focal, cams=self.cams)
+        self._records(cams=self.cams)
         rays, target, pix, views = _ops.select_rays_draw_views(self.height, self.width, self.cams, self.near, self.far, self.rng_state,
                                                                self.num_rays, self.images, want_pixels=True, ndc_focal=self.ndc_focal,
                                                                ndc_near=1.0)
@@ -277,7 +360,12 @@ class FusedPoseStep:
         d_rays, keep = _ops.render_rays_backward_geom(pc, pf, saved, g_c, g_f)
         g_cams = _ops.camera_grad_views(self.height, self.width, self.cams, views, pix, self.num_rays, d_rays[:, 0:3], d_rays[:, 3:6],
                                         d_rays[:, 8:11], self.ndc_focal or 0.0, 1.0)
-        _ops.pose_records_backward(g_cams, self.xi, self.e0, out=self._grad, keep=self.last_grad)
+        if self.camera_pair:
+            _ops.camera_records_backward(g_cams, self.xi, self.phi, self.e0, self.k, self.intrinsics_scale, self.pose_mask, out=self._grad,
+                                         keep=self.last_grad, out_phi=self._grad_phi, keep_phi=self.last_grad_phi,
+                                         want_phi=self.phi is not None)
+        else:
+            _ops.pose_records_backward(g_cams, self.xi, self.e0, out=self._grad, keep=self.last_grad)
         _ops.adam_step(self._flat[0], self._flat[1], self._flat[2], self._flat[3], self._adam_state, self.lr, 1.0, (0.9, 0.999), 1e-8, True)
         # alive until the next call (stream-ordered allocator; under capture they belong to the graph's pool)
         self._keep = (views, pix, rays, target, maps, saved, d_rays, g_cams, keep, g_c[0], g_f[0], g_c[1], g_f[1])
@@ -316,4 +404,13 @@ class FusedPoseStep:
 
     def extrinsics(self):
         """The current estimates se3_exp(xi[v]) @ extrinsics0[v], (V,4,4) fp32 on the device (dn_pose_records at the current xi)."""
-        return _ops.pose_records(self.xi, self.e0, self.k, self.ndc_focal, want_extrinsics=True)[1]
+        return self._records(want_extrinsics=True)[1]
+
+    def intrinsics(self):
+        """The current K on the device (fp32): `intrinsic` with [0,0], [0,2], [1,2] replaced by the records' fx, cx, cy, every other entry
+        as given; (3,3) when `intrinsic` is and the views share phi (or none is refined), else (V,3,3)."""
+        cams = self._records()
+        per_view = self.k.dim() == 3 or self.mode == "per_view"
+        out = (self.k if self.k.dim() == 3 else self.k.expand(self.n_views, 3, 3)).clone()
+        out[:, 0, 0], out[:, 0, 2], out[:, 1, 2] = cams[:, 12], cams[:, 13], cams[:, 14]
+        return out if per_view else out[0]
