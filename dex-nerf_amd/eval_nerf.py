@@ -58,6 +58,9 @@ def main(argv=None):
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"])
     ap.add_argument("--savedir", default="")
     ap.add_argument("--quiet", action="store_true")
+    ap.add_argument("--use-refined-poses", action="store_true",
+                    help="a checkpoint of train_dexnerf.py --refine-poses: render its training views at the refined cameras it carries "
+                         "(refined_extrinsics / refined_intrinsics) instead of the spherical sweep; --size must be the training size")
     args = ap.parse_args(argv)
 
     if args.depth_only and args.m_thres <= 0:
@@ -81,8 +84,15 @@ def main(argv=None):
     if args.savedir:
         os.makedirs(args.savedir, exist_ok=True)
     times, frames = [], []
-    for i in range(args.views):
-        pose = torch.from_numpy(syn.scene_pose(i, n_views=args.views)).to(dev)
+    if args.use_refined_poses:
+        if "refined_extrinsics" not in ck:
+            ap.error("--use-refined-poses: the checkpoint carries no refined cameras (train_dexnerf.py --refine-poses writes them)")
+        refined_e = torch.as_tensor(ck["refined_extrinsics"], dtype=torch.float32, device=dev)
+        refined_k = torch.as_tensor(ck["refined_intrinsics"], dtype=torch.float32, device=dev)
+        cameras = [(refined_e[v], refined_k[v] if refined_k.dim() == 3 else refined_k) for v in range(refined_e.shape[0])]
+    else:
+        cameras = [(torch.from_numpy(syn.scene_pose(i, n_views=args.views)).to(dev), k_mat) for i in range(args.views)]
+    for i, (pose, k_mat) in enumerate(cameras):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if args.depth_only:

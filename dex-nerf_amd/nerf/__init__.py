@@ -16,7 +16,7 @@ from .models import *  # noqa: F401,F403
 from .nerf_helpers import *  # noqa: F401,F403
 from .train_utils import *  # noqa: F401,F403
 from .volume_rendering_utils import *  # noqa: F401,F403
-from .pose import FusedPoseStep, MultiPoseRefiner, PoseRefiner, se3_exp  # noqa: F401
+from .pose import FusedJointStep, FusedPoseStep, MultiPoseRefiner, PoseRefiner, se3_exp  # noqa: F401
 
 
 from .datasets import (load_blender_data, load_llff_data, load_messytable_data, load_ray_cache, pose_spherical,  # noqa: F401,E402

@@ -2,7 +2,8 @@
 library's kernels (select_camera_rays forward / dn_camera_grad backward, predict_and_render_radiance with rows that require grad);
 MultiPoseRefiner: all cameras of a capture together, on mixed-camera batches (dn_select_rays_views / dn_camera_grad_views);
 FusedPoseStep: the same iteration as library launches only - twists, records, draw, render, loss, ray gradient, camera gradient,
-twist gradient and Adam all on the device, replayed as one HIP graph."""
+twist gradient and Adam all on the device, replayed as one HIP graph; FusedJointStep: that iteration with the networks trained in
+the same step - the packs inside the graph, the weight gradients from the same backward call, the networks' optimizer after it."""
 import torch
 
 from . import _hip, _ops
@@ -24,8 +25,9 @@ def se3_exp(xi):
 INTRINSICS_MODES = (None, "shared", "per_view")
 
 
-def _refinement_settings(who, n_views, refine_intrinsics, intrinsics_scale, fixed_views, refine_pose=True):
-    """The checked (mode, scale, pose mask as a list of V 0 / 1) of FusedPoseStep / MultiPoseRefiner."""
+def _refinement_settings(who, n_views, refine_intrinsics, intrinsics_scale, fixed_views, refine_pose=True, networks_train=False):
+    """The checked (mode, scale, pose mask as a list of V 0 / 1) of FusedPoseStep / MultiPoseRefiner.  networks_train (FusedJointStep):
+    the step has the networks to update, so holding every camera fixed is allowed."""
     if refine_intrinsics not in INTRINSICS_MODES:
         raise ValueError(f"{who}: refine_intrinsics is None, 'shared' or 'per_view' (got {refine_intrinsics!r})")
     scale = float(intrinsics_scale)
@@ -34,7 +36,7 @@ def _refinement_settings(who, n_views, refine_intrinsics, intrinsics_scale, fixe
     fixed = [int(v) for v in fixed_views]
     if any(v < 0 or v >= n_views for v in fixed):
         raise ValueError(f"{who}: fixed_views {fixed} out of range for {n_views} views")
-    if not refine_pose and refine_intrinsics is None:
+    if not refine_pose and refine_intrinsics is None and not networks_train:
         raise ValueError(f"{who}: refine_pose=False with refine_intrinsics=None leaves nothing to refine")
     mask = [0 if (not refine_pose or v in fixed) else 1 for v in range(n_views)]
     return refine_intrinsics, scale, mask
@@ -250,30 +252,37 @@ class FusedPoseStep:
     pair.  With all four at their defaults the step is the launches above.  phi (a device view into the flat buffer, None when the
     intrinsics are not refined), last_grad_phi, intrinsics()."""
 
+    _who = "FusedPoseStep"
+    _networks_train = False       # FusedJointStep: the networks are parameters of the step too
+    _other_route = "MultiPoseRefiner differentiates those"
+
     def __init__(self, model_coarse, model_fine, options, height, width, intrinsic, extrinsics0, images, encode_position_fn,
                  encode_direction_fn, num_rays, lr, seed=0, first_iteration=0, ndc_focal=None, use_graphs=True, eager_iterations=3,
                  depth_images=None, loss_weights=(1.0, 1.0), depth_weights=(0.0, 0.0), depth_range=(0.0, float("inf")),
                  refine_intrinsics=None, intrinsics_scale=1.0, fixed_views=(), refine_pose=True):
+        who = self._who
         if extrinsics0.dim() == 2:
             extrinsics0 = extrinsics0[None]
         if extrinsics0.dim() != 3 or tuple(extrinsics0.shape[1:]) != (4, 4):
-            raise ValueError("FusedPoseStep: extrinsics0 is (V,4,4) or (4,4)")
+            raise ValueError(f"{who}: extrinsics0 is (V,4,4) or (4,4)")
         self.n_views = int(extrinsics0.shape[0])
         if intrinsic.dim() == 3 and int(intrinsic.shape[0]) != self.n_views:
-            raise ValueError(f"FusedPoseStep: {self.n_views} extrinsics but {int(intrinsic.shape[0])} intrinsics")
+            raise ValueError(f"{who}: {self.n_views} extrinsics but {int(intrinsic.shape[0])} intrinsics")
         if images.dim() != 4 or int(images.shape[0]) != self.n_views:
-            raise ValueError(f"FusedPoseStep: {self.n_views} extrinsics but images of shape {tuple(images.shape)} (expected (V,H,W,C))")
+            raise ValueError(f"{who}: {self.n_views} extrinsics but images of shape {tuple(images.shape)} (expected (V,H,W,C))")
         self.height, self.width = int(height), int(width)
         if tuple(images.shape[1:3]) != (self.height, self.width):
-            raise ValueError(f"FusedPoseStep: images of shape {tuple(images.shape)} for {self.height} x {self.width} cameras")
-        self.mode, self.intrinsics_scale, mask = _refinement_settings("FusedPoseStep", self.n_views, refine_intrinsics, intrinsics_scale,
-                                                                      fixed_views, refine_pose)
+            raise ValueError(f"{who}: images of shape {tuple(images.shape)} for {self.height} x {self.width} cameras")
+        self.mode, self.intrinsics_scale, mask = _refinement_settings(who, self.n_views, refine_intrinsics, intrinsics_scale,
+                                                                      fixed_views, refine_pose, self._networks_train)
         # None: the reference's head (dn_mse2_loss); else the settings of dn_render_loss (a zero colour weight is allowed here: fp32 or
         # 16-bit saves, no per-launch 8-bit gradient scale)
-        self.head = loss_head_settings("FusedPoseStep", depth_images, loss_weights, depth_weights, depth_range,
+        self.head = loss_head_settings(who, depth_images, loss_weights, depth_weights, depth_range,
                                        shape=tuple(images.shape[:3]), ndc=ndc_focal is not None)
+        if self._networks_train:      # a step that trains the networks refuses the ones it cannot train before it asks for a device
+            self._check_networks(model_coarse, model_fine, encode_position_fn, encode_direction_fn)
         for t in (extrinsics0, intrinsic, images):
-            _require_device(t, "FusedPoseStep")
+            _require_device(t, who)
         opt = options.nerf.train
         self.models = (model_coarse, model_fine)
         self.nc = int(opt.num_coarse)
@@ -281,13 +290,9 @@ class FusedPoseStep:
         self.lindisp, self.perturb = bool(opt.lindisp), bool(opt.perturb)
         self.noise_std, self.white = float(opt.radiance_field_noise_std), bool(opt.white_background)
         self.near, self.far = float(options.dataset.near), float(options.dataset.far)
-        from ._train import train_fused_ok
-        from .train_utils import _fusable
-        nets = [m for m in self.models if m is not None]
-        if model_coarse is None or not all(_fusable(m, encode_position_fn, encode_direction_fn) and train_fused_ok(m) and m.use_viewdirs
-                                           for m in nets):
-            raise ValueError("FusedPoseStep: a network outside the fused training kernels (W in {128, 256}, L_xyz in {6, 10}, view "
-                             "directions, precision fp32 / bf16); MultiPoseRefiner differentiates those")
+        if not self._networks_train:
+            self._check_networks(model_coarse, model_fine, encode_position_fn, encode_direction_fn)
+        self.luminance = False
         self.logs = (encode_position_fn.log_sampling, encode_direction_fn.log_sampling)
         dev = self.device = extrinsics0.device
         self.num_rays = min(int(num_rays), self.n_views * self.height * self.width)
@@ -323,11 +328,23 @@ class FusedPoseStep:
         self.fallback_reason = None
         self._keep = None
 
+    def _check_networks(self, model_coarse, model_fine, encode_position_fn, encode_direction_fn):
+        """Host-side: raises ValueError for networks outside the fused training kernels."""
+        from ._train import train_fused_ok
+        from .train_utils import _fusable
+        nets = [m for m in (model_coarse, model_fine) if m is not None]
+        if model_coarse is None or not all(_fusable(m, encode_position_fn, encode_direction_fn) and train_fused_ok(m) and m.use_viewdirs
+                                           for m in nets):
+            raise ValueError(f"{self._who}: a network outside the fused training kernels (W in {{128, 256}}, L_xyz in {{6, 10}}, view "
+                             f"directions, precision fp32 / bf16); {self._other_route}")
+
     def _packs(self):
         """The packed networks (core stream) with their backward and input-gradient streams; brought up to date outside a capture
-        only - the networks are frozen, a captured step reads the streams the eager steps left."""
+        only - the networks are frozen, a captured step reads the streams the eager steps left.  (A step that trains the networks
+        packs every iteration, under capture too: the ensure_* calls and FlexibleNeRFModel._stale re-pack whenever the stream is
+        capturing, so the graph holds the packs of the weights it runs on.)"""
         packs = []
-        capturing = torch.cuda.is_current_stream_capturing()
+        capturing = torch.cuda.is_current_stream_capturing() and not self._networks_train
         for m in self.models:
             if m is None:
                 packs.append(None)
@@ -348,6 +365,17 @@ class FusedPoseStep:
             return _ops.camera_records(self.xi, self.phi, self.e0, self.k, self.intrinsics_scale, self.ndc_focal, **kw)
         return _ops.pose_records(self.xi, self.e0, self.k, self.ndc_focal, **kw)
 
+    def _clear_weight_gradients(self):
+        """Before the backward: nothing to clear, the networks are frozen."""
+
+    def _weight_gradient_views(self):
+        """(views_c, views_f) the geometry backward accumulates the weight gradients into: none, the networks are frozen."""
+        return None, None
+
+    def _update(self):
+        """The optimizer launches that end the iteration: Adam on [xi | phi] at a constant lr, the gradient cleared in the same pass."""
+        _ops.adam_step(self._flat[0], self._flat[1], self._flat[2], self._flat[3], self._adam_state, self.lr, 1.0, (0.9, 0.999), 1e-8, True)
+
     def _enqueue(self):
         pc, pf = self._packs()
         self._records(cams=self.cams)
@@ -356,8 +384,9 @@ class FusedPoseStep:
                                                                ndc_near=1.0)
         maps, saved = _ops.render_rays_train_geom(pc, pf, rays, self.nc, self.nf, self.lindisp, self.noise_std, self.white, [], None,
                                                   prec=pc.precision, rng_state=self.rng_state, perturb=self.perturb)
-        self.loss3, self.loss6, g_c, g_f = fused_loss_head(self.head, maps, target, self.rng_state, False, pix, views)
-        d_rays, keep = _ops.render_rays_backward_geom(pc, pf, saved, g_c, g_f)
+        self.loss3, self.loss6, g_c, g_f = fused_loss_head(self.head, maps, target, self.rng_state, self.luminance, pix, views)
+        self._clear_weight_gradients()
+        d_rays, keep = _ops.render_rays_backward_geom(pc, pf, saved, g_c, g_f, *self._weight_gradient_views())
         g_cams = _ops.camera_grad_views(self.height, self.width, self.cams, views, pix, self.num_rays, d_rays[:, 0:3], d_rays[:, 3:6],
                                         d_rays[:, 8:11], self.ndc_focal or 0.0, 1.0)
         if self.camera_pair:
@@ -366,7 +395,7 @@ class FusedPoseStep:
                                          want_phi=self.phi is not None)
         else:
             _ops.pose_records_backward(g_cams, self.xi, self.e0, out=self._grad, keep=self.last_grad)
-        _ops.adam_step(self._flat[0], self._flat[1], self._flat[2], self._flat[3], self._adam_state, self.lr, 1.0, (0.9, 0.999), 1e-8, True)
+        self._update()
         # alive until the next call (stream-ordered allocator; under capture they belong to the graph's pool)
         self._keep = (views, pix, rays, target, maps, saved, d_rays, g_cams, keep, g_c[0], g_f[0], g_c[1], g_f[1])
 
@@ -414,3 +443,115 @@ class FusedPoseStep:
         out = (self.k if self.k.dim() == 3 else self.k.expand(self.n_views, 3, 3)).clone()
         out[:, 0, 0], out[:, 0, 2], out[:, 1, 2] = cams[:, 12], cams[:, 13], cams[:, 14]
         return out if per_view else out[0]
+
+
+class FusedJointStep(FusedPoseStep):
+    """The training iteration with the cameras as parameters beside the networks: FusedPoseStep's launches with the networks NOT
+    frozen.  One `step()` enqueues, on the current stream and without a host read,
+
+        dn_pose_records | dn_camera_records          [xi | phi] -> camera records (FusedPoseStep's choice rule: camera_pair)
+        dn_select_rays_draw_views                    `num_rays` distinct (view, pixel) pairs, rows, targets (NDC rows with `ndc_focal`)
+        the packs of BOTH networks, every iteration  core stream, backward stream, input-gradient stream (three launches per network;
+                                                     a captured step holds them: it trains the weights it packs)
+        dn_render_rays_train_geom                    coarse + fine render; draws made in the kernels
+        dn_mse2_loss | dn_render_loss                FusedPoseStep's head (depth_images / loss_weights / depth_weights), `luminance`
+        dn_render_rays_backward_geom                 with views_c / views_f: the ray gradient AND the weight gradients of both networks,
+                                                     accumulated into the FlatGradBucket (one pair launch when the two networks share a
+                                                     shape, one launch per network when they do not)
+        dn_camera_grad_views, dn_pose_records_backward | dn_camera_records_backward    -> the gradient of [xi | phi]
+        dn_adam_step on [xi | phi]                   `lr_pose`, times pose_lr_decay[0] ** (t / pose_lr_decay[1]) when given
+        optimizer.step()                             the networks' own optimizer: nerf.FlatAdam on `bucket` (dn_adam_step) with its own
+                                                     learning rate and schedule
+
+    Both Adam steps come after both gradients: the two gradients are taken at the same iterate.  `bucket` (parallel.FlatGradBucket over
+    the two networks) and `optimizer` as GraphedTrainStep takes them: with FlatAdam(zero_grads=True) every step ends with the bucket
+    cleared, otherwise the step clears it (one memset) before the backward.  A parameter whose .grad is no longer the bucket's view
+    raises.  Precision: 'fp32' runs fp32; 'bf16', 'bf16-s8' and 'bf16-s16' run bf16 with 16-bit saved tensors (FusedPoseStep's rule -
+    the geometry entry points refuse the 8-bit saved layout).  Networks: the fused training kernels' set with view directions, a fine
+    network required; coarse and fine need not share a shape.  One rank only.
+
+    The first `eager_iterations` steps run eagerly (they create the pack buffers; the optimizers' moments exist from construction);
+    the next one is captured into one HIP graph and replayed from then on; nerf.models.mark_parameters_updated() follows every step,
+    so a later render packs the trained weights.  If capture fails the loop goes on eagerly and `fallback_reason` says why.
+
+    Gauge: with every view free the scene can drift by a rigid motion (and, with the intrinsics free, a scale) that the loss does not
+    see.  The step does not remove it; `fixed_views=(0,)` pins it to the first camera.  refine_pose=False with refine_intrinsics=None
+    is allowed here (the networks alone are trained, on the step's own mixed-view draws).
+
+    state_dict() / load_state_dict(): [xi | phi], the two Adam moments and dn_adam_step's state record; with the networks', the
+    optimizer's state and first_iteration = the number of steps taken, a fresh step continues the run."""
+
+    _who = "FusedJointStep"
+    _networks_train = True
+    _other_route = "MultiPoseRefiner + autograd (loss.backward() through its loss, torch.optim over the networks) trains those"
+
+    def __init__(self, model_coarse, model_fine, options, height, width, intrinsic, extrinsics0, images, encode_position_fn,
+                 encode_direction_fn, num_rays, bucket, optimizer, lr_pose, pose_lr_decay=None, luminance=False, **kw):
+        from .parallel import world_info
+        if pose_lr_decay is not None:
+            factor, steps = float(pose_lr_decay[0]), float(pose_lr_decay[1])
+            if not (0.0 < factor < float("inf") and 0.0 < steps < float("inf")):
+                raise ValueError(f"FusedJointStep: pose_lr_decay is (factor > 0, steps > 0) (got {pose_lr_decay!r})")
+        if not float(lr_pose) >= 0.0:
+            raise ValueError(f"FusedJointStep: lr_pose must be >= 0 (got {lr_pose!r})")
+        if world_info()[1] > 1:
+            raise ValueError("FusedJointStep: one rank only (multi-GPU joint training is not supported)")
+        super().__init__(model_coarse, model_fine, options, height, width, intrinsic, extrinsics0, images, encode_position_fn,
+                         encode_direction_fn, num_rays, lr_pose, **kw)
+        if self.nf <= 0:
+            raise ValueError("FusedJointStep: num_fine must be > 0 (the step trains a coarse and a fine network)")
+        sinks = [getattr(m, "_grad_sink", None) for m in self.models]
+        if any(s is None or s.bucket is not bucket for s in sinks):
+            raise ValueError("FusedJointStep: `bucket` is the parallel.FlatGradBucket built over both networks")
+        self.bucket, self.opt = bucket, optimizer
+        self.luminance = bool(luminance)
+        self.lr_decay_per_step = 1.0 if pose_lr_decay is None else factor ** (1.0 / steps)
+        self.zero_in_step = not getattr(optimizer, "zero_grads", False)
+        if not self.zero_in_step:
+            bucket.flat.zero_()         # every step ends with the bucket cleared
+
+    def _check_networks(self, model_coarse, model_fine, encode_position_fn, encode_direction_fn):
+        if model_fine is None:
+            raise ValueError(f"FusedJointStep: a fine network is required; {self._other_route}")
+        super()._check_networks(model_coarse, model_fine, encode_position_fn, encode_direction_fn)
+
+    def _clear_weight_gradients(self):
+        """The backward accumulates: one memset of the bucket, unless the optimizer leaves it cleared (FlatAdam(zero_grads=True))."""
+        if self.zero_in_step:
+            self.bucket.flat.zero_()
+
+    def _weight_gradient_views(self):
+        mc, mf = self.models
+        views_c, views_f = mc._grad_sink.views(mc), mf._grad_sink.views(mf)
+        if views_c is None or views_f is None:
+            raise RuntimeError("FusedJointStep: a parameter's .grad is no longer the FlatGradBucket's view")
+        return views_c, views_f
+
+    def _update(self):
+        _ops.adam_step(self._flat[0], self._flat[1], self._flat[2], self._flat[3], self._adam_state, self.lr, self.lr_decay_per_step,
+                       (0.9, 0.999), 1e-8, True)
+        self.opt.step()
+
+    def step(self):
+        """One training iteration.  Returns loss3 (device, [loss, mse_coarse, mse_fine]); nothing is read back."""
+        from .models import mark_parameters_updated
+        loss3 = super().step()
+        mark_parameters_updated()      # a replayed optimizer step ran no Python hook
+        return loss3
+
+    def state_dict(self):
+        """The camera half of the run: the flat buffer's rows [xi | phi | pad], exp_avg and exp_avg_sq, and dn_adam_step's state record
+        (raw words: the step count and the running products), as independent tensors."""
+        return dict(params=self._flat[0].detach().clone(), exp_avg=self._flat[2].detach().clone(), exp_avg_sq=self._flat[3].detach().clone(),
+                    adam_state=self._adam_state.detach().clone(), n_views=self.n_views, refine_intrinsics=self.mode)
+
+    def load_state_dict(self, state):
+        if int(state["n_views"]) != self.n_views or state["refine_intrinsics"] != self.mode \
+                or tuple(state["params"].shape) != tuple(self._flat[0].shape):
+            raise ValueError(f"FusedJointStep.load_state_dict: a state of {state['n_views']} views, refine_intrinsics="
+                             f"{state['refine_intrinsics']!r} for a step of {self.n_views} views, refine_intrinsics={self.mode!r}")
+        self._flat[0].copy_(state["params"])
+        self._flat[1].zero_()
+        self._flat[2].copy_(state["exp_avg"])
+        self._flat[3].copy_(state["exp_avg_sq"])
+        self._adam_state.copy_(state["adam_state"])

@@ -116,7 +116,50 @@ def llff_dataset(args, dev):
                 bounds=(float(bds.min()) * 0.9, float(bds.max()) * 1.0))
 
 
-def main(argv=None):
+JOINT_KEY = "joint_step_state_dict"      # checkpoint key of nerf.FusedJointStep.state_dict() (--refine-poses)
+
+
+def pose_distance(extrinsics, reference):
+    """(mean rotation angle in degrees, mean distance of the camera centres) between two (V,4,4) sets of world->camera extrinsics."""
+    a, b = extrinsics.detach().double().cpu(), reference.detach().double().cpu()
+    rel = a[:, :3, :3] @ b[:, :3, :3].transpose(1, 2)
+    cos = (rel.diagonal(dim1=1, dim2=2).sum(-1) - 1.0) * 0.5
+    skew = torch.stack([rel[:, 2, 1] - rel[:, 1, 2], rel[:, 0, 2] - rel[:, 2, 0], rel[:, 1, 0] - rel[:, 0, 1]], dim=1)
+    angle = torch.atan2(skew.norm(dim=1) * 0.5, cos)      # (well conditioned at 0, where acos is not)
+    centre = lambda e: -(e[:, :3, :3].transpose(1, 2) @ e[:, :3, 3:]).squeeze(-1)  # noqa: E731
+    return float(torch.rad2deg(angle).mean()), float((centre(a) - centre(b)).norm(dim=1).mean())
+
+
+def perturbed_poses(extrinsics, rot, trans, seed, keep=()):
+    """--pose-noise: E_v <- se3_exp(xi_v) E_v with seeded twists, |omega_v| = rot (radians), |t_v| = trans, directions uniform on the
+    sphere; the views in `keep` (the gauge: --fix-views) stay as given.  (V,4,4) fp32 on the device of `extrinsics`."""
+    gen = torch.Generator().manual_seed(int(seed))
+    n = int(extrinsics.shape[0])
+    unit = lambda: torch.nn.functional.normalize(torch.randn(n, 3, generator=gen, dtype=torch.float64), dim=1)  # noqa: E731
+    xi = torch.cat([unit() * float(rot), unit() * float(trans)], dim=1)
+    host = extrinsics.detach().double().cpu()
+    out = [host[v] if v in keep else nerf.se3_exp(xi[v]) @ host[v] for v in range(n)]
+    return torch.stack(out).to(extrinsics.device, torch.float32)
+
+
+def joint_checkpoint_entries(joint, train_ids, extrinsics0):
+    """What --refine-poses adds to the checkpoint dict: the step's state, and the cameras as plain host tensors for other tools (eval_nerf.py --use-refined-poses)."""
+    return {JOINT_KEY: joint.state_dict(), "refined_views": [int(v) for v in train_ids],
+            "refined_extrinsics": joint.extrinsics().cpu(), "refined_intrinsics": joint.intrinsics().cpu(),
+            "joint_initial_extrinsics": extrinsics0.detach().cpu()}
+
+
+def restore_joint_state(ck, joint):
+    """--load-checkpoint with --refine-poses: the step's state from the checkpoint dict.  False (and nothing is touched) for a
+    checkpoint without the key - one written without --refine-poses, or by the reference."""
+    state = ck.get(JOINT_KEY)
+    if state is None:
+        return False
+    joint.load_state_dict(state)
+    return True
+
+
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=2000)
     ap.add_argument("--size", type=int, default=100, help="image height = width of the synthetic views")
@@ -181,7 +224,52 @@ def main(argv=None):
     ap.add_argument("--depth-range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
                     help="pixels whose depth lies strictly inside (LO, HI) are supervised; default: the Dex validation mask, 0 to the "
                          "dataset's mask_hi")
+    ap.add_argument("--refine-poses", action="store_true",
+                    help="train the cameras of the training views together with the networks (nerf.FusedJointStep: twists on the given "
+                         "poses under their own Adam, in the same replayed step); implies --mix-views.  Training views are then rendered at "
+                         "their refined cameras; held-out views keep their given poses")
+    ap.add_argument("--pose-lr", type=float, default=None, help="--refine-poses: learning rate of the twists (and intrinsics); default 1e-3")
+    ap.add_argument("--pose-lr-decay", type=float, nargs=2, default=None, metavar=("FACTOR", "STEPS"),
+                    help="--refine-poses: the pose learning rate is multiplied by FACTOR ** (iteration / STEPS)")
+    ap.add_argument("--refine-intrinsics", default=None, choices=["shared", "per_view"],
+                    help="--refine-poses: refine fx, cx, cy as well, one set for all training views or one per view")
+    ap.add_argument("--intrinsics-scale", type=float, default=None,
+                    help="--refine-intrinsics: size of an intrinsics step relative to a twist step (default 1)")
+    ap.add_argument("--fix-views", type=int, nargs="+", default=None, metavar="I",
+                    help="--refine-poses: training views (positions in the training set) whose poses stay as given; default 0 - with "
+                         "every view free the scene can drift by a rigid motion, one fixed camera pins it")
+    ap.add_argument("--pose-noise", type=float, nargs=2, default=None, metavar=("ROT", "TRANS"),
+                    help="perturb the loaded training poses (all but --fix-views) by seeded twists of ROT radians and TRANS scene units "
+                         "before training: for experiments and tests")
+    return ap
+
+
+def parse_args(argv=None):
+    """The command line, checked: inconsistent combinations end in the parser's error (SystemExit 2)."""
+    ap = build_parser()
     args = ap.parse_args(argv)
+    if not args.refine_poses:
+        for flag, value in (("--pose-lr", args.pose_lr), ("--pose-lr-decay", args.pose_lr_decay), ("--refine-intrinsics", args.refine_intrinsics),
+                            ("--intrinsics-scale", args.intrinsics_scale), ("--fix-views", args.fix_views)):
+            if value is not None:
+                ap.error(f"{flag} needs --refine-poses")
+    else:
+        if args.autograd_step:
+            ap.error("--refine-poses runs on the fused step (nerf.FusedJointStep), not with --autograd-step")
+        if args.pose_lr is not None and not args.pose_lr >= 0.0:
+            ap.error("--pose-lr must be >= 0")
+        if args.pose_lr_decay is not None and not (args.pose_lr_decay[0] > 0.0 and args.pose_lr_decay[1] > 0.0):
+            ap.error("--pose-lr-decay FACTOR STEPS: both > 0")
+        if args.intrinsics_scale is not None and (args.refine_intrinsics is None or not args.intrinsics_scale > 0.0):
+            ap.error("--intrinsics-scale needs --refine-intrinsics and must be > 0")
+        if args.fix_views is not None and min(args.fix_views) < 0:
+            ap.error("--fix-views: positions in the training set, >= 0")
+        args.pose_lr = 1e-3 if args.pose_lr is None else args.pose_lr
+        args.intrinsics_scale = 1.0 if args.intrinsics_scale is None else args.intrinsics_scale
+        args.fix_views = [0] if args.fix_views is None else args.fix_views
+        args.mix_views = True
+    if args.pose_noise is not None and not (args.pose_noise[0] >= 0.0 and args.pose_noise[1] >= 0.0):
+        ap.error("--pose-noise ROT TRANS: both >= 0")
     if args.depth_weight < 0.0:
         ap.error("--depth-weight must be >= 0")
     if args.depth_weight > 0.0:
@@ -190,6 +278,11 @@ def main(argv=None):
         if args.autograd_step:
             ap.error("--depth-weight runs on the fused step (nerf.FusedTrainStep), not with --autograd-step")
         args.mix_views = True
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     user_bounds = args.near is not None or args.far is not None
     args.ndc = bool(args.llff) and not args.no_ndc
     if args.ndc:
@@ -284,6 +377,52 @@ def main(argv=None):
         head = dict(depth_images=torch.stack([depths[v].reshape(hw).to(torch.float32) for v in train_ids]),
                     depth_weights=(args.depth_weight, args.depth_weight),
                     depth_range=tuple(args.depth_range) if args.depth_range else (0.0, float(data["mask_hi"])))
+    joint = given_extrinsics = extrinsics0 = None
+    if args.refine_poses or args.pose_noise is not None:
+        given_extrinsics = torch.stack([poses[v].to(torch.float32) for v in train_ids])
+        extrinsics0 = given_extrinsics
+        if args.load_checkpoint and "joint_initial_extrinsics" in ck:       # the poses the saved twists are relative to
+            extrinsics0 = torch.as_tensor(ck["joint_initial_extrinsics"], dtype=torch.float32, device=dev)
+        elif args.pose_noise is not None:
+            extrinsics0 = perturbed_poses(given_extrinsics, args.pose_noise[0], args.pose_noise[1], args.seed + 31337,
+                                          keep=tuple(args.fix_views or ()) if args.refine_poses else ())
+        if not args.refine_poses:       # training at the perturbed poses: the selector's records are rebuilt from them
+            selector = nerf.MultiViewRaySelector(hw[0], hw[1], list(extrinsics0), [intrinsics[v] for v in train_ids], args.near, args.far,
+                                                 images=selector.images, device=dev)
+    if args.refine_poses:
+        if world > 1:
+            raise SystemExit("--refine-poses: one GPU only (nerf.FusedJointStep)")
+        if not fused_ok:
+            raise SystemExit("--refine-poses: this configuration is outside nerf.FusedJointStep (see FusedTrainStep.applicable); "
+                             "nerf.MultiPoseRefiner + autograd covers those")
+        if max(args.fix_views) >= len(train_ids):
+            raise SystemExit(f"--fix-views {args.fix_views}: the training set has {len(train_ids)} views")
+        joint = nerf.FusedJointStep(student[0], student[1], cfg, hw[0], hw[1], torch.stack([intrinsics[v] for v in train_ids]), extrinsics0,
+                                    selector.images, ex, ed, args.num_random_rays, bucket, opt, args.pose_lr,
+                                    pose_lr_decay=args.pose_lr_decay, luminance=args.ir, seed=args.seed, first_iteration=start,
+                                    ndc_focal=ndc_focal, use_graphs=use_graph, eager_iterations=3, refine_intrinsics=args.refine_intrinsics,
+                                    intrinsics_scale=args.intrinsics_scale, fixed_views=args.fix_views, **head)
+        if args.load_checkpoint:
+            restore_joint_state(ck, joint)
+        fused_ok = False                # the joint step is the training iteration
+
+    def camera_of(view):
+        """(extrinsic, K) a view is rendered at: a training view under --refine-poses at its refined camera, any other as given."""
+        if joint is not None and view in train_ids:
+            k_now = joint.intrinsics()
+            return joint.extrinsics()[train_ids.index(view)], (k_now[train_ids.index(view)] if k_now.dim() == 3 else k_now)
+        return poses[view], intrinsics[view]
+
+    def log_pose_distances(it):
+        current = joint.extrinsics()
+        rot0, trans0 = pose_distance(current, extrinsics0)
+        text = f"[pose]  iter {it:6d} from the initial poses: {rot0:.4f} deg, {trans0:.5f}"
+        if args.pose_noise is not None:
+            rot1, trans1 = pose_distance(current, given_extrinsics)
+            text += f"; from the unperturbed poses: {rot1:.4f} deg, {trans1:.5f}"
+        if not args.quiet:
+            print(text, flush=True)
+
     if fused_ok:
         fused = nerf.FusedTrainStep(student[0], student[1], selector, cfg, bucket, ex, ed, args.num_random_rays, seed=args.seed + 7919 * rank,
                                     luminance=args.ir, first_iteration=start, draw_view="rays" if args.mix_views else True,
@@ -325,7 +464,7 @@ def main(argv=None):
     t_steady = None
     loss_val = psnr = float("nan")
     for it in range(start, args.iters):
-        if fused is None:                                                            # (the fused step draws its view in the kernel)
+        if fused is None and joint is None:                                          # (the fused steps draw their views in the kernel)
             selector.view.fill_(int(np.random.randint(len(train_ids))))              # one random training view per iteration
         lr = args.lr * args.lr_decay_factor ** (it / (args.lr_decay * 1000))         # train_dexnerf_rgb.py:284-289
         if not flat_adam:
@@ -333,7 +472,12 @@ def main(argv=None):
         if it == start + 20:                   # past the eager iterations and the capture: the steady part is timed from here
             torch.cuda.synchronize()
             t_steady = time.perf_counter()
-        if graphed is not None:
+        if joint is not None:
+            joint.step()
+            if joint.fallback_reason and not args.quiet and not graph_warned:
+                graph_warned = True
+                print(f"[train] HIP-graph capture unavailable ({joint.fallback_reason}); launching eagerly", flush=True)
+        elif graphed is not None:
             graphed.step()
             if graphed.fallback_reason and rank == 0 and not args.quiet and not graph_warned:
                 graph_warned = True
@@ -360,7 +504,7 @@ def main(argv=None):
         else:
             iteration()
         if it % 100 == 0 or it == args.iters - 1:
-            loss_val = (fused.loss3[0] if fused is not None else loss_t).item()
+            loss_val = (joint.loss3[0] if joint is not None else fused.loss3[0] if fused is not None else loss_t).item()
             psnr = nerf.mse2psnr(loss_val)
             history.append((it, loss_val, psnr))
             if rank == 0 and not args.quiet:
@@ -375,7 +519,9 @@ def main(argv=None):
                           f"(scale {s8['scale']}): the loss is outside the range the fixed gradient scale covers (a sum-reduced or "
                           "scaled loss?) - pass --s8-grad-scale 0 (per-launch scale) or a smaller power of two", flush=True)
         if rank == 0 and args.validate_every and (it + 1) % args.validate_every == 0:
-            out = render_view(student, cfg, poses[held_out], intrinsics[held_out], hw, ex, ed, thres)
+            if joint is not None:
+                log_pose_distances(it + 1)
+            out = render_view(student, cfg, *camera_of(held_out), hw, ex, ed, thres)
             vmse = nerf.img2mse(out[3].reshape(-1, 3), images[held_out]).item()
             if depths[held_out] is None:     # (LLFF captures carry no depth maps: no Dex threshold sweep)
                 if not args.quiet:
@@ -391,13 +537,20 @@ def main(argv=None):
                   rays_per_s=world * args.num_random_rays * (args.iters - start) / max(elapsed, 1e-9))
     if t_steady is not None and args.iters - start > 20:
         result["steady_ms_per_iter"] = (t0 + elapsed - t_steady) * 1e3 / (args.iters - start - 20)
-    result["hip_graphs"] = len(graphed.graphs) if (graphed is not None and graphed.graphs) else int(graph is not None)   # graphs replayed per iteration
+    if joint is not None:
+        result["hip_graphs"] = int(joint.graph is not None)
+        result["pose_from_initial"] = pose_distance(joint.extrinsics(), extrinsics0)      # (degrees, scene units), means over the views
+        if args.pose_noise is not None:
+            result["pose_from_unperturbed"] = pose_distance(joint.extrinsics(), given_extrinsics)
+        result["xi"] = joint.xi.detach().cpu()
+    else:
+        result["hip_graphs"] = len(graphed.graphs) if (graphed is not None and graphed.graphs) else int(graph is not None)   # graphs replayed per iteration
     if args.precision in ("bf16", "bf16-s8"):
         result["s8_saturated_max"] = s8_saturated_max
     if args.save and rank != 0 and os.environ.get("DEXNERF_SAVE_ALL_RANKS"):   # rehearsals: compare the replicas
         torch.save({"model_coarse_state_dict": student[0].state_dict(), "model_fine_state_dict": student[1].state_dict()}, args.save)
     if rank == 0:
-        out = render_view(student, cfg, poses[held_out], intrinsics[held_out], hw, ex, ed, thres)
+        out = render_view(student, cfg, *camera_of(held_out), hw, ex, ed, thres)
         result["val_psnr"] = nerf.mse2psnr(nerf.img2mse(out[3].reshape(-1, 3), images[held_out]).item())
         if depths[held_out] is not None:
             m_best, err = dex_sweep(out, depths[held_out], thres, data["mask_hi"])
@@ -409,9 +562,10 @@ def main(argv=None):
             opt_state = opt.state_dict()
             for group in opt_state["param_groups"]:   # the reference stores a Python float (train_dexnerf_rgb.py:443-456), not the
                 group["lr"] = float(group["lr"])     # device scalar the captured graph reads the schedule from
+            extra = joint_checkpoint_entries(joint, train_ids, extrinsics0) if joint is not None else {}
             torch.save({"iter": args.iters, "model_coarse_state_dict": student[0].state_dict(),
                         "model_fine_state_dict": student[1].state_dict(), "optimizer_state_dict": opt_state,
-                        "loss": loss_val, "psnr": psnr}, args.save)
+                        "loss": loss_val, "psnr": psnr, **extra}, args.save)
         if not args.quiet:
             print(f"[done] {args.iters - start} iters in {elapsed:.1f} s = {result['rays_per_s']:.0f} rays/s; "
                   f"held-out psnr {result['val_psnr']:.2f} dB", flush=True)
