@@ -1,10 +1,12 @@
 // Library-level entry points: error string, ABI version, and the fused predict_and_render_radiance
 // forward (reference nerf/train_utils.py:92-202) sequenced on one stream from the per-stage kernels.
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <utility>
 #include <vector>
 
+#include "../../include/dexnerf_hip_ext.h"
 #include "dn_common.h"
 #include "composite_body.h"
 #include "dn_rng.h"
@@ -99,6 +101,30 @@ static DepthWorkspace carve_depth(void* base, int64_t n, int nc, int nf) {
     w.rf_f = take(static_cast<size_t>(n) * (nc + nf) * 4);
   }
   w.status = reinterpret_cast<unsigned*>(take(64));
+  w.bytes = off;
+  return w;
+}
+
+// the distortion regulariser inside the render backward (dn_render_rays_backward_reg): one network at a time, the launches are
+// stream-ordered.  The coarse weights need no room: the training forward left them in Workspace::w_c.
+struct RegWorkspace {
+  float *weights, *g_weights;   // (N, num_coarse + num_fine): the fine network's sample weights; dn_distortion_loss's gradient of either network
+  double* ray_loss;             // (N)
+  size_t bytes;
+};
+
+static RegWorkspace carve_reg(void* base, int64_t n, int nc, int nf) {
+  RegWorkspace w{};
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    void* p = base ? static_cast<void*>(static_cast<char*>(base) + off) : nullptr;
+    off += align256(bytes);
+    return p;
+  };
+  const size_t samples = static_cast<size_t>(n) * (nc + nf);
+  w.weights = static_cast<float*>(take(samples * sizeof(float)));
+  w.g_weights = static_cast<float*>(take(samples * sizeof(float)));
+  w.ray_loss = static_cast<double*>(take(static_cast<size_t>(n) * sizeof(double)));
   w.bytes = off;
   return w;
 }
@@ -324,6 +350,7 @@ struct BackwardNet {   // what one network brings
   const void *act, *masks;
   void* grads;
   float* const *h_dW, *const *h_db;
+  float dist_weight = 0.0f;   // the weight of the network's distortion term (dn_render_rays_backward_reg); 0: none
 };
 
 struct RenderBackwardArgs {
@@ -343,6 +370,9 @@ struct RenderBackwardArgs {
   void* geom_workspace;
   int lindisp, perturb;
   const float *t_rand, *z_samples;
+  // the distortion regulariser, for a network whose dist_weight is non-zero: reg_workspace as carve_reg lays it out
+  void* reg_workspace;
+  float* reg2;   // [mean L_ray coarse, mean L_ray fine]
 };
 
 static int render_rays_backward(const RenderBackwardArgs& a) {
@@ -351,6 +381,7 @@ static int render_rays_backward(const RenderBackwardArgs& a) {
   const int nc = a.num_coarse, nf = a.num_fine;
   const Workspace w = carve(a.workspace, n_rays, nc, nf, true);
   const GeomWorkspace g = geom ? carve_geom(a.geom_workspace, a.coarse.desc, a.fine.desc, n_rays, a.ray_stride, nc, nf) : GeomWorkspace{};
+  const RegWorkspace reg = carve_reg(a.reg_workspace, n_rays, nc, nf);
   int rc;
   // both networks, one architecture: the two backward-data chains first, then ONE weight-gradient launch for the layers of both
   // (dn_mlp_weight_grad_pair) - a caller that wants the fine half finished early (its all-reduce under the coarse half) asks for
@@ -359,7 +390,23 @@ static int render_rays_backward(const RenderBackwardArgs& a) {
                           std::memcmp(a.coarse.desc, a.fine.desc, sizeof(dn_mlp_desc)) == 0 &&
                           weight_grad_pair_fits(*a.fine.desc);   // (both networks' layers in one batch: two D <= 12 networks)
   auto half = [&](const BackwardNet& net, const float* rf, const float* z, int samples, uint32_t noise_stream, float* g_z, float* g_rd,
-                  float* d_rays_net, float* d_z) -> int {
+                  float* d_rays_net, float* d_z, const float* kept_weights, float* reg_word) -> int {
+    // the distortion term: the network's sample weights (as the forward kept them, or composited again - the same kernel, rows and
+    // noise stream, so the same bits), dn_distortion_loss, and its gradient as the compositing backward's upstream g_weights
+    const float* g_weights = nullptr;
+    if (net.dist_weight != 0.0f) {
+      const float* weights = kept_weights;
+      if (weights == nullptr) {
+        if ((rc = volume_render_counting(rf, z, a.rays + 3, a.ray_stride, net.noise, a.noise_std, a.white_background, nullptr, 0, n_rays, samples,
+                                         nullptr, nullptr, nullptr, reg.weights, nullptr, nullptr, nullptr, a.stream, a.rng_state, noise_stream)))
+          return rc;
+        weights = reg.weights;
+      }
+      if ((rc = dn_distortion_loss(weights, z, a.rays + 6, a.ray_stride, n_rays, samples, net.dist_weight / static_cast<float>(n_rays),
+                                   reg.g_weights, nullptr, 0, reg.ray_loss, reg_word, a.stream)))
+        return rc;
+      g_weights = reg.g_weights;
+    }
     // 8-bit saved tensors with the per-launch gradient scale: the compositing backward leaves the largest |gradient| of each of its
     // workgroups behind, and the network backward reduces those words itself - no pass over g_rf in between (a few thousand words at
     // most: beyond that the separate reduction kernel is the cheaper one)
@@ -369,7 +416,7 @@ static int render_rays_backward(const RenderBackwardArgs& a) {
                           ? w.absmax_part : nullptr;
     if ((rc = volume_render_backward_rng(geom ? "dn_volume_render_backward_geom" : "dn_volume_render_backward", rf, z, a.rays + 3, a.ray_stride,
                                          net.noise, a.noise_std, a.white_background, n_rays, samples, net.g_rgb, net.g_depth, net.g_acc, nullptr,
-                                         nullptr, w.g_rf, g_z, g_rd, a.rng_state, noise_stream, parts, a.stream)))
+                                         g_weights, w.g_rf, g_z, g_rd, a.rng_state, noise_stream, parts, a.stream)))
       return rc;
     const int64_t n_points = n_rays * samples;
     if ((rc = mlp_backward_data_partials(net.desc, a.precision, net.packed_bwd, w.g_rf, net.masks, n_points, net.grads, parts,
@@ -385,8 +432,10 @@ static int render_rays_backward(const RenderBackwardArgs& a) {
   };
   // the fine network first: autograd's order too (its graph node is the younger one), and the half a data-parallel caller
   // wants finished first so that its all-reduce overlaps the coarse half; its depth gradient feeds the coarse depths through the merge
-  if ((a.nets & 2) && fine && (rc = half(a.fine, w.rf_f, w.z_f, nc + nf, kRngStreamNoiseFine, g.g_z_f, g.g_rd_f, g.d_rays_f, g.d_z_f))) return rc;
-  if ((a.nets & 1) && (rc = half(a.coarse, w.rf_c, w.z_c, nc, kRngStreamNoiseCoarse, g.g_z_c, g.g_rd_c, g.d_rays_c, g.d_z_c))) return rc;
+  if ((a.nets & 2) && fine && (rc = half(a.fine, w.rf_f, w.z_f, nc + nf, kRngStreamNoiseFine, g.g_z_f, g.g_rd_f, g.d_rays_f, g.d_z_f, nullptr,
+                                            a.reg2 ? a.reg2 + 1 : nullptr)))
+    return rc;
+  if ((a.nets & 1) && (rc = half(a.coarse, w.rf_c, w.z_c, nc, kRngStreamNoiseCoarse, g.g_z_c, g.g_rd_c, g.d_rays_c, g.d_z_c, w.w_c, a.reg2))) return rc;
   if (pair_wgrad &&
       (rc = dn_mlp_weight_grad_pair_ws(a.fine.desc, a.precision, a.fine.act, a.fine.grads, n_rays * (nc + nf), a.fine.h_dW, a.fine.h_db,
                                        a.coarse.act, a.coarse.grads, n_rays * nc, a.coarse.h_dW, a.coarse.h_db, a.wg_scratch,
@@ -403,6 +452,47 @@ static int render_rays_backward(const RenderBackwardArgs& a) {
 }
 }  // namespace dn
 
+// dn_render_rays_backward_ws and dn_render_rays_backward_reg (`name`: the entry point, for messages; without the regulariser: weights 0)
+static int render_rays_backward_entry(const char* name, const dn_mlp_desc* desc_coarse, const void* packed_bwd_coarse,
+                                      const dn_mlp_desc* desc_fine, const void* packed_bwd_fine, int precision,
+                                      const float* rays, int ray_stride, int64_t n_rays, int num_coarse, int num_fine,
+                                      float noise_std, int white_background, const float* noise_c, const float* noise_f,
+                                      const float* g_rgb_c, const float* g_depth_c, const float* g_acc_c,
+                                      const float* g_rgb_f, const float* g_depth_f, const float* g_acc_f, void* workspace,
+                                      const void* act_c, const void* masks_c, void* grads_c, const void* act_f,
+                                      const void* masks_f, void* grads_f, float* const* h_dW_c, float* const* h_db_c,
+                                      float* const* h_dW_f, float* const* h_db_f, int nets, const uint32_t* rng_state,
+                                      void* wg_scratch, size_t wg_scratch_bytes, float dist_weight_c, float dist_weight_f,
+                                      void* reg_workspace, size_t reg_workspace_bytes, float* reg2, dn_stream_t stream) {
+  if (n_rays == 0) return 0;
+  // every argument is judged before any GPU work
+  DN_REQUIRE(rays && workspace && n_rays >= 0 && (nets & ~3) == 0 && (wg_scratch != nullptr || wg_scratch_bytes == 0), "%s: bad arguments", name);
+  DN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "%s: workspace must be 256-byte aligned", name);
+  DN_REQUIRE(std::isfinite(dist_weight_c) && std::isfinite(dist_weight_f) && dist_weight_c >= 0.0f && dist_weight_f >= 0.0f,
+             "%s: the distortion weights must be finite and >= 0", name);
+  if (num_fine <= 0 || !(nets & 2)) dist_weight_f = 0.0f;   // (a network outside this call brings no term)
+  if (!(nets & 1)) dist_weight_c = 0.0f;
+  if (dist_weight_c != 0.0f || dist_weight_f != 0.0f) {
+    DN_REQUIRE(num_coarse >= 1 && num_fine >= 0 && ray_stride >= 8, "%s: bad sample counts / ray stride", name);
+    DN_REQUIRE((dist_weight_f != 0.0f ? num_coarse + num_fine : num_coarse) <= 1024, "%s: the distortion term takes at most 1024 samples per ray", name);
+    DN_REQUIRE(reg_workspace && reg2, "%s: a non-zero distortion weight needs reg_workspace and reg2", name);
+    DN_REQUIRE((reinterpret_cast<uintptr_t>(reg_workspace) & 255) == 0, "%s: reg_workspace must be 256-byte aligned", name);
+    const size_t need = carve_reg(nullptr, n_rays, num_coarse, num_fine).bytes;
+    DN_REQUIRE(reg_workspace_bytes >= need, "%s: reg_workspace too small (%zu bytes needed)", name, need);
+  }
+  RenderBackwardArgs a{};
+  a.coarse = BackwardNet{desc_coarse, packed_bwd_coarse, nullptr, noise_c, g_rgb_c, g_depth_c, g_acc_c, act_c, masks_c, grads_c, h_dW_c, h_db_c};
+  a.fine = BackwardNet{desc_fine, packed_bwd_fine, nullptr, noise_f, g_rgb_f, g_depth_f, g_acc_f, act_f, masks_f, grads_f, h_dW_f, h_db_f};
+  auto complete = [](const BackwardNet& n) { return n.desc && n.packed_bwd && n.act && n.masks && n.grads && n.h_dW && n.h_db; };
+  DN_REQUIRE((!((nets & 2) && num_fine > 0) || complete(a.fine)) && (!(nets & 1) || complete(a.coarse)), "%s: a network's buffers are missing", name);
+  a.coarse.dist_weight = dist_weight_c; a.fine.dist_weight = dist_weight_f;
+  a.precision = precision; a.rays = rays; a.ray_stride = ray_stride; a.n_rays = n_rays;
+  a.num_coarse = num_coarse; a.num_fine = num_fine; a.noise_std = noise_std; a.white_background = white_background; a.workspace = workspace;
+  a.nets = nets; a.wgrad = true; a.rng_state = rng_state; a.wg_scratch = wg_scratch; a.wg_scratch_bytes = wg_scratch_bytes; a.stream = stream;
+  a.reg_workspace = reg_workspace; a.reg2 = reg2;
+  return render_rays_backward(a);
+}
+
 extern "C" int dn_render_rays_backward_ws(const dn_mlp_desc* desc_coarse, const void* packed_bwd_coarse,
                                           const dn_mlp_desc* desc_fine, const void* packed_bwd_fine, int precision,
                                           const float* rays, int ray_stride, int64_t n_rays, int num_coarse, int num_fine,
@@ -413,20 +503,34 @@ extern "C" int dn_render_rays_backward_ws(const dn_mlp_desc* desc_coarse, const 
                                           const void* masks_f, void* grads_f, float* const* h_dW_c, float* const* h_db_c,
                                           float* const* h_dW_f, float* const* h_db_f, int nets, const uint32_t* rng_state,
                                           void* wg_scratch, size_t wg_scratch_bytes, dn_stream_t stream) {
-  if (n_rays == 0) return 0;
-  // every argument is judged before any GPU work
-  DN_REQUIRE(rays && workspace && n_rays >= 0 && (nets & ~3) == 0 && (wg_scratch != nullptr || wg_scratch_bytes == 0), "dn_render_rays_backward: bad arguments");
-  DN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "dn_render_rays_backward: workspace must be 256-byte aligned");
-  RenderBackwardArgs a{};
-  a.coarse = BackwardNet{desc_coarse, packed_bwd_coarse, nullptr, noise_c, g_rgb_c, g_depth_c, g_acc_c, act_c, masks_c, grads_c, h_dW_c, h_db_c};
-  a.fine = BackwardNet{desc_fine, packed_bwd_fine, nullptr, noise_f, g_rgb_f, g_depth_f, g_acc_f, act_f, masks_f, grads_f, h_dW_f, h_db_f};
-  auto complete = [](const BackwardNet& n) { return n.desc && n.packed_bwd && n.act && n.masks && n.grads && n.h_dW && n.h_db; };
-  DN_REQUIRE((!((nets & 2) && num_fine > 0) || complete(a.fine)) && (!(nets & 1) || complete(a.coarse)),
-             "dn_render_rays_backward: a network's buffers are missing");
-  a.precision = precision; a.rays = rays; a.ray_stride = ray_stride; a.n_rays = n_rays;
-  a.num_coarse = num_coarse; a.num_fine = num_fine; a.noise_std = noise_std; a.white_background = white_background; a.workspace = workspace;
-  a.nets = nets; a.wgrad = true; a.rng_state = rng_state; a.wg_scratch = wg_scratch; a.wg_scratch_bytes = wg_scratch_bytes; a.stream = stream;
-  return render_rays_backward(a);
+  return render_rays_backward_entry("dn_render_rays_backward", desc_coarse, packed_bwd_coarse, desc_fine, packed_bwd_fine, precision, rays, ray_stride,
+                                    n_rays, num_coarse, num_fine, noise_std, white_background, noise_c, noise_f, g_rgb_c, g_depth_c, g_acc_c, g_rgb_f,
+                                    g_depth_f, g_acc_f, workspace, act_c, masks_c, grads_c, act_f, masks_f, grads_f, h_dW_c, h_db_c, h_dW_f, h_db_f,
+                                    nets, rng_state, wg_scratch, wg_scratch_bytes, 0.0f, 0.0f, nullptr, 0, nullptr, stream);
+}
+
+// ---- the same backward with the distortion regulariser (include/dexnerf_hip_ext.h) ---------------------------------------------------------
+extern "C" size_t dn_render_reg_workspace_bytes(int64_t n_rays, int num_coarse, int num_fine) {
+  if (n_rays < 0 || num_coarse < 1 || num_fine < 0) return 0;
+  return carve_reg(nullptr, n_rays, num_coarse, num_fine).bytes;
+}
+
+extern "C" int dn_render_rays_backward_reg(const dn_mlp_desc* desc_coarse, const void* packed_bwd_coarse,
+                                           const dn_mlp_desc* desc_fine, const void* packed_bwd_fine, int precision,
+                                           const float* rays, int ray_stride, int64_t n_rays, int num_coarse, int num_fine,
+                                           float noise_std, int white_background, const float* noise_c, const float* noise_f,
+                                           const float* g_rgb_c, const float* g_depth_c, const float* g_acc_c,
+                                           const float* g_rgb_f, const float* g_depth_f, const float* g_acc_f, void* workspace,
+                                           const void* act_c, const void* masks_c, void* grads_c, const void* act_f,
+                                           const void* masks_f, void* grads_f, float* const* h_dW_c, float* const* h_db_c,
+                                           float* const* h_dW_f, float* const* h_db_f, int nets, const uint32_t* rng_state,
+                                           void* wg_scratch, size_t wg_scratch_bytes, float dist_weight_c, float dist_weight_f,
+                                           void* reg_workspace, size_t reg_workspace_bytes, float* reg2, dn_stream_t stream) {
+  return render_rays_backward_entry("dn_render_rays_backward_reg", desc_coarse, packed_bwd_coarse, desc_fine, packed_bwd_fine, precision, rays,
+                                    ray_stride, n_rays, num_coarse, num_fine, noise_std, white_background, noise_c, noise_f, g_rgb_c, g_depth_c,
+                                    g_acc_c, g_rgb_f, g_depth_f, g_acc_f, workspace, act_c, masks_c, grads_c, act_f, masks_f, grads_f, h_dW_c,
+                                    h_db_c, h_dW_f, h_db_f, nets, rng_state, wg_scratch, wg_scratch_bytes, dist_weight_c, dist_weight_f,
+                                    reg_workspace, reg_workspace_bytes, reg2, stream);
 }
 
 extern "C" int dn_render_rays_backward(const dn_mlp_desc* desc_coarse, const void* packed_bwd_coarse,

@@ -43,6 +43,9 @@ EXPORTS = (
     "dn_camera_records", "dn_camera_records_scratch_bytes", "dn_camera_records_backward",
 )
 
+# include/dexnerf_hip_ext.h: the entry points added after ABI version 2 (the table above and DN_ABI_VERSION stay as they are)
+EXT_EXPORTS = ("dn_distortion_loss", "dn_render_reg_workspace_bytes", "dn_render_rays_backward_reg")
+
 
 class MlpDesc(ctypes.Structure):
     """dn_mlp_desc (mirrors FlexibleNeRFModel.__init__, reference nerf/models.py:186-196)."""
@@ -175,6 +178,13 @@ def _declare(lib):
                         "dn_mlp_input_grad_packed_bytes", "dn_mlp_backward_input_workspace_bytes", "dn_camera_grad_scratch_bytes",
                         "dn_camera_grad_views_scratch_bytes"):
             getattr(lib, name).restype = c_int
+    # the extension header
+    lib.dn_distortion_loss.argtypes = [fp, fp, fp, c_int, c_int64, c_int, c_float, fp, fp, c_int, vp, fp, vp]
+    lib.dn_distortion_loss.restype = c_int
+    lib.dn_render_reg_workspace_bytes.argtypes = [c_int64, c_int, c_int]
+    lib.dn_render_reg_workspace_bytes.restype = c_size_t
+    lib.dn_render_rays_backward_reg.argtypes = lib.dn_render_rays_backward_ws.argtypes[:-1] + [c_float, c_float, vp, c_size_t, fp, vp]
+    lib.dn_render_rays_backward_reg.restype = c_int
 
 
 def lib():

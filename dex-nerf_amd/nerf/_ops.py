@@ -1054,6 +1054,37 @@ class VolumeRenderFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------
+def distortion_loss(weights, z, near_far=None, scale=1.0, want_z=False, rays=None, g_z=None):
+    """dn_distortion_loss: the distortion regulariser of compositing's weights (N,S) and depths (N,S), S <= 1024.  The near / far of
+    every ray come from near_far (N,2) or from columns 6:8 of packed ray rows (`rays`).  Returns (mean (1) - the unweighted mean of
+    L_ray -, ray_loss (N) fp64, g_weights (N,S) = scale dL_ray/dw, g_z (N,S) = scale dL_ray/dz | None).  g_z given: the depth gradient
+    is ADDED to it (and returned); else want_z decides whether it is formed."""
+    if (near_far is None) == (rays is None):
+        raise ValueError("distortion_loss: give near_far (N,2) or rays (N, >= 8), one of them")
+    weights, z = f32c(weights), f32c(z)
+    n, s = z.shape
+    if tuple(weights.shape) != (n, s):
+        raise ValueError(f"distortion_loss: weights {tuple(weights.shape)} for depths {tuple(z.shape)}")
+    rows = f32c(near_far if rays is None else rays)
+    if rows.dim() != 2 or rows.shape[0] != n or rows.shape[1] < (2 if rays is None else 8):
+        raise ValueError(f"distortion_loss: near_far is (N,2), rays (N, >= 8) (got {tuple(rows.shape)} for {n} rays)")
+    assert rows.is_cuda, "HIP entry points need contiguous device tensors"
+    nf_ptr = None if n == 0 else ctypes.c_void_p(rows.data_ptr() + (0 if rays is None else 6 * 4))
+    dev = z.device
+    accumulate = g_z is not None
+    if accumulate:
+        assert g_z.dtype == torch.float32 and g_z.is_contiguous() and tuple(g_z.shape) == (n, s), "distortion_loss: g_z is (N,S) fp32, contiguous"
+    elif want_z:
+        g_z = torch.empty((n, s), dtype=torch.float32, device=dev)
+    g_w = torch.empty((n, s), dtype=torch.float32, device=dev)
+    ray_loss = torch.empty((n,), dtype=torch.float64, device=dev)
+    mean = torch.zeros((1,), dtype=torch.float32, device=dev) if n == 0 else torch.empty((1,), dtype=torch.float32, device=dev)
+    check(lib().dn_distortion_loss(ptr(weights), ptr(z), nf_ptr, rows.shape[1], n, s, float(scale), ptr(g_w), ptr(g_z), int(accumulate),
+                                   ptr(ray_loss), ptr(mean), stream()), "dn_distortion_loss")
+    return mean, ray_loss, g_w, g_z
+
+
+# ------------------------------------------------------------------------------------------------
 def sample_pdf(bins, weights, num_samples, u=None, want_inds=False):
     bins, weights = f32c(bins), f32c(weights)
     n, b = bins.shape
@@ -1286,21 +1317,33 @@ def _backward_args(packed_c, packed_f, saved, g_c, g_f, views_c, views_f, nets, 
     return fine, grads_c, grads_f, ptrs, gs, scratch
 
 
-def render_rays_backward(packed_c, packed_f, saved, g_c, g_f, views_c, views_f, nets=3):
+def render_rays_backward(packed_c, packed_f, saved, g_c, g_f, views_c, views_f, nets=3, reg=None):
     """dn_render_rays_backward: composite backward -> backward-data chain -> weight gradients for the networks selected by
     `nets` (bit 0 coarse, bit 1 fine), ACCUMULATING into views_* = [(dW, db)] in linear_modules() order.
-    g_c / g_f = (g_rgb, g_depth, g_acc) upstream gradients (None = zero)."""
+    g_c / g_f = (g_rgb, g_depth, g_acc) upstream gradients (None = zero).
+    reg = ((weight_coarse, weight_fine), reg2): dn_render_rays_backward_reg in its place - the distortion regulariser of each network
+    in `nets` with a non-zero weight, its gradient added ahead of the compositing backward and the mean L_ray written to reg2 (2) fp32
+    ([coarse, fine]; a half writes its own word)."""
     n, nc, nf, prec = saved["n"], saved["nc"], saved["nf"], saved["prec"]
     fine, grads_c, grads_f, ptrs, gs, (scratch, scratch_bytes) = _backward_args(packed_c, packed_f, saved, g_c, g_f, views_c, views_f, nets, True)
-    check(lib().dn_render_rays_backward_ws(
-        ctypes.byref(packed_c.desc), ptr(packed_c.buffers_bwd[prec]),
-        ctypes.byref(packed_f.desc) if fine else None, ptr(packed_f.buffers_bwd[prec]) if fine else None, prec,
-        ptr(saved["rays"]), saved["rays"].shape[1], n, nc, nf, saved["noise_std"], int(saved["white"]),
-        ptr(saved["noise_c"]), ptr(saved["noise_f"]), *[ptr(g) for g in gs],
-        ptr(saved["ws"]), ptr(saved["act_c"]), ptr(saved["masks_c"]), ptr(grads_c), ptr(saved["act_f"]), ptr(saved["masks_f"]),
-        ptr(grads_f), *ptrs, int(nets), ptr(saved.get("rng_state")), ptr(scratch), scratch_bytes, stream()), "dn_render_rays_backward")
+    args = [ctypes.byref(packed_c.desc), ptr(packed_c.buffers_bwd[prec]),
+            ctypes.byref(packed_f.desc) if fine else None, ptr(packed_f.buffers_bwd[prec]) if fine else None, prec,
+            ptr(saved["rays"]), saved["rays"].shape[1], n, nc, nf, saved["noise_std"], int(saved["white"]),
+            ptr(saved["noise_c"]), ptr(saved["noise_f"]), *[ptr(g) for g in gs],
+            ptr(saved["ws"]), ptr(saved["act_c"]), ptr(saved["masks_c"]), ptr(grads_c), ptr(saved["act_f"]), ptr(saved["masks_f"]),
+            ptr(grads_f), *ptrs, int(nets), ptr(saved.get("rng_state")), ptr(scratch), scratch_bytes]
+    reg_ws = None
+    if reg is None:
+        check(lib().dn_render_rays_backward_ws(*args, stream()), "dn_render_rays_backward")
+    else:
+        (w_c, w_f), reg2 = reg
+        assert reg2.dtype == torch.float32 and reg2.is_contiguous() and reg2.numel() == 2, "render_rays_backward: reg2 is two fp32 words"
+        nbytes = int(lib().dn_render_reg_workspace_bytes(n, nc, nf))
+        reg_ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=saved["rays"].device)
+        check(lib().dn_render_rays_backward_reg(*args, float(w_c), float(w_f), ptr(reg_ws), nbytes, ptr(reg2), stream()),
+              "dn_render_rays_backward_reg")
     _note_s8_record(grads_c, prec); _note_s8_record(grads_f, prec)
-    return grads_c, grads_f, scratch   # (kept alive by the caller until the stream has consumed them: PyTorch's caching allocator is stream-ordered)
+    return grads_c, grads_f, scratch, reg_ws   # (kept alive by the caller until the stream has consumed them: PyTorch's caching allocator is stream-ordered)
 
 
 # ---- the render with its ray gradient, and camera records from twists: the pieces of nerf.FusedPoseStep ----------------------------

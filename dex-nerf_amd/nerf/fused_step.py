@@ -16,6 +16,10 @@ fine render -> mse + mse -> backward -> Adam) with nothing in it but this librar
     dn_render_rays_backward  composite backward + backward-data chain per network, then ONE weight-gradient launch for the
                              layers of both (one rank; with several ranks the networks are done one at a time so that the
                              fine network's all-reduce overlaps the coarse half)                                       (5 kernels)
+                             (distortion_weights given: dn_render_rays_backward_reg in its place - per network with a non-zero
+                             weight the distortion regulariser of its sample weights, dn_distortion_loss, ahead of the compositing
+                             backward, which takes its gradient as the upstream of every sample weight: 2 kernels, and for the
+                             fine network one more compositing launch that forms the weights again)
     dn_adam_step             nerf.FlatAdam: step, learning-rate schedule and gradient clearing                         (1 kernel)
 
 The networks: W in {128, 256} with L_xyz in {6, 10} (the shipped fern / LLFF nets are 4 x 128, L_xyz = 6), view directions.
@@ -27,16 +31,18 @@ import torch
 
 from . import _ops
 from ._train import train_fused_ok
-from .loss import fused_loss_head, loss_head_settings
+from .loss import distortion_weight_settings, fused_loss_head, loss_head_settings
 from .train_utils import _fusable
 
 
 class FusedTrainStep:
     def __init__(self, model_coarse, model_fine, selector, options, bucket, encode_position_fn, encode_direction_fn, num_rays, seed=0,
                  luminance=False, first_iteration=0, draw_view=False, ndc_focal=None, depth_images=None, loss_weights=(1.0, 1.0),
-                 depth_weights=(0.0, 0.0), depth_range=(0.0, float("inf"))):
+                 depth_weights=(0.0, 0.0), depth_range=(0.0, float("inf")), distortion_weights=(0.0, 0.0)):
         if not (isinstance(draw_view, bool) or draw_view == "rays"):
             raise ValueError(f"FusedTrainStep: draw_view must be False, True or \"rays\" (got {draw_view!r})")
+        # the distortion regulariser of each network's sample weights (dn_render_rays_backward_reg); (0, 0): the backward as ever
+        self.distortion_weights = distortion_weight_settings("FusedTrainStep", distortion_weights)
         opt = options.nerf.train
         self.ndc = getattr(options.dataset, "no_ndc", True) is False
         if depth_images is not None and draw_view is True:
@@ -62,6 +68,9 @@ class FusedTrainStep:
             raise ValueError("FusedTrainStep: configuration outside the fused training kernels (see FusedTrainStep.applicable)")
         dev = next(model_coarse.parameters()).device
         self.rng_state = _ops.new_rng_state(seed, dev, first_iteration)
+        # [mean L_ray coarse, mean L_ray fine] of the latest step (a network with weight 0: 0); None without the regulariser.  Not part
+        # of loss3 / loss6, which keep their meaning: the step minimises loss3[0] + w_c reg2[0] + w_f reg2[1]
+        self.reg2 = torch.zeros(2, dtype=torch.float32, device=dev) if max(self.distortion_weights) > 0.0 else None
         self.loss3 = self.loss6 = None       # loss6 (general head only) = [loss, mse_c, mse_f, D_c, D_f, valid rays]; loss3 its first three
         # True: the iteration's training view is drawn in the kernel too (else: selector.view); "rays": the view of EVERY ray is drawn
         # with its pixel, a batch across all training images (dn_select_rays_draw_views)
@@ -122,13 +131,15 @@ class FusedTrainStep:
         views_c, views_f = mc._grad_sink.views(mc), mf._grad_sink.views(mf)
         if views_c is None or views_f is None:
             raise RuntimeError("FusedTrainStep: a parameter's .grad is no longer the FlatGradBucket's view")
-        keep = [_ops.render_rays_backward(pc, pf, saved, g_c if both else (None, None, None), g_f, views_c, views_f, nets=3 if both else 2)]
+        self._reg = None if self.reg2 is None else (self.distortion_weights, self.reg2)
+        keep = [_ops.render_rays_backward(pc, pf, saved, g_c if both else (None, None, None), g_f, views_c, views_f, nets=3 if both else 2,
+                                          reg=self._reg)]
         self._half = (pc, pf, saved, g_c, views_c, views_f)
         self._keep = (keep, saved, maps, rays, target, g_c[0], g_f[0], pix, views, g_c[1], g_f[1])   # alive until the next call (stream-ordered allocator)
 
     def coarse_backward(self):
         pc, pf, saved, g_c, views_c, views_f = self._half
-        self._keep[0].append(_ops.render_rays_backward(pc, pf, saved, g_c, (None, None, None), views_c, views_f, nets=1))
+        self._keep[0].append(_ops.render_rays_backward(pc, pf, saved, g_c, (None, None, None), views_c, views_f, nets=1, reg=self._reg))
 
     def latest_draw(self):
         """(view_index (N) int32 | None, pixel_index (N) int64 | None, rows, target) of the latest step - the pairs only with

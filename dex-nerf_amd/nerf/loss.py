@@ -1,5 +1,6 @@
 """The loss head of the training loop under autograd: weighted mse(rgb_coarse) + mse(rgb_fine) plus a masked depth term, value and
-gradients from ONE kernel launch (dn_render_loss).  FusedTrainStep / FusedPoseStep call the same head without an autograd graph."""
+gradients from ONE kernel launch (dn_render_loss).  FusedTrainStep / FusedPoseStep call the same head without an autograd graph.
+distortion_loss: the distortion regulariser of compositing's weights (dn_distortion_loss) under autograd."""
 import torch
 
 from . import _hip, _ops
@@ -104,3 +105,49 @@ def render_loss(rgb_c, rgb_f, target, depth_c=None, depth_f=None, target_depth=N
                                      tuple(weights), tuple(depth_weights), tuple(depth_range), bool(luminance))
     loss.terms = terms
     return loss
+
+
+def distortion_weight_settings(who, distortion_weights):
+    """(coarse, fine) weights of the distortion regulariser on a fused step, validated: finite and >= 0, else ValueError."""
+    try:
+        weights = tuple(float(w) for w in distortion_weights)
+    except TypeError:
+        raise ValueError(f"{who}: distortion_weights is a pair (coarse, fine) (got {distortion_weights!r})") from None
+    if len(weights) != 2:
+        raise ValueError(f"{who}: distortion_weights is a pair (coarse, fine) (got {distortion_weights!r})")
+    if not all(w == w and abs(w) != float("inf") and w >= 0.0 for w in weights):
+        raise ValueError(f"{who}: distortion_weights must be finite and >= 0 (got {weights})")
+    return weights
+
+
+class DistortionLossFn(torch.autograd.Function):
+    """(weights (N,S), z (N,S)) -> mean over the rays of L_ray.  The forward runs dn_distortion_loss with scale = 1 / N and keeps the
+    gradients it wrote; the backward multiplies them by grad_output."""
+
+    @staticmethod
+    def forward(ctx, weights, z, near_far):
+        n = z.shape[0]
+        mean, _, g_w, g_z = _ops.distortion_loss(weights.detach(), z.detach(), near_far, scale=1.0 / max(n, 1), want_z=ctx.needs_input_grad[1])
+        ctx.save_for_backward(g_w, *([g_z] if g_z is not None else []))
+        return mean[0].clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss):
+        g_w, *g_z = ctx.saved_tensors
+        return (g_w * g_loss if ctx.needs_input_grad[0] else None, g_z[0] * g_loss if (g_z and ctx.needs_input_grad[1]) else None, None)
+
+
+def distortion_loss(weights, z_vals, near, far):
+    """The distortion regulariser of mip-NeRF 360 on the weights (..., S) volume_render_radiance_field returns and their depths
+    z_vals (..., S), S <= 1024: the mean over the rays of sum_ij w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 delta_i, with compositing's
+    interval midpoints m and lengths delta (the last, open interval has length 0) in units of far - near.  near / far: numbers or
+    per-ray tensors (...); they get no gradient, and a ray without far > near contributes zero.  Differentiable in weights and z_vals
+    (tied depths: the subgradient of their order).  Device tensors only."""
+    _require_device(weights, "distortion_loss")
+    _require_device(z_vals, "distortion_loss")
+    s = z_vals.shape[-1]
+    w2, z2 = weights.reshape(-1, s), z_vals.reshape(-1, s)
+    n = z2.shape[0]
+    cols = [torch.as_tensor(v, dtype=torch.float32, device=z2.device).detach().reshape(-1).expand(n) for v in (near, far)]
+    return DistortionLossFn.apply(w2, z2, torch.stack(cols, dim=1).contiguous())

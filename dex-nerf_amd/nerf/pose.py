@@ -7,7 +7,7 @@ the same step - the packs inside the graph, the weight gradients from the same b
 import torch
 
 from . import _hip, _ops
-from .loss import fused_loss_head, loss_head_settings
+from .loss import distortion_weight_settings, fused_loss_head, loss_head_settings
 from .nerf_helpers import _require_device, img2mse, random_view_pixel_pairs, select_camera_rays
 from .train_utils import predict_and_render_radiance
 
@@ -259,8 +259,11 @@ class FusedPoseStep:
     def __init__(self, model_coarse, model_fine, options, height, width, intrinsic, extrinsics0, images, encode_position_fn,
                  encode_direction_fn, num_rays, lr, seed=0, first_iteration=0, ndc_focal=None, use_graphs=True, eager_iterations=3,
                  depth_images=None, loss_weights=(1.0, 1.0), depth_weights=(0.0, 0.0), depth_range=(0.0, float("inf")),
-                 refine_intrinsics=None, intrinsics_scale=1.0, fixed_views=(), refine_pose=True):
+                 refine_intrinsics=None, intrinsics_scale=1.0, fixed_views=(), refine_pose=True, distortion_weights=(0.0, 0.0)):
         who = self._who
+        if max(distortion_weight_settings(who, distortion_weights)) > 0.0:
+            raise ValueError(f"{who}: the geometry route takes no distortion regulariser yet (distortion_weights {tuple(distortion_weights)}): its "
+                             "depth gradient is not added into the ray gradient - train with FusedTrainStep(distortion_weights=...)")
         if extrinsics0.dim() == 2:
             extrinsics0 = extrinsics0[None]
         if extrinsics0.dim() != 3 or tuple(extrinsics0.shape[1:]) != (4, 4):

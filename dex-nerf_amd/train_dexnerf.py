@@ -224,6 +224,12 @@ def build_parser():
     ap.add_argument("--depth-range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
                     help="pixels whose depth lies strictly inside (LO, HI) are supervised; default: the Dex validation mask, 0 to the "
                          "dataset's mask_hi")
+    ap.add_argument("--distortion-weight", type=float, default=0.0, metavar="W",
+                    help="weight of the distortion regulariser (mip-NeRF 360) on the fine network's sample weights: it penalises density "
+                         "spread out or split into clusters along a ray - floaters, which move the Dex depth "
+                         "(nerf.FusedTrainStep(distortion_weights=...))")
+    ap.add_argument("--distortion-weight-coarse", type=float, default=None, metavar="WC",
+                    help="the regulariser's weight on the coarse network (default 0)")
     ap.add_argument("--refine-poses", action="store_true",
                     help="train the cameras of the training views together with the networks (nerf.FusedJointStep: twists on the given "
                          "poses under their own Adam, in the same replayed step); implies --mix-views.  Training views are then rendered at "
@@ -270,6 +276,15 @@ def parse_args(argv=None):
         args.mix_views = True
     if args.pose_noise is not None and not (args.pose_noise[0] >= 0.0 and args.pose_noise[1] >= 0.0):
         ap.error("--pose-noise ROT TRANS: both >= 0")
+    args.distortion_weight_coarse = 0.0 if args.distortion_weight_coarse is None else args.distortion_weight_coarse
+    for flag, value in (("--distortion-weight", args.distortion_weight), ("--distortion-weight-coarse", args.distortion_weight_coarse)):
+        if not 0.0 <= value < float("inf"):
+            ap.error(f"{flag} must be finite and >= 0")
+    if max(args.distortion_weight, args.distortion_weight_coarse) > 0.0:
+        if args.refine_poses:
+            ap.error("--distortion-weight does not run with --refine-poses yet: the geometry route (nerf.FusedJointStep) takes no distortion regulariser")
+        if args.autograd_step:
+            ap.error("--distortion-weight runs on the fused step (nerf.FusedTrainStep), not with --autograd-step")
     if args.depth_weight < 0.0:
         ap.error("--depth-weight must be >= 0")
     if args.depth_weight > 0.0:
@@ -377,6 +392,9 @@ def main(argv=None):
         head = dict(depth_images=torch.stack([depths[v].reshape(hw).to(torch.float32) for v in train_ids]),
                     depth_weights=(args.depth_weight, args.depth_weight),
                     depth_range=tuple(args.depth_range) if args.depth_range else (0.0, float(data["mask_hi"])))
+    distortion = (args.distortion_weight_coarse, args.distortion_weight)
+    if max(distortion) > 0.0 and not fused_ok:
+        raise SystemExit("--distortion-weight: this configuration is outside nerf.FusedTrainStep (see FusedTrainStep.applicable)")
     joint = given_extrinsics = extrinsics0 = None
     if args.refine_poses or args.pose_noise is not None:
         given_extrinsics = torch.stack([poses[v].to(torch.float32) for v in train_ids])
@@ -426,7 +444,7 @@ def main(argv=None):
     if fused_ok:
         fused = nerf.FusedTrainStep(student[0], student[1], selector, cfg, bucket, ex, ed, args.num_random_rays, seed=args.seed + 7919 * rank,
                                     luminance=args.ir, first_iteration=start, draw_view="rays" if args.mix_views else True,
-                                    ndc_focal=ndc_focal, **head)
+                                    ndc_focal=ndc_focal, distortion_weights=distortion, **head)
     graphed = nerf.GraphedTrainStep(fused, opt, eager_iterations=3, use_graphs=use_graph) if fused is not None else None
     use_graph = use_graph and world == 1      # (the autograd step's single graph below: one rank only)
 
@@ -508,7 +526,8 @@ def main(argv=None):
             psnr = nerf.mse2psnr(loss_val)
             history.append((it, loss_val, psnr))
             if rank == 0 and not args.quiet:
-                print(f"[train] iter {it:6d} loss {loss_val:.5f} psnr {psnr:.2f} dB lr {lr:.2e} "
+                reg = "" if fused is None or fused.reg2 is None else "distortion coarse {:.5f} fine {:.5f} ".format(*fused.reg2.tolist())
+                print(f"[train] iter {it:6d} loss {loss_val:.5f} psnr {psnr:.2f} dB {reg}lr {lr:.2e} "
                       f"{(time.perf_counter() - t0):.1f} s", flush=True)
             s8 = nerf.s8_grad_stats() if args.precision in ("bf16", "bf16-s8") else None
             if s8 is not None:
