@@ -70,6 +70,11 @@ def main(argv=None):
     ck = torch.load(args.checkpoint, map_location="cpu")
     coarse = model_from_state_dict(ck["model_coarse_state_dict"], dev)
     fine = model_from_state_dict(ck["model_fine_state_dict"], dev) if ck.get("model_fine_state_dict") else None
+    if ck.get("encoding_anneal") is not None:      # a checkpoint from inside a coarse-to-fine schedule: rendered at its stored amplitudes
+        anneal = nerf.EncodingAnneal.from_state_dict(ck["encoding_anneal"]).attach(coarse, fine)
+        if not args.quiet:
+            print(f"encoding anneal {anneal.start:g}..{anneal.end:g} at iteration {anneal.iteration}: amplitudes "
+                  f"{[round(a, 4) for a in anneal.amplitudes().tolist()]}", flush=True)
     size = args.size or int(ck.get("height", 100))
     mode = dict(chunksize=size * size, lindisp=False, num_coarse=args.num_coarse, num_fine=args.num_fine if fine else 0,
                 perturb=False, radiance_field_noise_std=0.0, white_background=args.white_background)

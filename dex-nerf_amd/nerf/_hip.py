@@ -46,6 +46,10 @@ EXPORTS = (
 # include/dexnerf_hip_ext.h: the entry points added after ABI version 2 (the table above and DN_ABI_VERSION stay as they are)
 EXT_EXPORTS = ("dn_distortion_loss", "dn_render_reg_workspace_bytes", "dn_render_rays_backward_reg")
 
+# include/dexnerf_hip_anneal.h: the coarse-to-fine positional encoding (nerf.EncodingAnneal)
+ANNEAL_EXPORTS = ("dn_encoding_anneal_amplitudes", "dn_encoding_anneal_scale_weights", "dn_encoding_anneal_scale_grads",
+                  "dn_encoding_anneal_scale_weights_pair", "dn_encoding_anneal_scale_grads_pair")
+
 
 class MlpDesc(ctypes.Structure):
     """dn_mlp_desc (mirrors FlexibleNeRFModel.__init__, reference nerf/models.py:186-196)."""
@@ -185,6 +189,15 @@ def _declare(lib):
     lib.dn_render_reg_workspace_bytes.restype = c_size_t
     lib.dn_render_rays_backward_reg.argtypes = lib.dn_render_rays_backward_ws.argtypes[:-1] + [c_float, c_float, vp, c_size_t, fp, vp]
     lib.dn_render_rays_backward_reg.restype = c_int
+    # the encoding-anneal header
+    lib.dn_encoding_anneal_amplitudes.argtypes = [vp, c_int64, dbl, dbl, c_int, c_int, c_int, fp, vp]
+    lib.dn_encoding_anneal_scale_weights.argtypes = [POINTER(MlpDesc), POINTER(c_void_p), fp, POINTER(c_void_p), vp]
+    lib.dn_encoding_anneal_scale_grads.argtypes = [POINTER(MlpDesc), fp, POINTER(c_void_p), vp]
+    pv = POINTER(c_void_p)
+    lib.dn_encoding_anneal_scale_weights_pair.argtypes = [POINTER(MlpDesc), pv, pv, POINTER(MlpDesc), pv, pv, fp, vp]
+    lib.dn_encoding_anneal_scale_grads_pair.argtypes = [POINTER(MlpDesc), pv, POINTER(MlpDesc), pv, fp, vp]
+    for name in ANNEAL_EXPORTS:
+        getattr(lib, name).restype = c_int
 
 
 def lib():

@@ -734,7 +734,7 @@ def ensure_backward_stream(model, packed, prec=None):
     prec = train_precision(packed) if prec is None else prec
     key = model.param_key()
     if packed.keys_bwd.get(prec) != key or torch.cuda.is_current_stream_capturing():
-        pack_backward(packed, [m.weight for m in model.linear_modules()], prec)
+        pack_backward(packed, model.pack_weights(scaled=False), prec)
         packed.keys_bwd[prec] = key
     return packed.buffers_bwd[prec]
 
@@ -747,7 +747,7 @@ def ensure_input_grad_stream(model, packed):
             nbytes = _sized(lib().dn_mlp_input_grad_packed_bytes(ctypes.byref(packed.desc), packed.precision),
                             "dn_mlp_input_grad_packed_bytes")
             packed.buffer_ig = torch.empty(nbytes, dtype=torch.uint8, device=packed.buffer.device)
-        wp, packed._keep_ig = _ptr_array([m.weight for m in model.linear_modules()], sources=True)
+        wp, packed._keep_ig = _ptr_array(model.pack_weights(), sources=True)
         check(lib().dn_mlp_pack_input_grad(ctypes.byref(packed.desc), packed.precision, wp, ptr(packed.buffer_ig), stream()),
               "dn_mlp_pack_input_grad")
         packed.key_ig = key
@@ -796,9 +796,11 @@ def pack_train_pair(model_a, model_b, logs):
                 pk.buffers_bwd[prec] = torch.empty(lib().dn_mlp_backward_packed_bytes(ctypes.byref(pk.desc), prec), dtype=torch.uint8,
                                                    device=pk.buffer.device)
         arrays, keep = [], []
-        for model in (model_a, model_b):
+        anneal = model_a._encoding_anneal      # one schedule on both networks: their scaled copies in one launch
+        paired = anneal.scaled_weights_pair(model_a, model_b) if (anneal is not None and anneal is model_b._encoding_anneal) else None
+        for k, model in enumerate((model_a, model_b)):
             mods = model.linear_modules()
-            wp, ws = _ptr_array([m.weight for m in mods], sources=True)
+            wp, ws = _ptr_array(model.pack_weights() if paired is None else paired[k], sources=True)
             bp, bs = _ptr_array([m.bias for m in mods], sources=True)
             keep.append((ws, bs))
             arrays.append((wp, bp))

@@ -27,6 +27,16 @@ def inputs_need_grad(*tensors):
     return torch.is_grad_enabled() and any(t is not None and torch.is_tensor(t) and t.requires_grad for t in tensors)
 
 
+def refuse_annealed_training(*models):
+    """The autograd route forms weight gradients w.r.t. the weights the kernels ran on; with an EncodingAnneal attached those are the
+    column-scaled copies, and nothing here scales the gradient back: refuse.  (No-grad calls, and calls that differentiate w.r.t.
+    inputs only against frozen weights, go through the packs and are right.)"""
+    if any(m is not None and getattr(m, "_encoding_anneal", None) is not None for m in models):
+        raise RuntimeError("a model with an EncodingAnneal attached cannot be trained through autograd (its weight gradients would miss the "
+                           "bands' column scale): train it with FusedTrainStep(encoding_anneal=...) or FusedJointStep(encoding_anneal=...), "
+                           "or freeze its parameters (requires_grad_(False)) for input gradients alone")
+
+
 TRAIN_L_XYZ = (6, 10)   # xyz encodings the training kernels are instantiated for (csrc/mlp_layout.h train_lxyz_supported)
 
 
@@ -63,6 +73,7 @@ class FusedNetFn(torch.autograd.Function):
             raise RuntimeError("FusedNetFn differentiates w.r.t. the model parameters only; points / rays / view directions that "
                                "require grad must go through FusedNetInputFn, or the nn.Linear composition for nets outside the "
                                "training kernels (run_network routes them by itself)")
+        refuse_annealed_training(model)
         pk = model.packed(log_xyz, log_dir, train=True)
         prec = _ops.train_precision(pk)
         _ops.ensure_backward_stream(model, pk, prec)
@@ -113,6 +124,8 @@ class FusedNetInputFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, pts, viewdirs, samples_per_ray, log_xyz, log_dir, *params):
         """`pts` (..., 3) + `viewdirs` (N,3), or - when `samples_per_ray` is None - packed ray rows (N, 8|11) + depths (N,S)."""
+        if any(ctx.needs_input_grad[6:]):
+            refuse_annealed_training(model)
         pk = _packed_core(model, log_xyz, log_dir)
         prec = pk.precision
         _ops.ensure_backward_stream(model, pk, prec)
@@ -177,6 +190,7 @@ class RenderRaysTrainFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model_c, model_f, rays, cfg, draws, thres, logs, *params):
         num_coarse, num_fine, lindisp, noise_std, white = cfg
+        refuse_annealed_training(model_c, model_f)
         pc = model_c.packed(*logs, train=True)
         pf = model_f.packed(*logs, train=True) if model_f is not None else None
         prec = _ops.train_precision(pc)
@@ -242,6 +256,7 @@ def render_rays_train(model_c, model_f, rays, cfg, draws, thres, logs):
 def mlp_encoded(model, x):
     """FlexibleNeRFModel.forward(x) on already-embedded device rows."""
     if needs_grad(model, x):
+        refuse_annealed_training(model)     # (the nn.Linear composition knows no schedule at all)
         return model._forward_modules(x)
     return _ops.mlp_forward_encoded(model.packed(), x)
 
@@ -261,6 +276,7 @@ def _torch_encoding(x, num_fns, log_sampling):
 def _modules_on_points(model, pts, viewdirs, log_xyz, log_dir):
     """(N,S,3) points + (N,3) view directions through torch encodings + the nn.Linear composition: (N*S, 4), differentiable
     w.r.t. everything."""
+    refuse_annealed_training(model)         # (the nn.Linear composition knows no schedule at all)
     n, s = pts.shape[0], pts.shape[1]
     emb = _torch_encoding(pts.reshape(-1, 3), model.num_encoding_fn_xyz, log_xyz)
     if model.use_viewdirs:

@@ -22,6 +22,10 @@ fine render -> mse + mse -> backward -> Adam) with nothing in it but this librar
                              fine network one more compositing launch that forms the weights again)
     dn_adam_step             nerf.FlatAdam: step, learning-rate schedule and gradient clearing                         (1 kernel)
 
+encoding_anneal (nerf.EncodingAnneal) given: three launches more on one rank in the default 'bf16' mode - dn_encoding_anneal_amplitudes
+ahead of everything, dn_encoding_anneal_scale_weights_pair ahead of the pack, dn_encoding_anneal_scale_grads_pair behind the backward
+(the per-network packs and the two halves of a data-parallel step: one dn_encoding_anneal_scale_weights / _scale_grads per network).
+
 The networks: W in {128, 256} with L_xyz in {6, 10} (the shipped fern / LLFF nets are 4 x 128, L_xyz = 6), view directions.
 No autograd graph, no ATen elementwise / reduction / RNG launches (profiles/r03_as_shipped_kernel_summary.md).  The gradients land in
 a parallel.FlatGradBucket (the `.grad` tensors of the parameters).  GraphedTrainStep replays the iteration as HIP graphs (three
@@ -38,7 +42,7 @@ from .train_utils import _fusable
 class FusedTrainStep:
     def __init__(self, model_coarse, model_fine, selector, options, bucket, encode_position_fn, encode_direction_fn, num_rays, seed=0,
                  luminance=False, first_iteration=0, draw_view=False, ndc_focal=None, depth_images=None, loss_weights=(1.0, 1.0),
-                 depth_weights=(0.0, 0.0), depth_range=(0.0, float("inf")), distortion_weights=(0.0, 0.0)):
+                 depth_weights=(0.0, 0.0), depth_range=(0.0, float("inf")), distortion_weights=(0.0, 0.0), encoding_anneal=None):
         if not (isinstance(draw_view, bool) or draw_view == "rays"):
             raise ValueError(f"FusedTrainStep: draw_view must be False, True or \"rays\" (got {draw_view!r})")
         # the distortion regulariser of each network's sample weights (dn_render_rays_backward_reg); (0, 0): the backward as ever
@@ -76,6 +80,12 @@ class FusedTrainStep:
         # with its pixel, a batch across all training images (dn_select_rays_draw_views)
         self.draw_view = draw_view
         self.zero_in_step = True     # False: the optimizer leaves the gradient bucket cleared (FlatAdam(zero_grads=True))
+        # nerf.EncodingAnneal: the coarse-to-fine schedule of the encoding's bands, attached to both networks here.  Once per iteration,
+        # before any pack, its table is formed on the device from rng_state's iteration counter (a replayed graph follows it); each
+        # network's weight gradients get the bands' column scale right after the backward that forms them (before the exchange)
+        self.anneal = encoding_anneal
+        if encoding_anneal is not None:
+            encoding_anneal.attach(model_coarse, model_fine)
 
     @staticmethod
     def applicable(model_coarse, model_fine, options, encode_position_fn, encode_direction_fn, num_rays, ndc_focal=None):
@@ -113,6 +123,8 @@ class FusedTrainStep:
         of both networks in ONE launch (dn_mlp_weight_grad_pair); coarse_backward() must not follow."""
         mc, mf = self.models
         sel = self.selector
+        if self.anneal is not None:
+            self.anneal.advance(self.rng_state)
         gather = self.head is not None and self.head["depth_images"] is not None
         # the draw: every ray's view with its pixel ("rays"), or pixels of one view - the selector's, or one drawn in the kernel;
         # the drawn (pixel, view) come back only when the depth targets are gathered at them
@@ -134,12 +146,18 @@ class FusedTrainStep:
         self._reg = None if self.reg2 is None else (self.distortion_weights, self.reg2)
         keep = [_ops.render_rays_backward(pc, pf, saved, g_c if both else (None, None, None), g_f, views_c, views_f, nets=3 if both else 2,
                                           reg=self._reg)]
+        if self.anneal is not None and both:
+            self.anneal.scale_grads_pair(mc, views_c, mf, views_f)
+        elif self.anneal is not None:
+            self.anneal.scale_grads(mf, views_f)
         self._half = (pc, pf, saved, g_c, views_c, views_f)
         self._keep = (keep, saved, maps, rays, target, g_c[0], g_f[0], pix, views, g_c[1], g_f[1])   # alive until the next call (stream-ordered allocator)
 
     def coarse_backward(self):
         pc, pf, saved, g_c, views_c, views_f = self._half
         self._keep[0].append(_ops.render_rays_backward(pc, pf, saved, g_c, (None, None, None), views_c, views_f, nets=1, reg=self._reg))
+        if self.anneal is not None:
+            self.anneal.scale_grads(self.models[0], views_c)
 
     def latest_draw(self):
         """(view_index (N) int32 | None, pixel_index (N) int64 | None, rows, target) of the latest step - the pairs only with

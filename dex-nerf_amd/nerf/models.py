@@ -63,6 +63,7 @@ class FlexibleNeRFModel(torch.nn.Module):
         self.relu = torch.nn.functional.relu
         self._packed = {}
         self._packed_density = {}
+        self._encoding_anneal = None   # nerf.EncodingAnneal.attach(): the coarse-to-fine schedule the packs read the weights through
 
     # ---- HIP side ---------------------------------------------------------------------------------
     def linear_modules(self):
@@ -75,8 +76,10 @@ class FlexibleNeRFModel(torch.nn.Module):
 
     def param_key(self):
         """Changes whenever the parameters may have (see packed())."""
-        return tuple((m.weight.data_ptr(), m.weight._version, m.bias.data_ptr(), m.bias._version)
-                     for m in self.linear_modules()) + (_optimizer_steps[0],)
+        key = tuple((m.weight.data_ptr(), m.weight._version, m.bias.data_ptr(), m.bias._version)
+                    for m in self.linear_modules()) + (_optimizer_steps[0],)
+        anneal = self._encoding_anneal
+        return key if anneal is None else key + (("anneal", id(anneal), anneal.version),)
 
     def desc_kwargs(self, log_sampling_xyz=True, log_sampling_dir=True):
         return dict(num_layers=self.num_layers, hidden_size=self.hidden_size,
@@ -103,9 +106,18 @@ class FlexibleNeRFModel(torch.nn.Module):
         cache believes at capture time."""
         return packed_from != key or (self.layer1.weight.device.type == "cuda" and torch.cuda.is_current_stream_capturing())
 
+    def pack_weights(self, scaled=True):
+        """The weights every pack kernel reads, in linear_modules() order.  With an EncodingAnneal attached (and `scaled`): the entries
+        of the layers that read an encoding replaced by fp32 copies scaled, just now and from the CURRENT values, by the schedule's
+        band amplitudes (one launch); scaled=False - the backward-data stream, which reads hidden columns only - and a model with
+        nothing attached: the parameters themselves."""
+        weights = [m.weight for m in self.linear_modules()]
+        if self._encoding_anneal is None or not scaled:
+            return weights
+        return self._encoding_anneal.scaled_weights(self, weights)
+
     def _weights_and_biases(self):
-        mods = self.linear_modules()
-        return [m.weight for m in mods], [m.bias for m in mods]
+        return self.pack_weights(), [m.bias for m in self.linear_modules()]
 
     def packed(self, log_sampling_xyz=True, log_sampling_dir=True, train=False, precision=None, parts=None):
         """MFMA fragment streams for the current parameters (re-packed when any parameter changed: _stale).  `train=True` (the

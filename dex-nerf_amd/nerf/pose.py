@@ -330,6 +330,7 @@ class FusedPoseStep:
         self.graph = None
         self.fallback_reason = None
         self._keep = None
+        self.anneal = None            # FusedJointStep(encoding_anneal=)
 
     def _check_networks(self, model_coarse, model_fine, encode_position_fn, encode_direction_fn):
         """Host-side: raises ValueError for networks outside the fused training kernels."""
@@ -380,6 +381,8 @@ class FusedPoseStep:
         _ops.adam_step(self._flat[0], self._flat[1], self._flat[2], self._flat[3], self._adam_state, self.lr, 1.0, (0.9, 0.999), 1e-8, True)
 
     def _enqueue(self):
+        if self.anneal is not None:       # the table of this iteration (rng_state's counter, read on the device) before any pack
+            self.anneal.advance(self.rng_state)
         pc, pf = self._packs()
         self._records(cams=self.cams)
         rays, target, pix, views = _ops.select_rays_draw_views(self.height, self.width, self.cams, self.near, self.far, self.rng_state,
@@ -389,7 +392,10 @@ class FusedPoseStep:
                                                   prec=pc.precision, rng_state=self.rng_state, perturb=self.perturb)
         self.loss3, self.loss6, g_c, g_f = fused_loss_head(self.head, maps, target, self.rng_state, self.luminance, pix, views)
         self._clear_weight_gradients()
-        d_rays, keep = _ops.render_rays_backward_geom(pc, pf, saved, g_c, g_f, *self._weight_gradient_views())
+        w_views = self._weight_gradient_views()
+        d_rays, keep = _ops.render_rays_backward_geom(pc, pf, saved, g_c, g_f, *w_views)
+        if self.anneal is not None:       # dL/dW = (dL/dW_eff) diag(a): the bucket holds this backward's contribution only
+            self.anneal.scale_grads_pair(self.models[0], w_views[0], self.models[1], w_views[1])
         g_cams = _ops.camera_grad_views(self.height, self.width, self.cams, views, pix, self.num_rays, d_rays[:, 0:3], d_rays[:, 3:6],
                                         d_rays[:, 8:11], self.ndc_focal or 0.0, 1.0)
         if self.camera_pair:
@@ -477,6 +483,10 @@ class FusedJointStep(FusedPoseStep):
     the next one is captured into one HIP graph and replayed from then on; nerf.models.mark_parameters_updated() follows every step,
     so a later render packs the trained weights.  If capture fails the loop goes on eagerly and `fallback_reason` says why.
 
+    `encoding_anneal` (nerf.EncodingAnneal): the coarse-to-fine schedule of the encoding's bands (BARF), attached to both networks -
+    dn_encoding_anneal_amplitudes from rng_state's counter ahead of the packs, a dn_encoding_anneal_scale_weights per network ahead of its
+    core and input-gradient packs, one dn_encoding_anneal_scale_grads_pair behind the backward; all inside the captured step.
+
     Gauge: with every view free the scene can drift by a rigid motion (and, with the intrinsics free, a scale) that the loss does not
     see.  The step does not remove it; `fixed_views=(0,)` pins it to the first camera.  refine_pose=False with refine_intrinsics=None
     is allowed here (the networks alone are trained, on the step's own mixed-view draws).
@@ -489,7 +499,7 @@ class FusedJointStep(FusedPoseStep):
     _other_route = "MultiPoseRefiner + autograd (loss.backward() through its loss, torch.optim over the networks) trains those"
 
     def __init__(self, model_coarse, model_fine, options, height, width, intrinsic, extrinsics0, images, encode_position_fn,
-                 encode_direction_fn, num_rays, bucket, optimizer, lr_pose, pose_lr_decay=None, luminance=False, **kw):
+                 encode_direction_fn, num_rays, bucket, optimizer, lr_pose, pose_lr_decay=None, luminance=False, encoding_anneal=None, **kw):
         from .parallel import world_info
         if pose_lr_decay is not None:
             factor, steps = float(pose_lr_decay[0]), float(pose_lr_decay[1])
@@ -512,6 +522,9 @@ class FusedJointStep(FusedPoseStep):
         self.zero_in_step = not getattr(optimizer, "zero_grads", False)
         if not self.zero_in_step:
             bucket.flat.zero_()         # every step ends with the bucket cleared
+        self.anneal = encoding_anneal
+        if encoding_anneal is not None:
+            encoding_anneal.attach(model_coarse, model_fine)
 
     def _check_networks(self, model_coarse, model_fine, encode_position_fn, encode_direction_fn):
         if model_fine is None:

@@ -244,6 +244,11 @@ def build_parser():
     ap.add_argument("--fix-views", type=int, nargs="+", default=None, metavar="I",
                     help="--refine-poses: training views (positions in the training set) whose poses stay as given; default 0 - with "
                          "every view free the scene can drift by a rigid motion, one fixed camera pins it")
+    ap.add_argument("--anneal-encoding", type=int, nargs=2, default=None, metavar=("START", "END"),
+                    help="coarse-to-fine positional encoding (BARF): the bands of the encodings are switched on one after the other "
+                         "between iterations START and END (nerf.EncodingAnneal on the fused steps; with and without --refine-poses). The "
+                         "checkpoint stores the schedule; --load-checkpoint resumes it")
+    ap.add_argument("--anneal-xyz-only", action="store_true", help="--anneal-encoding: leave the view-direction encoding un-annealed")
     ap.add_argument("--pose-noise", type=float, nargs=2, default=None, metavar=("ROT", "TRANS"),
                     help="perturb the loaded training poses (all but --fix-views) by seeded twists of ROT radians and TRANS scene units "
                          "before training: for experiments and tests")
@@ -274,6 +279,13 @@ def parse_args(argv=None):
         args.intrinsics_scale = 1.0 if args.intrinsics_scale is None else args.intrinsics_scale
         args.fix_views = [0] if args.fix_views is None else args.fix_views
         args.mix_views = True
+    if args.anneal_encoding is not None:
+        if args.autograd_step:
+            ap.error("--anneal-encoding runs on the fused steps (nerf.FusedTrainStep / nerf.FusedJointStep), not with --autograd-step")
+        if not 0 <= args.anneal_encoding[0] <= args.anneal_encoding[1]:
+            ap.error("--anneal-encoding START END: iterations with 0 <= START <= END")
+    elif args.anneal_xyz_only:
+        ap.error("--anneal-xyz-only needs --anneal-encoding")
     if args.pose_noise is not None and not (args.pose_noise[0] >= 0.0 and args.pose_noise[1] >= 0.0):
         ap.error("--pose-noise ROT TRANS: both >= 0")
     args.distortion_weight_coarse = 0.0 if args.distortion_weight_coarse is None else args.distortion_weight_coarse
@@ -376,6 +388,15 @@ def main(argv=None):
             for group in opt.param_groups:
                 group["lr"] = lr_t
         start = ck["iter"]
+    # the coarse-to-fine schedule of the encodings: the command line's, else the one a loaded checkpoint was saved inside.  It follows
+    # the iteration counter of the fused step's RNG record (first_iteration=start), so resuming needs nothing else
+    anneal = None
+    if args.anneal_encoding is not None:
+        anneal = nerf.EncodingAnneal(args.anneal_encoding[0], args.anneal_encoding[1], anneal_dir=not args.anneal_xyz_only)
+    elif args.load_checkpoint and ck.get("encoding_anneal") is not None and not args.autograd_step:
+        anneal = nerf.EncodingAnneal.from_state_dict(ck["encoding_anneal"])
+    if anneal is not None and not fused_ok:
+        raise SystemExit("--anneal-encoding: this configuration is outside the fused steps (see FusedTrainStep.applicable)")
     train_ids = data["train"][rank::world] or [data["train"][rank % len(data["train"])]]
     # All training cameras + images live on the device and the view is a device scalar: from pixel draws to packed ray rows
     # + target pixels is ONE kernel with no per-view host constant (reference: full-image bundle + coordinate grid + three
@@ -419,7 +440,7 @@ def main(argv=None):
                                     selector.images, ex, ed, args.num_random_rays, bucket, opt, args.pose_lr,
                                     pose_lr_decay=args.pose_lr_decay, luminance=args.ir, seed=args.seed, first_iteration=start,
                                     ndc_focal=ndc_focal, use_graphs=use_graph, eager_iterations=3, refine_intrinsics=args.refine_intrinsics,
-                                    intrinsics_scale=args.intrinsics_scale, fixed_views=args.fix_views, **head)
+                                    intrinsics_scale=args.intrinsics_scale, fixed_views=args.fix_views, encoding_anneal=anneal, **head)
         if args.load_checkpoint:
             restore_joint_state(ck, joint)
         fused_ok = False                # the joint step is the training iteration
@@ -444,7 +465,7 @@ def main(argv=None):
     if fused_ok:
         fused = nerf.FusedTrainStep(student[0], student[1], selector, cfg, bucket, ex, ed, args.num_random_rays, seed=args.seed + 7919 * rank,
                                     luminance=args.ir, first_iteration=start, draw_view="rays" if args.mix_views else True,
-                                    ndc_focal=ndc_focal, distortion_weights=distortion, **head)
+                                    ndc_focal=ndc_focal, distortion_weights=distortion, encoding_anneal=anneal, **head)
     graphed = nerf.GraphedTrainStep(fused, opt, eager_iterations=3, use_graphs=use_graph) if fused is not None else None
     use_graph = use_graph and world == 1      # (the autograd step's single graph below: one rank only)
 
@@ -540,6 +561,8 @@ def main(argv=None):
         if rank == 0 and args.validate_every and (it + 1) % args.validate_every == 0:
             if joint is not None:
                 log_pose_distances(it + 1)
+            if anneal is not None:
+                anneal.set_iteration(it + 1)     # renders see the amplitudes of the steps taken (the next step forms its own table)
             out = render_view(student, cfg, *camera_of(held_out), hw, ex, ed, thres)
             vmse = nerf.img2mse(out[3].reshape(-1, 3), images[held_out]).item()
             if depths[held_out] is None:     # (LLFF captures carry no depth maps: no Dex threshold sweep)
@@ -568,6 +591,9 @@ def main(argv=None):
         result["s8_saturated_max"] = s8_saturated_max
     if args.save and rank != 0 and os.environ.get("DEXNERF_SAVE_ALL_RANKS"):   # rehearsals: compare the replicas
         torch.save({"model_coarse_state_dict": student[0].state_dict(), "model_fine_state_dict": student[1].state_dict()}, args.save)
+    if anneal is not None:
+        anneal.set_iteration(args.iters)
+        result["encoding_amplitudes"] = anneal.amplitudes().tolist()
     if rank == 0:
         out = render_view(student, cfg, *camera_of(held_out), hw, ex, ed, thres)
         result["val_psnr"] = nerf.mse2psnr(nerf.img2mse(out[3].reshape(-1, 3), images[held_out]).item())
@@ -582,6 +608,8 @@ def main(argv=None):
             for group in opt_state["param_groups"]:   # the reference stores a Python float (train_dexnerf_rgb.py:443-456), not the
                 group["lr"] = float(group["lr"])     # device scalar the captured graph reads the schedule from
             extra = joint_checkpoint_entries(joint, train_ids, extrinsics0) if joint is not None else {}
+            if anneal is not None:
+                extra["encoding_anneal"] = anneal.state_dict(iteration=args.iters)
             torch.save({"iter": args.iters, "model_coarse_state_dict": student[0].state_dict(),
                         "model_fine_state_dict": student[1].state_dict(), "optimizer_state_dict": opt_state,
                         "loss": loss_val, "psnr": psnr, **extra}, args.save)
