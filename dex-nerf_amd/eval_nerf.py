@@ -61,10 +61,15 @@ def main(argv=None):
     ap.add_argument("--use-refined-poses", action="store_true",
                     help="a checkpoint of train_dexnerf.py --refine-poses: render its training views at the refined cameras it carries "
                          "(refined_extrinsics / refined_intrinsics) instead of the spherical sweep; --size must be the training size")
+    ap.add_argument("--apply-exposure", action="store_true",
+                    help="--use-refined-poses on a checkpoint of train_dexnerf.py --refine-exposure: show every training view in its own "
+                         "stored exposure (nerf.apply_exposure); the default render is at the canonical exposure, the identity")
     args = ap.parse_args(argv)
 
     if args.depth_only and args.m_thres <= 0:
         ap.error("--depth-only renders the Dex depth maps: give --m-thres > 0")
+    if args.apply_exposure and (not args.use_refined_poses or args.depth_only):
+        ap.error("--apply-exposure corrects the colours of training views: it needs --use-refined-poses and no --depth-only")
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     nerf.set_precision(args.precision)
     ck = torch.load(args.checkpoint, map_location="cpu")
@@ -95,6 +100,8 @@ def main(argv=None):
         refined_e = torch.as_tensor(ck["refined_extrinsics"], dtype=torch.float32, device=dev)
         refined_k = torch.as_tensor(ck["refined_intrinsics"], dtype=torch.float32, device=dev)
         cameras = [(refined_e[v], refined_k[v] if refined_k.dim() == 3 else refined_k) for v in range(refined_e.shape[0])]
+        if args.apply_exposure and "refined_exposure" not in ck:
+            ap.error("--apply-exposure: the checkpoint carries no exposure rows (train_dexnerf.py --refine-exposure writes them)")
     else:
         cameras = [(torch.from_numpy(syn.scene_pose(i, n_views=args.views)).to(dev), k_mat) for i in range(args.views)]
     for i, (pose, k_mat) in enumerate(cameras):
@@ -124,6 +131,9 @@ def main(argv=None):
         torch.cuda.synchronize()
         times.append(time.perf_counter() - t0)
         rgb = out[3] if fine is not None else out[0]
+        if args.apply_exposure:      # training view i as its camera saw it
+            rgb = nerf.apply_exposure(rgb, torch.as_tensor(ck["refined_exposure"])[i], ck["refined_exposure_mode"],
+                                      float(ck["refined_exposure_scale"]))
         depth = out[4] if fine is not None else out[1]
         frames.append((rgb, depth))
         if args.savedir:

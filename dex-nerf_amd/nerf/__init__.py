@@ -11,7 +11,7 @@ from ._ops import get_precision, get_render_policy, s8_grad_stats, set_precision
 from .anneal import EncodingAnneal  # noqa: F401
 from .cfgnode import CfgNode  # noqa: F401
 from .fused_step import FusedTrainStep, GraphedTrainStep  # noqa: F401
-from .loss import distortion_loss, render_loss  # noqa: F401
+from .loss import apply_exposure, distortion_loss, render_loss  # noqa: F401
 from .parallel import FlatAdam  # noqa: F401
 from .models import *  # noqa: F401,F403
 from .nerf_helpers import *  # noqa: F401,F403

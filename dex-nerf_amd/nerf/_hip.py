@@ -50,6 +50,9 @@ EXT_EXPORTS = ("dn_distortion_loss", "dn_render_reg_workspace_bytes", "dn_render
 ANNEAL_EXPORTS = ("dn_encoding_anneal_amplitudes", "dn_encoding_anneal_scale_weights", "dn_encoding_anneal_scale_grads",
                   "dn_encoding_anneal_scale_weights_pair", "dn_encoding_anneal_scale_grads_pair")
 
+# include/dexnerf_hip_exposure.h: the loss head with a per-view exposure correction (refine_exposure= on the fused steps)
+EXPOSURE_EXPORTS = ("dn_render_loss_exposure",)
+
 
 class MlpDesc(ctypes.Structure):
     """dn_mlp_desc (mirrors FlexibleNeRFModel.__init__, reference nerf/models.py:186-196)."""
@@ -198,6 +201,9 @@ def _declare(lib):
     lib.dn_encoding_anneal_scale_grads_pair.argtypes = [POINTER(MlpDesc), pv, POINTER(MlpDesc), pv, fp, vp]
     for name in ANNEAL_EXPORTS:
         getattr(lib, name).restype = c_int
+    # the exposure header: dn_render_loss's arguments, then eps, P, n_views, exposure_scale, view_mask ahead of the outputs, g_eps behind them
+    lib.dn_render_loss_exposure.argtypes = lib.dn_render_loss.argtypes[:18] + [fp, c_int, c_int, c_float, vp, fp, fp, fp, fp, fp, fp, vp, vp]
+    lib.dn_render_loss_exposure.restype = c_int
 
 
 def lib():

@@ -566,6 +566,65 @@ def render_loss(rgb_c, rgb_f, target, depth_c=None, depth_f=None, depth_src=None
     return loss6, g_c, g_f, gd_c, gd_f
 
 
+def render_loss_exposure(rgb_c, rgb_f, target, eps, exposure_scale=1.0, view_index=None, view=None, view_mask=None, depth_c=None, depth_f=None,
+                         depth_src=None, pixel_index=None, weights=(1.0, 1.0), depth_weights=(0.0, 0.0), depth_range=(0.0, float("inf")),
+                         luminance=False, rng_state=None, g_eps=None, want_eps=True):
+    """render_loss with the colours of every ray corrected by its view's exposure row (dn_render_loss_exposure): eps (V,1) "gain" |
+    (V,6) "affine", the view of ray i view_index[i] ((N) int32), else `view` (device int32 scalar), else 0 - the view the depth targets
+    are gathered at too.  view_mask (V) int32: rows whose gradient is formed (None: all).  Returns (loss6, g_rgb_coarse, g_rgb_fine,
+    g_depth_coarse, g_depth_fine, g_eps (V,P)); g_eps is written into the tensor given, or allocated (want_eps=False: None, one launch
+    less)."""
+    rgb_c, target = f32c(rgb_c), f32c(target)
+    n = rgb_c.shape[0]
+    dev = rgb_c.device
+    assert eps.is_cuda and eps.dtype == torch.float32 and eps.is_contiguous() and eps.dim() == 2 and eps.shape[1] in (1, 6)
+    n_views, p = int(eps.shape[0]), int(eps.shape[1])
+    loss6 = torch.empty(6, dtype=torch.float32, device=dev)
+    g_c = torch.empty_like(rgb_c)
+    g_f = None
+    if rgb_f is not None:
+        rgb_f = f32c(rgb_f)
+        g_f = torch.empty_like(rgb_f)
+    views = None
+    if view_index is not None:
+        views = _view_index(view_index, n)
+    elif view is not None:
+        assert view.dtype == torch.int32 and view.is_cuda and view.numel() == 1
+    if view_mask is not None:
+        assert view_mask.dtype == torch.int32 and view_mask.is_cuda and view_mask.is_contiguous() and view_mask.numel() == n_views
+    gd_c = gd_f = pix = None
+    hw = 0
+    if depth_src is not None:
+        if depth_c is None:
+            raise ValueError("render_loss_exposure: a depth target needs depth_c")
+        depth_src, depth_c = f32c(depth_src), f32c(depth_c)
+        assert depth_c.numel() == n and depth_src.is_cuda
+        gd_c = torch.empty_like(depth_c)
+        if depth_f is not None:
+            depth_f = f32c(depth_f)
+            assert depth_f.numel() == n
+            gd_f = torch.empty_like(depth_f)
+        if pixel_index is None:
+            assert depth_src.numel() == n, "render_loss_exposure: direct depth targets are (N)"
+        else:
+            pix = pixel_index.contiguous()
+            assert pix.dtype == torch.int64 and pix.is_cuda and pix.numel() == n and depth_src.dim() >= 2
+            hw = depth_src[0].numel()
+    else:
+        depth_c = depth_f = None
+    if g_eps is None and want_eps:
+        g_eps = torch.empty((n_views, p), dtype=torch.float32, device=dev)
+    if g_eps is not None:
+        assert g_eps.is_cuda and g_eps.dtype == torch.float32 and g_eps.is_contiguous() and tuple(g_eps.shape) == (n_views, p)
+    check(lib().dn_render_loss_exposure(ptr(rgb_c), ptr(rgb_f), ptr(target), ptr(depth_c), ptr(depth_f), ptr(depth_src), ptr(pix), ptr(views),
+                                        ptr(view) if views is None else None, hw, n, int(bool(luminance)), float(weights[0]),
+                                        float(weights[1]), float(depth_weights[0]), float(depth_weights[1]), float(depth_range[0]),
+                                        float(depth_range[1]), ptr(eps), p, n_views, float(exposure_scale), ptr(view_mask), ptr(loss6),
+                                        ptr(g_c), ptr(g_f), ptr(gd_c), ptr(gd_f), ptr(g_eps), ptr(rng_state), stream()),
+          "dn_render_loss_exposure")
+    return loss6, g_c, g_f, gd_c, gd_f, g_eps
+
+
 def ndc_rays(height, width, focal, near, rays_o, rays_d):
     ro, rd = f32c(rays_o), f32c(rays_d)
     n = ro.numel() // 3

@@ -26,6 +26,9 @@ encoding_anneal (nerf.EncodingAnneal) given: three launches more on one rank in 
 ahead of everything, dn_encoding_anneal_scale_weights_pair ahead of the pack, dn_encoding_anneal_scale_grads_pair behind the backward
 (the per-network packs and the two halves of a data-parallel step: one dn_encoding_anneal_scale_weights / _scale_grads per network).
 
+Per-view exposure rows (refine_exposure=, dn_render_loss_exposure) belong to the steps that own the cameras, nerf.FusedPoseStep /
+nerf.FusedJointStep; this step trains on fixed cameras and has none.
+
 The networks: W in {128, 256} with L_xyz in {6, 10} (the shipped fern / LLFF nets are 4 x 128, L_xyz = 6), view directions.
 No autograd graph, no ATen elementwise / reduction / RNG launches (profiles/r03_as_shipped_kernel_summary.md).  The gradients land in
 a parallel.FlatGradBucket (the `.grad` tensors of the parameters).  GraphedTrainStep replays the iteration as HIP graphs (three

@@ -42,11 +42,58 @@ def loss_head_settings(who, depth_images, loss_weights, depth_weights, depth_ran
     return dict(depth_images=depth_images, weights=weights, depth_weights=d_weights, depth_range=d_range)
 
 
-def fused_loss_head(head, maps, target, rng_state, luminance=False, pixel_index=None, view_index=None, view=None):
+EXPOSURE_MODES = {None: 0, "gain": 1, "affine": 6}      # refine_exposure -> P, the floats of a view's exposure row
+
+
+def exposure_settings(who, n_views, refine_exposure, exposure_scale, exposure_fixed_views):
+    """The checked (mode, P, scale, mask as a list of V 0 / 1 - 0: the row is held) of a fused step's exposure refinement.  Raises
+    ValueError; asks for no device."""
+    if refine_exposure not in EXPOSURE_MODES:
+        raise ValueError(f"{who}: refine_exposure is None, 'gain' or 'affine' (got {refine_exposure!r})")
+    try:
+        scale = float(exposure_scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: exposure_scale must be a positive finite number (got {exposure_scale!r})") from None
+    if not 0.0 < scale < float("inf"):
+        raise ValueError(f"{who}: exposure_scale must be a positive finite number (got {exposure_scale!r})")
+    fixed = [int(v) for v in exposure_fixed_views]
+    if any(v < 0 or v >= n_views for v in fixed):
+        raise ValueError(f"{who}: exposure_fixed_views {fixed} out of range for {n_views} views")
+    if refine_exposure is None and fixed:
+        raise ValueError(f"{who}: exposure_fixed_views {fixed} without refine_exposure")
+    return refine_exposure, EXPOSURE_MODES[refine_exposure], scale, [0 if v in fixed else 1 for v in range(n_views)]
+
+
+def apply_exposure(rgb, eps_row, mode, scale=1.0):
+    """A render (..., 3) in one view's exposure: exp(s a) rgb for mode "gain" (eps_row = [a]), exp(s a_k) rgb_k + s b_k for "affine"
+    (eps_row = [a_r, a_g, a_b, b_r, b_g, b_b]), s = scale - what the loss head of a step with refine_exposure compares with that view's
+    pixels.  Plain torch on any device, differentiable; for showing or scoring a render, not a hot path."""
+    if mode not in ("gain", "affine"):
+        raise ValueError(f"apply_exposure: mode is 'gain' or 'affine' (got {mode!r})")
+    row = torch.as_tensor(eps_row, dtype=rgb.dtype, device=rgb.device).reshape(-1)
+    if row.numel() != EXPOSURE_MODES[mode]:
+        raise ValueError(f"apply_exposure: a {mode!r} row holds {EXPOSURE_MODES[mode]} numbers (got {row.numel()})")
+    if mode == "gain":
+        return torch.exp(scale * row[0]) * rgb
+    return torch.exp(scale * row[:3]) * rgb + scale * row[3:]
+
+
+def fused_loss_head(head, maps, target, rng_state, luminance=False, pixel_index=None, view_index=None, view=None, exposure=None):
     """The loss head of a fused step on the maps of render_rays_train: dn_mse2_loss for head None (loss_head_settings), else
     dn_render_loss with the depth targets gathered from head["depth_images"] at (view_index | view, pixel_index).  Returns (loss3,
     loss6 | None, g_c, g_f): loss6 = [loss, mse_c, mse_f, D_c, D_f, valid rays], loss3 its first three words; g_c / g_f the upstream
-    (g_rgb, g_depth, g_acc) of the coarse / fine maps - no depth gradient where its weight is 0 (the backward of a photometric step)."""
+    (g_rgb, g_depth, g_acc) of the coarse / fine maps - no depth gradient where its weight is 0 (the backward of a photometric step).
+    `exposure` (a step that refines it): dict(eps (V,P), scale, mask (V) int32 | None, grad (V,P)) - dn_render_loss_exposure in the place
+    of either head (head None: its weights are (1, 1), no depth term), the rows' gradient written into exposure["grad"]; loss6 always."""
+    if exposure is not None:
+        h = head or dict(depth_images=None, weights=(1.0, 1.0), depth_weights=(0.0, 0.0), depth_range=(0.0, float("inf")))
+        gather = h["depth_images"] is not None
+        loss6, g_c, g_f, gd_c, gd_f, _ = _ops.render_loss_exposure(
+            maps[0], maps[3], target, exposure["eps"], exposure["scale"], view_index, view if view_index is None else None, exposure["mask"],
+            maps[1] if gather else None, maps[4] if gather else None, h["depth_images"], pixel_index if gather else None, h["weights"],
+            h["depth_weights"], h["depth_range"], luminance, rng_state, g_eps=exposure["grad"])
+        w_c, w_f = h["depth_weights"]
+        return loss6[:3], loss6, (g_c, gd_c if w_c != 0.0 else None, None), (g_f, gd_f if w_f != 0.0 else None, None)
     if head is None:
         loss3, g_c, g_f = _ops.mse2_loss(maps[0], maps[3], target, luminance, rng_state)
         return loss3, None, (g_c, None, None), (g_f, None, None)
@@ -84,14 +131,56 @@ class RenderLossFn(torch.autograd.Function):
         return tuple(out) + (None,) * 6
 
 
+class RenderLossExposureFn(torch.autograd.Function):
+    """RenderLossFn with the exposure rows as a fifth differentiable input: (rgb_c, rgb_f | None, depth_c | None, depth_f | None,
+    exposure (V,P)) -> (loss (), loss6 (6)).  The forward runs dn_render_loss_exposure and keeps the gradients it wrote."""
+
+    @staticmethod
+    def forward(ctx, rgb_c, rgb_f, depth_c, depth_f, exposure, view_index, scale, target, target_depth, weights, depth_weights, depth_range,
+                luminance):
+        loss6, *grads = _ops.render_loss_exposure(rgb_c.detach(), None if rgb_f is None else rgb_f.detach(), target, exposure.detach(), scale,
+                                                  view_index, None, None, None if depth_c is None else depth_c.detach(),
+                                                  None if depth_f is None else depth_f.detach(), target_depth, None, weights, depth_weights,
+                                                  depth_range, luminance, want_eps=ctx.needs_input_grad[4])
+        ctx.present = [g is not None for g in grads]
+        ctx.save_for_backward(*[g for g in grads if g is not None])
+        ctx.mark_non_differentiable(loss6)
+        return loss6[0].clone(), loss6
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss, _g_terms):
+        saved = iter(ctx.saved_tensors)
+        out = []
+        for present, needs in zip(ctx.present, ctx.needs_input_grad[:5]):
+            g = next(saved) if present else None
+            out.append(g * g_loss if (g is not None and needs) else None)
+        return tuple(out) + (None,) * 8
+
+
 def render_loss(rgb_c, rgb_f, target, depth_c=None, depth_f=None, target_depth=None, weights=(1.0, 1.0), depth_weights=(0.0, 0.0),
-                depth_range=(0.0, float("inf")), luminance=False):
+                depth_range=(0.0, float("inf")), luminance=False, exposure=None, view_index=None, exposure_mode=None, exposure_scale=1.0):
     """weights[0] mse(rgb_c, target) + weights[1] mse(rgb_f, target) + depth_weights[0] D(depth_c) + depth_weights[1] D(depth_f), with
     D(depth) the mean of (depth - target_depth)^2 over the rays whose target depth lies inside depth_range (exclusive; NaN: outside).
     `luminance`: the IR head (both colour sides through 0.299 r + 0.587 g + 0.114 b).  rgb_f / depth_f may be None (coarse only);
     target_depth None: no depth term.  Returns the scalar loss, differentiable in the four maps; its `.terms` is the device tensor
-    [loss, mse_coarse, mse_fine, D_coarse, D_fine, number of valid rays].  Device tensors only."""
-    for t in (rgb_c, rgb_f, target, depth_c, depth_f, target_depth):
+    [loss, mse_coarse, mse_fine, D_coarse, D_fine, number of valid rays].  Device tensors only.
+
+    `exposure` (V,1) | (V,6) with `view_index` (N) int32: the colours of ray i enter the colour terms as apply_exposure(rgb[i],
+    exposure[view_index[i]], mode, exposure_scale) (dn_render_loss_exposure; `exposure_mode` "gain" | "affine", None: by the row length);
+    the loss is then differentiable in `exposure` as well.  None: the head above, untouched."""
+    if exposure is not None:
+        if view_index is None:
+            raise ValueError("render_loss: exposure needs view_index (the view of every ray)")
+        mode = exposure_mode if exposure_mode is not None else {1: "gain", 6: "affine"}.get(int(exposure.shape[-1]) if exposure.dim() == 2 else -1)
+        if mode not in ("gain", "affine") or exposure.dim() != 2 or int(exposure.shape[1]) != EXPOSURE_MODES[mode]:
+            raise ValueError(f"render_loss: exposure is (V,1) for exposure_mode 'gain', (V,6) for 'affine' (got {tuple(exposure.shape)}, "
+                             f"{exposure_mode!r})")
+        if not 0.0 < float(exposure_scale) < float("inf"):
+            raise ValueError(f"render_loss: exposure_scale must be a positive finite number (got {exposure_scale!r})")
+    elif view_index is not None or exposure_mode is not None:
+        raise ValueError("render_loss: view_index / exposure_mode without exposure")
+    for t in (rgb_c, rgb_f, target, depth_c, depth_f, target_depth, exposure, view_index):
         if t is not None:
             _require_device(t, "render_loss")
     if target_depth is None:
@@ -101,8 +190,12 @@ def render_loss(rgb_c, rgb_f, target, depth_c=None, depth_f=None, target_depth=N
     n = rgb_c.reshape(-1, 3).shape[0]
     flat = [rgb_c.reshape(n, 3), None if rgb_f is None else rgb_f.reshape(n, 3), None if depth_c is None else depth_c.reshape(n),
             None if depth_f is None else depth_f.reshape(n)]
-    loss, terms = RenderLossFn.apply(*flat, target.detach().reshape(n, -1)[:, :3], None if target_depth is None else target_depth.detach().reshape(n),
-                                     tuple(weights), tuple(depth_weights), tuple(depth_range), bool(luminance))
+    rest = (target.detach().reshape(n, -1)[:, :3], None if target_depth is None else target_depth.detach().reshape(n), tuple(weights),
+            tuple(depth_weights), tuple(depth_range), bool(luminance))
+    if exposure is None:
+        loss, terms = RenderLossFn.apply(*flat, *rest)
+    else:
+        loss, terms = RenderLossExposureFn.apply(*flat, _hip.f32c(exposure), view_index.detach().reshape(n), float(exposure_scale), *rest)
     loss.terms = terms
     return loss
 

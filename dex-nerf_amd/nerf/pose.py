@@ -7,7 +7,7 @@ the same step - the packs inside the graph, the weight gradients from the same b
 import torch
 
 from . import _hip, _ops
-from .loss import distortion_weight_settings, fused_loss_head, loss_head_settings
+from .loss import distortion_weight_settings, exposure_settings, fused_loss_head, loss_head_settings
 from .nerf_helpers import _require_device, img2mse, random_view_pixel_pairs, select_camera_rays
 from .train_utils import predict_and_render_radiance
 
@@ -25,9 +25,11 @@ def se3_exp(xi):
 INTRINSICS_MODES = (None, "shared", "per_view")
 
 
-def _refinement_settings(who, n_views, refine_intrinsics, intrinsics_scale, fixed_views, refine_pose=True, networks_train=False):
+def _refinement_settings(who, n_views, refine_intrinsics, intrinsics_scale, fixed_views, refine_pose=True, networks_train=False,
+                         refine_exposure=None):
     """The checked (mode, scale, pose mask as a list of V 0 / 1) of FusedPoseStep / MultiPoseRefiner.  networks_train (FusedJointStep):
-    the step has the networks to update, so holding every camera fixed is allowed."""
+    the step has the networks to update, so holding every camera fixed is allowed; so it is with refine_exposure (the exposure rows are
+    something refined)."""
     if refine_intrinsics not in INTRINSICS_MODES:
         raise ValueError(f"{who}: refine_intrinsics is None, 'shared' or 'per_view' (got {refine_intrinsics!r})")
     scale = float(intrinsics_scale)
@@ -36,7 +38,7 @@ def _refinement_settings(who, n_views, refine_intrinsics, intrinsics_scale, fixe
     fixed = [int(v) for v in fixed_views]
     if any(v < 0 or v >= n_views for v in fixed):
         raise ValueError(f"{who}: fixed_views {fixed} out of range for {n_views} views")
-    if not refine_pose and refine_intrinsics is None and not networks_train:
+    if not refine_pose and refine_intrinsics is None and not networks_train and refine_exposure is None:
         raise ValueError(f"{who}: refine_pose=False with refine_intrinsics=None leaves nothing to refine")
     mask = [0 if (not refine_pose or v in fixed) else 1 for v in range(n_views)]
     return refine_intrinsics, scale, mask
@@ -250,7 +252,18 @@ class FusedPoseStep:
     backward's one launch).  `fixed_views` (view indices) and `refine_pose=False` (every view) hold poses fixed:
     those views' twist gradients are exact zeros, which leaves their xi untouched bit for bit; either also puts the step on the new
     pair.  With all four at their defaults the step is the launches above.  phi (a device view into the flat buffer, None when the
-    intrinsics are not refined), last_grad_phi, intrinsics()."""
+    intrinsics are not refined), last_grad_phi, intrinsics().
+
+    `refine_exposure` "gain" | "affine": a photometric row per view is refined with the cameras - eps[v] = [a] | [a_r, a_g, a_b, b_r,
+    b_g, b_b], and a ray of view v meets its pixel as exp(s a_k) c_k (+ s b_k), s = `exposure_scale` (nerf.apply_exposure; the handle on
+    the rows' step relative to the twists', as intrinsics_scale is for phi).  The flat buffer becomes [xi (6V) | phi | eps (P V) | pad to
+    4] under the same ONE dn_adam_step; dn_render_loss_exposure stands in the head's place (the head and one workgroup per view that
+    reduces the rows' gradient: one launch more) and a device-to-device copy of P V floats keeps last_grad_eps.
+    `exposure_fixed_views` holds rows at their values (the kernel's mask: their gradients are exact zeros) - a common gain of all views
+    is a gauge the networks absorb, (0,) pins it.  refine_pose=False with refine_exposure fits the appearance of (held-out) views on
+    frozen networks.  eps (a device view into the flat buffer, None when the exposure is not refined), last_grad_eps, exposure().  With
+    refine_exposure=None the step enqueues the launches above on the buffers above, nothing else.  Not covered: the 8-bit saved layout
+    and the distortion term (the geometry route takes neither), several ranks; FusedTrainStep (fixed cameras) has no exposure rows."""
 
     _who = "FusedPoseStep"
     _networks_train = False       # FusedJointStep: the networks are parameters of the step too
@@ -259,7 +272,8 @@ class FusedPoseStep:
     def __init__(self, model_coarse, model_fine, options, height, width, intrinsic, extrinsics0, images, encode_position_fn,
                  encode_direction_fn, num_rays, lr, seed=0, first_iteration=0, ndc_focal=None, use_graphs=True, eager_iterations=3,
                  depth_images=None, loss_weights=(1.0, 1.0), depth_weights=(0.0, 0.0), depth_range=(0.0, float("inf")),
-                 refine_intrinsics=None, intrinsics_scale=1.0, fixed_views=(), refine_pose=True, distortion_weights=(0.0, 0.0)):
+                 refine_intrinsics=None, intrinsics_scale=1.0, fixed_views=(), refine_pose=True, distortion_weights=(0.0, 0.0),
+                 refine_exposure=None, exposure_scale=1.0, exposure_fixed_views=()):
         who = self._who
         if max(distortion_weight_settings(who, distortion_weights)) > 0.0:
             raise ValueError(f"{who}: the geometry route takes no distortion regulariser yet (distortion_weights {tuple(distortion_weights)}): its "
@@ -276,8 +290,10 @@ class FusedPoseStep:
         self.height, self.width = int(height), int(width)
         if tuple(images.shape[1:3]) != (self.height, self.width):
             raise ValueError(f"{who}: images of shape {tuple(images.shape)} for {self.height} x {self.width} cameras")
+        self.exposure_mode, n_exp, self.exposure_scale, exposure_mask = exposure_settings(who, self.n_views, refine_exposure, exposure_scale,
+                                                                                          exposure_fixed_views)
         self.mode, self.intrinsics_scale, mask = _refinement_settings(who, self.n_views, refine_intrinsics, intrinsics_scale,
-                                                                      fixed_views, refine_pose, self._networks_train)
+                                                                      fixed_views, refine_pose, self._networks_train, self.exposure_mode)
         # None: the reference's head (dn_mse2_loss); else the settings of dn_render_loss (a zero colour weight is allowed here: fp32 or
         # 16-bit saves, no per-launch 8-bit gradient scale)
         self.head = loss_head_settings(who, depth_images, loss_weights, depth_weights, depth_range,
@@ -306,7 +322,8 @@ class FusedPoseStep:
         self.images = _hip.f32c(images.detach())
         n = 6 * self.n_views
         n_phi = {None: 0, "shared": 3, "per_view": 3 * self.n_views}[self.mode]
-        padded = (n + n_phi + 3) // 4 * 4         # dn_adam_step works on multiples of four elements
+        n_eps = n_exp * self.n_views
+        padded = (n + n_phi + n_eps + 3) // 4 * 4         # dn_adam_step works on multiples of four elements
         self._flat = torch.zeros(4, padded, dtype=torch.float32, device=dev)    # rows: xi, gradient, exp_avg, exp_avg_sq
         self.xi = self._flat[0, :n].view(self.n_views, 6)
         self._grad = self._flat[1, :n].view(self.n_views, 6)
@@ -317,6 +334,14 @@ class FusedPoseStep:
             self.phi = self._flat[0, n:n + n_phi].view(shape)
             self._grad_phi = self._flat[1, n:n + n_phi].view(shape)
             self.last_grad_phi = torch.zeros(shape, dtype=torch.float32, device=dev)
+        # the exposure rows behind phi; _exposure: what fused_loss_head hands dn_render_loss_exposure (None: the heads as ever)
+        self.eps = self.last_grad_eps = self._exposure = None
+        if self.exposure_mode is not None:
+            at = n + n_phi
+            self.eps = self._flat[0, at:at + n_eps].view(self.n_views, n_exp)
+            self.last_grad_eps = torch.zeros(self.n_views, n_exp, dtype=torch.float32, device=dev)
+            self._exposure = dict(eps=self.eps, scale=self.exposure_scale, grad=self._flat[1, at:at + n_eps].view(self.n_views, n_exp),
+                                  mask=None if all(exposure_mask) else torch.tensor(exposure_mask, dtype=torch.int32, device=dev))
         # dn_pose_records and its backward unless something of the new pair is asked for
         self.camera_pair = self.mode is not None or not all(mask)
         self.pose_mask = None if all(mask) else torch.tensor(mask, dtype=torch.int32, device=dev)
@@ -390,7 +415,10 @@ class FusedPoseStep:
                                                                ndc_near=1.0)
         maps, saved = _ops.render_rays_train_geom(pc, pf, rays, self.nc, self.nf, self.lindisp, self.noise_std, self.white, [], None,
                                                   prec=pc.precision, rng_state=self.rng_state, perturb=self.perturb)
-        self.loss3, self.loss6, g_c, g_f = fused_loss_head(self.head, maps, target, self.rng_state, self.luminance, pix, views)
+        self.loss3, self.loss6, g_c, g_f = fused_loss_head(self.head, maps, target, self.rng_state, self.luminance, pix, views,
+                                                           exposure=self._exposure)
+        if self._exposure is not None:    # dn_adam_step clears the gradient row: the rows' gradient of this step, kept
+            self.last_grad_eps.copy_(self._exposure["grad"])
         self._clear_weight_gradients()
         w_views = self._weight_gradient_views()
         d_rays, keep = _ops.render_rays_backward_geom(pc, pf, saved, g_c, g_f, *w_views)
@@ -453,6 +481,11 @@ class FusedPoseStep:
         out[:, 0, 0], out[:, 0, 2], out[:, 1, 2] = cams[:, 12], cams[:, 13], cams[:, 14]
         return out if per_view else out[0]
 
+    def exposure(self):
+        """The current exposure rows, (V,P) fp32 on the device (a copy; row v with nerf.apply_exposure(rgb, row, refine_exposure,
+        exposure_scale) shows a render as view v saw it); None when the exposure is not refined."""
+        return None if self.eps is None else self.eps.detach().clone()
+
 
 class FusedJointStep(FusedPoseStep):
     """The training iteration with the cameras as parameters beside the networks: FusedPoseStep's launches with the networks NOT
@@ -491,8 +524,14 @@ class FusedJointStep(FusedPoseStep):
     see.  The step does not remove it; `fixed_views=(0,)` pins it to the first camera.  refine_pose=False with refine_intrinsics=None
     is allowed here (the networks alone are trained, on the step's own mixed-view draws).
 
-    state_dict() / load_state_dict(): [xi | phi], the two Adam moments and dn_adam_step's state record; with the networks', the
-    optimizer's state and first_iteration = the number of steps taken, a fresh step continues the run."""
+    `refine_exposure` / `exposure_scale` / `exposure_fixed_views`: FusedPoseStep's per-view exposure rows, trained with the cameras and
+    the networks - [xi | phi | eps] under the one dn_adam_step at `lr_pose`, dn_render_loss_exposure in the head's place.  A view that is
+    brighter than its neighbours is then explained by its row, not by view-dependent colour or haze in front of its camera.  Same limits:
+    one rank, no 8-bit saved layout, no distortion term.
+
+    state_dict() / load_state_dict(): [xi | phi | eps], the two Adam moments and dn_adam_step's state record (with refine_exposure its
+    mode and scale too; a state without them is one without exposure rows, and a mismatch raises like refine_intrinsics'); with the
+    networks', the optimizer's state and first_iteration = the number of steps taken, a fresh step continues the run."""
 
     _who = "FusedJointStep"
     _networks_train = True
@@ -558,14 +597,20 @@ class FusedJointStep(FusedPoseStep):
     def state_dict(self):
         """The camera half of the run: the flat buffer's rows [xi | phi | pad], exp_avg and exp_avg_sq, and dn_adam_step's state record
         (raw words: the step count and the running products), as independent tensors."""
-        return dict(params=self._flat[0].detach().clone(), exp_avg=self._flat[2].detach().clone(), exp_avg_sq=self._flat[3].detach().clone(),
-                    adam_state=self._adam_state.detach().clone(), n_views=self.n_views, refine_intrinsics=self.mode)
+        state = dict(params=self._flat[0].detach().clone(), exp_avg=self._flat[2].detach().clone(), exp_avg_sq=self._flat[3].detach().clone(),
+                     adam_state=self._adam_state.detach().clone(), n_views=self.n_views, refine_intrinsics=self.mode)
+        if self.exposure_mode is not None:      # (a state without the two keys: no exposure rows in the flat buffer)
+            state.update(refine_exposure=self.exposure_mode, exposure_scale=self.exposure_scale)
+        return state
 
     def load_state_dict(self, state):
-        if int(state["n_views"]) != self.n_views or state["refine_intrinsics"] != self.mode \
+        exposure = (state.get("refine_exposure"), float(state.get("exposure_scale", 1.0)) if state.get("refine_exposure") is not None else None)
+        mine = (self.exposure_mode, self.exposure_scale if self.exposure_mode is not None else None)
+        if int(state["n_views"]) != self.n_views or state["refine_intrinsics"] != self.mode or exposure != mine \
                 or tuple(state["params"].shape) != tuple(self._flat[0].shape):
             raise ValueError(f"FusedJointStep.load_state_dict: a state of {state['n_views']} views, refine_intrinsics="
-                             f"{state['refine_intrinsics']!r} for a step of {self.n_views} views, refine_intrinsics={self.mode!r}")
+                             f"{state['refine_intrinsics']!r}, refine_exposure={exposure[0]!r} (scale {exposure[1]}) for a step of "
+                             f"{self.n_views} views, refine_intrinsics={self.mode!r}, refine_exposure={mine[0]!r} (scale {mine[1]})")
         self._flat[0].copy_(state["params"])
         self._flat[1].zero_()
         self._flat[2].copy_(state["exp_avg"])

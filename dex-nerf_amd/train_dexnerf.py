@@ -144,9 +144,13 @@ def perturbed_poses(extrinsics, rot, trans, seed, keep=()):
 
 def joint_checkpoint_entries(joint, train_ids, extrinsics0):
     """What --refine-poses adds to the checkpoint dict: the step's state, and the cameras as plain host tensors for other tools (eval_nerf.py --use-refined-poses)."""
-    return {JOINT_KEY: joint.state_dict(), "refined_views": [int(v) for v in train_ids],
-            "refined_extrinsics": joint.extrinsics().cpu(), "refined_intrinsics": joint.intrinsics().cpu(),
-            "joint_initial_extrinsics": extrinsics0.detach().cpu()}
+    entries = {JOINT_KEY: joint.state_dict(), "refined_views": [int(v) for v in train_ids],
+               "refined_extrinsics": joint.extrinsics().cpu(), "refined_intrinsics": joint.intrinsics().cpu(),
+               "joint_initial_extrinsics": extrinsics0.detach().cpu()}
+    if joint.exposure_mode is not None:      # --refine-exposure: the rows (V,P) with what nerf.apply_exposure needs to read them
+        entries.update(refined_exposure=joint.exposure().cpu(), refined_exposure_mode=joint.exposure_mode,
+                       refined_exposure_scale=joint.exposure_scale)
+    return entries
 
 
 def restore_joint_state(ck, joint):
@@ -244,6 +248,15 @@ def build_parser():
     ap.add_argument("--fix-views", type=int, nargs="+", default=None, metavar="I",
                     help="--refine-poses: training views (positions in the training set) whose poses stay as given; default 0 - with "
                          "every view free the scene can drift by a rigid motion, one fixed camera pins it")
+    ap.add_argument("--refine-exposure", default=None, choices=["gain", "affine"],
+                    help="--refine-poses: refine a photometric row per training view as well - one gain, or a gain and an offset per "
+                         "channel - so that a view's exposure / white balance is not explained by the networks; with every view in "
+                         "--fix-views (or --pose-lr 0) the run trains the networks and the exposure alone")
+    ap.add_argument("--exposure-scale", type=float, default=None,
+                    help="--refine-exposure: size of an exposure step relative to a twist step (default 1)")
+    ap.add_argument("--fix-exposure-views", type=int, nargs="+", default=None, metavar="I",
+                    help="--refine-exposure: training views (positions in the training set) whose rows stay at the identity; default 0 - a "
+                         "common gain of all views is absorbed by the networks, one fixed view pins it")
     ap.add_argument("--anneal-encoding", type=int, nargs=2, default=None, metavar=("START", "END"),
                     help="coarse-to-fine positional encoding (BARF): the bands of the encodings are switched on one after the other "
                          "between iterations START and END (nerf.EncodingAnneal on the fused steps; with and without --refine-poses). The "
@@ -261,7 +274,9 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if not args.refine_poses:
         for flag, value in (("--pose-lr", args.pose_lr), ("--pose-lr-decay", args.pose_lr_decay), ("--refine-intrinsics", args.refine_intrinsics),
-                            ("--intrinsics-scale", args.intrinsics_scale), ("--fix-views", args.fix_views)):
+                            ("--intrinsics-scale", args.intrinsics_scale), ("--fix-views", args.fix_views),
+                            ("--refine-exposure", args.refine_exposure), ("--exposure-scale", args.exposure_scale),
+                            ("--fix-exposure-views", args.fix_exposure_views)):
             if value is not None:
                 ap.error(f"{flag} needs --refine-poses")
     else:
@@ -275,6 +290,13 @@ def parse_args(argv=None):
             ap.error("--intrinsics-scale needs --refine-intrinsics and must be > 0")
         if args.fix_views is not None and min(args.fix_views) < 0:
             ap.error("--fix-views: positions in the training set, >= 0")
+        if args.exposure_scale is not None and (args.refine_exposure is None or not 0.0 < args.exposure_scale < float("inf")):
+            ap.error("--exposure-scale needs --refine-exposure and must be > 0")
+        if args.fix_exposure_views is not None and (args.refine_exposure is None or min(args.fix_exposure_views) < 0):
+            ap.error("--fix-exposure-views needs --refine-exposure: positions in the training set, >= 0")
+        args.exposure_scale = 1.0 if args.exposure_scale is None else args.exposure_scale
+        if args.refine_exposure is not None and args.fix_exposure_views is None:
+            args.fix_exposure_views = [0]
         args.pose_lr = 1e-3 if args.pose_lr is None else args.pose_lr
         args.intrinsics_scale = 1.0 if args.intrinsics_scale is None else args.intrinsics_scale
         args.fix_views = [0] if args.fix_views is None else args.fix_views
@@ -436,11 +458,15 @@ def main(argv=None):
                              "nerf.MultiPoseRefiner + autograd covers those")
         if max(args.fix_views) >= len(train_ids):
             raise SystemExit(f"--fix-views {args.fix_views}: the training set has {len(train_ids)} views")
+        if args.refine_exposure is not None and max(args.fix_exposure_views) >= len(train_ids):
+            raise SystemExit(f"--fix-exposure-views {args.fix_exposure_views}: the training set has {len(train_ids)} views")
         joint = nerf.FusedJointStep(student[0], student[1], cfg, hw[0], hw[1], torch.stack([intrinsics[v] for v in train_ids]), extrinsics0,
                                     selector.images, ex, ed, args.num_random_rays, bucket, opt, args.pose_lr,
                                     pose_lr_decay=args.pose_lr_decay, luminance=args.ir, seed=args.seed, first_iteration=start,
                                     ndc_focal=ndc_focal, use_graphs=use_graph, eager_iterations=3, refine_intrinsics=args.refine_intrinsics,
-                                    intrinsics_scale=args.intrinsics_scale, fixed_views=args.fix_views, encoding_anneal=anneal, **head)
+                                    intrinsics_scale=args.intrinsics_scale, fixed_views=args.fix_views, encoding_anneal=anneal,
+                                    refine_exposure=args.refine_exposure, exposure_scale=args.exposure_scale,
+                                    exposure_fixed_views=tuple(args.fix_exposure_views or ()), **head)
         if args.load_checkpoint:
             restore_joint_state(ck, joint)
         fused_ok = False                # the joint step is the training iteration
@@ -585,6 +611,8 @@ def main(argv=None):
         if args.pose_noise is not None:
             result["pose_from_unperturbed"] = pose_distance(joint.extrinsics(), given_extrinsics)
         result["xi"] = joint.xi.detach().cpu()
+        if joint.exposure_mode is not None:      # the final rows, (V,P)
+            result["exposure"] = joint.exposure().cpu().tolist()
     else:
         result["hip_graphs"] = len(graphed.graphs) if (graphed is not None and graphed.graphs) else int(graph is not None)   # graphs replayed per iteration
     if args.precision in ("bf16", "bf16-s8"):
