@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/dexnerf_hip_ext.h"
+#include "../../include/dexnerf_hip_normals.h"
 #include "dn_common.h"
 #include "composite_body.h"
 #include "dn_rng.h"
@@ -244,6 +245,105 @@ extern "C" int dn_render_rays_depth(const dn_mlp_desc* desc_coarse, const void* 
     return rc;
   return composite_density_counting(w.rf_f, w.z_f, rays + 3, ray_stride, noise_f, noise_std, d_m_thres, n_thres, n_rays,
                                     num_coarse + num_fine, depth_f, acc_f, dex_f, w.status, stream);
+}
+
+// ---- the normal render (include/dexnerf_hip_normals.h): dn_render_rays_depth with the last pass differentiated ---------------------
+namespace dn {
+// carve_depth's regions, then what the differentiated pass keeps: the training forward's saved tensors, the gradient records, the seed
+// and the per-point gradient
+struct NormalsWorkspace {
+  DepthWorkspace d;
+  void *act, *masks, *grads;
+  float *g_out, *g_pts;
+  size_t bytes;   // 0: the differentiated network's descriptor / precision is not covered
+};
+
+static NormalsWorkspace carve_normals(void* base, const dn_mlp_desc* desc_last, int precision, int64_t n, int nc, int nf) {
+  NormalsWorkspace w{};
+  w.d = carve_depth(base, n, nc, nf);
+  const int64_t points = n * (nc + nf);
+  size_t act = 0, masks = 0, grads = 0;
+  if (dn_mlp_train_sizes(desc_last, precision, points, &act, &masks, &grads)) return w;
+  size_t off = w.d.bytes;
+  auto take = [&](size_t bytes) {
+    void* p = base ? static_cast<void*>(static_cast<char*>(base) + off) : nullptr;
+    off += align256(bytes);
+    return p;
+  };
+  w.act = take(act); w.masks = take(masks); w.grads = take(grads);
+  w.g_out = static_cast<float*>(take(static_cast<size_t>(points) * 4 * sizeof(float)));
+  w.g_pts = static_cast<float*>(take(static_cast<size_t>(points) * 3 * sizeof(float)));
+  w.bytes = off;
+  return w;
+}
+}  // namespace dn
+
+extern "C" size_t dn_render_normals_workspace_bytes(const dn_mlp_desc* desc_coarse, const dn_mlp_desc* desc_fine, int precision,
+                                                    int64_t n_rays, int num_coarse, int num_fine) {
+  if (!desc_coarse || n_rays < 0 || num_coarse < 1 || num_fine < 0 || (num_fine > 0 && !desc_fine)) return 0;
+  const dn_mlp_desc* last = num_fine > 0 ? desc_fine : desc_coarse;
+  if (desc_coarse->use_viewdirs || last->use_viewdirs || validate_desc(desc_coarse, precision) ||
+      input_grad_check(last, precision, "dn_render_normals_workspace_bytes"))
+    return 0;
+  return carve_normals(nullptr, last, precision, n_rays, num_coarse, num_fine).bytes;
+}
+
+extern "C" int dn_render_rays_normals(const dn_mlp_desc* desc_coarse, const void* packed_coarse, const dn_mlp_desc* desc_fine,
+                                      const void* packed_fine, const void* packed_bwd, const void* packed_ig, int precision,
+                                      const float* rays, int ray_stride, int64_t n_rays, int num_coarse, int num_fine, int lindisp,
+                                      float noise_std, const float* d_m_thres, int n_thres, const float* t_rand, const float* noise_c,
+                                      const float* u, const float* noise_f, float* depth_c, float* acc_c, float* depth, float* acc,
+                                      float* dex, float* normal, float* dex_normal, void* workspace, size_t workspace_bytes,
+                                      dn_stream_t stream) {
+  // every argument is judged before any GPU work
+  DN_REQUIRE(desc_coarse && packed_coarse && packed_bwd && packed_ig && rays && workspace && n_rays >= 0, "dn_render_rays_normals: bad arguments");
+  DN_REQUIRE(num_coarse >= 1 && num_fine >= 0 && ray_stride >= 8, "dn_render_rays_normals: bad sample counts / ray stride");
+  DN_REQUIRE(num_fine == 0 || (desc_fine && packed_fine), "dn_render_rays_normals: fine pass requested without a fine net");
+  DN_REQUIRE(n_thres >= 0, "dn_render_rays_normals: negative threshold count");
+  DN_REQUIRE(n_thres == 0 || (d_m_thres && (dex || dex_normal)), "dn_render_rays_normals: thresholds given without dex or dex_normal output");
+  DN_REQUIRE(!desc_coarse->use_viewdirs && (num_fine == 0 || !desc_fine->use_viewdirs),
+             "dn_render_rays_normals: takes density sub-networks (dn_mlp_density_desc / dn_mlp_pack_density): use_viewdirs must be 0");
+  DN_REQUIRE(num_fine == 0 || (num_coarse >= 10 && num_coarse <= 512 && num_coarse + num_fine <= 2048),
+             "dn_render_rays_normals: need 10 <= num_coarse <= 512 and num_coarse + num_fine <= 2048");
+  DN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "dn_render_rays_normals: workspace must be 256-byte aligned");
+  DN_REQUIRE(((reinterpret_cast<uintptr_t>(packed_bwd) | reinterpret_cast<uintptr_t>(packed_ig)) & 15) == 0,
+             "dn_render_rays_normals: the backward and input-gradient streams must be 16-byte aligned");
+  const bool fine = num_fine > 0;
+  const dn_mlp_desc* last = fine ? desc_fine : desc_coarse;
+  int rc;
+  if ((rc = input_grad_check(last, precision, "dn_render_rays_normals"))) return rc;   // F32, or BF16 with 16-bit saves; L_xyz in {6, 10}
+  if (fine && (rc = validate_desc(desc_coarse, precision))) return rc;
+  const NormalsWorkspace w = carve_normals(workspace, last, precision, n_rays, num_coarse, num_fine);
+  DN_REQUIRE(w.bytes != 0 && workspace_bytes >= w.bytes, "dn_render_rays_normals: workspace too small (%zu bytes needed)", w.bytes);
+  if (n_rays == 0) return 0;
+  {
+    hipError_t e = hipMemsetAsync(w.d.status, 0, 256, as_stream(stream));
+    if (e != hipSuccess) { set_error("dn_render_rays_normals: hipMemsetAsync: %s", hipGetErrorString(e)); return -static_cast<int>(e); }
+  }
+  if ((rc = dn_coarse_depths(rays, ray_stride, n_rays, num_coarse, lindisp, t_rand, w.d.z_c, stream))) return rc;
+  const float* z_last = w.d.z_c;
+  float* rf_last = w.d.rf_c;
+  const int samples = num_coarse + num_fine;
+  if (fine) {
+    if ((rc = run_network_flagged(desc_coarse, precision, packed_coarse, nullptr, nullptr, rays, ray_stride, w.d.z_c, n_rays, num_coarse,
+                                  w.d.rf_c, w.d.status + 1, stream)))
+      return rc;
+    if ((rc = density_resample_counting(w.d.rf_c, w.d.z_c, rays + 3, ray_stride, noise_c, noise_std, u, n_rays, num_coarse, num_fine, depth_c,
+                                        acc_c, w.d.z_f, w.d.status, stream)))
+      return rc;
+    z_last = w.d.z_f;
+    rf_last = w.d.rf_f;
+  }
+  // the differentiated pass: training forward (saves kept), seed, backward-data chain, per-point input gradient, compositing
+  if ((rc = dn_run_network_train(last, precision, fine ? packed_fine : packed_coarse, nullptr, nullptr, rays, ray_stride, z_last, n_rays,
+                                 samples, rf_last, w.act, w.masks, stream)))
+    return rc;
+  const int64_t points = n_rays * samples;
+  if ((rc = density_seed(w.g_out, points, stream))) return rc;
+  if ((rc = dn_mlp_backward_data(last, precision, packed_bwd, w.g_out, w.masks, points, w.grads, stream))) return rc;
+  if ((rc = input_grad_points_from_rays(last, precision, packed_ig, w.grads, rays, ray_stride, z_last, n_rays, samples, w.g_pts, stream))) return rc;
+  return composite_normals_counting(rf_last, z_last, rays + 3, ray_stride, fine ? noise_f : noise_c, noise_std, w.g_pts, d_m_thres, n_thres, n_rays,
+                                    samples, depth, acc, dex, normal, dex_normal, w.d.status, stream);
 }
 
 // ---- predict_and_render_radiance under autograd (reference nerf/train_utils.py:92-202 + loss.backward(),

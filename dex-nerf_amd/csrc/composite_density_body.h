@@ -4,8 +4,11 @@
 // same bits as dn_volume_render's for the same sigma and depths.  Shared by composite_density_kernel and density_resample_kernel.
 #pragma once
 #include "composite_body.h"
+#include <type_traits>
 
 namespace dn {
+
+struct NoFirstHook {};   // density_ray without the first-crossing hook
 
 // sample_terms' sigma alone (the Dex passes over threshold groups past the first re-read the column)
 __device__ __forceinline__ float density_sigma(float raw_sigma, float noise, float noise_std) {
@@ -17,12 +20,15 @@ __device__ __forceinline__ float density_sigma(float raw_sigma, float noise, flo
 // rfr: the ray's (S,4) raw rows (only .w is read); on_weight(s, w): called once per sample with its compositing weight;
 // d_thres: n_thres thresholds in DEVICE memory, any count - lane k of a wave tracks threshold 64 g + k of group g; group 0 rides
 // in the compositing pass, every further group is one more pass over the ray's sigma column (L2-resident by then).
-template <class OnWeight>
+// on_first(k, idx) - optional - is called by the lane that holds threshold k with the index of the first sample whose sigma exceeds it
+// (-1: none; the Dex depth then falls back to z[0]), for every threshold, whether or not `dex` is given (composite_normals_kernel).
+template <class OnWeight, class OnFirst = NoFirstHook>
 __device__ __forceinline__ void density_ray(const float4* __restrict__ rfr, const float* __restrict__ zr, const float* __restrict__ rd3,
                                             int64_t ray, bool live, int lane, const float* __restrict__ noise, float noise_std,
                                             const float* __restrict__ d_thres, int n_thres, int64_t n_rays, int S,
                                             float* __restrict__ acc, float* __restrict__ depth, float* __restrict__ dex,
-                                            unsigned* __restrict__ nonfinite, OnWeight on_weight) {
+                                            unsigned* __restrict__ nonfinite, OnWeight on_weight, OnFirst on_first = OnFirst{}) {
+  constexpr bool kFirstHook = !std::is_same<OnFirst, NoFirstHook>::value;
   const float* sig = reinterpret_cast<const float*>(rfr) + 3;   // raw sigma of sample s: sig[4 s]
   unsigned n_bad = 0;
   const float dx = rd3[0], dy = rd3[1], dz = rd3[2];
@@ -77,9 +83,14 @@ __device__ __forceinline__ void density_ray(const float4* __restrict__ rfr, cons
     if (depth != nullptr) depth[ray] = s_d;
     if (acc != nullptr) acc[ray] = s_a;
   }
-  if (dex == nullptr) return;
+  if constexpr (!kFirstHook) {
+    if (dex == nullptr) return;
+  }
   // argmax of an all-zero row is index 0 -> z[0] (volume_rendering_utils.py:54-58)
-  if (lane < k0 && live) dex[static_cast<int64_t>(lane) * n_rays + ray] = zr[first_idx < 0 ? 0 : first_idx];
+  if (lane < k0 && live) {
+    if (dex != nullptr) dex[static_cast<int64_t>(lane) * n_rays + ray] = zr[first_idx < 0 ? 0 : first_idx];
+    if constexpr (kFirstHook) on_first(lane, first_idx);
+  }
   for (int kg = 64; kg < n_thres; kg += 64) {   // thresholds 64.. : sigma only
     const int kn = (n_thres - kg) < 64 ? (n_thres - kg) : 64;
     const float m = (lane < kn) ? d_thres[kg + lane] : 0.0f;
@@ -91,7 +102,10 @@ __device__ __forceinline__ void density_ray(const float4* __restrict__ rfr, cons
       const int sc = valid ? s : S - 1;
       dex_chunk(density_sigma(sig[4 * sc], noise_at(sc), noise_std), valid, base, m, kn, first, fnd);
     }
-    if (lane < kn && live) dex[static_cast<int64_t>(kg + lane) * n_rays + ray] = zr[first < 0 ? 0 : first];
+    if (lane < kn && live) {
+      if (dex != nullptr) dex[static_cast<int64_t>(kg + lane) * n_rays + ray] = zr[first < 0 ? 0 : first];
+      if constexpr (kFirstHook) on_first(kg + lane, first);
+    }
   }
 }
 

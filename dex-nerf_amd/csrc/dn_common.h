@@ -47,6 +47,17 @@ int composite_density_counting(const float* rf, const float* z, const float* rd,
                                const float* d_m_thres, int n_thres, int64_t n_rays, int n_samples, float* depth, float* acc, float* dex,
                                unsigned* nonfinite, dn_stream_t stream);
 
+// composite_normals.hip: dn_composite_normals with the non-finite count; the density gradient's seed g_out = (0,0,0,1) per point
+int composite_normals_counting(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise, float noise_std,
+                               const float* g_pts, const float* d_m_thres, int n_thres, int64_t n_rays, int n_samples, float* depth,
+                               float* acc, float* dex, float* normal, float* dex_normal, unsigned* nonfinite, dn_stream_t stream);
+int density_seed(float* g_out, int64_t n_points, dn_stream_t stream);
+// mlp_input_grad.hip: dn_mlp_backward_input's descriptor / precision rule, and its first launch alone - the per-point d_pts (P,3) of a
+// no-view-direction network from rays + z into the caller's buffer
+int input_grad_check(const dn_mlp_desc* desc, int precision, const char* who);
+int input_grad_points_from_rays(const dn_mlp_desc* desc, int precision, const void* packed_ig, const void* grads, const float* rays,
+                                int ray_stride, const float* z_vals, int64_t n_rays, int samples_per_ray, float* d_pts, dn_stream_t stream);
+
 // mlp_fused.hip: dn_run_network with the fp16 range flag (a device word the 48-point fp16 kernel bumps when a hidden activation
 // left fp16's range; NULL = not wanted)
 bool weight_grad_pair_fits(const dn_mlp_desc& d);   // mlp_wgrad.hip: the layers of two such networks fit one weight-gradient batch

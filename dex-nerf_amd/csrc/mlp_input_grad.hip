@@ -329,6 +329,58 @@ static size_t input_grad_workspace(const dn_mlp_desc& d, int64_t n_points, int r
   return per_pad * ((ray_form ? 1 : 0) + (d.use_viewdirs ? 1 : 0));
 }
 
+// The first launch of dn_mlp_backward_input alone: the per-point d_pts (P,3) - and d_viewdir (P,3) with view directions - from the
+// gradient records, the points given as pts (+ viewdirs) or formed from rays + z.  Arguments already judged by the caller.
+static int point_input_grads(const dn_mlp_desc* desc, int precision, const void* packed_ig, const void* grads, const float* pts,
+                             const float* viewdirs, const float* rays, int ray_stride, const float* z_vals, int64_t n_points,
+                             int samples_per_ray, float* d_pts, float* d_vd, dn_stream_t stream) {
+  IgLayout g;
+  build_input_grad_layout(*desc, precision, &g);
+  FwdParams fp;
+  int rc;
+  if ((rc = setup_params(desc, precision, packed_ig, &fp))) return rc;   // (for the frequency tables)
+  const bool vdirs = desc->use_viewdirs != 0;
+  IgParams p{};
+  p.stream = static_cast<const char*>(packed_ig);
+  p.stream_bytes = g.total_pieces * kPieceBytes;
+  p.grads = static_cast<const char*>(grads);
+  p.grad_pieces = g.grad_pieces;
+  p.n_x = g.n_x; p.kh = g.kh;
+  for (int s = 0; s < g.n_x; ++s) p.gslot[s] = g.gslot[s];
+  p.gslot_dirout = g.gslot_dirout; p.dir_piece0 = g.dir_piece0; p.use_viewdirs = vdirs;
+  p.mode = pts == nullptr ? 0 : 1;
+  p.rays = rays; p.ray_stride = ray_stride; p.z = z_vals; p.pts = pts; p.viewdirs = viewdirs;
+  p.n_points = n_points; p.S = samples_per_ray;
+  p.d_pts = d_pts;
+  p.d_vd = vdirs ? d_vd : nullptr;
+  for (int i = 0; i < 16; ++i) p.fx[i] = fp.fx[i];
+  for (int i = 0; i < 8; ++i) p.fd[i] = fp.fd[i];
+
+  const bool bf = precision == DN_PREC_BF16;
+  const int LX = desc->num_encoding_fn_xyz;
+  if (bf && LX == 10) return launch_input_grad<1, 10>(p, as_stream(stream));
+  if (bf) return launch_input_grad<1, 6>(p, as_stream(stream));
+  if (LX == 10) return launch_input_grad<0, 10>(p, as_stream(stream));
+  return launch_input_grad<0, 6>(p, as_stream(stream));
+}
+
+// api.cpp (dn_render_rays_normals): the descriptor / precision rule of the input gradient, and the per-point d_pts (P,3) of a
+// no-view-direction network from rays + z into the caller's buffer - no per-ray reduction, no workspace
+int input_grad_check(const dn_mlp_desc* desc, int precision, const char* who) { return validate_input_grad(desc, precision, who); }
+
+int input_grad_points_from_rays(const dn_mlp_desc* desc, int precision, const void* packed_ig, const void* grads, const float* rays,
+                                int ray_stride, const float* z_vals, int64_t n_rays, int samples_per_ray, float* d_pts, dn_stream_t stream) {
+  int rc = validate_input_grad(desc, precision, "input_grad_points_from_rays");
+  if (rc) return rc;
+  DN_REQUIRE(!desc->use_viewdirs && packed_ig && grads && rays && z_vals && d_pts && n_rays >= 0 && samples_per_ray >= 1 && ray_stride >= 8,
+             "input_grad_points_from_rays: bad arguments");
+  DN_REQUIRE(((reinterpret_cast<uintptr_t>(packed_ig) | reinterpret_cast<uintptr_t>(grads)) & 15) == 0,
+             "input_grad_points_from_rays: buffers must be 16-byte aligned");
+  if (n_rays == 0) return 0;
+  return point_input_grads(desc, precision, packed_ig, grads, nullptr, nullptr, rays, ray_stride, z_vals, n_rays * samples_per_ray,
+                           samples_per_ray, d_pts, nullptr, stream);
+}
+
 }  // namespace dn
 
 using namespace dn;
@@ -384,38 +436,16 @@ extern "C" int dn_mlp_backward_input(const dn_mlp_desc* desc, int precision, con
   DN_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), "dn_mlp_backward_input: workspace too small (%zu bytes needed)", need);
   if (n_points == 0) return 0;
 
-  IgLayout g;
-  build_input_grad_layout(*desc, precision, &g);
-  FwdParams fp;
-  if ((rc = setup_params(desc, precision, packed_ig, &fp))) return rc;   // (for the frequency tables)
-  IgParams p{};
-  p.stream = static_cast<const char*>(packed_ig);
-  p.stream_bytes = g.total_pieces * kPieceBytes;
-  p.grads = static_cast<const char*>(grads);
-  p.grad_pieces = g.grad_pieces;
-  p.n_x = g.n_x; p.kh = g.kh;
-  for (int s = 0; s < g.n_x; ++s) p.gslot[s] = g.gslot[s];
-  p.gslot_dirout = g.gslot_dirout; p.dir_piece0 = g.dir_piece0; p.use_viewdirs = vdirs;
-  p.mode = ray_form ? 0 : 1;
-  p.rays = rays; p.ray_stride = ray_stride; p.z = z_vals; p.pts = pts; p.viewdirs = viewdirs;
-  p.n_points = n_points; p.S = samples_per_ray;
   const size_t per_pad = (static_cast<size_t>(n_points) * 3 * sizeof(float) + 255) / 256 * 256;
   char* ws = static_cast<char*>(workspace);
-  p.d_pts = ray_form ? reinterpret_cast<float*>(ws) : d_pts;
-  p.d_vd = vdirs ? reinterpret_cast<float*>(ws + (ray_form ? per_pad : 0)) : nullptr;
-  for (int i = 0; i < 16; ++i) p.fx[i] = fp.fx[i];
-  for (int i = 0; i < 8; ++i) p.fd[i] = fp.fd[i];
-
-  const bool bf = precision == DN_PREC_BF16;
-  const int LX = desc->num_encoding_fn_xyz;
-  if (bf && LX == 10) rc = launch_input_grad<1, 10>(p, as_stream(stream));
-  else if (bf) rc = launch_input_grad<1, 6>(p, as_stream(stream));
-  else if (LX == 10) rc = launch_input_grad<0, 10>(p, as_stream(stream));
-  else rc = launch_input_grad<0, 6>(p, as_stream(stream));
-  if (rc) return rc;
+  float* pt_grads = ray_form ? reinterpret_cast<float*>(ws) : d_pts;
+  float* vd_grads = vdirs ? reinterpret_cast<float*>(ws + (ray_form ? per_pad : 0)) : nullptr;
+  if ((rc = point_input_grads(desc, precision, packed_ig, grads, pts, viewdirs, rays, ray_stride, z_vals, n_points, samples_per_ray, pt_grads,
+                              vd_grads, stream)))
+    return rc;
   if (!ray_form && !vdirs) return 0;
   const unsigned blocks = static_cast<unsigned>((n_rays + 3) / 4);
-  hipLaunchKernelGGL(input_grad_rays_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), p.d_pts, p.d_vd, ray_form ? rays : nullptr,
+  hipLaunchKernelGGL(input_grad_rays_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), pt_grads, vd_grads, ray_form ? rays : nullptr,
                      ray_stride, z_vals, static_cast<long long>(n_rays), samples_per_ray, d_rays, d_z, d_viewdirs);
   return check_launch("mlp_input_grad_rays");
 }

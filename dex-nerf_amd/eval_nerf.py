@@ -4,6 +4,9 @@ model_coarse_state_dict / model_fine_state_dict, optional height / width / focal
 poses in validation mode, optionally save RGB / disparity-style depth PNGs, and print the average time per image.
 `--depth-only --m-thres M` renders the depth and Dex depth maps alone (nerf.render_dex_depth): no colour is evaluated, no RGB PNG
 is written, and the maps go to dex_<view>.npz beside depth_<view>.png.
+`--normals` renders density-gradient surface normals (nerf.render_dex_normals) instead: normal_<view>.npy holds the expected normal
+(H,W,3) (not renormalised: its length is a confidence), normal_<view>.png shows (n/|n| + 1)/2, black where n = 0; with `--m-thres M` the
+same pair per threshold, dex_normal_<view>_m<threshold>.npy / .png - the normal at the sample the Dex depth reports.
 
     python dex-nerf_amd/eval_nerf.py --checkpoint ckpt.ckpt --size 400 --views 8 --precision fp16 --savedir out/
 
@@ -55,6 +58,9 @@ def main(argv=None):
     ap.add_argument("--m-thres", type=int, default=0, help="> 0: also produce the Dex depth maps for thresholds 5..m")
     ap.add_argument("--depth-only", action="store_true",
                     help="render depth / Dex depth maps only (nerf.render_dex_depth: density sub-networks, no colour); needs --m-thres > 0")
+    ap.add_argument("--normals", action="store_true",
+                    help="render surface normals only (nerf.render_dex_normals: the density gradient at the samples, composited like the "
+                         "depth; with --m-thres also the normal at every Dex depth); not with --precision fp16")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"])
     ap.add_argument("--savedir", default="")
     ap.add_argument("--quiet", action="store_true")
@@ -68,6 +74,10 @@ def main(argv=None):
 
     if args.depth_only and args.m_thres <= 0:
         ap.error("--depth-only renders the Dex depth maps: give --m-thres > 0")
+    if args.normals and args.precision == "fp16":
+        ap.error("--normals differentiates the density network on the training kernels, which exist for fp32 and bf16: not with --precision fp16")
+    if args.normals and (args.depth_only or args.apply_exposure):
+        ap.error("--normals is a render of its own: not with --depth-only or --apply-exposure")
     if args.apply_exposure and (not args.use_refined_poses or args.depth_only):
         ap.error("--apply-exposure corrects the colours of training views: it needs --use-refined-poses and no --depth-only")
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
@@ -107,6 +117,27 @@ def main(argv=None):
     for i, (pose, k_mat) in enumerate(cameras):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        if args.normals:
+            with torch.no_grad():
+                ro, rd = nerf.get_ray_bundle(size, size, float(k_mat[0, 0]), pose, k_mat)
+                out = nerf.render_dex_normals(size, size, float(k_mat[0, 0]), coarse, fine, ro, rd, cfg, mode="validation",
+                                              encode_position_fn=ex, encode_direction_fn=ed, m_thres_cand=thres)
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+            frames.append((None, out.depth, out))
+            if args.savedir:   # every normal map as float32, and as a PNG of the unit normal (black: no normal)
+                from PIL import Image
+
+                def save(stem, n):
+                    n = n.cpu().numpy()
+                    np.save(os.path.join(args.savedir, stem + ".npy"), n)
+                    length = np.linalg.norm(n, axis=-1, keepdims=True)
+                    unit = np.where(length > 0, (n / np.maximum(length, 1e-30) + 1.0) / 2.0, 0.0)
+                    Image.fromarray((255 * unit).astype(np.uint8)).save(os.path.join(args.savedir, stem + ".png"))
+                save(f"normal_{i:04d}", out.normal)
+                for m, n in zip(thres if thres is not None else [], out.dex_normal):
+                    save(f"dex_normal_{i:04d}_m{int(m)}", n)
+            continue
         if args.depth_only:
             with torch.no_grad():
                 ro, rd = nerf.get_ray_bundle(size, size, float(k_mat[0, 0]), pose, k_mat)

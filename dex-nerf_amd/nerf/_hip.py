@@ -53,6 +53,9 @@ ANNEAL_EXPORTS = ("dn_encoding_anneal_amplitudes", "dn_encoding_anneal_scale_wei
 # include/dexnerf_hip_exposure.h: the loss head with a per-view exposure correction (refine_exposure= on the fused steps)
 EXPOSURE_EXPORTS = ("dn_render_loss_exposure",)
 
+# include/dexnerf_hip_normals.h: density-gradient surface normals composited beside the Dex depths (nerf.render_dex_normals)
+NORMALS_EXPORTS = ("dn_composite_normals", "dn_render_normals_workspace_bytes", "dn_render_rays_normals")
+
 
 class MlpDesc(ctypes.Structure):
     """dn_mlp_desc (mirrors FlexibleNeRFModel.__init__, reference nerf/models.py:186-196)."""
@@ -204,6 +207,14 @@ def _declare(lib):
     # the exposure header: dn_render_loss's arguments, then eps, P, n_views, exposure_scale, view_mask ahead of the outputs, g_eps behind them
     lib.dn_render_loss_exposure.argtypes = lib.dn_render_loss.argtypes[:18] + [fp, c_int, c_int, c_float, vp, fp, fp, fp, fp, fp, fp, vp, vp]
     lib.dn_render_loss_exposure.restype = c_int
+    # the normals header
+    lib.dn_composite_normals.argtypes = [fp, fp, fp, c_int, fp, c_float, fp, fp, c_int, c_int64, c_int, fp, fp, fp, fp, fp, vp]
+    lib.dn_composite_normals.restype = c_int
+    lib.dn_render_normals_workspace_bytes.argtypes = [POINTER(MlpDesc), POINTER(MlpDesc), c_int, c_int64, c_int, c_int]
+    lib.dn_render_normals_workspace_bytes.restype = c_size_t
+    lib.dn_render_rays_normals.argtypes = [POINTER(MlpDesc), vp, POINTER(MlpDesc), vp, vp, vp, c_int, fp, c_int, c_int64, c_int, c_int, c_int,
+                                           c_float, fp, c_int, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, vp, c_size_t, vp]
+    lib.dn_render_rays_normals.restype = c_int
 
 
 def lib():

@@ -766,6 +766,7 @@ class PackedDensityMLP(_Packed):
         full = self.full_desc = _desc(desc_kwargs)
         super().__init__(_density_desc(full), device, precision, lambda prec: lib().dn_mlp_density_packed_bytes(ctypes.byref(full), prec),
                          "dn_mlp_density_packed_bytes")
+        self.grad_streams = None   # DensityGradStreams, created by FlexibleNeRFModel.packed_density_grad on first use
 
     def pack(self, weights, biases):
         """weights/biases: the FULL network's device tensors in the reference parameter order."""
@@ -1304,6 +1305,129 @@ def render_rays_depth(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, n
         ptr(m_thres) if k else None, k, ptr(t_rand), ptr(noise_c), ptr(u), ptr(noise_f),
         ptr(depth_c), ptr(acc_c), ptr(depth_f), ptr(acc_f), ptr(dex), ptr(ws), stream()), "dn_render_rays_depth")
     return depth_c, acc_c, depth_f, acc_f, dex
+
+
+# ---- density-gradient surface normals (include/dexnerf_hip_normals.h) ---------------------------------------------------------------
+class DensityGradStreams:
+    """The backward-data and input-gradient streams of the DENSITY sub-network a PackedDensityMLP holds (dn_mlp_pack_backward /
+    dn_mlp_pack_input_grad on its density descriptor), packed from a no-view-direction network's weight list
+    [layer1, trunk..., head (4,W)] (FlexibleNeRFModel.packed_density_grad builds the head).  fp32, or bf16 with 16-bit saves: the
+    library refuses the sizes of anything else."""
+
+    def __init__(self, packed_density):
+        self.desc, self.precision = packed_density.desc, packed_density.precision
+        dev = packed_density.buffer.device
+        d, prec = ctypes.byref(self.desc), self.precision
+        self.buffer_ig = torch.empty(_sized(lib().dn_mlp_input_grad_packed_bytes(d, prec), "dn_mlp_input_grad_packed_bytes"),
+                                     dtype=torch.uint8, device=dev)
+        self.buffer_bwd = torch.empty(_sized(lib().dn_mlp_backward_packed_bytes(d, prec), "dn_mlp_backward_packed_bytes"),
+                                      dtype=torch.uint8, device=dev)
+        self.key = None          # parameter key both streams were packed from
+
+    def pack(self, weights_bwd, weights_ig):
+        wb, keep_b = _ptr_array(weights_bwd, sources=True)
+        wi, keep_i = _ptr_array(weights_ig, sources=True)
+        self._keep = (keep_b, keep_i)   # until the pack kernels have run on this stream
+        d = ctypes.byref(self.desc)
+        check(lib().dn_mlp_pack_backward(d, self.precision, wb, ptr(self.buffer_bwd), stream()), "dn_mlp_pack_backward")
+        check(lib().dn_mlp_pack_input_grad(d, self.precision, wi, ptr(self.buffer_ig), stream()), "dn_mlp_pack_input_grad")
+
+
+def composite_normals(rf, z, rd, g_pts, noise, noise_std, m_thres, want_dex=True):
+    """dn_composite_normals: (depth, acc, dex (K,N) | None, normal (N,3), dex_normal (K,N,3) | None) from the sigma column of rf (N,S,4)
+    and the per-sample density gradients g_pts (N,S,3).  m_thres: a list of K thresholds or a device tensor of them (any K);
+    want_dex=False leaves the Dex depths out (the Dex normals alone)."""
+    rf, z, g_pts = f32c(rf), f32c(z), f32c(g_pts)
+    n, s = z.shape
+    dev = rf.device
+    rd_ptr, rd_stride, rd = _dir_rows(rd)
+    th = m_thres
+    if th is not None and not torch.is_tensor(th):
+        th = torch.tensor([float(m) for m in th], dtype=torch.float32, device=dev) if len(th) else None
+    k = 0 if th is None else int(th.numel())
+    depth, acc, normal = _empty(dev, n), _empty(dev, n), _empty(dev, n, 3)
+    dex = _empty(dev, k, n) if (k and want_dex) else None
+    dex_normal = _empty(dev, k, n, 3) if k else None
+    nz = None if (noise is None or noise_std <= 0.0) else f32c(noise)
+    check(lib().dn_composite_normals(ptr(rf), ptr(z), rd_ptr, rd_stride, ptr(nz), float(noise_std), ptr(g_pts), ptr(th) if k else None, k, n, s,
+                                     ptr(depth), ptr(acc), ptr(dex), ptr(normal), ptr(dex_normal), stream()), "dn_composite_normals")
+    return depth, acc, dex, normal, dex_normal
+
+
+def density_gradient(packed_density, streams, rays=None, pts=None, z=None):
+    """(sigma_raw, d sigma_raw / d x) of the density sub-network at points given as `pts` (..., 3) -> ((...), (..., 3)) or as ray rows
+    `rays` (N, >= 8) + depths `z` (N,S) -> ((N,S), (N,S,3)); x is the network's input space.  The training forward of the density
+    pack, the seed g_out = (0,0,0,1), dn_mlp_backward_data on streams.buffer_bwd and dn_mlp_backward_input on streams.buffer_ig - in
+    the ray form its per-point d_pts are read where it leaves them, the first region of its workspace.  Precision = the pack's
+    (fp32, or bf16 with 16-bit saves)."""
+    desc, prec = ctypes.byref(packed_density.desc), packed_density.precision
+    if rays is not None:
+        rays, z = f32c(rays), f32c(z)
+        n, s = z.shape
+        out, _, masks = run_network_train(packed_density, None, None, None, rays=rays, z_vals=z, prec=prec)
+        shape = (n, s)
+    else:
+        shape = tuple(pts.shape[:-1])
+        pts = f32c(pts).reshape(-1, 3)
+        n, s = pts.shape[0], 1
+        out, _, masks = run_network_train(packed_density, pts, None, 1, prec=prec)
+    n_pts = n * s
+    dev = out.device
+    g_out = torch.zeros((n_pts, 4), dtype=torch.float32, device=dev)
+    g_out[:, 3] = 1.0
+    grads = _grads_buf(packed_density, n_pts, prec, dev)
+    check(lib().dn_mlp_backward_data(desc, prec, ptr(streams.buffer_bwd), ptr(g_out), ptr(masks), n_pts, ptr(grads), stream()),
+          "dn_mlp_backward_data")
+    if rays is None:
+        g_pts = torch.empty_like(pts)
+        check(lib().dn_mlp_backward_input(desc, prec, ptr(streams.buffer_ig), ptr(grads), ptr(pts), None, None, 0, None, n, s, ptr(g_pts), None,
+                                          None, None, None, 0, stream()), "dn_mlp_backward_input")
+    else:
+        nbytes = int(lib().dn_mlp_backward_input_workspace_bytes(desc, n_pts, 1))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        d_rays, d_z = torch.empty_like(rays), torch.empty_like(z)
+        check(lib().dn_mlp_backward_input(desc, prec, ptr(streams.buffer_ig), ptr(grads), None, None, ptr(rays), rays.shape[1], ptr(z), n, s, None,
+                                          None, ptr(d_rays), ptr(d_z), ptr(ws), nbytes, stream()), "dn_mlp_backward_input")
+        g_pts = ws[:n_pts * 12].view(torch.float32)
+    return out[:, 3].reshape(shape), g_pts.reshape(shape + (3,))
+
+
+def render_normals_workspace_bytes(packed_c, packed_f, n, num_coarse, num_fine):
+    """dn_render_normals_workspace_bytes for these density packs (0: sizes / precision the normal render does not cover)."""
+    fine = num_fine > 0 and packed_f is not None
+    return int(lib().dn_render_normals_workspace_bytes(ctypes.byref(packed_c.desc), ctypes.byref(packed_f.desc) if fine else None,
+                                                       packed_c.precision, n, num_coarse, num_fine if fine else 0))
+
+
+def render_rays_normals(packed_c, packed_f, streams, rays, num_coarse, num_fine, lindisp, noise_std, m_thres, draws=None):
+    """dn_render_rays_normals: the depth-only render of one ray chunk with its last pass differentiated, on density packs and the
+    DensityGradStreams of the last pass's network (the fine one; the coarse one with num_fine == 0).  m_thres: a device tensor of K
+    thresholds (any K) or None.  Returns (depth_c, acc_c, depth, acc, dex (K,N) | None, normal (N,3), dex_normal (K,N,3) | None);
+    depth_c / acc_c are None without a fine pass."""
+    rays = f32c(rays)
+    n = rays.shape[0]
+    dev = rays.device
+    k = 0 if m_thres is None else int(m_thres.numel())
+    fine = num_fine > 0 and packed_f is not None
+    nf = num_fine if fine else 0
+    nbytes = _sized(render_normals_workspace_bytes(packed_c, packed_f, n, num_coarse, nf), "dn_render_normals_workspace_bytes")
+    # (a stream-ordered allocation per call, not the cached render workspace: the saved tensors make it large, and its status
+    # block is not where render_status_words looks)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    depth_c, acc_c = (_empty(dev, n), _empty(dev, n)) if fine else (None, None)
+    depth, acc, normal = _empty(dev, n), _empty(dev, n), _empty(dev, n, 3)
+    dex = _empty(dev, k, n) if k else None
+    dex_normal = _empty(dev, k, n, 3) if k else None
+    t_rand, noise_c, u, noise_f = _draw_tensors(draws)
+    check(lib().dn_render_rays_normals(
+        ctypes.byref(packed_c.desc), ptr(packed_c.buffer),
+        ctypes.byref(packed_f.desc) if fine else None, ptr(packed_f.buffer) if fine else None,
+        ptr(streams.buffer_bwd), ptr(streams.buffer_ig), packed_c.precision,
+        ptr(rays), rays.shape[1], n, num_coarse, nf, int(bool(lindisp)), float(noise_std),
+        ptr(m_thres) if k else None, k, ptr(t_rand), ptr(noise_c), ptr(u), ptr(noise_f),
+        ptr(depth_c), ptr(acc_c), ptr(depth), ptr(acc), ptr(dex), ptr(normal), ptr(dex_normal), ptr(ws), nbytes, stream()),
+        "dn_render_rays_normals")
+    return depth_c, acc_c, depth, acc, dex, normal, dex_normal
 
 
 def render_status_words(ws=None):

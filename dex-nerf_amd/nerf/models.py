@@ -154,6 +154,29 @@ class FlexibleNeRFModel(torch.nn.Module):
             pk.key = key
         return pk
 
+    def packed_density_grad(self, log_sampling_xyz=True, log_sampling_dir=True, precision=None):
+        """The backward-data and input-gradient streams of the density sub-network (_ops.DensityGradStreams: what differentiates
+        sigma_raw w.r.t. the input points - density_gradient, render_dex_normals) for the current parameters, cached by param_key()
+        like packed_density()'s pack, whose descriptor and precision they share.  The streams take a no-view-direction network's
+        weight list [layer1, trunk..., head (4,W)]: the head is zeros with row 3 = fc_alpha.weight (a net without view directions
+        brings its own fc_out)."""
+        pk = self.packed_density(log_sampling_xyz, log_sampling_dir, precision)
+        if pk.grad_streams is None:
+            pk.grad_streams = _ops.DensityGradStreams(pk)
+        streams = pk.grad_streams
+        key = self.param_key()
+        if self._stale(streams.key, key):
+            def trunk_and_head(weights):
+                if not self.use_viewdirs:
+                    return weights
+                head = torch.zeros((4, self.hidden_size), dtype=torch.float32, device=weights[0].device)
+                head[3] = self.fc_alpha.weight.detach()[0]
+                return weights[:self.num_layers] + [head]
+            # (the backward-data stream reads hidden columns only: unscaled weights, as ensure_backward_stream packs them)
+            streams.pack(trunk_and_head(self.pack_weights(scaled=False)), trunk_and_head(self.pack_weights()))
+            streams.key = key
+        return streams
+
     def _packed_slot(self, log_sampling_xyz=True, log_sampling_dir=True, precision=None):
         """The PackedMLP object of (precision, sampling flags, device), as it is (packed() brings it up to date)."""
         return self._pack_of(self._packed, _ops.PackedMLP, log_sampling_xyz, log_sampling_dir, precision)

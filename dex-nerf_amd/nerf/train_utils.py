@@ -1,5 +1,6 @@
 """run_network / predict_and_render_radiance / run_one_iter_of_nerf with the reference's call surface
 (reference nerf/train_utils.py:72-288), plus the Dex depth-error helpers (:9-70)."""
+import collections
 import os
 
 import numpy as np
@@ -428,3 +429,129 @@ def render_dex_depth(height, width, focal_length, model_coarse, model_fine, ray_
         return maps
     maps = _render_chunks(rays, opt.chunksize, render_chunk)
     return _to_image(maps, [img_shape[:-1]] * len(maps)) if mode == "validation" else tuple(maps)
+
+
+# ---- density-gradient surface normals ------------------------------------------------------------------------------------------------
+DexNormals = collections.namedtuple("DexNormals", "depth acc normal dex_depth dex_normal")
+
+
+def _normals_precision(who):
+    """Precision code of the differentiated density network: 'fp32' runs fp32, 'bf16' and 'bf16-s16' both run bf16 with 16-bit saved
+    tensors; 'fp16' raises (there is no fp16 instance of the training kernels)."""
+    if _ops._precision == _ops._hip.PREC_F16:
+        raise RuntimeError(f"{who}: the density gradient runs on the training kernels, which exist for fp32 and bf16 - not under "
+                           "nerf.set_precision('fp16')")
+    return _ops._precision
+
+
+def _require_density_net(model, encode_position_fn, who):
+    if not _fusable(model, encode_position_fn, None, density=True):
+        raise RuntimeError(f"{who}: needs FlexibleNeRFModel networks the fused HIP kernels cover (fused_ok()) and this package's "
+                           "position embedder with the network's encoding; there is no fallback")
+    _require_device(model.layer1.weight, who)
+
+
+def density_gradient(model, pts, encode_position_fn, chunksize=1 << 16):
+    """The density field and its gradient at arbitrary points: (sigma (P,), grad (P,3)) for pts (..., 3) flattened to (P,3) - sigma the
+    network's RAW density output (before noise and ReLU), grad = d sigma / d x in the network's input space (world space, or NDC space
+    for forward-facing scenes; nothing converts it).  For surface extraction and planners; -grad / |grad| is the surface normal
+    render_dex_normals composites.  No-grad only, device tensors only, `chunksize` points per launch chain; runs in nerf.set_precision's
+    mode: 'fp32', or bf16 with 16-bit saved tensors ('bf16' and 'bf16-s16' alike); 'fp16' raises."""
+    prec = _normals_precision("density_gradient")
+    if _wants_grad(model) or inputs_need_grad(pts):
+        raise RuntimeError("density_gradient is a no-grad evaluation: call it under torch.no_grad() (or with parameters and points that "
+                           "do not require grad); gradients through the normals are second order and not provided")
+    _require_device(pts, "density_gradient")
+    _require_density_net(model, encode_position_fn, "density_gradient")
+    lx = encode_position_fn.log_sampling
+    pack = model.packed_density(lx, True, precision=prec)
+    streams = model.packed_density_grad(lx, True, precision=prec)
+    flat = pts.reshape(-1, 3).float()
+    parts = [_ops.density_gradient(pack, streams, pts=batch) for batch in get_minibatches(flat, chunksize=int(chunksize))]
+    if len(parts) == 1:
+        return parts[0]
+    return torch.cat([p[0] for p in parts], dim=0), torch.cat([p[1] for p in parts], dim=0)
+
+
+def _rays_within_workspace(packs, n, nc, nf, max_bytes):
+    """The largest ray count <= n whose dn_render_normals_workspace_bytes stays at or below max_bytes."""
+    need = _ops.render_normals_workspace_bytes(*packs, n, nc, nf)
+    if need <= max_bytes:
+        return n
+    m = max(1, min(n, int(max_bytes // -(-need // n))))
+    while m > 1 and _ops.render_normals_workspace_bytes(*packs, m, nc, nf) > max_bytes:
+        m -= max(1, m // 64)
+    if _ops.render_normals_workspace_bytes(*packs, m, nc, nf) > max_bytes:
+        raise RuntimeError(f"render_dex_normals: max_workspace_bytes={max_bytes} does not hold one ray of {nc}+{nf} samples")
+    return m
+
+
+def render_dex_normals(height, width, focal_length, model_coarse, model_fine, ray_origins, ray_directions, options,
+                       mode="validation", encode_position_fn=None, encode_direction_fn=None, m_thres_cand=None,
+                       max_workspace_bytes=2 ** 31):
+    """render_dex_depth's last pass with surface normals: the density sub-network of the last pass (the fine one; the coarse one
+    without a fine pass) is differentiated w.r.t. its input points, and n = -grad sigma_raw / |grad sigma_raw| is composited beside
+    the depths (dn_render_rays_normals).
+
+    Returns DexNormals(depth, acc, normal, dex_depth, dex_normal): depth / acc of the last pass; normal = sum_s w_s n_s with the
+    compositing weights - NOT renormalised: its length is at most acc and works as a confidence; dex_depth / dex_normal: tuples of K
+    maps, the Dex depth of threshold k and n at the same first-crossing sample, (0,0,0) where no sample crosses (the depth then
+    falls back to z[0]; the zero vector is the only "no surface" marker).  Flat (N,) / (N,3) in train mode, image-shaped in
+    validation mode (normals (H,W,3)).  Normals live in the network's input space: world space, or NDC space for forward-facing
+    scenes (dataset.no_ndc False) - nothing converts them.
+
+    Rays, chunking, NDC, lindisp and the perturb / noise draws (rand, randn, rand, randn per chunk) follow render_dex_depth.  The
+    differentiated pass keeps its saved tensors: each chunk is split so that dn_render_normals_workspace_bytes stays at or below
+    `max_workspace_bytes`; rays are independent, so the maps do not depend on the split.  No-grad only, device tensors only,
+    networks the fused kernels cover only: anything else raises.  Precision follows nerf.set_precision: 'fp32' runs fp32, 'bf16' and
+    'bf16-s16' both run bf16 with 16-bit saved tensors, 'fp16' raises - there is no fp16 instance of the training kernels, so the
+    fp16 render policy (nerf.set_render_policy) and its range guard do not apply here.  The last pass's sigma comes from the
+    training-forward kernel: depth may differ from render_dex_depth's in the last bits."""
+    prec = _normals_precision("render_dex_normals")
+    opt = getattr(options.nerf, mode)
+    nc, nf = int(opt.num_coarse), int(opt.num_fine)
+    fine = nf > 0 and bool(model_fine)
+    nf = nf if fine else 0
+    models = [model_coarse] + ([model_fine] if fine else [])
+    if _wants_grad(*models) or inputs_need_grad(ray_origins, ray_directions):
+        raise RuntimeError("render_dex_normals is a no-grad render: call it under torch.no_grad() (or with parameters and rays that do "
+                           "not require grad); gradients through the normals are second order and not provided")
+    _require_device(ray_directions, "render_dex_normals")
+    _require_device(ray_origins, "render_dex_normals")
+    for m in models:
+        _require_density_net(m, encode_position_fn, "render_dex_normals")
+    thres = _thresholds(m_thres_cand)
+    dev = ray_directions.device
+    img_shape = ray_directions.shape
+    if options.dataset.no_ndc is False:
+        ro, rd = ndc_rays(height, width, focal_length, 1.0, ray_origins, ray_directions)
+    else:
+        ro, rd = ray_origins, ray_directions
+    ro, rd = ro.reshape((-1, 3)).float(), rd.reshape((-1, 3)).float()
+    rays = _ops.pack_ray_rows(ro.contiguous(), rd.contiguous(), None, options.dataset.near, options.dataset.far)
+    perturb = bool(opt.perturb)
+    std = float(opt.radiance_field_noise_std)
+    lindisp = bool(opt.lindisp)
+    lx = encode_position_fn.log_sampling
+    m_thres = _threshold_tensor(thres, dev)
+    packs = (model_coarse.packed_density(lx, True, precision=prec), model_fine.packed_density(lx, True, precision=prec) if fine else None)
+    streams = models[-1].packed_density_grad(lx, True, precision=prec)
+    max_bytes = int(max_workspace_bytes)
+
+    def render_chunk(batch):
+        n = batch.shape[0]
+        draws = _draws(n, nc, nf, fine, perturb, std, dev)
+        step = _rays_within_workspace(packs, n, nc, nf, max_bytes)
+        pieces = []
+        for r0 in range(0, n, step):
+            rows = slice(r0, min(r0 + step, n))
+            _, _, depth, acc, dex, normal, dex_normal = _ops.render_rays_normals(
+                *packs, streams, batch[rows], nc, nf, lindisp, std, m_thres, {name: d[rows] for name, d in draws.items()})
+            pieces.append([depth, acc, normal] + [dex[k] for k in range(len(thres))] + [dex_normal[k] for k in range(len(thres))])
+        return _join_chunks(pieces)
+    maps = _join_chunks([render_chunk(batch) for batch in get_minibatches(rays, chunksize=opt.chunksize)])
+    if mode == "validation":
+        flat, vec = img_shape[:-1], img_shape
+        maps = _to_image(maps, [flat, flat, vec] + [flat] * len(thres) + [vec] * len(thres))
+    k = len(thres)
+    return DexNormals(maps[0], maps[1], maps[2], tuple(maps[3:3 + k]), tuple(maps[3 + k:3 + 2 * k]))
