@@ -12,6 +12,7 @@ import torch
 
 from conftest import REPO, rel_err
 from golden_cases import CASES, M_THRES, draws_of
+from training_slots import s8_slots
 
 pytestmark = pytest.mark.gpu
 
@@ -2154,15 +2155,7 @@ def test_s8_training_kernels_in_the_48_point_geometry(dev, depth, width, viewdir
         # stage by stage through the unpackers of the two layouts
         slots, gslots, kh = _train._slots(m, _hip.PREC_BF16)            # 32-point layout: slots in 16-deep pieces
         d, w = depth, width
-        khu = w // 64                                                    # s8-48 layout: slots in 64-feature units per 16-point group
-        s8 = {"xyz": 0, "dir": 1, "layer1": 1 + (1 if viewdirs else 0)}
-        s8["trunk0"] = s8["layer1"] + khu
-        s8["feat"] = s8["trunk0"] + (d - 1) * khu
-        s8["dirout"] = s8["feat"] + (khu if viewdirs else 0)
-        g8 = {"dirout": 0, "feat": (w // 128) if viewdirs else 0}
-        g8["trunk0"] = g8["feat"] + (khu if viewdirs else 0)
-        g8["layer1"] = g8["trunk0"] + (d - 1) * khu
-        g8["out"] = g8["layer1"] + khu
+        s8, g8, khu = s8_slots(d, w, viewdirs)                           # s8-48 layout: slots in 64-feature units per 16-point group
 
         def rows16(which, buf, slot, width_, kind=0):
             return C(_ops.mlp_unpack(pk, which, buf, n, slot, width_, kind, torch.zeros((n, width_), dtype=torch.float32, device=dev))).astype(np.float64)
