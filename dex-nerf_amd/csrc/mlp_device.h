@@ -27,6 +27,8 @@ constexpr int kRingPhases = 5;
 constexpr int kSlotBytes = kPhasePieces * kPieceBytes;  // 16 KiB
 constexpr int kRingBytes = kRingPhases * kSlotBytes;    // 80 KiB
 constexpr int kInRows = 10;                             // per-wave input staging rows
+// role of a wave in the explicit-schedule tile pass (PipeT::xs_period_begin): fetches its share of the weight stream / only consumes it
+enum { kXsFetcher = 0, kXsConsumer = 1 };
 
 // arithmetic mode (the template parameter is still called BF16: 0 = fp32, 1 = bf16, 2 = fp16; non-zero = 16-bit MFMA)
 template <int BF16> struct Prec;
@@ -291,23 +293,31 @@ struct PipeT {
   // Scalar state per period: this wave's global source and LDS destination of its four pieces of either phase.
   unsigned long long xs_src[2];
   unsigned xs_dst[2];
+  // ROLE: the tile pass is compiled once per role and a wave picks its copy once, after the kernel's prologue (mlp_fused48_kernel.h).
+  // kXsFetcher (waves 0-3) is the pass described above.  kXsConsumer (waves 4-7) never fetches: its pass has no fetch step at all -
+  // as one pass for everyone, a consumer executed a compare and a TAKEN branch behind every piece of a period's first half only to
+  // jump over loads that are not its own - and none of the fetch bookkeeping (q_issue, slot_wr, xs_src / xs_dst).  What the roles
+  // share stays identical in both copies: one barrier per period (s_barrier counts arrivals, whatever address they come from), the
+  // vmcnt wait in front of it (a consumer's covers its input-row DMAs), the read-slot rotation and every counted LDS wait.
   // PERIOD = 32 (one barrier per two phases: the W = 256 instance, see phase_begin2) or 16 (one per phase: phase_begin's ring
   // accounting - two younger phases of four loads per fetching wave stay in flight - with the fetch of phase p + 4 spread over
   // positions 0 .. 7 of phase p, wave w at 2w and 2w + 1)
-  template <int PERIOD>
+  template <int PERIOD, int ROLE = kXsFetcher>
   __device__ __forceinline__ void xs_period_begin() {
     static_assert(PERIOD == kPhasePieces || PERIOD == 2 * kPhasePieces, "barrier period: one or two phases");
     if constexpr (PERIOD == 2 * kPhasePieces) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     __builtin_amdgcn_s_barrier();
+    if constexpr (ROLE == kXsFetcher) {
 #pragma unroll
-    for (int h = 0; h < PERIOD / kPhasePieces; ++h) {
-      advance_issue();   // (pend_src / pend_dst: this wave's 4 KiB of the phase)
-      const unsigned long long bits = reinterpret_cast<unsigned long long>(wsrc + pend_src);
-      const unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(bits));
-      const unsigned hi = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(bits >> 32));
-      xs_src[h] = (static_cast<unsigned long long>(hi) << 32) | lo;
-      xs_dst[h] = __builtin_amdgcn_readfirstlane(ring_addr + pend_dst);
+      for (int h = 0; h < PERIOD / kPhasePieces; ++h) {
+        advance_issue();   // (pend_src / pend_dst: this wave's 4 KiB of the phase)
+        const unsigned long long bits = reinterpret_cast<unsigned long long>(wsrc + pend_src);
+        const unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(bits));
+        const unsigned hi = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(bits >> 32));
+        xs_src[h] = (static_cast<unsigned long long>(hi) << 32) | lo;
+        xs_dst[h] = __builtin_amdgcn_readfirstlane(ring_addr + pend_dst);
+      }
     }
   }
   // fetch step Q of the period (0 .. PERIOD / 2 - 1): ONE wave issues two loads (1 KiB each); everyone else skips (branch inside the statement)
@@ -331,19 +341,19 @@ struct PipeT {
         : [wave] "s"(wave), [who] "n"(Q / STEPS), [lds] "s"(xs_dst[H]), [voff] "v"(lane16), [sbase] "s"(xs_src[H]), [o0] "n"(OFF), [o1] "n"(OFF + 1024)
         : "memory", "scc");
   }
-  template <int PERIOD, int POS>
+  template <int PERIOD, int POS, int ROLE = kXsFetcher>
   __device__ __forceinline__ void at_position_xs() {
-    if constexpr (POS % PERIOD == 0) xs_period_begin<PERIOD>();
+    if constexpr (POS % PERIOD == 0) xs_period_begin<PERIOD, ROLE>();
     if constexpr (POS % kPhasePieces == 0) {
       slot_nxt = (slot_nxt + 1 == kRingPhases) ? 0 : slot_nxt + 1;
       rda_cur = slot_cur_base + lane16;
       slot_cur_base = __builtin_amdgcn_readfirstlane(ring_addr + slot_nxt * kSlotBytes);
     }
   }
-  // the piece position POS has been consumed: its fetch step, if it has one
-  template <int PERIOD, int POS>
+  // the piece position POS has been consumed: its fetch step, if it has one (a consumer's pass has none)
+  template <int PERIOD, int POS, int ROLE = kXsFetcher>
   __device__ __forceinline__ void xs_after_piece() {
-    if constexpr ((POS % PERIOD) < PERIOD / 2) xs_dma_step<PERIOD, POS % PERIOD>();
+    if constexpr (ROLE == kXsFetcher && (POS % PERIOD) < PERIOD / 2) xs_dma_step<PERIOD, POS % PERIOD>();
   }
   // phase boundary / mid-phase hooks at position POS of a stream whose barrier period is PH pieces (16, or 32: see above)
   template <int PH, int POS>
@@ -375,13 +385,13 @@ struct PipeT {
   }
 
   // the same for the explicit-schedule pass: the fetch steps of the skipped positions still happen
-  template <int PERIOD, int POS, int N>
+  template <int PERIOD, int POS, int N, int ROLE = kXsFetcher>
   __device__ __forceinline__ void skip_xs() {
     static_for<N>([&](auto i_c) {
       constexpr int pos = POS + decltype(i_c)::value;
       static_assert(pos % kPhasePieces != 0 || decltype(i_c)::value == 0, "padding never crosses a phase");
       static_assert(pos % PERIOD != 0, "padding never opens a barrier period");
-      xs_after_piece<PERIOD, pos>();
+      xs_after_piece<PERIOD, pos, ROLE>();
       if constexpr (decltype(i_c)::value >= N - G::PREFETCH) prefetch<pos>();
     });
     settle<true>();

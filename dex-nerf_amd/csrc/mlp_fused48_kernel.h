@@ -1,5 +1,5 @@
 // The 48-points-per-wave forward kernel (template) and, below it, the one list of its instances: included by the translation units
-// that instantiate their rows of it - mlp_fused48_{paper_bf16,paper_fp16,w128}.hip and mlp_fused48.hip (the remaining W = 256
+// that instantiate their rows of it - mlp_fused48_{paper_bf16,paper_fp16}{,_plain}.hip, mlp_fused48_w128.hip and mlp_fused48.hip (the remaining W = 256
 // instances and the host side) - so the instance list compiles in parallel.  Design notes: the comment at the top of mlp_fused48.hip.
 #pragma once
 #include "mlp_stage48.h"
@@ -194,9 +194,16 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
   auto bias_at = [&](int tile) { return pipe.ring_addr + kRingBytes + ((fresh_lane() >> 4) << 4) + tile * 64; };
   pipe.rda_cur = pipe.ring_addr + lane * 16;
   pipe.slot_cur_base = pipe.ring_addr;       // phase 0 lives in slot 0: phase_begin() of phase 0 turns this into rda_cur
-  static_for<PipeGeo48::PREFETCH - 1>([&](auto e_c) { pipe.template prologue_read<decltype(e_c)::value>(); });
-  pipe.template bias_prefetch<0>(bias_at(0));    // same order as in steady state: ..., bias, one more A read
-  pipe.template prologue_read<PipeGeo48::PREFETCH - 1>();
+  // the tile pass of the W = 256 explicit-schedule instances is compiled once per wave role (tile_loop, below)
+  constexpr bool SPLIT = XS && W == 256;
+  auto first_reads = [&]() {
+    static_for<PipeGeo48::PREFETCH - 1>([&](auto e_c) { pipe.template prologue_read<decltype(e_c)::value>(); });
+    pipe.template bias_prefetch<0>(bias_at(0));    // same order as in steady state: ..., bias, one more A read
+    pipe.template prologue_read<PipeGeo48::PREFETCH - 1>();
+  };
+  // (SPLIT: issued at the top of either copy of the loop - a fragment in flight across the role branch is a value the compiler
+  // may copy, or park in scratch, on the way into one of the two loops before it has arrived)
+  if constexpr (!SPLIT) first_reads();
 
   unsigned trk = 0;   // fp16 instances: running maximum of the stage inputs' 16-bit patterns (run_stage48, TRK)
   int vset = 0;  // which view-direction rows hold this tile's directions (wave-uniform, next set every tile)
@@ -223,6 +230,13 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
     for (int u = 0; u < 3; ++u) idm[u] = __ballot(tabx[u][2] != 0.0f);
   }
   const int n_tiles = static_cast<int>(p.n_tiles);
+  // The persistent tile loop, compiled once per role (mlp_device.h PipeT::xs_period_begin).  The W = 256 explicit-schedule instances
+  // run two copies: a wave picks its own below, once, on the wave-uniform `wave < 4` - a scalar branch taken behind the prologue -
+  // and stays in it for all its tiles.  The consumer copy has no fetch step; every MFMA, conversion, LDS read, counted wait and
+  // barrier is the same statement in the same order in both.  Every other instance runs the one (fetcher) copy as before.
+  auto tile_loop = [&](auto role_c) __attribute__((always_inline)) {
+  constexpr int ROLE = decltype(role_c)::value;
+  if constexpr (SPLIT) first_reads();
   for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x, vset = (VSETS == 2 ? vset ^ 1 : (vset == 2 ? 0 : vset + 1))) {
     // training forward: this wave's three point groups' saved-unit bases and its mask words' (s8-48 layout, mlp_geo48.h) - wave-
     // uniform, kept in scalar registers for the tile; every store adds a small offset (store16_uniform_at)
@@ -359,7 +373,7 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
         for (int t = 0; t < PT; ++t)
 #pragma unroll
           for (int k = 0; k < KXP; ++k) pe[t][k] = pe_xyz(t, k);
-        run_stage48x<F, PX, NT, KXP, 0, 0, false, 0, 6, 0, 0>(pipe, pe, no_pe, bias_at(0), 0u, pacc,
+        run_stage48x<ROLE, F, PX, NT, KXP, 0, 0, false, 0, 6, 0, 0>(pipe, pe, no_pe, bias_at(0), 0u, pacc,
             [&](auto nt_c, auto s_c) { hidden_op48<F, false, decltype(nt_c)::value, decltype(s_c)::value>(pacc, ba); }, nothing);
       }
       bias_tile += NT;
@@ -379,9 +393,9 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
           for (int t = 0; t < PT; ++t)
 #pragma unroll
             for (int k = 0; k < KXP; ++k) pe[t][k] = pe_xyz(t, k);
-          run_stage48x<F, PX, NT, KH, KXP, P0, false, 0, 12, PN, BY, (i == 0 ? 2 : 1)>(pipe, bin, [&](int t, int k) { return pe[t][k]; }, bias_at(bias_tile), 0u, pacc, ops, pend, &trk);
+          run_stage48x<ROLE, F, PX, NT, KH, KXP, P0, false, 0, 12, PN, BY, (i == 0 ? 2 : 1)>(pipe, bin, [&](int t, int k) { return pe[t][k]; }, bias_at(bias_tile), 0u, pacc, ops, pend, &trk);
         } else {
-          run_stage48x<F, PX, NT, KH, 0, P0, false, 0, 12, PN, BY, (i == 0 ? 2 : 1)>(pipe, bin, no_pe, bias_at(bias_tile), 0u, pacc, ops, pend, &trk);
+          run_stage48x<ROLE, F, PX, NT, KH, 0, P0, false, 0, 12, PN, BY, (i == 0 ? 2 : 1)>(pipe, bin, no_pe, bias_at(bias_tile), 0u, pacc, ops, pend, &trk);
         }
         bias_tile += NT;
       });
@@ -389,11 +403,11 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
       auto& hy = ((DC - 1) % 2 == 0) ? bb : ba;
       // ---- fc_alpha (its own 16-row tile, row 0, streamed first) + fc_feat with ReLU (models.py:248-249) ----
       constexpr int POS_A = xs_trunk_pos(DC - 1, NT, KH, KXP, MASKC) % PX;
-      run_stage48x<F, PX, 1, KH, 0, POS_A, false, 0, 3, (DC > 1 ? 12 : 6), (NT - 1) / 2>(pipe, hx, no_pe, bias_at(bias_tile), 0u, pacc,
+      run_stage48x<ROLE, F, PX, 1, KH, 0, POS_A, false, 0, 3, (DC > 1 ? 12 : 6), (NT - 1) / 2>(pipe, hx, no_pe, bias_at(bias_tile), 0u, pacc,
           [&](auto, auto s_c) { constexpr int t = decltype(s_c)::value; pick_op48(out4[t][3], pacc[t][0]); },   // row 0: lane group 0, register 0
           [&](auto s_c) { hidden_op48<F, (DC > 1), NT - 1, decltype(s_c)::value>(pacc, hx); });
       constexpr int POS_F = (POS_A + KH) % PX;
-      run_stage48x<F, PX, NT, KH, 0, POS_F, false, 0, 12, 3, KH, 1>(pipe, hx, no_pe, bias_at(bias_tile + 1), 0u, pacc,
+      run_stage48x<ROLE, F, PX, NT, KH, 0, POS_F, false, 0, 12, 3, KH, 1>(pipe, hx, no_pe, bias_at(bias_tile + 1), 0u, pacc,
           [&](auto nt_c, auto s_c) { hidden_op48<F, true, decltype(nt_c)::value, decltype(s_c)::value>(pacc, hy); },
           [&](auto s_c) { constexpr int t = decltype(s_c)::value; pick_op48(out4[t][3], pacc[t][0]); }, &trk);
       bias_tile += NT + 1;
@@ -434,14 +448,10 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
         static_assert(kEncOps <= enc_begin((NT / 2) * KT_D, KT_D), "the view-direction stage has a gap for every encoding op");
         // the next tile's inputs: their DMAs were issued a whole tile ago (the first tile's: at its top).  Waves 4-7 issue no weight
         // DMAs, so no counted wait of theirs pushes input DMAs through: they wait here (their queue holds nothing else but the last
-        // output stores); waves 0-3 have passed dozens of barrier-period waits (vmcnt(0)) since.  Branch inside the statement.
-        {
-          const unsigned must_wait = __builtin_amdgcn_readfirstlane(wave >= 4 ? 1u : 0u);
-          asm volatile("s_cmp_eq_u32 %0, 0\n\t"
-                       "s_cbranch_scc1 .Ldn_ovx_nowait%=\n\t"
-                       "s_waitcnt vmcnt(0)\n"
-                       ".Ldn_ovx_nowait%=:" ::"s"(must_wait) : "scc", "memory");
-        }
+        // output stores); waves 0-3 have passed dozens of barrier-period waits (vmcnt(0)) since.  The role is this copy's: no branch.
+        static_assert(SPLIT, "in-stage encoding: an instance whose pass is compiled per role");
+        if constexpr (ROLE == kXsConsumer) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        else asm volatile("" ::: "memory");   // (the rows are read below this point in either copy)
         const int ln = fresh_lane();
         const int j = ln & 15;
 #pragma unroll
@@ -515,7 +525,7 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
           else if constexpr (w == 2) static_for<cap - 2>([&](auto j_c) { one(std::integral_constant<int, q0 + 2 + decltype(j_c)::value>{}); });
         }
       };
-      run_stage48x<F, PX, NT / 2, KH, KDP, POS_D, false, 0, 12, 12, (NT - 1) / 2, 1>(pipe, hy, [&](int t, int) { return ped[t]; }, bias_at(bias_tile), 0u, pacc,
+      run_stage48x<ROLE, F, PX, NT / 2, KH, KDP, POS_D, false, 0, 12, 12, (NT - 1) / 2, 1>(pipe, hy, [&](int t, int) { return ped[t]; }, bias_at(bias_tile), 0u, pacc,
           [&](auto nt_c, auto s_c) { hidden_op48<F, true, decltype(nt_c)::value, decltype(s_c)::value>(pacc, bg); },
           [&](auto s_c) { hidden_op48<F, true, NT - 1, decltype(s_c)::value>(pacc, hy); }, &trk, enc_hook);
       bias_tile += NT / 2;
@@ -525,10 +535,10 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
       static_assert(END <= PX && (END - 1) / kPhasePieces == POS_R / kPhasePieces, "the tail stays inside one phase");
       constexpr int PAD_R = (kPhasePieces - END % kPhasePieces) % kPhasePieces;
       static_assert((END + PAD_R) % PX == 0, "a tile pass is a whole number of barrier periods");
-      run_stage48x<F, PX, 1, KH / 2, 0, POS_R, true, PAD_R, 9, 12, (NT / 2 - 1) / 2, 1>(pipe, bg, no_pe, bias_at(bias_tile), bias_at(0), pacc,
+      run_stage48x<ROLE, F, PX, 1, KH / 2, 0, POS_R, true, PAD_R, 9, 12, (NT / 2 - 1) / 2, 1>(pipe, bg, no_pe, bias_at(bias_tile), bias_at(0), pacc,
           [&](auto, auto s_c) { constexpr int sv = decltype(s_c)::value; pick_op48(out4[sv / 3][sv % 3], pacc[sv / 3][sv % 3]); },
           [&](auto s_c) { hidden_op48<F, true, NT / 2 - 1, decltype(s_c)::value>(pacc, bg); }, &trk);
-      if constexpr (PAD_R != 0) pipe.template skip_xs<PX, END, PAD_R>();   // (settles at its end)
+      if constexpr (PAD_R != 0) pipe.template skip_xs<PX, END, PAD_R, ROLE>();   // (settles at its end)
       else pipe.settle();
       // the last tile's rows: nothing rides behind this stage, so its accumulators are read here - behind the wait states a 4-pass
       // MFMA's result needs (7; the compiler sees no MFMA and pads nothing)
@@ -796,6 +806,13 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
       }
     }
   }
+  };   // tile_loop
+  if constexpr (SPLIT) {
+    if (wave < 4) tile_loop(std::integral_constant<int, kXsFetcher>{});
+    else tile_loop(std::integral_constant<int, kXsConsumer>{});
+  } else {
+    tile_loop(std::integral_constant<int, kXsFetcher>{});
+  }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   if constexpr (F == 2) {
     const bool out_of_range = (trk & 0xFFFFu) >= 0x7C00u || (trk >> 16) >= 0x7C00u;
@@ -805,10 +822,15 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
 
 // ---- the instances: one row each, X(W, F, DC, MASKC, VIEWC, SAVE, OVLP, COMP), all eight template arguments --------------------
 // One sub-list per translation unit; DN_FWD48_INSTANCES is the whole family.  mlp_geo48.h g48_pick picks among them.
-#define DN_FWD48_PAPER_BF16(X) /* mlp_fused48_paper_bf16.hip: the explicit-schedule bf16 instances of the paper network */ \
-  X(256, 1, 8, 0x10u, 1, 0, 2, 0) X(256, 1, 8, 0x10u, 1, 0, 0, 0)
-#define DN_FWD48_PAPER_FP16(X) /* mlp_fused48_paper_fp16.hip: the same in fp16 */ \
-  X(256, 2, 8, 0x10u, 1, 0, 2, 0) X(256, 2, 8, 0x10u, 1, 0, 0, 0)
+/* the explicit-schedule instances of the paper network: the tile pass is compiled once per role (two copies of the straight-line pass
+   per instance), so every instance is a translation unit of its own - rays + depths with the next tile's encoding in the stage
+   (mlp_fused48_paper_{bf16,fp16}.hip) and the plain form (mlp_fused48_paper_{bf16,fp16}_plain.hip) */
+#define DN_FWD48_PAPER_BF16_ENC(X) X(256, 1, 8, 0x10u, 1, 0, 2, 0)
+#define DN_FWD48_PAPER_BF16_PLAIN(X) X(256, 1, 8, 0x10u, 1, 0, 0, 0)
+#define DN_FWD48_PAPER_FP16_ENC(X) X(256, 2, 8, 0x10u, 1, 0, 2, 0)
+#define DN_FWD48_PAPER_FP16_PLAIN(X) X(256, 2, 8, 0x10u, 1, 0, 0, 0)
+#define DN_FWD48_PAPER_BF16(X) DN_FWD48_PAPER_BF16_ENC(X) DN_FWD48_PAPER_BF16_PLAIN(X)
+#define DN_FWD48_PAPER_FP16(X) DN_FWD48_PAPER_FP16_ENC(X) DN_FWD48_PAPER_FP16_PLAIN(X)
 #define DN_FWD48_W128(X) /* mlp_fused48_w128.hip: every W = 128 instance */ \
   X(128, 1, 0, 0u, 0, 0, 0, 0) X(128, 2, 0, 0u, 0, 0, 0, 0) /* run-time shape */ \
   X(128, 1, 4, 0u, 1, 0, 0, 0) X(128, 2, 4, 0u, 1, 0, 0, 0) /* as-shipped 4 x 128 */ \

@@ -261,6 +261,7 @@ constexpr int enc_table_slot_at(int q) {   // the slot whose table read rides at
 // One GEMM stage, explicit schedule.  NOPS: ops per tile of THIS stage, run by ops(nt_c, s_c) on `pacc` during the following tile;
 // PX: the barrier period in pieces (Pipe48::xs_period_begin).  PEND_N / PEND_BY: the ops the caller still owes for the previous stage's last tile (pend(s_c)) and the block of this stage's
 // first tile by which they must be done.  On return `pacc` holds the last tile's accumulators and the caller owes ITS NOPS ops.
+// ROLE: kXsFetcher / kXsConsumer (mlp_device.h) - which copy of the pass this is; it reaches the pipe's period and fetch hooks only.
 // TRK: as run_stage48 (fp16 range tracker on the stage's input pieces), two dwords per instruction, in the op-free blocks.
 // Hook: other work riding in the stage's blocks - hook(block_c, where_c) is called behind the ops of MFMA gap `where` = 0, 1, 2 of
 // block `block` = nt * KT + k, and with where = 3 just BEFORE the block's A-fragment read: an LDS operation issued there is older
@@ -269,8 +270,8 @@ struct XsNoHook {
   template <class B, class W>
   __device__ __forceinline__ void operator()(B, W) const {}
 };
-template <int F, int PX, int NT_OUT, int KH, int KP, int POS0, bool LAST, int PAD, int NOPS, int PEND_N, int PEND_BY, int TRK = 0, class PipeT, class BH,
-          class BP, class Ops, class Pend, class Hook = XsNoHook>
+template <int ROLE, int F, int PX, int NT_OUT, int KH, int KP, int POS0, bool LAST, int PAD, int NOPS, int PEND_N, int PEND_BY, int TRK = 0, class PipeT,
+          class BH, class BP, class Ops, class Pend, class Hook = XsNoHook>
 __device__ __forceinline__ void run_stage48x(PipeT& pipe, const BH& bh, BP&& bp, unsigned bias_addr, unsigned next_addr, f32x4 (&pacc)[3],
                                              Ops&& ops, Pend&& pend, unsigned* trk = nullptr, Hook&& hook = Hook{}) {
   constexpr int PT = 3, KT = KH + KP;
@@ -316,7 +317,7 @@ __device__ __forceinline__ void run_stage48x(PipeT& pipe, const BH& bh, BP&& bp,
     static_for<KT>([&](auto k_c) {
       constexpr int k = decltype(k_c)::value;
       constexpr int pos = POS0 + nt * KT + k;
-      pipe.template at_position_xs<PX, pos>();
+      pipe.template at_position_xs<PX, pos, ROLE>();
       f32x4 b = {0.0f, 0.0f, 0.0f, 0.0f};
       if constexpr (k == 0) b = pipe.template bias_take<1>();
       constexpr int newer = g48_issued<LAST, POS0 + NT_OUT * KT, PAD>(pos + 1, pos + PipeGeo48::PREFETCH) + ((k == KT - 1) ? 1 : 0);
@@ -343,7 +344,7 @@ __device__ __forceinline__ void run_stage48x(PipeT& pipe, const BH& bh, BP&& bp,
       });
       if constexpr (KT - E <= 0 && NTRK > 0 && k == KT - 1)   // no op-free block: the tracker's ops behind the tile's last MFMA
         static_for<NTRK>([&](auto q_c) { run_trk(q_c); });
-      pipe.template xs_after_piece<PX, pos>();
+      pipe.template xs_after_piece<PX, pos, ROLE>();
       hook(std::integral_constant<int, nt * KT + k>{}, std::integral_constant<int, 3>{});
       if constexpr (g48_issued<LAST, POS0 + NT_OUT * KT, PAD>(pos + PipeGeo48::PREFETCH, pos + PipeGeo48::PREFETCH + 1) == 1) pipe.template prefetch<pos>();
       if constexpr (k == KT - 2) {
