@@ -200,22 +200,22 @@ def _geom_case(dev, rf, z, rows, noise, noise_std, white, ups, stride, what):
     assert torch.equal(g_rf, plain), (what, "g_rf differs from dn_volume_render_backward's")
     only_z = _ops.volume_render_bwd_geom(*args, want_rf=False, want_rd=False)
     assert only_z[0] is None and only_z[2] is None and torch.equal(only_z[1], g_z), what
-    _, ref_z, ref_rd = oracle_grads64(rf, z, rows[:, 3:6], noise if noise_std > 0.0 else None, noise_std, white, ups)
-    e_z, e_rd = rel_err(C(g_z), ref_z.numpy()), rel_err(C(g_rd), ref_rd.numpy())
-    assert e_z <= 1e-4 and e_rd <= 1e-4, (what, e_z, e_rd)
-    return e_z, e_rd
+    ref_rf, ref_z, ref_rd = oracle_grads64(rf, z, rows[:, 3:6], noise if noise_std > 0.0 else None, noise_std, white, ups)
+    e_rf, e_z, e_rd = rel_err(C(g_rf), ref_rf.numpy()), rel_err(C(g_z), ref_z.numpy()), rel_err(C(g_rd), ref_rd.numpy())
+    assert e_rf <= 1e-4 and e_z <= 1e-4 and e_rd <= 1e-4, (what, e_rf, e_z, e_rd)
+    return e_rf, e_z, e_rd
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("s", [1, 2, 64, 65, 192, 300, 520])
+@pytest.mark.parametrize("s", [1, 2, 64, 65, 192, 300, 520, 1024])
 def test_geometry_kernel_against_float64_autograd_of_the_oracle(dev, s):
-    """dn_volume_render_backward_geom, N = 5 (the last workgroup is not full), S on both sides of every chunk boundary and in every
-    MAXC instance, rd_stride 3 and 11, white background on / off, injected noise (std 0.2) and none, each upstream gradient alone and
-    all five together; one ray holds two equal consecutive depths.  A second data set has one ray with every sigma <= 0 (no g_disp
-    there: disp is NaN in the reference too).  g_z, g_rd <= 1e-4 against float64 autograd of oracle.volume_render on the same fp32
-    inputs; g_rf bit-equal to dn_volume_render_backward's."""
+    """dn_volume_render_backward_geom, N = 5 (the last workgroup is not full), S on both sides of every chunk boundary, in every
+    MAXC instance and at the maximum (1024: 16 full chunks), rd_stride 3 and 11, white background on / off, injected noise (std 0.2)
+    and none, each upstream gradient alone and all five together; one ray holds two equal consecutive depths.  A second data set
+    has one ray with every sigma <= 0 (no g_disp there: disp is NaN in the reference too).  g_rf, g_z, g_rd <= 1e-4 against float64
+    autograd of oracle.volume_render on the same fp32 inputs; g_rf bit-equal to dn_volume_render_backward's."""
     rf, z, rows, noise, ups = render_inputs(5, s, seed=10 + s)
-    worst = [0.0, 0.0]
+    worst = [0.0, 0.0, 0.0]
     for stride in (3, 11):
         for white in (False, True):
             for noise_std in (0.0, 0.2):
@@ -230,7 +230,7 @@ def test_geometry_kernel_against_float64_autograd_of_the_oracle(dev, s):
             for noise_std in (0.0, 0.2):
                 e = _geom_case(dev, rf, z, rows, noise, noise_std, white, ups, stride, (s, stride, white, noise_std, "dead ray"))
                 worst = [max(a, b) for a, b in zip(worst, e)]
-    print(f"geometry kernel S={s}: worst g_z {worst[0]:.2e}, g_rd {worst[1]:.2e}")
+    print(f"geometry kernel S={s}: worst g_rf {worst[0]:.2e}, g_z {worst[1]:.2e}, g_rd {worst[2]:.2e}")
 
 
 @pytest.mark.gpu
