@@ -8,6 +8,7 @@
 
 #include "../../include/dexnerf_hip_ext.h"
 #include "../../include/dexnerf_hip_normals.h"
+#include "../../include/dexnerf_hip_quantile.h"
 #include "dn_common.h"
 #include "composite_body.h"
 #include "dn_rng.h"
@@ -204,47 +205,78 @@ extern "C" size_t dn_render_depth_workspace_bytes(int64_t n_rays, int num_coarse
   return carve_depth(nullptr, n_rays, num_coarse, num_fine).bytes;
 }
 
-extern "C" int dn_render_rays_depth(const dn_mlp_desc* desc_coarse, const void* packed_coarse, const dn_mlp_desc* desc_fine,
-                                    const void* packed_fine, int precision, const float* rays, int ray_stride, int64_t n_rays,
-                                    int num_coarse, int num_fine, int lindisp, float noise_std, const float* d_m_thres, int n_thres,
-                                    const float* t_rand, const float* noise_c, const float* u, const float* noise_f, float* depth_c,
-                                    float* acc_c, float* depth_f, float* acc_f, float* dex_f, void* workspace, dn_stream_t stream) {
+// the one driver of dn_render_rays_depth and dn_render_rays_depth_quantiles (`who`: the entry point, for messages): with n_quant > 0
+// the last pass is composited by composite_quantile_kernel, otherwise by composite_density_kernel - the launches are the same in number
+static int render_rays_depth_impl(const char* who, const dn_mlp_desc* desc_coarse, const void* packed_coarse, const dn_mlp_desc* desc_fine,
+                                  const void* packed_fine, int precision, const float* rays, int ray_stride, int64_t n_rays,
+                                  int num_coarse, int num_fine, int lindisp, float noise_std, const float* d_m_thres, int n_thres,
+                                  const float* t_rand, const float* noise_c, const float* u, const float* noise_f, float* depth_c,
+                                  float* acc_c, float* depth_f, float* acc_f, float* dex_f, const float* d_quantiles, int n_quant,
+                                  int interp, float* qdepth, void* workspace, dn_stream_t stream) {
   // every argument is judged before any GPU work
-  DN_REQUIRE(desc_coarse && packed_coarse && rays && workspace && n_rays >= 0, "dn_render_rays_depth: bad arguments");
-  DN_REQUIRE(num_coarse >= 1 && num_fine >= 0 && ray_stride >= 8, "dn_render_rays_depth: bad sample counts / ray stride");
-  DN_REQUIRE(num_fine == 0 || (desc_fine && packed_fine), "dn_render_rays_depth: fine pass requested without a fine net");
-  DN_REQUIRE(n_thres >= 0, "dn_render_rays_depth: negative threshold count");
-  DN_REQUIRE(n_thres == 0 || (d_m_thres && dex_f), "dn_render_rays_depth: thresholds given without dex output");
+  DN_REQUIRE(desc_coarse && packed_coarse && rays && workspace && n_rays >= 0, "%s: bad arguments", who);
+  DN_REQUIRE(num_coarse >= 1 && num_fine >= 0 && ray_stride >= 8, "%s: bad sample counts / ray stride", who);
+  DN_REQUIRE(num_fine == 0 || (desc_fine && packed_fine), "%s: fine pass requested without a fine net", who);
+  DN_REQUIRE(n_thres >= 0, "%s: negative threshold count", who);
+  DN_REQUIRE(n_thres == 0 || (d_m_thres && dex_f), "%s: thresholds given without dex output", who);
   DN_REQUIRE(!desc_coarse->use_viewdirs && (num_fine == 0 || !desc_fine->use_viewdirs),
-             "dn_render_rays_depth: takes density sub-networks (dn_mlp_density_desc / dn_mlp_pack_density): use_viewdirs must be 0");
+             "%s: takes density sub-networks (dn_mlp_density_desc / dn_mlp_pack_density): use_viewdirs must be 0", who);
   DN_REQUIRE(num_fine == 0 || (num_coarse >= 10 && num_coarse <= 512 && num_coarse + num_fine <= 2048),
-             "dn_render_rays_depth: need 10 <= num_coarse <= 512 and num_coarse + num_fine <= 2048");
-  DN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "dn_render_rays_depth: workspace must be 256-byte aligned");
+             "%s: need 10 <= num_coarse <= 512 and num_coarse + num_fine <= 2048", who);
+  DN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "%s: workspace must be 256-byte aligned", who);
   int rc;
+  if ((rc = quantile_args_check(who, d_quantiles, n_quant, interp, qdepth))) return rc;
   if ((rc = validate_desc(desc_coarse, precision))) return rc;
   if (num_fine > 0 && (rc = validate_desc(desc_fine, precision))) return rc;
   if (n_rays == 0) return 0;
   DepthWorkspace w = carve_depth(workspace, n_rays, num_coarse, num_fine);
   {
     hipError_t e = hipMemsetAsync(w.status, 0, 256, as_stream(stream));
-    if (e != hipSuccess) { set_error("dn_render_rays_depth: hipMemsetAsync: %s", hipGetErrorString(e)); return -static_cast<int>(e); }
+    if (e != hipSuccess) { set_error("%s: hipMemsetAsync: %s", who, hipGetErrorString(e)); return -static_cast<int>(e); }
   }
   if ((rc = dn_coarse_depths(rays, ray_stride, n_rays, num_coarse, lindisp, t_rand, w.z_c, stream))) return rc;
   if ((rc = run_network_flagged(desc_coarse, precision, packed_coarse, nullptr, nullptr, rays, ray_stride, w.z_c, n_rays, num_coarse,
                                 w.rf_c, w.status + 1, stream)))
     return rc;
   // Dex depths come from the fine pass (train_utils.py:199-201); coarse-only renders report the coarse ones.
-  if (num_fine == 0)
-    return composite_density_counting(w.rf_c, w.z_c, rays + 3, ray_stride, noise_c, noise_std, d_m_thres, n_thres, n_rays, num_coarse,
-                                      depth_c, acc_c, dex_f, w.status, stream);
+  auto composite_last = [&](const float* rf, const float* z, const float* noise, int samples, float* depth, float* acc) {
+    if (n_quant > 0)
+      return composite_quantile_counting(rf, z, rays + 3, ray_stride, noise, noise_std, d_m_thres, n_thres, d_quantiles, n_quant, interp,
+                                         n_rays, samples, depth, acc, dex_f, qdepth, w.status, stream);
+    return composite_density_counting(rf, z, rays + 3, ray_stride, noise, noise_std, d_m_thres, n_thres, n_rays, samples, depth, acc, dex_f,
+                                      w.status, stream);
+  };
+  if (num_fine == 0) return composite_last(w.rf_c, w.z_c, noise_c, num_coarse, depth_c, acc_c);
   if ((rc = density_resample_counting(w.rf_c, w.z_c, rays + 3, ray_stride, noise_c, noise_std, u, n_rays, num_coarse, num_fine, depth_c,
                                       acc_c, w.z_f, w.status, stream)))
     return rc;
   if ((rc = run_network_flagged(desc_fine, precision, packed_fine, nullptr, nullptr, rays, ray_stride, w.z_f, n_rays,
                                 num_coarse + num_fine, w.rf_f, w.status + 1, stream)))
     return rc;
-  return composite_density_counting(w.rf_f, w.z_f, rays + 3, ray_stride, noise_f, noise_std, d_m_thres, n_thres, n_rays,
-                                    num_coarse + num_fine, depth_f, acc_f, dex_f, w.status, stream);
+  return composite_last(w.rf_f, w.z_f, noise_f, num_coarse + num_fine, depth_f, acc_f);
+}
+
+extern "C" int dn_render_rays_depth(const dn_mlp_desc* desc_coarse, const void* packed_coarse, const dn_mlp_desc* desc_fine,
+                                    const void* packed_fine, int precision, const float* rays, int ray_stride, int64_t n_rays,
+                                    int num_coarse, int num_fine, int lindisp, float noise_std, const float* d_m_thres, int n_thres,
+                                    const float* t_rand, const float* noise_c, const float* u, const float* noise_f, float* depth_c,
+                                    float* acc_c, float* depth_f, float* acc_f, float* dex_f, void* workspace, dn_stream_t stream) {
+  return render_rays_depth_impl("dn_render_rays_depth", desc_coarse, packed_coarse, desc_fine, packed_fine, precision, rays, ray_stride, n_rays,
+                                num_coarse, num_fine, lindisp, noise_std, d_m_thres, n_thres, t_rand, noise_c, u, noise_f, depth_c, acc_c,
+                                depth_f, acc_f, dex_f, nullptr, 0, 0, nullptr, workspace, stream);
+}
+
+// the depth-only render with the opacity-quantile depths of its last pass (include/dexnerf_hip_quantile.h)
+extern "C" int dn_render_rays_depth_quantiles(const dn_mlp_desc* desc_coarse, const void* packed_coarse, const dn_mlp_desc* desc_fine,
+                                              const void* packed_fine, int precision, const float* rays, int ray_stride, int64_t n_rays,
+                                              int num_coarse, int num_fine, int lindisp, float noise_std, const float* d_m_thres,
+                                              int n_thres, const float* t_rand, const float* noise_c, const float* u, const float* noise_f,
+                                              float* depth_c, float* acc_c, float* depth_f, float* acc_f, float* dex_f,
+                                              const float* d_quantiles, int n_quant, int interp, float* qdepth, void* workspace,
+                                              dn_stream_t stream) {
+  return render_rays_depth_impl("dn_render_rays_depth_quantiles", desc_coarse, packed_coarse, desc_fine, packed_fine, precision, rays, ray_stride,
+                                n_rays, num_coarse, num_fine, lindisp, noise_std, d_m_thres, n_thres, t_rand, noise_c, u, noise_f, depth_c,
+                                acc_c, depth_f, acc_f, dex_f, d_quantiles, n_quant, interp, qdepth, workspace, stream);
 }
 
 // ---- the normal render (include/dexnerf_hip_normals.h): dn_render_rays_depth with the last pass differentiated ---------------------

@@ -47,6 +47,14 @@ int composite_density_counting(const float* rf, const float* z, const float* rd,
                                const float* d_m_thres, int n_thres, int64_t n_rays, int n_samples, float* depth, float* acc, float* dex,
                                unsigned* nonfinite, dn_stream_t stream);
 
+// composite_quantile.hip: the quantile arguments' rule (`who`: the entry point, for messages) and dn_composite_density_quantiles with
+// the non-finite count
+int quantile_args_check(const char* who, const float* d_quantiles, int n_quant, int interp, const float* qdepth);
+int composite_quantile_counting(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise, float noise_std,
+                                const float* d_m_thres, int n_thres, const float* d_quantiles, int n_quant, int interp, int64_t n_rays,
+                                int n_samples, float* depth, float* acc, float* dex, float* qdepth, unsigned* nonfinite,
+                                dn_stream_t stream);
+
 // composite_normals.hip: dn_composite_normals with the non-finite count; the density gradient's seed g_out = (0,0,0,1) per point
 int composite_normals_counting(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise, float noise_std,
                                const float* g_pts, const float* d_m_thres, int n_thres, int64_t n_rays, int n_samples, float* depth,

@@ -3,7 +3,8 @@
 model_coarse_state_dict / model_fine_state_dict, optional height / width / focal_length), render a sweep of spherical
 poses in validation mode, optionally save RGB / disparity-style depth PNGs, and print the average time per image.
 `--depth-only --m-thres M` renders the depth and Dex depth maps alone (nerf.render_dex_depth): no colour is evaluated, no RGB PNG
-is written, and the maps go to dex_<view>.npz beside depth_<view>.png.
+is written, and the maps go to dex_<view>.npz beside depth_<view>.png.  `--depth-quantiles 0.1,0.5,0.9 [--quantile-interp]` adds the
+opacity-quantile depth maps (0.5: the median depth) to the same render and the same file (quantiles / qdepth), with or without --m-thres.
 `--normals` renders density-gradient surface normals (nerf.render_dex_normals) instead: normal_<view>.npy holds the expected normal
 (H,W,3) (not renormalised: its length is a confidence), normal_<view>.png shows (n/|n| + 1)/2, black where n = 0; with `--m-thres M` the
 same pair per threshold, dex_normal_<view>_m<threshold>.npy / .png - the normal at the sample the Dex depth reports.
@@ -26,7 +27,7 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
 import nerf  # noqa: E402
-from nerf import synthetic as syn  # noqa: E402
+from nerf import _ops, synthetic as syn  # noqa: E402
 
 
 def model_from_state_dict(sd, dev):
@@ -57,7 +58,13 @@ def main(argv=None):
     ap.add_argument("--white-background", action="store_true")
     ap.add_argument("--m-thres", type=int, default=0, help="> 0: also produce the Dex depth maps for thresholds 5..m")
     ap.add_argument("--depth-only", action="store_true",
-                    help="render depth / Dex depth maps only (nerf.render_dex_depth: density sub-networks, no colour); needs --m-thres > 0")
+                    help="render depth / Dex depth maps only (nerf.render_dex_depth: density sub-networks, no colour); needs --m-thres > 0 or "
+                         "--depth-quantiles")
+    ap.add_argument("--depth-quantiles", default="", metavar="Q,Q,...",
+                    help="--depth-only: also the opacity-quantile depth maps - the depth at which the ray's accumulated opacity reaches q "
+                         "(0.5: the median depth), e.g. 0.1,0.5,0.9; at most 64 values strictly inside (0, 1); saved as quantiles / qdepth")
+    ap.add_argument("--quantile-interp", action="store_true",
+                    help="--depth-quantiles: the piecewise-linear CDF inversion instead of the depth of the crossing sample")
     ap.add_argument("--normals", action="store_true",
                     help="render surface normals only (nerf.render_dex_normals: the density gradient at the samples, composited like the "
                          "depth; with --m-thres also the normal at every Dex depth); not with --precision fp16")
@@ -72,8 +79,16 @@ def main(argv=None):
                          "stored exposure (nerf.apply_exposure); the default render is at the canonical exposure, the identity")
     args = ap.parse_args(argv)
 
-    if args.depth_only and args.m_thres <= 0:
-        ap.error("--depth-only renders the Dex depth maps: give --m-thres > 0")
+    try:
+        quantiles = _ops.check_quantiles([float(q) for q in args.depth_quantiles.split(",") if q.strip()], "--depth-quantiles")
+    except ValueError as e:
+        ap.error(str(e))
+    if (quantiles or args.quantile_interp) and not args.depth_only:
+        ap.error("--depth-quantiles / --quantile-interp belong to --depth-only")
+    if args.quantile_interp and not quantiles:
+        ap.error("--quantile-interp needs --depth-quantiles")
+    if args.depth_only and args.m_thres <= 0 and not quantiles:
+        ap.error("--depth-only renders the Dex / quantile depth maps: give --m-thres > 0 or --depth-quantiles")
     if args.normals and args.precision == "fp16":
         ap.error("--normals differentiates the density network on the training kernels, which exist for fp32 and bf16: not with --precision fp16")
     if args.normals and (args.depth_only or args.apply_exposure):
@@ -142,18 +157,25 @@ def main(argv=None):
             with torch.no_grad():
                 ro, rd = nerf.get_ray_bundle(size, size, float(k_mat[0, 0]), pose, k_mat)
                 out = nerf.render_dex_depth(size, size, float(k_mat[0, 0]), coarse, fine, ro, rd, cfg, mode="validation",
-                                            encode_position_fn=ex, encode_direction_fn=ed, m_thres_cand=thres)
+                                            encode_position_fn=ex, encode_direction_fn=ed, m_thres_cand=thres,
+                                            quantiles=quantiles or None, quantile_interp=args.quantile_interp)
             torch.cuda.synchronize()
             times.append(time.perf_counter() - t0)
             depth = out[2] if fine is not None else out[0]
-            frames.append((None, depth, out[4:]))
+            n_dex = 0 if thres is None else len(thres)
+            dex_maps, q_maps = out[4:4 + n_dex], out[4 + n_dex:]
+            frames.append((None, depth, dex_maps) + ((q_maps,) if quantiles else ()))
             if args.savedir:   # the expected depth as a PNG, every map (depth + one Dex depth per threshold) as float32
                 from PIL import Image
                 d = depth.cpu().numpy()
                 d = (255 * (d - d.min()) / max(d.max() - d.min(), 1e-8)).astype(np.uint8)
                 Image.fromarray(d).save(os.path.join(args.savedir, f"depth_{i:04d}.png"))
-                np.savez(os.path.join(args.savedir, f"dex_{i:04d}.npz"), depth=depth.cpu().numpy(), m_thres=np.asarray(thres, np.float32),
-                         dex=torch.stack(list(out[4:])).cpu().numpy())
+                arrays = dict(depth=depth.cpu().numpy())
+                if n_dex:
+                    arrays.update(m_thres=np.asarray(thres, np.float32), dex=torch.stack(list(dex_maps)).cpu().numpy())
+                if quantiles:
+                    arrays.update(quantiles=np.asarray(quantiles, np.float32), qdepth=torch.stack(list(q_maps)).cpu().numpy())
+                np.savez(os.path.join(args.savedir, f"dex_{i:04d}.npz"), **arrays)
             continue
         with torch.no_grad():
             ro, rd = nerf.get_ray_bundle(size, size, float(k_mat[0, 0]), pose, k_mat)

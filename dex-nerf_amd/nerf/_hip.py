@@ -56,6 +56,10 @@ EXPOSURE_EXPORTS = ("dn_render_loss_exposure",)
 # include/dexnerf_hip_normals.h: density-gradient surface normals composited beside the Dex depths (nerf.render_dex_normals)
 NORMALS_EXPORTS = ("dn_composite_normals", "dn_render_normals_workspace_bytes", "dn_render_rays_normals")
 
+# include/dexnerf_hip_quantile.h: opacity-quantile (median) depth maps beside the Dex depths (nerf.render_dex_depth(quantiles=...))
+QUANTILE_EXPORTS = ("dn_composite_density_quantiles", "dn_render_rays_depth_quantiles")
+MAX_QUANTILES = 64   # DN_MAX_QUANTILES
+
 
 class MlpDesc(ctypes.Structure):
     """dn_mlp_desc (mirrors FlexibleNeRFModel.__init__, reference nerf/models.py:186-196)."""
@@ -215,6 +219,11 @@ def _declare(lib):
     lib.dn_render_rays_normals.argtypes = [POINTER(MlpDesc), vp, POINTER(MlpDesc), vp, vp, vp, c_int, fp, c_int, c_int64, c_int, c_int, c_int,
                                            c_float, fp, c_int, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, vp, c_size_t, vp]
     lib.dn_render_rays_normals.restype = c_int
+    # the quantile header: dn_composite_density's / dn_render_rays_depth's arguments with d_quantiles, n_quant, interp (and qdepth)
+    lib.dn_composite_density_quantiles.argtypes = [fp, fp, fp, c_int, fp, c_float, fp, c_int, fp, c_int, c_int, c_int64, c_int, fp, fp, fp, fp, vp]
+    lib.dn_composite_density_quantiles.restype = c_int
+    lib.dn_render_rays_depth_quantiles.argtypes = lib.dn_render_rays_depth.argtypes[:-2] + [fp, c_int, c_int, fp, vp, vp]
+    lib.dn_render_rays_depth_quantiles.restype = c_int
 
 
 def lib():

@@ -4,6 +4,7 @@ Every function here requires ROCm device tensors and calls straight into libdexn
 no alternative implementation behind them.
 """
 import ctypes
+import math
 from ctypes import c_void_p
 
 import torch
@@ -1268,6 +1269,43 @@ def composite_density(rf, z, rd, noise, noise_std, m_thres):
     return depth, acc, dex
 
 
+def check_quantiles(quantiles, who="quantiles"):
+    """The host-side rule of the opacity quantiles (the C layer cannot read device memory): a list of at most 64 finite values
+    strictly inside (0, 1) as fp32 - returned as Python floats of those fp32 values.  Raises ValueError before any GPU work."""
+    qs = [float(q) for q in quantiles]
+    if len(qs) > _hip.MAX_QUANTILES:
+        raise ValueError(f"{who}: at most {_hip.MAX_QUANTILES} quantiles per call, got {len(qs)}")
+    out = []
+    for q in qs:
+        q32 = ctypes.c_float(q).value if math.isfinite(q) else q
+        if not (math.isfinite(q32) and 0.0 < q32 < 1.0):
+            raise ValueError(f"{who}: every quantile must be finite and strictly inside (0, 1) as fp32, got {q!r}")
+        out.append(q32)
+    return out
+
+
+def composite_density_quantiles(rf, z, rd, noise, noise_std, m_thres, quantiles, interp=False):
+    """dn_composite_density_quantiles: composite_density's (depth, acc, dex (K,N) or None) and qdepth (Q,N) or None - the depth at
+    which the accumulated opacity first reaches each quantile (interp: the piecewise-linear inversion instead of the sample's z)."""
+    qs = check_quantiles(quantiles, "composite_density_quantiles")
+    rf, z = f32c(rf), f32c(z)
+    n, s = z.shape
+    dev = rf.device
+    rd_ptr, rd_stride, rd = _dir_rows(rd)
+    k, nq = len(m_thres), len(qs)
+    depth = torch.empty((n,), dtype=torch.float32, device=dev)
+    acc = torch.empty_like(depth)
+    dex = torch.empty((k, n), dtype=torch.float32, device=dev) if k else None
+    qdepth = torch.empty((nq, n), dtype=torch.float32, device=dev) if nq else None
+    th = torch.tensor([float(m) for m in m_thres], dtype=torch.float32, device=dev) if k else None
+    qt = torch.tensor(qs, dtype=torch.float32, device=dev) if nq else None
+    nz = None if (noise is None or noise_std <= 0.0) else f32c(noise)
+    check(lib().dn_composite_density_quantiles(ptr(rf), ptr(z), rd_ptr, rd_stride, ptr(nz), float(noise_std), ptr(th), k, ptr(qt), nq,
+                                               int(bool(interp)), n, s, ptr(depth), ptr(acc), ptr(dex), ptr(qdepth), stream()),
+          "dn_composite_density_quantiles")
+    return depth, acc, dex, qdepth
+
+
 def density_resample(rf, z, rd, num_fine, noise=None, noise_std=0.0, u=None):
     """dn_density_resample: coarse sigma compositing fused with fine_depths -> (depth_c, acc_c, z_fine)."""
     rf, z = f32c(rf), f32c(z)
@@ -1284,9 +1322,13 @@ def density_resample(rf, z, rd, num_fine, noise=None, noise_std=0.0, u=None):
     return depth, acc, z_fine
 
 
-def render_rays_depth(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, noise_std, m_thres, draws=None):
+def render_rays_depth(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, noise_std, m_thres, draws=None, quantiles=None,
+                      interp=False):
     """dn_render_rays_depth: the depth-only predict_and_render_radiance forward for one ray chunk (no autograd, no colour) on
-    density packs (FlexibleNeRFModel.packed_density).  m_thres: a device tensor of K thresholds (any K) or None."""
+    density packs (FlexibleNeRFModel.packed_density).  m_thres: a device tensor of K thresholds (any K) or None.
+    quantiles: a device tensor of Q <= 64 opacity quantiles the caller has validated (check_quantiles) - the call then goes to
+    dn_render_rays_depth_quantiles (same launches, the last pass composited by the quantile kernel) and returns qdepth (Q,N) as a
+    sixth value; None: the call and the return are what they were."""
     rays = f32c(rays)
     n = rays.shape[0]
     dev = rays.device
@@ -1298,6 +1340,19 @@ def render_rays_depth(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, n
     depth_f, acc_f = (_empty(dev, n), _empty(dev, n)) if fine else (None, None)
     dex = _empty(dev, k, n) if k else None
     t_rand, noise_c, u, noise_f = _draw_tensors(draws)
+    if quantiles is not None:
+        nq = int(quantiles.numel())
+        if not 1 <= nq <= _hip.MAX_QUANTILES or quantiles.dtype != torch.float32:
+            raise ValueError(f"render_rays_depth: quantiles must be a float32 device tensor of 1 .. {_hip.MAX_QUANTILES} values")
+        qdepth = _empty(dev, nq, n)
+        check(lib().dn_render_rays_depth_quantiles(
+            ctypes.byref(packed_c.desc), ptr(packed_c.buffer),
+            ctypes.byref(packed_f.desc) if fine else None, ptr(packed_f.buffer) if fine else None, packed_c.precision,
+            ptr(rays), rays.shape[1], n, num_coarse, nf, int(bool(lindisp)), float(noise_std),
+            ptr(m_thres) if k else None, k, ptr(t_rand), ptr(noise_c), ptr(u), ptr(noise_f),
+            ptr(depth_c), ptr(acc_c), ptr(depth_f), ptr(acc_f), ptr(dex), ptr(quantiles), nq, int(bool(interp)), ptr(qdepth),
+            ptr(ws), stream()), "dn_render_rays_depth_quantiles")
+        return depth_c, acc_c, depth_f, acc_f, dex, qdepth
     check(lib().dn_render_rays_depth(
         ctypes.byref(packed_c.desc), ptr(packed_c.buffer),
         ctypes.byref(packed_f.desc) if fine else None, ptr(packed_f.buffer) if fine else None, packed_c.precision,

@@ -370,7 +370,8 @@ def _threshold_tensor(thres, dev):
 
 
 def render_dex_depth(height, width, focal_length, model_coarse, model_fine, ray_origins, ray_directions, options,
-                     mode="validation", encode_position_fn=None, encode_direction_fn=None, m_thres_cand=None):
+                     mode="validation", encode_position_fn=None, encode_direction_fn=None, m_thres_cand=None, quantiles=None,
+                     quantile_interp=False):
     """The depth half of run_one_iter_of_nerf and nothing else: expected depth, accumulation and the Dex first-crossing depths
     depend on sigma alone (reference nerf/volume_rendering_utils.py:33-58), so this render evaluates only the density
     sub-networks (trunk + fc_alpha: FlexibleNeRFModel.packed_density) and composites no colour (dn_render_rays_depth).
@@ -379,7 +380,15 @@ def render_dex_depth(height, width, focal_length, model_coarse, model_fine, ray_
     mode; num_fine == 0 / model_fine None gives None for the fine maps and the coarse Dex depths.  Rays, chunking, NDC, lindisp,
     perturb / noise draws (rand, randn, rand, randn: the generator ends where a full render leaves it) follow
     run_one_iter_of_nerf; the number of thresholds is not limited.  No-grad only, device tensors only, networks the fused kernels
-    cover only: anything else raises.  Follows nerf.set_render_policy like every no-grad render (guarded fp16 under 'bf16')."""
+    cover only: anything else raises.  Follows nerf.set_render_policy like every no-grad render (guarded fp16 under 'bf16').
+
+    quantiles: Q <= 64 fractions strictly inside (0, 1) (checked here, on the host, before anything else) - Q more maps follow the K
+    Dex maps: the depth at which the ray's accumulated opacity first reaches q (0.5: the median depth; z(0.9) - z(0.1): a per-pixel
+    depth confidence), from the same pass (dn_render_rays_depth_quantiles: the same launches).  quantile_interp=False gives the z of
+    the crossing sample, the convention of the Dex depth; True the piecewise-linear CDF inversion the fine-depth sampler uses.  A ray
+    whose accumulation stays below q reports its LAST sample's depth (it went through) - not z[0] like a Dex depth without a crossing.
+    quantiles=None: the launches and the return are what they were."""
+    qs = None if quantiles is None else _ops.check_quantiles(quantiles, "render_dex_depth: quantiles")
     _require_device(ray_directions, "render_dex_depth")
     _require_device(ray_origins, "render_dex_depth")
     opt = getattr(options.nerf, mode)
@@ -409,6 +418,7 @@ def render_dex_depth(height, width, focal_length, model_coarse, model_fine, ray_
     lindisp = bool(opt.lindisp)
     lx = encode_position_fn.log_sampling
     m_thres = _threshold_tensor(thres, dev)
+    q_dev = _threshold_tensor(qs, dev) if qs else None   # (the same cache: one host-to-device copy per quantile set)
     guard = _fp16_guard(models, density=True)
     # precision code -> the density packs: fetched once per pass over the chunks, not per chunk (a pass runs in one precision, and
     # the re-render after a trip in another - the configured one is never the guarded one - so it fetches its own)
@@ -420,9 +430,15 @@ def render_dex_depth(height, width, focal_length, model_coarse, model_fine, ray_
             packs[prec] = (model_coarse.packed_density(lx, True, precision=prec),
                            model_fine.packed_density(lx, True, precision=prec) if fine else None)
         draws = _draws(batch.shape[0], nc, nf, fine, perturb, std, dev)
-        depth_c, acc_c, depth_f, acc_f, dex = _ops.render_rays_depth(*packs[prec], batch, nc, nf if fine else 0, lindisp, std, m_thres,
-                                                                    draws)
+        if q_dev is None:
+            depth_c, acc_c, depth_f, acc_f, dex = _ops.render_rays_depth(*packs[prec], batch, nc, nf if fine else 0, lindisp, std, m_thres,
+                                                                        draws)
+            qdepth = None
+        else:
+            depth_c, acc_c, depth_f, acc_f, dex, qdepth = _ops.render_rays_depth(*packs[prec], batch, nc, nf if fine else 0, lindisp, std,
+                                                                                m_thres, draws, quantiles=q_dev, interp=quantile_interp)
         maps = [depth_c, acc_c, depth_f, acc_f] + ([] if dex is None else [dex[k] for k in range(dex.shape[0])])
+        maps += [] if qdepth is None else [qdepth[k] for k in range(qdepth.shape[0])]
         words = _ops.render_status_words()   # (copied for unguarded chunks too, as it always was: same launches on every path)
         if guarded:
             status.append(words)

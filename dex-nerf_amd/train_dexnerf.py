@@ -65,6 +65,26 @@ def dex_sweep(outputs, depth_gt, thres, gt_hi=6.0):
     return thres[best], errs[best]
 
 
+def parse_quantiles(text):
+    """'0.1,0.5,0.9' -> the opacity quantiles of --val-quantiles / eval_nerf.py --depth-quantiles, under the library's host-side rule
+    (finite, strictly inside (0, 1), at most 64): ValueError otherwise."""
+    from nerf import _ops
+    return _ops.check_quantiles([float(q) for q in text.split(",") if q.strip()], "quantiles")
+
+
+def quantile_sweep(models, cfg, pose, k_mat, hw, ex, depth_gt, quantiles, gt_hi=6.0):
+    """--val-quantiles: one depth-only render of the view with the opacity-quantile depth maps (nerf.render_dex_depth), scored like
+    the Dex thresholds (nerf.dex_error_sweep, the same mask and metric): (best quantile, its error record)."""
+    h, w = hw
+    ro, rd = nerf.get_ray_bundle(h, w, float(k_mat[0, 0]), pose, k_mat)
+    with torch.no_grad():
+        out = nerf.render_dex_depth(h, w, float(k_mat[0, 0]), models[0], models[1], ro, rd, cfg, mode="validation",
+                                    encode_position_fn=ex, quantiles=quantiles)
+    best, errs = nerf.dex_error_sweep(depth_gt, list(out[4:]), gt_lo=0.0, gt_hi=gt_hi)
+    best = int(np.argmin([e["depth_abs_err"] for e in errs])) if best is None else best
+    return quantiles[best], errs[best]
+
+
 def synthetic_dataset(args, kw, cfg, ex, ed, thres, dev):
     """No dataset ships with the reference: a fixed random coarse/fine FlexibleNeRFModel pair ("teacher") is rendered from
     `views` + 1 spherical poses; the last pose is held out."""
@@ -179,6 +199,9 @@ def build_parser():
     ap.add_argument("--lr-decay", type=int, default=250)
     ap.add_argument("--lr-decay-factor", type=float, default=0.1)
     ap.add_argument("--m-thres", type=int, default=100)
+    ap.add_argument("--val-quantiles", default="", metavar="Q,Q,...",
+                    help="at validation also render the opacity-quantile depth maps (one nerf.render_dex_depth with these quantiles, e.g. "
+                         "0.1,0.5,0.9) and log the best quantile and its depth error beside the best Dex threshold; off by default")
     ap.add_argument("--ir", action="store_true", help="IR head of train_nerf_ir.py / train_dexnerf_ir.py: MSE on the luminance "
                                                       "0.299 r + 0.587 g + 0.114 b of prediction and target (:260-263)")
     ap.add_argument("--s8-grad-scale", type=float, default=None,
@@ -272,6 +295,10 @@ def parse_args(argv=None):
     """The command line, checked: inconsistent combinations end in the parser's error (SystemExit 2)."""
     ap = build_parser()
     args = ap.parse_args(argv)
+    try:      # "" (the default): no quantile render at validation
+        args.val_quantiles = parse_quantiles(args.val_quantiles)
+    except ValueError as e:
+        ap.error(f"--val-quantiles: {e}")
     if not args.refine_poses:
         for flag, value in (("--pose-lr", args.pose_lr), ("--pose-lr-decay", args.pose_lr_decay), ("--refine-intrinsics", args.refine_intrinsics),
                             ("--intrinsics-scale", args.intrinsics_scale), ("--fix-views", args.fix_views),
@@ -596,9 +623,14 @@ def main(argv=None):
                     print(f"[val]   iter {it + 1:6d} held-out view psnr {nerf.mse2psnr(vmse):.2f} dB", flush=True)
                 continue
             m_best, err = dex_sweep(out, depths[held_out], thres, data["mask_hi"])
+            q_log = ""
+            val_quantiles = args.val_quantiles
+            if val_quantiles:
+                q_best, q_err = quantile_sweep(student, cfg, *camera_of(held_out), hw, ex, depths[held_out], val_quantiles, data["mask_hi"])
+                q_log = f"; quantile best q={q_best:g} abs depth err {q_err['depth_abs_err']:.1f} mm"
             if not args.quiet:
                 print(f"[val]   iter {it + 1:6d} held-out view psnr {nerf.mse2psnr(vmse):.2f} dB; Dex best m={m_best} "
-                      f"abs depth err {err['depth_abs_err']:.1f} mm", flush=True)
+                      f"abs depth err {err['depth_abs_err']:.1f} mm{q_log}", flush=True)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     result = dict(history=history, final_loss=loss_val, final_psnr=psnr, seconds=elapsed,
@@ -631,6 +663,10 @@ def main(argv=None):
             # the expected depth sum(w z) of the fine pass - what --depth-weight supervises - under the same mask and metric
             _, expected = nerf.dex_error_sweep(depths[held_out], [out[4]], gt_lo=0.0, gt_hi=data["mask_hi"])
             result["expected_depth_abs_err_mm"] = expected[0]["depth_abs_err"]
+            if args.val_quantiles:
+                q_best, q_err = quantile_sweep(student, cfg, *camera_of(held_out), hw, ex, depths[held_out], args.val_quantiles,
+                                               data["mask_hi"])
+                result["quantile_best"], result["quantile_abs_err_mm"] = float(q_best), q_err["depth_abs_err"]
         if args.save:
             opt_state = opt.state_dict()
             for group in opt_state["param_groups"]:   # the reference stores a Python float (train_dexnerf_rgb.py:443-456), not the
