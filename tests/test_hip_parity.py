@@ -1967,7 +1967,8 @@ def test_device_pixel_draw_is_a_permutation_with_uniform_marginals(dev):
     hits every pixel exactly once (several image sizes, incl. non-powers of two); consecutive iterations give different draws, the
     same (seed, iteration) the same one; over 4,000 iterations of 256-ray draws on a 37 x 29 image every pixel is chosen about
     equally often (chi-square over the 1,073 pixels within 5 sigma of its mean) and no draw repeats a pixel; the ray rows and
-    targets equal dn_select_rays_indirect's on the drawn pixels."""
+    targets equal dn_select_rays_indirect's on the drawn pixels.
+    (The exact checks - which pixel, which view, which counter - are in tests/test_device_draws.py.)"""
     from nerf import _ops
     cams = torch.zeros(2, 16, device=dev)
     cams[:, 0] = cams[:, 4] = cams[:, 8] = 1.0
@@ -2029,7 +2030,8 @@ def test_device_pixel_draw_is_a_permutation_with_uniform_marginals(dev):
 def test_in_kernel_uniforms_and_normals(dev):
     """The jitter / resampling uniforms and the density-noise normals the training kernels draw themselves (Philox-4x32-10 + Box-
     Muller, csrc/dn_rng.h; reference: torch.rand / torch.randn, nerf/train_utils.py:126-133, volume_rendering_utils.py:32-38):
-    moments, range, independence across streams and iterations, reproducibility."""
+    moments, range, independence across streams and iterations, reproducibility.
+    (The exact checks - every number against a restatement of the generator - are in tests/test_device_draws.py.)"""
     from nerf import _ops
     st = _ops.new_rng_state(123, dev)
     n = 1 << 20
