@@ -21,8 +21,8 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(
   const int64_t ray = static_cast<int64_t>(blockIdx.x) * kRaysPerBlock + (threadIdx.x >> 6);
   if (ray >= n_rays) return;  // wave-uniform exit; no block-level sync in this kernel
   const float4* rfr = rf + ray * S;
-  composite_ray([&](int sc) { return rfr[sc]; }, z + ray * S, rd + ray * rd_stride, ray, lane, noise, noise_std, white, th, n_thres, n_rays, S,
-                rgb, disp, acc, weights, depth, dex, nonfinite, rng);
+  composite_ray([&](int sc) { return rfr[sc]; }, DrawnNoise{noise, rng, noise_std, ray, S}, z + ray * S, rd + ray * rd_stride, ray, lane,
+                white, th, n_thres, n_rays, S, rgb, disp, acc, weights, depth, dex, nonfinite);
 }
 
 // Backward w.r.t. rf (checked against autograd of the reference in fp64):
@@ -76,6 +76,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
   float dzv_[GEOM ? MAXC : 1], dd_[GEOM ? MAXC : 1];
   double carry = 1.0;
   float sum_d = 0.f, sum_a = 0.f;
+  const DrawnNoise noise_at{noise, rng, noise_std, ray, S};
 #pragma unroll
   for (int c = 0; c < MAXC; ++c) {
     const int base = c * 64;
@@ -85,16 +86,8 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
     const float4 raw = rfr[sc];
     const float z0 = zr[sc];
     const float z1 = (sc + 1 < S) ? zr[sc + 1] : z0;
-    // (the forward's noise again: the same pure function of (seed, iteration, stream, element) when it was drawn in the kernel)
-    const float nz = noise_std > 0.0f ? (noise != nullptr ? noise[ray * S + sc]
-                                                          : (rng.state != nullptr ? rng_normal(rng, static_cast<uint64_t>(ray) * S + sc) : 0.0f)) : 0.0f;
-    const SampleTerms t = sample_terms(raw.w, nz, noise_std, z0, z1, sc == S - 1, rd_norm);
-    const double f = valid ? static_cast<double>(t.one_m_alpha) : 1.0;
-    const double incl = wave_scan_mul(f) * carry;
-    const double excl = wave_shift_up1(incl, carry);
-    carry = wave_last(incl);
-    const float trans = (s == 0) ? 1.0f : static_cast<float>(excl);
-    const float w = valid ? t.alpha * trans : 0.0f;
+    const SampleTerms t = sample_terms(raw.w, noise_at(sc), noise_std, z0, z1, sc == S - 1, rd_norm);   // (the forward's noise again)
+    const auto [trans, w] = transmittance_step(t.alpha, t.one_m_alpha, valid, s, carry);
     c0_[c] = sigmoidf_(raw.x); c1_[c] = sigmoidf_(raw.y); c2_[c] = sigmoidf_(raw.z);
     w_[c] = w; t_[c] = trans; om_[c] = t.one_m_alpha;
     de_[c] = t.dist * expf(-t.sigma * t.dist);  // dalpha/dsigma

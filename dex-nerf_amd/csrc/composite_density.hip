@@ -5,7 +5,7 @@
 //                             LDS row and runs the sampler's own code on it: the (N, Nc) weights never reach HBM.
 //   composite_density_kernel: depth, acc and dex (K, N) for any K (thresholds in device memory, 64 per pass).
 // One wave64 per ray, four rays per workgroup, like composite.hip / the sampler.
-#include "composite_density_body.h"
+#include "composite_body.h"
 #include "sampler_body.h"
 
 namespace dn {
@@ -30,9 +30,9 @@ __global__ __launch_bounds__(256) void density_resample_kernel(const float4* __r
   const float* zc = z + ray * nc;
   for (int i = lane; i < B; i += 64) bins[i] = 0.5f * (zc[i + 1] + zc[i]);
   for (int i = lane; i < nc; i += 64) sbuf[i] = zc[i];
-  density_ray(rf + ray * nc, zc, rd + ray * rd_stride, ray, live, lane, noise, noise_std, static_cast<const float*>(nullptr), 0, n_rays, nc,
-              acc, depth, static_cast<float*>(nullptr), nonfinite,
-              [&](int s, float wt) { if (s >= 1 && s <= nc - 2) w[s - 1] = wt + 1e-5f; });   // weights[..., 1:-1] + 1e-5
+  forward_ray(SigmaColumn(rf + ray * nc), TensorNoise{noise, noise_std, ray, nc}, DeviceThres{nullptr, 0}, zc, rd + ray * rd_stride, ray, live,
+              lane, n_rays, nc, acc, depth, static_cast<float*>(nullptr), nonfinite,
+              [&](int s, bool valid, float wt, float) { if (valid && s >= 1 && s <= nc - 2) w[s - 1] = wt + 1e-5f; });   // weights[..., 1:-1] + 1e-5
   sampler_resample<1>(w, cdf, bins, sbuf, u, ray, live, B, nf, static_cast<float*>(nullptr), static_cast<int64_t*>(nullptr), z_fine,
                       sort_len, RngRef{nullptr, 0u});
 }
@@ -45,8 +45,8 @@ __global__ __launch_bounds__(256) void composite_density_kernel(const float4* __
   const int lane = lane_id();
   const int64_t ray = static_cast<int64_t>(blockIdx.x) * kSamplerWaves + (threadIdx.x >> 6);
   if (ray >= n_rays) return;  // wave-uniform exit; no block-level sync in this kernel
-  density_ray(rf + ray * S, z + ray * S, rd + ray * rd_stride, ray, true, lane, noise, noise_std, d_thres, n_thres, n_rays, S, acc, depth,
-              dex, nonfinite, [](int, float) {});
+  forward_ray(SigmaColumn(rf + ray * S), TensorNoise{noise, noise_std, ray, S}, DeviceThres{d_thres, n_thres}, z + ray * S,
+              rd + ray * rd_stride, ray, true, lane, n_rays, S, acc, depth, dex, nonfinite, [](int, bool, float, float) {});
 }
 
 static int next_pow2(int v) {

@@ -2,14 +2,14 @@
 // pass - expected depth, accumulation, Dex depths, the same bits - that also composites the per-sample unit normals
 //     n_s = -g_s / |g_s|,   g_s = d sigma_raw / d x  (g_pts, (N,S,3)),
 // into the expected normal sum_s w_s n_s and picks n at each threshold's first-crossing sample (the sample whose z the Dex depth
-// reports).  One wave64 per ray, four rays per workgroup, built on density_ray: the expected normal rides on its on_weight hook, the
+// reports).  One wave64 per ray, four rays per workgroup, built on forward_ray: the expected normal rides on its on_weight hook, the
 // Dex normals on its on_first hook.  Plain stores, no atomics; the grid is a function of (N, S) alone.
 //
 // Memory: HBM-bound, 16 B (raw row, .w used) + 4 B (z) + 12 B (gradient) read per sample.  A lane reads its sample's three gradient
 // components as three dwords 12 B apart; the wave's three loads cover ONE contiguous 768 B span between them, so every cache line
 // fetched is used in full (the second and third load hit the lines the first brought in) - no staging through LDS.
 #include "../../include/dexnerf_hip_normals.h"
-#include "composite_density_body.h"
+#include "composite_body.h"
 #include "sampler_body.h"
 
 namespace dn {
@@ -35,11 +35,12 @@ __global__ __launch_bounds__(256) void composite_normals_kernel(const float4* __
   const int64_t ray = static_cast<int64_t>(blockIdx.x) * kSamplerWaves + (threadIdx.x >> 6);
   if (ray >= n_rays) return;  // wave-uniform exit; no block-level sync in this kernel
   const float* gr = g_pts + ray * S * 3;
-  float s_n[3] = {0.0f, 0.0f, 0.0f};   // lane-local over ascending chunks, then wave_sum: the order of density_ray's depth sum
-  density_ray(
-      rf + ray * S, z + ray * S, rd + ray * rd_stride, ray, true, lane, noise, noise_std, d_thres, n_thres, n_rays, S, acc, depth, dex, nonfinite,
-      [&](int s, float w) {
-        if (normal == nullptr) return;
+  float s_n[3] = {0.0f, 0.0f, 0.0f};   // lane-local over ascending chunks, then wave_sum: the order of forward_ray's depth sum
+  forward_ray(
+      SigmaColumn(rf + ray * S), TensorNoise{noise, noise_std, ray, S}, DeviceThres{d_thres, n_thres}, z + ray * S, rd + ray * rd_stride, ray,
+      true, lane, n_rays, S, acc, depth, dex, nonfinite,
+      [&](int s, bool valid, float w, float) {
+        if (!valid || normal == nullptr) return;
         float n[3];
         unit_normal(gr + 3 * s, n);
 #pragma unroll

@@ -1,14 +1,14 @@
 // The opacity-quantile compositing of the depth path (include/dexnerf_hip_quantile.h): dn_composite_density's pass - expected depth,
 // accumulation, Dex depths, the same bits - that also reads out, per quantile q_k, the depth at which the ray's accumulated opacity
 // C_s = sum_{j <= s} w_j first reaches q_k (q = 0.5: the median depth).  One wave64 per ray, four rays per workgroup, built on
-// density_ray with its Quantiles<> argument: lane k tracks quantile k, the prefix sum is an fp64 wave scan with a carry between the
+// forward_ray with its Quantiles<> argument: lane k tracks quantile k, the prefix sum is an fp64 wave scan with a carry between the
 // 64-sample chunks, and a chunk is searched for quantile k only when its last C reaches q_k (a wave-uniform test).  Plain vector
 // stores, no atomics (but the non-finite count of the render's status block); the grid is a function of (N, S) alone.
 //
 // Memory: HBM-bound like composite_density_kernel - 16 B (raw row, .w used) + 4 B (z) read per sample; the quantiles add Q floats
 // read and Q floats written per ray and no pass over the samples.
 #include "../../include/dexnerf_hip_quantile.h"
-#include "composite_density_body.h"
+#include "composite_body.h"
 #include "sampler_body.h"
 
 namespace dn {
@@ -23,8 +23,9 @@ __global__ __launch_bounds__(256) void composite_quantile_kernel(const float4* _
   const int lane = lane_id();
   const int64_t ray = static_cast<int64_t>(blockIdx.x) * kSamplerWaves + (threadIdx.x >> 6);
   if (ray >= n_rays) return;  // wave-uniform exit; no block-level sync in this kernel
-  density_ray(rf + ray * S, z + ray * S, rd + ray * rd_stride, ray, true, lane, noise, noise_std, d_thres, n_thres, n_rays, S, acc, depth,
-              dex, nonfinite, [](int, float) {}, NoFirstHook{}, Quantiles<>{d_quant, n_quant, interp, qdepth, NoQuantileHook{}});
+  forward_ray(SigmaColumn(rf + ray * S), TensorNoise{noise, noise_std, ray, S}, DeviceThres{d_thres, n_thres}, z + ray * S,
+              rd + ray * rd_stride, ray, true, lane, n_rays, S, acc, depth, dex, nonfinite, [](int, bool, float, float) {}, NoFirstHook{},
+              Quantiles<>{d_quant, n_quant, interp, qdepth, NoQuantileHook{}});
 }
 
 int quantile_args_check(const char* who, const float* d_quantiles, int n_quant, int interp, const float* qdepth) {

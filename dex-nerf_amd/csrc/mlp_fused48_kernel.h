@@ -786,10 +786,9 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
         const long long ray = static_cast<long long>(tile) * rays_per_tile + r;
         if (ray < q.comp.n_rays) {
           const f32x4* rows = stage + r * S;
-          composite_ray([&](int sc) { const f32x4 r = rows[sc]; return make_float4(r[0], r[1], r[2], r[3]); }, p.z + ray * S,
-                        p.rays + ray * p.ray_stride + 3, ray, lo, static_cast<const float*>(nullptr), 0.0f, q.comp.white, q.comp.th,
-                        q.comp.n_thres, q.comp.n_rays, S, q.comp.rgb, q.comp.disp, q.comp.acc, q.comp.weights, q.comp.depth, q.comp.dex,
-                        q.comp.nonfinite, RngRef{nullptr, 0u});
+          composite_ray([&](int sc) { const f32x4 r = rows[sc]; return make_float4(r[0], r[1], r[2], r[3]); }, TensorNoise{nullptr, 0.0f, ray, S},
+                        p.z + ray * S, p.rays + ray * p.ray_stride + 3, ray, lo, q.comp.white, q.comp.th, q.comp.n_thres, q.comp.n_rays, S,
+                        q.comp.rgb, q.comp.disp, q.comp.acc, q.comp.weights, q.comp.depth, q.comp.dex, q.comp.nonfinite);
         }
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the stash is the next tile's encodings' again

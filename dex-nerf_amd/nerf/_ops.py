@@ -5,6 +5,7 @@ no alternative implementation behind them.
 """
 import ctypes
 import math
+import types
 from ctypes import c_void_p
 
 import torch
@@ -502,20 +503,54 @@ def select_rays_draw(height, width, cams, view, near, far, rng_state, n_rays, im
     return (rays, target, pix) if want_pixels else (rays, target)
 
 
+def _loss_head_args(name, n_out, rgb_c, rgb_f, target, depth_c=None, depth_f=None, depth_src=None, pixel_index=None, view_index=None, view=None,
+                    views_gather_only=False):
+    """What the loss heads share (`name`: the caller, for messages): the colour inputs as contiguous fp32, `out` (n_out) and the
+    gradient buffers, the depth-target arguments (depth_c / depth_f / depth_src, pix, hw; all None / 0 without a depth target) and the
+    view arguments (views (N) int32, else the `view` scalar, else None).  views_gather_only: the views only say where depth targets
+    are gathered - there must be none beside direct targets, and they are dropped without gathered ones."""
+    a = types.SimpleNamespace(rgb_c=f32c(rgb_c), rgb_f=None, target=f32c(target), g_f=None, depth_c=None, depth_f=None, depth_src=None,
+                              gd_c=None, gd_f=None, pix=None, hw=0, views=None, view=None)
+    a.n = n = a.rgb_c.shape[0]
+    a.out = torch.empty(n_out, dtype=torch.float32, device=a.rgb_c.device)
+    a.g_c = torch.empty_like(a.rgb_c)
+    if rgb_f is not None:
+        a.rgb_f = f32c(rgb_f)
+        a.g_f = torch.empty_like(a.rgb_f)
+    if depth_src is not None:
+        if depth_c is None:
+            raise ValueError(f"{name}: a depth target needs depth_c")
+        a.depth_src, a.depth_c = f32c(depth_src), f32c(depth_c)
+        assert a.depth_c.numel() == n and a.depth_src.is_cuda
+        a.gd_c = torch.empty_like(a.depth_c)
+        if depth_f is not None:
+            a.depth_f = f32c(depth_f)
+            assert a.depth_f.numel() == n
+            a.gd_f = torch.empty_like(a.depth_f)
+        if pixel_index is None:
+            assert a.depth_src.numel() == n and not (views_gather_only and (view_index is not None or view is not None)), \
+                f"{name}: direct depth targets are (N)"
+        else:
+            a.pix = pixel_index.contiguous()
+            assert a.pix.dtype == torch.int64 and a.pix.is_cuda and a.pix.numel() == n and a.depth_src.dim() >= 2
+            a.hw = a.depth_src[0].numel()     # (an empty stack of maps raises here)
+    if views_gather_only and a.pix is None:
+        return a
+    if view_index is not None:
+        a.views = _view_index(view_index, n)
+    elif view is not None:
+        assert view.dtype == torch.int32 and view.is_cuda and view.numel() == 1
+        a.view = view
+    return a
+
+
 def mse2_loss(rgb_c, rgb_f, target, luminance=False, rng_state=None):
     """(loss3 = [loss, mse_coarse, mse_fine] on the device, g_rgb_coarse, g_rgb_fine): the loss head + its upstream gradients in
     one launch (dn_mse2_loss); advances `rng_state`'s iteration counter."""
-    rgb_c, target = f32c(rgb_c), f32c(target)
-    n = rgb_c.shape[0]
-    loss3 = torch.empty(3, dtype=torch.float32, device=rgb_c.device)
-    g_c = torch.empty_like(rgb_c)
-    g_f = None
-    if rgb_f is not None:
-        rgb_f = f32c(rgb_f)
-        g_f = torch.empty_like(rgb_f)
-    check(lib().dn_mse2_loss(ptr(rgb_c), ptr(rgb_f), ptr(target), n, int(bool(luminance)), ptr(loss3), ptr(g_c), ptr(g_f), ptr(rng_state),
-                             stream()), "dn_mse2_loss")
-    return loss3, g_c, g_f
+    a = _loss_head_args("mse2_loss", 3, rgb_c, rgb_f, target)
+    check(lib().dn_mse2_loss(ptr(a.rgb_c), ptr(a.rgb_f), ptr(a.target), a.n, int(bool(luminance)), ptr(a.out), ptr(a.g_c), ptr(a.g_f),
+                             ptr(rng_state), stream()), "dn_mse2_loss")
+    return a.out, a.g_c, a.g_f
 
 
 def render_loss(rgb_c, rgb_f, target, depth_c=None, depth_f=None, depth_src=None, pixel_index=None, view_index=None, view=None,
@@ -524,47 +559,12 @@ def render_loss(rgb_c, rgb_f, target, depth_c=None, depth_f=None, depth_src=None
     the general loss head + its upstream gradients in one launch (dn_render_loss); advances `rng_state`'s iteration counter.
     depth_src: (N) target depths, or with pixel_index (N) int64 the (V, H W) / (V,H,W) depth maps they are gathered from - the view of
     ray i is view_index[i] ((N) int32), else `view` (device int32 scalar), else 0.  None: no depth term (both depth gradients None)."""
-    rgb_c, target = f32c(rgb_c), f32c(target)
-    n = rgb_c.shape[0]
-    dev = rgb_c.device
-    loss6 = torch.empty(6, dtype=torch.float32, device=dev)
-    g_c = torch.empty_like(rgb_c)
-    g_f = None
-    if rgb_f is not None:
-        rgb_f = f32c(rgb_f)
-        g_f = torch.empty_like(rgb_f)
-    gd_c = gd_f = pix = views = None
-    hw = 0
-    if depth_src is not None:
-        if depth_c is None:
-            raise ValueError("render_loss: a depth target needs depth_c")
-        depth_src, depth_c = f32c(depth_src), f32c(depth_c)
-        assert depth_c.numel() == n and depth_src.is_cuda
-        gd_c = torch.empty_like(depth_c)
-        if depth_f is not None:
-            depth_f = f32c(depth_f)
-            assert depth_f.numel() == n
-            gd_f = torch.empty_like(depth_f)
-        if pixel_index is None:
-            assert depth_src.numel() == n and view_index is None and view is None, "render_loss: direct depth targets are (N)"
-        else:
-            pix = pixel_index.contiguous()
-            assert pix.dtype == torch.int64 and pix.is_cuda and pix.numel() == n and depth_src.dim() >= 2
-            hw = depth_src[0].numel()
-            if view_index is not None:
-                views = _view_index(view_index, n)
-            elif view is not None:
-                assert view.dtype == torch.int32 and view.is_cuda and view.numel() == 1
-            else:
-                assert depth_src.shape[0] >= 1
-    else:
-        depth_c = depth_f = view = None
-    check(lib().dn_render_loss(ptr(rgb_c), ptr(rgb_f), ptr(target), ptr(depth_c), ptr(depth_f), ptr(depth_src), ptr(pix), ptr(views),
-                               ptr(view) if (pix is not None and views is None) else None, hw, n, int(bool(luminance)),
-                               float(weights[0]), float(weights[1]), float(depth_weights[0]), float(depth_weights[1]),
-                               float(depth_range[0]), float(depth_range[1]), ptr(loss6), ptr(g_c), ptr(g_f), ptr(gd_c), ptr(gd_f),
-                               ptr(rng_state), stream()), "dn_render_loss")
-    return loss6, g_c, g_f, gd_c, gd_f
+    a = _loss_head_args("render_loss", 6, rgb_c, rgb_f, target, depth_c, depth_f, depth_src, pixel_index, view_index, view, views_gather_only=True)
+    check(lib().dn_render_loss(ptr(a.rgb_c), ptr(a.rgb_f), ptr(a.target), ptr(a.depth_c), ptr(a.depth_f), ptr(a.depth_src), ptr(a.pix),
+                               ptr(a.views), ptr(a.view), a.hw, a.n, int(bool(luminance)), float(weights[0]), float(weights[1]),
+                               float(depth_weights[0]), float(depth_weights[1]), float(depth_range[0]), float(depth_range[1]), ptr(a.out),
+                               ptr(a.g_c), ptr(a.g_f), ptr(a.gd_c), ptr(a.gd_f), ptr(rng_state), stream()), "dn_render_loss")
+    return a.out, a.g_c, a.g_f, a.gd_c, a.gd_f
 
 
 def render_loss_exposure(rgb_c, rgb_f, target, eps, exposure_scale=1.0, view_index=None, view=None, view_mask=None, depth_c=None, depth_f=None,
@@ -575,55 +575,21 @@ def render_loss_exposure(rgb_c, rgb_f, target, eps, exposure_scale=1.0, view_ind
     are gathered at too.  view_mask (V) int32: rows whose gradient is formed (None: all).  Returns (loss6, g_rgb_coarse, g_rgb_fine,
     g_depth_coarse, g_depth_fine, g_eps (V,P)); g_eps is written into the tensor given, or allocated (want_eps=False: None, one launch
     less)."""
-    rgb_c, target = f32c(rgb_c), f32c(target)
-    n = rgb_c.shape[0]
-    dev = rgb_c.device
     assert eps.is_cuda and eps.dtype == torch.float32 and eps.is_contiguous() and eps.dim() == 2 and eps.shape[1] in (1, 6)
     n_views, p = int(eps.shape[0]), int(eps.shape[1])
-    loss6 = torch.empty(6, dtype=torch.float32, device=dev)
-    g_c = torch.empty_like(rgb_c)
-    g_f = None
-    if rgb_f is not None:
-        rgb_f = f32c(rgb_f)
-        g_f = torch.empty_like(rgb_f)
-    views = None
-    if view_index is not None:
-        views = _view_index(view_index, n)
-    elif view is not None:
-        assert view.dtype == torch.int32 and view.is_cuda and view.numel() == 1
+    a = _loss_head_args("render_loss_exposure", 6, rgb_c, rgb_f, target, depth_c, depth_f, depth_src, pixel_index, view_index, view)
     if view_mask is not None:
         assert view_mask.dtype == torch.int32 and view_mask.is_cuda and view_mask.is_contiguous() and view_mask.numel() == n_views
-    gd_c = gd_f = pix = None
-    hw = 0
-    if depth_src is not None:
-        if depth_c is None:
-            raise ValueError("render_loss_exposure: a depth target needs depth_c")
-        depth_src, depth_c = f32c(depth_src), f32c(depth_c)
-        assert depth_c.numel() == n and depth_src.is_cuda
-        gd_c = torch.empty_like(depth_c)
-        if depth_f is not None:
-            depth_f = f32c(depth_f)
-            assert depth_f.numel() == n
-            gd_f = torch.empty_like(depth_f)
-        if pixel_index is None:
-            assert depth_src.numel() == n, "render_loss_exposure: direct depth targets are (N)"
-        else:
-            pix = pixel_index.contiguous()
-            assert pix.dtype == torch.int64 and pix.is_cuda and pix.numel() == n and depth_src.dim() >= 2
-            hw = depth_src[0].numel()
-    else:
-        depth_c = depth_f = None
     if g_eps is None and want_eps:
-        g_eps = torch.empty((n_views, p), dtype=torch.float32, device=dev)
+        g_eps = torch.empty((n_views, p), dtype=torch.float32, device=a.out.device)
     if g_eps is not None:
         assert g_eps.is_cuda and g_eps.dtype == torch.float32 and g_eps.is_contiguous() and tuple(g_eps.shape) == (n_views, p)
-    check(lib().dn_render_loss_exposure(ptr(rgb_c), ptr(rgb_f), ptr(target), ptr(depth_c), ptr(depth_f), ptr(depth_src), ptr(pix), ptr(views),
-                                        ptr(view) if views is None else None, hw, n, int(bool(luminance)), float(weights[0]),
-                                        float(weights[1]), float(depth_weights[0]), float(depth_weights[1]), float(depth_range[0]),
-                                        float(depth_range[1]), ptr(eps), p, n_views, float(exposure_scale), ptr(view_mask), ptr(loss6),
-                                        ptr(g_c), ptr(g_f), ptr(gd_c), ptr(gd_f), ptr(g_eps), ptr(rng_state), stream()),
-          "dn_render_loss_exposure")
-    return loss6, g_c, g_f, gd_c, gd_f, g_eps
+    check(lib().dn_render_loss_exposure(ptr(a.rgb_c), ptr(a.rgb_f), ptr(a.target), ptr(a.depth_c), ptr(a.depth_f), ptr(a.depth_src), ptr(a.pix),
+                                        ptr(a.views), ptr(a.view), a.hw, a.n, int(bool(luminance)), float(weights[0]), float(weights[1]),
+                                        float(depth_weights[0]), float(depth_weights[1]), float(depth_range[0]), float(depth_range[1]),
+                                        ptr(eps), p, n_views, float(exposure_scale), ptr(view_mask), ptr(a.out), ptr(a.g_c), ptr(a.g_f),
+                                        ptr(a.gd_c), ptr(a.gd_f), ptr(g_eps), ptr(rng_state), stream()), "dn_render_loss_exposure")
+    return a.out, a.g_c, a.g_f, a.gd_c, a.gd_f, g_eps
 
 
 def ndc_rays(height, width, focal, near, rays_o, rays_d):

@@ -12,7 +12,13 @@ render; two seeded 4 x 128 networks with view directions; world and NDC rows.  T
 five sources of (view, pixel)), dn_render_rays_train_geom, dn_render_rays_backward_ws with nets = 1, 2, 3 in fp32, bf16 with 16-bit
 saves and the 8-bit-saved mode (absmax partials from the compositing backward, and DEXNERF_S8_ABSMAX_KERNEL=1),
 dn_render_rays_backward_geom in fp32 / bf16 with and without weight-gradient views, dn_volume_render_backward(_geom) at 16 and 130
-samples, dn_mse2_loss, dn_render_loss, dn_camera_grad, dn_camera_grad_views."""
+samples, dn_mse2_loss, dn_render_loss, dn_camera_grad, dn_camera_grad_views.
+
+The one-body refactor of the loss heads and the forward compositing added loss_heads() and forward_compositing() (their docstrings
+list the cases): dn_mse2_loss, dn_render_loss and dn_render_loss_exposure at 1, 65 and 1025 rays, and on 5 rays dn_volume_render,
+dn_composite_density(_quantiles), dn_composite_normals, dn_density_resample, dn_volume_render_backward(_geom), a training render that
+draws its density noise in the compositing kernel and a render with DEXNERF_FUSED_COMPOSITE=1.  Their thousands of small outputs are
+folded into one digest per group of cases (fold_into)."""
 import argparse
 import hashlib
 import json
@@ -38,14 +44,28 @@ H = W = 12
 V = 3
 NDC_FOCAL = 14.0
 OUT = {}
+FOLD = []
 
 
 def record(name, *tensors):
-    """sha256 of each tensor's bytes (None: "-") under name, name.1, ..."""
+    """sha256 of each tensor's bytes (None: "-") under name, name.1, ...; after fold_into(label) the bytes go, in call order, into the
+    one digest kept under the label instead."""
+    if FOLD:
+        for t in tensors:
+            FOLD[-1][1].update(b"-" if t is None else t.detach().contiguous().cpu().numpy().tobytes())
+        OUT[FOLD[-1][0]] = FOLD[-1][1].hexdigest()
+        return
     for k, t in enumerate(tensors):
         key = name if k == 0 else f"{name}.{k}"
         assert key not in OUT, key
         OUT[key] = "-" if t is None else hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
+
+
+def fold_into(label):
+    """From here on one sha256 under `label` over every tensor recorded (thousands of small outputs: one line per group of cases in the
+    record); None: back to a hash per tensor."""
+    assert label not in OUT, label
+    FOLD[:] = [] if label is None else [(label, hashlib.sha256())]
 
 
 def rand(seed, *shape, normal=False):
@@ -196,6 +216,137 @@ def moved(dev, batches, cams, cams_ndc):
                    _ops.camera_grad_views(H, W, records, b["views"], b["pix"], n, g[:, 0:3], g[:, 3:6], g[:, 8:11], focal, 1.0))
 
 
+def loss_heads(dev):
+    """The three loss heads (one kernel template): one ray, not a multiple of 64, a second trip of the 1024-thread loop; luminance;
+    with and without rgb_f; depth targets absent / direct / gathered by view_index / gathered by the `view` word, over a range that
+    keeps every ray, some and none; exposure rows (P = 1, 6; 3 views) with an all-zero row, a view_index out of range, a masked view,
+    g_eps wanted and not."""
+    from nerf import _ops
+    view = torch.tensor(2, dtype=torch.int32, device=dev)
+    mask = torch.tensor([1, 0, 1], dtype=torch.int32, device=dev)
+    for n in (1, 65, 1025):
+        g = torch.Generator().manual_seed(n)
+        pix = torch.randint(0, H * W, (n,), generator=g).to(dev)
+        views = torch.randint(0, V, (n,), generator=g).to(dev, torch.int32)
+        stray = views.clone()
+        stray[-1] = 7      # no such view: the ray takes the uncorrected expressions (never used to gather depth targets)
+        rgb_c, rgb_f, target = rand(n, n, 3), rand(n + 1, n, 3), rand(n + 5, n, 3)
+        depth_c, depth_f, depth_maps = 2.0 + 4.0 * rand(n + 2, n), 2.0 + 4.0 * rand(n + 3, n), 1.0 + 6.0 * rand(n + 4, V, H, W)
+        targets = {"none": {}, "direct": dict(depth_src=1.0 + 6.0 * rand(n + 9, n)),
+                   "view_index": dict(depth_src=depth_maps, pixel_index=pix, view_index=views),
+                   "view": dict(depth_src=depth_maps, pixel_index=pix, view=view)}
+        for luminance in (False, True):
+            fold_into(f"loss heads n={n} luminance={luminance}")
+            for fine in (rgb_f, None):
+                what = f"n={n} luminance={luminance} fine={fine is not None}"
+                state = _ops.new_rng_state(3, dev, 9)
+                record(f"heads mse2_loss {what}", *_ops.mse2_loss(rgb_c, fine, target, luminance, state), state)
+                for tname, tkw in targets.items():
+                    for rname, lohi in (("all", (0.0, float("inf"))), ("some", (2.0, 6.0)), ("none", (100.0, 200.0))):
+                        if tname == "none" and rname != "all":
+                            continue
+                        state = _ops.new_rng_state(3, dev, 9)
+                        dkw = dict(tkw, depth_c=depth_c, depth_f=depth_f if fine is not None else None) if tkw else {}
+                        record(f"heads render_loss {what} target={tname} range={rname}",
+                               *_ops.render_loss(rgb_c, fine, target, weights=(0.7, 1.3), depth_weights=(0.1, 0.2), depth_range=lohi,
+                                                 luminance=luminance, rng_state=state, **dkw), state)
+                        if rname == "some":
+                            continue
+                        for p in (1, 6):
+                            eps = 0.3 * rand(n + 6 + p, V, p, normal=True)
+                            eps[1] = 0.0
+                            # (the depth targets of the exposure head are gathered at the exposure views: the stray view goes with
+                            # direct targets or none)
+                            vkw = dict(view=view) if tname == "view" else dict(view_index=views if tname == "view_index" else stray)
+                            ekw = {k: v for k, v in dkw.items() if k not in ("view", "view_index")}
+                            for want_eps in (True, False):
+                                record(f"heads render_loss_exposure {what} target={tname} range={rname} P={p} g_eps={want_eps}",
+                                       *_ops.render_loss_exposure(rgb_c, fine, target, eps, 0.5, view_mask=mask, weights=(0.7, 1.3),
+                                                                  depth_weights=(0.1, 0.2), depth_range=lohi, luminance=luminance,
+                                                                  want_eps=want_eps, **vkw, **ekw))
+
+
+def forward_compositing(dev):
+    """Every client of the forward compositing body on 5 rays (four per workgroup): one sample, a ragged chunk, exactly one chunk, one
+    sample more, three chunks; noise from a tensor and drawn in the kernel (a training render); white background; the weights map
+    wanted and not; thresholds from the host (0, 1, 64), on the device (0, 64, 65, 100), quantiles (1, 64; both modes), normals, the
+    fused coarse pass + resampling, the compositing backward with and without g_disp / g_weights, and one render whose network
+    launches composite their own rays."""
+    import nerf
+    from nerf import _hip, _ops
+    n = 5
+    rd = rand(70, n, 3, normal=True)
+    thres = lambda k: [0.05 + 2.5 * i / max(k, 1) for i in range(k)]
+    for s in (1, 63, 64, 65, 129):
+        rf = rand(s, n, s, 4, normal=True)
+        z = torch.sort(2.0 + 4.0 * rand(s + 1, n, s), dim=1).values
+        g_pts = rand(s + 8, n, s, 3, normal=True)
+        g_pts[0, 0] = 0.0     # a zero gradient: the zero normal
+        fold_into(f"forward compositing, 5 rays, s={s}")
+        for noise_std, white in ((0.0, False), (0.3, True)):
+            noise = rand(s + 7, n, s, normal=True) if noise_std else None
+            what = f"s={s} noise={noise_std}"
+            for k in (0, 1, 64):
+                for want_weights in (True, False):
+                    record(f"volume_render {what} white={white} K={k} weights={want_weights}",
+                           *_ops.volume_render_fwd(rf, z, rd, noise, noise_std, white, thres(k), want_weights))
+            for k in (0, 64, 65, 100):
+                record(f"composite_density {what} K={k}", *_ops.composite_density(rf, z, rd, noise, noise_std, thres(k)))
+            for q in (1, 64):
+                for interp in (False, True):
+                    record(f"composite_density_quantiles {what} Q={q} interp={interp}",
+                           *_ops.composite_density_quantiles(rf, z, rd, noise, noise_std, thres(3), [(i + 1.0) / (q + 1.0) for i in range(q)], interp))
+            record(f"composite_normals {what}", *_ops.composite_normals(rf, z, rd, g_pts, noise, noise_std, thres(65)))
+    for nc, nf in ((10, 1), (64, 65)):
+        fold_into(f"density_resample, 5 rays, nc={nc} nf={nf}")
+        rf = rand(nc, n, nc, 4, normal=True)
+        z = torch.sort(2.0 + 4.0 * rand(nc + 1, n, nc), dim=1).values
+        for noise_std in (0.0, 0.3):
+            record(f"density_resample nc={nc} nf={nf} noise={noise_std}",
+                   *_ops.density_resample(rf, z, rd, nf, rand(nc + 2, n, nc, normal=True) if noise_std else None, noise_std, rand(nc + 3, n, nf)))
+    for s in (16, 64, 65, 130):
+        fold_into(f"backward compositing, 5 rays, s={s}")
+        rf = rand(s, n, s, 4, normal=True)
+        z = torch.sort(2.0 + 4.0 * rand(s + 1, n, s), dim=1).values
+        ups = [rand(s + 2, n, 3), rand(s + 3, n), rand(s + 4, n), rand(s + 5, n), rand(s + 6, n, s)]
+        for noise_std, white in ((0.0, False), (0.3, True)):
+            noise = rand(s + 7, n, s, normal=True) if noise_std else None
+            for extras in (True, False):
+                u = ups if extras else ups[:3] + [None, None]
+                what = f"5 rays s={s} noise={noise_std} g_disp, g_weights={extras}"
+                record(f"volume_render_backward {what}", _ops.volume_render_bwd(rf, z, rd, noise, noise_std, white, *u))
+                record(f"volume_render_backward_geom {what}", *_ops.volume_render_bwd_geom(rf, z, rd, noise, noise_std, white, *u))
+    fold_into(None)
+    # the density noise drawn in the compositing kernel: a training render of 65 + 64 samples
+    rows = torch.cat([rand(80, n, 3) - 0.5, rd, torch.full((n, 1), 2.0, device=dev), torch.full((n, 1), 6.0, device=dev),
+                      torch.nn.functional.normalize(rd, dim=-1)], dim=1).contiguous()
+    mc, mf = models_on(dev)
+    nerf.set_precision("fp32")
+    packs = []
+    for m in (mc, mf):
+        pk = m.packed(True, True, parts=_hip.PACK_CORE)
+        _ops.ensure_backward_stream(m, pk, pk.precision)
+        packs.append(pk)
+    state = _ops.new_rng_state(5, dev, 3)
+    maps, _ = _ops.render_rays_train(packs[0], packs[1], rows, 65, 64, False, 0.3, True, [], None, prec=packs[0].precision, rng_state=state, perturb=True)
+    record("train 5 rays 65+64 noise drawn in the kernel", *maps[:6])
+    # the network launches compositing their own rays (16-bit, whole rays per 384-point tile), and the same render without
+    nerf.set_precision("bf16")
+    try:
+        pc, pf = mc.packed(precision=_hip.PREC_BF16), mf.packed(precision=_hip.PREC_BF16)
+        for fused in (False, True):
+            if fused:
+                os.environ["DEXNERF_FUSED_COMPOSITE"] = "1"
+            fold_into(f"render_rays 5 rays 64+128 bf16 fused={fused} (the two must agree)")
+            try:
+                record(f"render_rays 5 rays 64+128 bf16 fused={fused}", *_ops.render_rays(pc, pf, rows, 64, 128, False, 0.0, True, thres(3)))
+            finally:
+                os.environ.pop("DEXNERF_FUSED_COMPOSITE", None)
+    finally:
+        fold_into(None)
+        nerf.set_precision("fp32")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tree", default="", help="import the package of this checkout (built there) instead of this script's")
@@ -212,6 +363,9 @@ def main():
     render(dev, batches)
     compositing(dev, batches)
     moved(dev, batches, cams, cams_ndc)
+    loss_heads(dev)
+    fold_into(None)
+    forward_compositing(dev)
     torch.cuda.synchronize()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as fh:
