@@ -58,6 +58,11 @@ struct Workspace {
   unsigned* status;   // the last 256 bytes: word 0 = non-finite raw radiance-field values met by this call's compositing
   size_t bytes;
 };
+// Words of the status block (zeroed by the one hipMemsetAsync at the top of a render call): 0 and 1 are what Python reads and sums
+// (non-finite count, fp16 range flag).  dn_render_rays hands two more to its network launches as tile counters (mlp_geo48.h
+// G48Params::tile_counter), 64 bytes apart: the coarse launch's and the fine launch's.  The depth, quantile and normal renders run the
+// density instances, which do not claim tiles: they pass none.
+constexpr int kStatusTilesCoarse = 16, kStatusTilesFine = 32;
 
 static Workspace carve(void* base, int64_t n, int nc, int nf, bool train = false) {
   Workspace w{};
@@ -179,7 +184,8 @@ extern "C" int dn_render_rays(const dn_mlp_desc* desc_coarse, const void* packed
   {
     const CompParams c = comp_for(rgb_c, acc_c, w.w_c, depth_c, fine ? nullptr : dex_f, fine ? 0 : n_thres);
     if ((rc = run_network_flagged(desc_coarse, precision, packed_coarse, nullptr, nullptr, rays, ray_stride, w.z_c, n_rays,
-                                  num_coarse, w.rf_c, w.status + 1, stream, (may_fuse && rgb_c) ? &c : nullptr, &done)))
+                                  num_coarse, w.rf_c, w.status + 1, stream, (may_fuse && rgb_c) ? &c : nullptr, &done,
+                                  w.status + kStatusTilesCoarse)))
       return rc;
   }
   if (!done && (rc = volume_render_counting(w.rf_c, w.z_c, rays + 3, ray_stride, noise_c, noise_std, white_background, h_m_thres,
@@ -191,7 +197,8 @@ extern "C" int dn_render_rays(const dn_mlp_desc* desc_coarse, const void* packed
   {
     const CompParams c = comp_for(rgb_f, acc_f, nullptr, depth_f, dex_f, n_thres);
     if ((rc = run_network_flagged(desc_fine, precision, packed_fine, nullptr, nullptr, rays, ray_stride, w.z_f, n_rays,
-                                  num_coarse + num_fine, w.rf_f, w.status + 1, stream, (may_fuse && rgb_f) ? &c : nullptr, &done)))
+                                  num_coarse + num_fine, w.rf_f, w.status + 1, stream, (may_fuse && rgb_f) ? &c : nullptr, &done,
+                                  w.status + kStatusTilesFine)))
       return rc;
   }
   if (done) return 0;

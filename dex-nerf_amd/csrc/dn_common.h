@@ -67,12 +67,14 @@ int input_grad_points_from_rays(const dn_mlp_desc* desc, int precision, const vo
                                 int ray_stride, const float* z_vals, int64_t n_rays, int samples_per_ray, float* d_pts, dn_stream_t stream);
 
 // mlp_fused.hip: dn_run_network with the fp16 range flag (a device word the 48-point fp16 kernel bumps when a hidden activation
-// left fp16's range; NULL = not wanted)
+// left fp16's range; NULL = not wanted) and the tile counter of the render drivers (a zeroed device word of the caller's from which the
+// launch's workgroups claim their tiles where the picked kernel can: mlp_geo48.h G48Params::tile_counter; NULL = fixed stride)
 bool weight_grad_pair_fits(const dn_mlp_desc& d);   // mlp_wgrad.hip: the layers of two such networks fit one weight-gradient batch
 struct CompParams;   // composite_body.h
 int run_network_flagged(const dn_mlp_desc* desc, int precision, const void* packed, const float* pts, const float* viewdirs,
                         const float* rays, int ray_stride, const float* z_vals, int64_t n_rays, int samples_per_ray, float* out,
-                        unsigned* range_flag, dn_stream_t stream, const CompParams* comp = nullptr, int* composited = nullptr);
+                        unsigned* range_flag, dn_stream_t stream, const CompParams* comp = nullptr, int* composited = nullptr,
+                        unsigned* tile_counter = nullptr);
 
 // rays_sampling.hip / composite.hip: the stage entry points with an RNG state (dn_rng.h) - a NULL draw pointer together with a
 // state means "draw it in the kernel"

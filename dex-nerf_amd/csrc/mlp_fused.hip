@@ -98,7 +98,8 @@ static int launch_forward(FwdParams p, hipStream_t stream) {
   return check_launch("mlp_forward");
 }
 
-int dispatch_forward(const dn_mlp_desc& d, int precision, FwdParams& p, hipStream_t stream, const CompParams* comp, int* composited) {
+int dispatch_forward(const dn_mlp_desc& d, int precision, FwdParams& p, hipStream_t stream, const CompParams* comp, int* composited,
+                     unsigned* tile_counter) {
   const bool bf = precision == DN_PREC_BF16;
   const bool hf = precision == DN_PREC_F16;
   // bf16 geometry: PT=1 (8 waves x 32 points, two waves per SIMD) measured fastest (1327 vs 1277 TFLOP/s for
@@ -107,7 +108,7 @@ int dispatch_forward(const dn_mlp_desc& d, int precision, FwdParams& p, hipStrea
   // DEXNERF_BF16_GEOM=32 keeps the 32-point kernels (same results up to bf16 accumulation order and the cosine's phase form)
   const char* region48 = p.packed + core_stream_bytes(p.bias_bytes, p.total_pieces);
   if ((bf || hf) && !read_switches().geom32 && p.act == nullptr && p.mode != 2 && p.n_points < (1LL << 31) - 1024 && g48_supported(d, precision))
-    return launch_forward48(d, precision, p, region48, stream, comp, composited);
+    return launch_forward48(d, precision, p, region48, stream, comp, composited, tile_counter);
   if (p.act != nullptr && hf) { set_error("mlp_forward(train): fp16 is a render-only mode"); return DN_E_UNSUPPORTED; }
   if (p.act != nullptr && p.save8) {   // training forward with 8-bit saved units: a kernel of the 48-point geometry (mlp_fused48.hip)
     if (!bf || p.mode == 2 || !g48_train_supported(d) || p.n_points >= (1LL << 31) - 1024) {
@@ -253,7 +254,7 @@ extern "C" int dn_run_network(const dn_mlp_desc* desc, int precision, const void
 int dn::run_network_flagged(const dn_mlp_desc* desc, int precision, const void* packed, const float* pts,
                             const float* viewdirs, const float* rays, int ray_stride, const float* z_vals,
                             int64_t n_rays, int samples_per_ray, float* out, unsigned* range_flag, dn_stream_t stream,
-                            const CompParams* comp, int* composited) {
+                            const CompParams* comp, int* composited, unsigned* tile_counter) {
   if (composited) *composited = 0;
   FwdParams p;
   int rc = setup_params(desc, precision, packed, &p);
@@ -265,7 +266,7 @@ int dn::run_network_flagged(const dn_mlp_desc* desc, int precision, const void* 
   p.out = out;
   p.range_flag = range_flag;
   if (p.n_points == 0) return 0;
-  return dispatch_forward(*desc, precision, p, as_stream(stream), comp, composited);
+  return dispatch_forward(*desc, precision, p, as_stream(stream), comp, composited, tile_counter);
 }
 
 extern "C" int dn_mlp_forward_encoded(const dn_mlp_desc* desc, int precision, const void* packed, const float* x,

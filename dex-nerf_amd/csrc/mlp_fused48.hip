@@ -129,13 +129,40 @@ int launch_pack48(const dn_mlp_desc& d, int precision, const PackPtrs& a, char* 
   return check_launch(density ? "mlp_pack48_density" : "mlp_pack48");
 }
 
+#ifdef DN_TILE_STAMP
+// Diagnostic build only (scripts/tile_stamps.py): the per-workgroup stamp records of the last kTileStampLaunches forward launches, in a
+// device buffer of their own that no kernel reads; dn_tile_stamp_read copies them out.  Not part of the library's interface.
+static unsigned long long* g_tile_stamps = nullptr;
+static long long g_tile_stamp_launches = 0;
+constexpr size_t kTileStampLaunchWords = static_cast<size_t>(kTileStampMaxWgs) * kTileStampWords;
+static unsigned long long* tile_stamp_slot(long long grid) {
+  if (grid > kTileStampMaxWgs) return nullptr;
+  if (g_tile_stamps == nullptr) {
+    const size_t bytes = kTileStampLaunches * kTileStampLaunchWords * sizeof(unsigned long long);
+    if (hipMalloc(reinterpret_cast<void**>(&g_tile_stamps), bytes) != hipSuccess) { g_tile_stamps = nullptr; return nullptr; }
+    if (hipMemset(g_tile_stamps, 0, bytes) != hipSuccess) return nullptr;
+  }
+  return g_tile_stamps + static_cast<size_t>(g_tile_stamp_launches++ % kTileStampLaunches) * kTileStampLaunchWords;
+}
+}  // namespace dn
+// dst: kTileStampLaunches * kTileStampMaxWgs * kTileStampWords 64-bit words; launch i (counted from 0) is in slot i % kTileStampLaunches.
+// Returns the number of launches stamped so far, or -1.
+extern "C" __attribute__((visibility("default"))) long long dn_tile_stamp_read(unsigned long long* dst) {
+  using namespace dn;
+  if (g_tile_stamps == nullptr || hipDeviceSynchronize() != hipSuccess) return -1;
+  if (hipMemcpy(dst, g_tile_stamps, kTileStampLaunches * kTileStampLaunchWords * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  return g_tile_stamp_launches;
+}
+namespace dn {
+#endif
+
 // In-kernel compositing is OFF unless DEXNERF_FUSED_COMPOSITE=1 (Switches::fused_composite).  It is bit-identical to the two-kernel path and
 // takes the raw radiance field out of HBM (fine launch of the headline configuration: see HISTORY.md section 4.7f for the PMC bytes),
 // but it costs time: a ray is composited by ONE wave with its SIMD to itself - exponentials, divisions and an fp64 scan as one
 // dependency chain - where the standalone kernel hides that latency behind eight waves per SIMD; measured +3 % on a D8/W256
 // render and +26 % on the as-shipped 4 x 128 nets.  The network kernels are not byte-bound, so the bytes saved buy nothing back.
 int launch_forward48(const dn_mlp_desc& d, int precision, const FwdParams& p_in, const char* region, hipStream_t stream,
-                     const CompParams* comp, int* composited) {
+                     const CompParams* comp, int* composited, unsigned* tile_counter) {
   if (composited) *composited = 0;
   NetLayout L;
   build_layout48(d, &L);
@@ -151,12 +178,19 @@ int launch_forward48(const dn_mlp_desc& d, int precision, const FwdParams& p_in,
   const int tile_points = k.SAVE == 3 ? 256 : kG48PointsPerWg;   // two point groups per wave: 256-point tiles
   p.n_tiles = (p.n_points + tile_points - 1) / tile_points;
   if (k.OVLP == 1) lds += static_cast<size_t>(kG48Waves) * 3 * kG48PointsPerWave * sizeof(float);   // a third set of view-direction rows
+  if (g48_claims(k) && lds + kG48ClaimBytes <= 160 * 1024) {   // (the claim words: always there for these instances, read or not)
+    lds += kG48ClaimBytes;
+    q.tile_counter = tile_counter;
+  }
   if (k.COMP) {
     q.comp = *comp;
     if (composited) *composited = 1;
   }
   auto launch = [&](auto kern) -> int {
     if (int rc = ensure_big_lds(reinterpret_cast<const void*>(kern))) return rc;
+#ifdef DN_TILE_STAMP
+    q.stamp = tile_stamp_slot(persistent_grid(p.n_tiles, cus));
+#endif
     hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(persistent_grid(p.n_tiles, cus))), dim3(kG48Waves * 64), lds, stream, p, q);
     return check_launch("mlp_forward48");
   };

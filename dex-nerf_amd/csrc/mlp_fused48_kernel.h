@@ -151,6 +151,38 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
     for (int i = threadIdx.x; i < (q.bias_bytes + kG48TableBytes) / 16; i += WAVES * 64) l[i] = gsrc[i];
   }
   issue_inputs(blockIdx.x, 0);
+  // ---- claimed tiles (CLAIM instances, q.tile_counter != NULL) ----
+  // A workgroup's first tile is blockIdx.x; every later one is gridDim.x + what an atomic add on the caller's zeroed word returned, so
+  // an XCD that holds a higher clock runs more tiles and the launch does not wait for the slowest XCD's fixed share
+  // (profiles/tile_claim.md).  The input DMAs run two tiles ahead, so the workgroup holds two claimed ids beyond the tile it runs
+  // (next_tile, and one more that travels through LDS) and claims one per tile - no deeper: a claimed tile nobody has started is tail.
+  // Who claims: wave 4, lane 0 - a consumer wave.  A returning atomic counts in the wave's vmcnt, in issue order, with its LDS-DMA
+  // loads; every vector-memory wait of these instances is a vmcnt(0) (the barrier period of two phases begins with one in every
+  // wave: mlp_device.h xs_period_begin; the consumer's waits for its input rows are vmcnt(0) too), so one more entry in the queue
+  // retires no wait early or late - and a consumer wave's queue never holds weight DMAs that such a wait would have to sit out.
+  // Steady state, pass k of the workgroup's own sequence:
+  //   in front of the view-direction stage every wave reads claim word 1 (id k + 2) next to its other LDS reads, behind the
+  //   lgkmcnt(0) that is there anyway, and prefetches that tile's inputs; wave 4 then issues the atomic for id k + 3;
+  //   the vmcnt(0) of wave 4's next barrier period retires it (72 MFMAs on; the compiler sees the destination register as an
+  //   ordinary value from the asm statement on, and nothing names it in between - checked in the disassembly, as for the LDS read
+  //   pipeline); the vmcnt(0) at the end of the pass (consumer copy) is the wait the hand-off below is written against;
+  //   there wave 4 stores the id into claim word 1, in front of the output stores.  The readers are a whole trunk and its barriers
+  //   away: LDS operations of a wave complete in order, and wave 4 waits for younger LDS reads before its next barrier.
+  // The prologue claims ids 1 and 2 with one atomic add of 2 (retired by the prologue's vmcnt(0)).  Ids are handed out in rising
+  // order, so a workgroup whose next id is past the end stops claiming; each workgroup gives up exactly the two ids it holds at its
+  // end, and the word (which starts at zero) ends at n_tiles + gridDim.x.
+  // Per-tile results do not depend on who computes the tile: every output is bit-identical to the fixed stride's.
+  constexpr bool CLAIM = XS && W == 256 && OVLP == 2;
+  unsigned* const claim_lds = reinterpret_cast<unsigned*>(smem + kRingBytes + q.bias_bytes + kG48TableBytes + WAVES * PT * KXP * kPieceBytes +
+                                                          WAVES * IN_ROWS * PPW * sizeof(float));
+  const bool claim = CLAIM && q.tile_counter != nullptr;   // kernel-uniform
+  if constexpr (CLAIM) {
+    if (claim && threadIdx.x == 4 * 64) {
+      const unsigned v = gridDim.x + __hip_atomic_fetch_add(q.tile_counter, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      claim_lds[0] = v;
+      claim_lds[1] = v + 1u;
+    }
+  }
   // OVL: the same DMAs without control flow (mid-pass a branch is a merge point the compiler may park copies of in-flight weight
   // fragments at): the lane mask is set inside the asm statement, the tile index is clamped by the caller
   const unsigned inbuf_addr = static_cast<unsigned>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) char*)inbuf));
@@ -230,6 +262,20 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
     for (int u = 0; u < 3; ++u) idm[u] = __ballot(tabx[u][2] != 0.0f);
   }
   const int n_tiles = static_cast<int>(p.n_tiles);
+  // CLAIM instances: the workgroup's tile after this one and the one after that (wave-uniform; claimed ids, or the stride's); the
+  // second is known from the view-direction stage of a pass to its end.  `claimed`: wave 4, lane 0 - the id in flight.
+  int next_tile = static_cast<int>(blockIdx.x + gridDim.x), after_next = 0;
+  if constexpr (CLAIM) {
+    if (claim) next_tile = __builtin_amdgcn_readfirstlane(static_cast<int>(claim_lds[0]));   // (behind the prologue's barrier)
+  }
+  unsigned claimed = 0u;
+  auto advance = [&](int tile) {
+    if constexpr (CLAIM) { const int t = next_tile; next_tile = after_next; return t; }
+    else return tile + static_cast<int>(gridDim.x);
+  };
+#ifdef DN_TILE_STAMP
+  int tiles_run = 0;   // (wave-uniform; diagnostic build only)
+#endif
   // The persistent tile loop, compiled once per role (mlp_device.h PipeT::xs_period_begin).  The W = 256 explicit-schedule instances
   // run two copies: a wave picks its own below, once, on the wave-uniform `wave < 4` - a scalar branch taken behind the prologue -
   // and stays in it for all its tiles.  The consumer copy has no fetch step; every MFMA, conversion, LDS read, counted wait and
@@ -237,7 +283,7 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
   auto tile_loop = [&](auto role_c) __attribute__((always_inline)) {
   constexpr int ROLE = decltype(role_c)::value;
   if constexpr (SPLIT) first_reads();
-  for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x, vset = (VSETS == 2 ? vset ^ 1 : (vset == 2 ? 0 : vset + 1))) {
+  for (int tile = blockIdx.x; tile < n_tiles; tile = advance(tile), vset = (VSETS == 2 ? vset ^ 1 : (vset == 2 ? 0 : vset + 1))) {
     // training forward: this wave's three point groups' saved-unit bases and its mask words' (s8-48 layout, mlp_geo48.h) - wave-
     // uniform, kept in scalar registers for the tile; every store adds a small offset (store16_uniform_at)
     const char* act_grp[PT] = {};
@@ -253,7 +299,11 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
     }
     // ---- xyz encoding of this lane's three points, its 16 columns each, into the per-wave LDS stash ----
     // (OVL: only a workgroup's first tile is encoded here; every later one was encoded during the tile before it)
+    // (this workgroup's first tile, whatever the schedule: a claimed id is at least gridDim.x, so no later tile has this id)
     const bool first_tile = tile == static_cast<int>(blockIdx.x);
+#ifdef DN_TILE_STAMP
+    ++tiles_run;
+#endif
     if ((!OVL && !OVX) || first_tile) {
       const int ln = fresh_lane();
       const int j = ln & 15;
@@ -269,7 +319,7 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
         for (int c = 0; c < 7; ++c) in[t][c] = inbuf[c * PPW + t * 16 + j];
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       {
-        const int nxt = tile + gridDim.x;
+        const int nxt = CLAIM ? next_tile : tile + static_cast<int>(gridDim.x);
         if (nxt < n_tiles) issue_inputs(nxt, vset ^ 1);
       }
 #pragma unroll
@@ -464,12 +514,43 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
       }
 #pragma unroll
       for (int t = 0; t < PT; ++t) ped[t] = *reinterpret_cast<const BP8*>(pex_of(pipe.lane16 >> 4) + t * kPieceBytes);
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ped[0]), "+v"(ped[1]), "+v"(ped[2]), "+v"(pipe.af[0]), "+v"(pipe.af[1]), "+v"(pipe.bias_nxt), "+v"(tbl[0]));
+      // CLAIM: claim word 1 - the id of the tile after next, stored by wave 4 at the end of the pass before this one (the first
+      // tile's: in the prologue) - read with the pieces above, behind the same wait
+      unsigned claim_q = 0u;
+      if constexpr (CLAIM) {
+        claim_q = claim_lds[1];
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ped[0]), "+v"(ped[1]), "+v"(ped[2]), "+v"(pipe.af[0]), "+v"(pipe.af[1]), "+v"(pipe.bias_nxt), "+v"(tbl[0]), "+v"(claim_q));
+      } else {
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ped[0]), "+v"(ped[1]), "+v"(ped[2]), "+v"(pipe.af[0]), "+v"(pipe.af[1]), "+v"(pipe.bias_nxt), "+v"(tbl[0]));
+      }
       if constexpr (OVX) {
         // rows 0 - 6 and this tile's view-direction set are free again: the inputs of the tile after next (clamped: a tile that
         // does not exist re-reads this one's, nobody looks at the result)
-        const int t2 = tile + 2 * static_cast<int>(gridDim.x);
+        int t2 = tile + 2 * static_cast<int>(gridDim.x);
+        if constexpr (CLAIM) {
+          if (claim) t2 = __builtin_amdgcn_readfirstlane(static_cast<int>(claim_q));
+          after_next = t2;
+        }
         issue_inputs_flat(t2 < n_tiles ? t2 : tile, vset);
+        if constexpr (CLAIM && ROLE == kXsConsumer) {
+          // wave 4, lane 0 claims the id after that one - unless the workgroup's next tile is already past the end (ids rise: so
+          // would this one be).  One returning atomic add, device scope, on the vector memory path; the lane mask is set and restored
+          // inside the statement (every lane is active here), so the pass stays straight-line code.  Retired by this wave's
+          // next vmcnt(0): the one that begins its next barrier period, at the latest the one at the end of the pass (below).
+          const unsigned m = __builtin_amdgcn_readfirstlane((claim && wave == 4 && next_tile < n_tiles) ? 1u : 0u);
+          const unsigned* ctr = q.tile_counter;
+          const unsigned one = 1u;
+          unsigned c = claimed;
+          asm volatile(
+              "s_mov_b32 exec_lo, %[m]\n\t"
+              "s_mov_b32 exec_hi, 0\n\t"
+              "global_atomic_add %[r], %[a], %[o], off sc0\n\t"
+              "s_mov_b64 exec, -1"
+              : [r] "+v"(c)
+              : [m] "s"(m), [a] "v"(ctr), [o] "v"(one)
+              : "memory");
+          claimed = c;
+        }
         const int ln = fresh_lane();
 #pragma unroll
         for (int t = 0; t < PT; ++t) {
@@ -766,6 +847,25 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
       else heads(ba, bb, std::false_type{});
     }
     }   // !XS
+    if constexpr (CLAIM && ROLE == kXsConsumer) {
+      // the claim of this pass has had the view-direction stage to return (the barrier periods in between began with a vmcnt(0)
+      // each): behind this vmcnt(0) the id is in its register whatever the periods were (the output stores below are younger).
+      // Wave 4, lane 0 hands it on through claim word 1; every wave reads it in front of the next pass's view-direction stage.
+      // (A pass that claimed nothing stores a stale id: it is the last.)
+      unsigned c = claimed;
+      asm volatile("s_waitcnt vmcnt(0)" : "+v"(c) : : "memory");
+      const unsigned id = c + gridDim.x;
+      const unsigned m = __builtin_amdgcn_readfirstlane((claim && wave == 4) ? 1u : 0u);
+      const unsigned word1 = pipe.ring_addr + static_cast<unsigned>(reinterpret_cast<char*>(claim_lds) - smem) + 4u;
+      asm volatile(
+          "s_mov_b32 exec_lo, %[m]\n\t"
+          "s_mov_b32 exec_hi, 0\n\t"
+          "ds_write_b32 %[a], %[v]\n\t"
+          "s_mov_b64 exec, -1"
+          :
+          : [m] "s"(m), [a] "v"(word1), [v] "v"(id)
+          : "memory");
+    }
     const int lo = fresh_lane();
     if constexpr (COMP != 0) {
       // the tile's 384 raw rows go into the xyz stash (dead from the trunk to the next tile's top; one 6 KiB image, point order)
@@ -806,6 +906,19 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
     }
   }
   };   // tile_loop
+#ifdef DN_TILE_STAMP
+  // Diagnostic build only (scripts/tile_stamps.py; in the shipped kernel no stamp executes): when a workgroup begins its first tile and
+  // ends its last, on the 100 MHz clock all XCDs share (s_memrealtime) and on its own shader clock (s_memtime), and which XCD it ran
+  // on.  The record is this workgroup's own, nothing in the kernel reads it and no output is computed from it.  Wave 7 writes it: it
+  // issues no weight DMAs and waits on its vector-memory queue only with vmcnt(0), so a store of its own retires no counted wait early
+  // or late (in a fetching wave the counted waits of the ring would count it).  Plain vector stores from lane 0.
+  unsigned long long* const stamp_rec = q.stamp + static_cast<size_t>(blockIdx.x) * kTileStampWords;
+  const bool stamps = q.stamp != nullptr && wave == WAVES - 1;
+  if (stamps && lane == 0) {
+    stamp_rec[0] = __builtin_amdgcn_s_memrealtime();
+    stamp_rec[1] = __builtin_amdgcn_s_memtime();
+  }
+#endif
   if constexpr (SPLIT) {
     if (wave < 4) tile_loop(std::integral_constant<int, kXsFetcher>{});
     else tile_loop(std::integral_constant<int, kXsConsumer>{});
@@ -813,6 +926,18 @@ __global__ __launch_bounds__(kG48Waves * 64, 2) void mlp_forward48_kernel(FwdPar
     tile_loop(std::integral_constant<int, kXsFetcher>{});
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+#ifdef DN_TILE_STAMP
+  if (stamps && lane == 0) {
+    unsigned xcc;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(xcc));
+    stamp_rec[2] = __builtin_amdgcn_s_memrealtime();
+    stamp_rec[3] = __builtin_amdgcn_s_memtime();
+    stamp_rec[4] = xcc;
+    stamp_rec[5] = static_cast<unsigned>(tiles_run);
+    stamp_rec[6] = gridDim.x;
+    stamp_rec[7] = static_cast<unsigned>(n_tiles);
+  }
+#endif
   if constexpr (F == 2) {
     const bool out_of_range = (trk & 0xFFFFu) >= 0x7C00u || (trk >> 16) >= 0x7C00u;
     if (p.range_flag != nullptr && __ballot(out_of_range) != 0ull && (threadIdx.x & 63) == 0) atomicAdd(p.range_flag, 1u);

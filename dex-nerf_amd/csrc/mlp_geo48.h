@@ -49,7 +49,21 @@ struct G48Params {
   int bias_bytes;    // bias rows (padded to 1 KiB); the tables follow, then the pieces
   int total_pieces;
   CompParams comp;   // the instances that composite their own rays (COMP): where the maps go; otherwise unread
+  // not NULL (the W = 256 render instances that encode tile t + 1 inside tile t, launched by a render driver): a zeroed word of the
+  // caller's from which the workgroups claim their tiles after the first - id = gridDim.x + the value an atomic add returns - instead
+  // of striding by gridDim.x (mlp_fused48_kernel.h, "claimed tiles").  NULL, and every other instance: the fixed stride.
+  unsigned* tile_counter;
+#ifdef DN_TILE_STAMP
+  // diagnostic build only (scripts/tile_stamps.py; never in the shipped library): this launch's record array, kTileStampWords 64-bit
+  // words per workgroup, which nothing else reads - see the stamps around tile_loop (mlp_fused48_kernel.h)
+  unsigned long long* stamp;
+#endif
 };
+// a workgroup's stamp record: [0] s_memrealtime and [1] s_memtime at the top of its first tile, [2] / [3] the same behind its last,
+// [4] HW_REG_XCC_ID, [5] tiles it ran, [6] gridDim.x, [7] n_tiles
+constexpr int kTileStampWords = 8;
+constexpr int kTileStampMaxWgs = 1024;
+constexpr int kTileStampLaunches = 4;   // the records of the last four launches are kept (a render: coarse, then fine)
 
 
 // NetLayout reused with 16-row tiles: n_tiles / bias0 count 16-row tiles, pieces_per_tile counts 32-deep pieces.
@@ -98,6 +112,10 @@ inline size_t g48_lds_bytes(const NetLayout& L) {
   return static_cast<size_t>(kRingBytes) + L.bias_bytes + kG48TableBytes + kG48Waves * 3 * kG48XyzPieces * kPieceBytes +
          kG48Waves * kG48InRows * kG48PointsPerWave * sizeof(float);
 }
+
+// the instances that can claim tiles keep two claimed ids in LDS behind the input rows (their launch adds these bytes: the paper
+// network's layout leaves 1 KiB of the 160)
+constexpr int kG48ClaimBytes = 16;
 
 // bf16 / fp16 nets whose bias rows leave room for the stash in 160 KiB of LDS (W = 256: D <= 9 with view directions)
 inline bool g48_supported(const dn_mlp_desc& d, int precision) {
@@ -350,14 +368,19 @@ inline G48Pick g48_pick(const dn_mlp_desc& d, int precision, const FwdParams& p,
   return (paper || shipped) ? fixed(0, 0, 0) : run_time(0);
 }
 
+// the instances whose workgroups can claim tiles from a counter (mlp_fused48_kernel.h CLAIM): the paper network's render instances
+// that encode tile t + 1 inside tile t - what a render of rays + depths runs
+inline bool g48_claims(const G48Key& k) { return k.W == 256 && k.DC > 0 && k.VIEWC != 0 && k.SAVE == 0 && k.OVLP == 2 && k.COMP == 0; }
+
 // b != NULL: two networks of one architecture (bf16; the coarse and the fine net of a training step) in one launch
 int launch_pack48(const dn_mlp_desc& d, int precision, const PackPtrs& a, char* region_a, hipStream_t stream, bool density = false,
                   const PackPtrs* b = nullptr, char* region_b = nullptr);
 // comp != NULL: the caller would like the launch to composite its rays itself (rays + depths input, no density noise); *composited
 // says whether it did (the fixed-shape instances, samples per ray dividing the 384-point workgroup tile) - if not, `out` holds the
 // raw radiance field as always and the caller runs the compositing kernel
+// tile_counter != NULL: a zeroed word from which the workgroups claim their tiles, if the picked instance can (g48_claims)
 int launch_forward48(const dn_mlp_desc& d, int precision, const FwdParams& p, const char* region, hipStream_t stream,
-                     const CompParams* comp = nullptr, int* composited = nullptr);
+                     const CompParams* comp = nullptr, int* composited = nullptr, unsigned* tile_counter = nullptr);
 int backward48_entry(const dn_mlp_desc* desc, const void* packed_bwd, const float* g_out, const void* masks, int64_t n_points,
                      void* grads, float grad_scale, hipStream_t stream, const unsigned* partials = nullptr, int n_partials = 0);   // mlp_train48.hip
 int unpack48_entry(const dn_mlp_desc* desc, int which, const void* native, int64_t n_points, int slot, int width, int kind, float* out,

@@ -107,7 +107,9 @@ inline long long persistent_grid(long long n_tiles, int cus = device_cus()) { re
 
 int setup_params(const dn_mlp_desc* desc, int precision, const void* packed, FwdParams* p);
 struct CompParams;
-int dispatch_forward(const dn_mlp_desc& d, int precision, FwdParams& p, hipStream_t stream, const CompParams* comp = nullptr, int* composited = nullptr);
+// tile_counter: a zeroed device word of the caller's for the instances that claim their tiles (mlp_geo48.h G48Params); NULL = fixed stride
+int dispatch_forward(const dn_mlp_desc& d, int precision, FwdParams& p, hipStream_t stream, const CompParams* comp = nullptr, int* composited = nullptr,
+                     unsigned* tile_counter = nullptr);
 int launch_pack(const NetLayout& L, const PackPtrs& ptrs, void* packed, int precision, hipStream_t stream, bool density = false);
 void fill_freqs(float* f, int num_fns, int log_sampling);  // rays_sampling.hip
 
