@@ -8,6 +8,9 @@ opacity-quantile depth maps (0.5: the median depth) to the same render and the s
 `--normals` renders density-gradient surface normals (nerf.render_dex_normals) instead: normal_<view>.npy holds the expected normal
 (H,W,3) (not renormalised: its length is a confidence), normal_<view>.png shows (n/|n| + 1)/2, black where n = 0; with `--m-thres M` the
 same pair per threshold, dex_normal_<view>_m<threshold>.npy / .png - the normal at the sample the Dex depth reports.
+`--mesh OUT.ply --mesh-bounds=x0,y0,z0,x1,y1,z1 --mesh-resolution N[,N,N] --mesh-thres T` renders nothing: it extracts the Dex threshold
+surface {sigma > T} of the fine network (the coarse one without a fine network) as a triangle mesh with vertex normals
+(nerf.extract_dex_mesh) and writes it as a binary PLY.
 
     python dex-nerf_amd/eval_nerf.py --checkpoint ckpt.ckpt --size 400 --views 8 --precision fp16 --savedir out/
 
@@ -68,6 +71,13 @@ def main(argv=None):
     ap.add_argument("--normals", action="store_true",
                     help="render surface normals only (nerf.render_dex_normals: the density gradient at the samples, composited like the "
                          "depth; with --m-thres also the normal at every Dex depth); not with --precision fp16")
+    ap.add_argument("--mesh", default="", metavar="OUT.ply",
+                    help="extract the Dex threshold surface of the fine network (the coarse one without a fine network) as a triangle mesh "
+                         "with vertex normals (nerf.extract_dex_mesh) and write it as a binary PLY instead of rendering; needs "
+                         "--mesh-bounds and --mesh-thres; not with --precision fp16")
+    ap.add_argument("--mesh-bounds", default="", metavar="x0,y0,z0,x1,y1,z1", help="--mesh: the box the grid spans, in the network's input space (write --mesh-bounds=-1,... when it starts with a minus)")
+    ap.add_argument("--mesh-resolution", default="128", metavar="N[,N,N]", help="--mesh: grid points per axis (one number, or nx,ny,nz)")
+    ap.add_argument("--mesh-thres", type=float, default=None, metavar="T", help="--mesh: the Dex threshold m_thres on the raw density")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"])
     ap.add_argument("--savedir", default="")
     ap.add_argument("--quiet", action="store_true")
@@ -95,6 +105,26 @@ def main(argv=None):
         ap.error("--normals is a render of its own: not with --depth-only or --apply-exposure")
     if args.apply_exposure and (not args.use_refined_poses or args.depth_only):
         ap.error("--apply-exposure corrects the colours of training views: it needs --use-refined-poses and no --depth-only")
+    mesh_bounds = mesh_res = None
+    if args.mesh:
+        if args.precision == "fp16":
+            ap.error("--mesh samples the density on the kernels of the density gradient, which exist for fp32 and bf16: not with --precision fp16")
+        if args.depth_only or args.normals or args.apply_exposure or args.use_refined_poses:
+            ap.error("--mesh is an extraction of its own: not with --depth-only, --normals, --use-refined-poses or --apply-exposure")
+        try:
+            mesh_bounds = [float(v) for v in args.mesh_bounds.split(",") if v.strip()]
+            mesh_res = [int(v) for v in args.mesh_resolution.split(",") if v.strip()]
+        except ValueError as e:
+            ap.error(f"--mesh-bounds / --mesh-resolution: {e}")
+        if len(mesh_bounds) != 6 or len(mesh_res) not in (1, 3) or min(mesh_res) < 2:
+            ap.error("--mesh needs --mesh-bounds x0,y0,z0,x1,y1,z1 and --mesh-resolution N or nx,ny,nz with at least 2 points per axis")
+        if not all(np.isfinite(mesh_bounds)) or any(mesh_bounds[a + 3] <= mesh_bounds[a] for a in range(3)):
+            ap.error("--mesh-bounds: x1 > x0, y1 > y0, z1 > z0, all finite")
+        if args.mesh_thres is None or not np.isfinite(np.float32(args.mesh_thres)):
+            ap.error("--mesh needs a finite --mesh-thres")
+        mesh_res = mesh_res * 3 if len(mesh_res) == 1 else mesh_res
+    elif args.mesh_bounds or args.mesh_thres is not None:
+        ap.error("--mesh-bounds / --mesh-thres belong to --mesh")
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     nerf.set_precision(args.precision)
     ck = torch.load(args.checkpoint, map_location="cpu")
@@ -112,6 +142,21 @@ def main(argv=None):
                             nerf=dict(use_viewdirs=coarse.use_viewdirs, train=dict(mode), validation=dict(mode))))
     ex = nerf.get_embedding_function(coarse.num_encoding_fn_xyz, True, True)
     ed = nerf.get_embedding_function(coarse.num_encoding_fn_dir, True, True) if coarse.use_viewdirs else None
+    if args.mesh:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            mesh = nerf.extract_dex_mesh(fine if fine is not None else coarse, ex, mesh_bounds, mesh_res, args.mesh_thres)
+        torch.cuda.synchronize()
+        seconds = time.perf_counter() - t0
+        if os.path.dirname(args.mesh):
+            os.makedirs(os.path.dirname(args.mesh), exist_ok=True)
+        nerf.save_ply(args.mesh, mesh)
+        if not args.quiet:
+            print(f"mesh: {mesh.vertices.shape[0]} vertices, {mesh.triangles.shape[0]} triangles at m_thres {args.mesh_thres:g} on a "
+                  f"{mesh_res[0]}x{mesh_res[1]}x{mesh_res[2]} grid ({mesh.n_nonfinite} non-finite samples) in {seconds:.3f} s -> {args.mesh}",
+                  flush=True)
+        return dict(mesh=mesh, seconds=seconds, n_vertices=int(mesh.vertices.shape[0]), n_triangles=int(mesh.triangles.shape[0]))
     thres = np.arange(5, args.m_thres + 5, 5) if args.m_thres > 0 else None
     k_mat = torch.from_numpy(syn.intrinsic(size, size)).to(dev)
     if "focal_length" in ck:

@@ -60,6 +60,11 @@ NORMALS_EXPORTS = ("dn_composite_normals", "dn_render_normals_workspace_bytes", 
 QUANTILE_EXPORTS = ("dn_composite_density_quantiles", "dn_render_rays_depth_quantiles")
 MAX_QUANTILES = 64   # DN_MAX_QUANTILES
 
+# include/dexnerf_hip_mesh.h: the Dex threshold surface of a sampled density field as a triangle mesh (nerf.extract_dex_mesh)
+MESH_EXPORTS = ("dn_isosurface_workspace_bytes", "dn_isosurface_count", "dn_isosurface_emit")
+ISO_SCAN_BLOCK = 1024               # DN_ISO_SCAN_BLOCK: elements per workgroup at each of the three scan levels
+ISO_MAX_GRID_VERTICES = 1 << 28     # DN_ISO_MAX_GRID_VERTICES
+
 
 class MlpDesc(ctypes.Structure):
     """dn_mlp_desc (mirrors FlexibleNeRFModel.__init__, reference nerf/models.py:186-196)."""
@@ -224,6 +229,13 @@ def _declare(lib):
     lib.dn_composite_density_quantiles.restype = c_int
     lib.dn_render_rays_depth_quantiles.argtypes = lib.dn_render_rays_depth.argtypes[:-2] + [fp, c_int, c_int, fp, vp, vp]
     lib.dn_render_rays_depth_quantiles.restype = c_int
+    # the mesh header
+    lib.dn_isosurface_workspace_bytes.argtypes = [c_int, c_int, c_int]
+    lib.dn_isosurface_workspace_bytes.restype = c_size_t
+    lib.dn_isosurface_count.argtypes = [fp, c_int, fp, fp, fp, c_int, c_int, c_int, c_float, vp, vp, vp]
+    lib.dn_isosurface_count.restype = c_int
+    lib.dn_isosurface_emit.argtypes = [fp, c_int, fp, fp, fp, c_int, c_int, c_int, c_float, vp, c_int64, c_int64, fp, vp, vp]
+    lib.dn_isosurface_emit.restype = c_int
 
 
 def lib():

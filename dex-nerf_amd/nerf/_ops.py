@@ -1686,3 +1686,89 @@ def camera_records_backward(g_cams, xi, phi, e0, k, intrinsics_scale=1.0, pose_m
                                            ptr(pose_mask), n_views, ptr(g_out), ptr(keep), ptr(out_phi), ptr(keep_phi), ptr(scratch), nbytes,
                                            stream()), "dn_camera_records_backward")
     return out, out_phi
+
+
+# ---- the Dex threshold surface as a triangle mesh (include/dexnerf_hip_mesh.h) ----------------------------------------------------------
+def check_isosurface_grid(xs, ys, zs, level, who="isosurface"):
+    """The host-side rule of the grid and the level (the C layer cannot read device memory, and takes the level by value): the level
+    finite as fp32, every axis a 1-D fp32 tensor of >= 2 finite, strictly increasing coordinates.  Returns the level as the Python
+    float of its fp32 value.  Raises ValueError before any GPU work."""
+    level = float(level)
+    l32 = ctypes.c_float(level).value if math.isfinite(level) else level
+    if not math.isfinite(l32):
+        raise ValueError(f"{who}: the level must be finite as fp32, got {level!r}")
+    for name, c in (("xs", xs), ("ys", ys), ("zs", zs)):
+        if not (torch.is_tensor(c) and c.dim() == 1 and c.dtype == torch.float32 and c.numel() >= 2):
+            raise ValueError(f"{who}: {name} must be a 1-D fp32 tensor of at least 2 coordinates")
+        h = c.detach().cpu()
+        if not (bool(torch.isfinite(h).all()) and bool((h[1:] > h[:-1]).all())):
+            raise ValueError(f"{who}: {name} must be finite and strictly increasing")
+    return l32
+
+
+class IsosurfaceCount:
+    """What dn_isosurface_count leaves behind: the arguments, the workspace the scans filled and the device record `counts`
+    (int32 x 4: n_vertices, n_triangles, n_nonfinite, 0) - isosurface_emit's input."""
+
+    def __init__(self, field, stride, xs, ys, zs, level, workspace, counts):
+        self.field, self.stride, self.xs, self.ys, self.zs, self.level = field, stride, xs, ys, zs, level
+        self.workspace, self.counts = workspace, counts
+
+    def totals(self):
+        """(n_vertices, n_triangles, n_nonfinite) on the host: the one read a data-dependent output size needs."""
+        return tuple(int(c) for c in self.counts[:3].tolist())
+
+    def _grid_args(self):
+        return (c_void_p(self.field.data_ptr()), self.stride, ptr(self.xs), ptr(self.ys), ptr(self.zs), self.xs.numel(), self.ys.numel(),
+                self.zs.numel(), self.level, ptr(self.workspace))
+
+
+def isosurface_count(field, xs, ys, zs, level):
+    """dn_isosurface_count on field (nx,ny,nz) fp32 - dense, or a view whose strides are (ny*nz*s, nz*s, s) floats such as column 3 of
+    the network's (P,4) rows (s = 4), which is read in place - over the grid xs (nx), ys (ny), zs (nz) -> IsosurfaceCount."""
+    level = check_isosurface_grid(xs, ys, zs, level, "isosurface")
+    if not (torch.is_tensor(field) and field.dim() == 3 and tuple(field.shape) == (xs.numel(), ys.numel(), zs.numel())):
+        raise ValueError("isosurface: the field must be (nx, ny, nz) for the coordinate tensors xs (nx), ys (ny), zs (nz)")
+    for t in (field, xs, ys, zs):
+        if not t.is_cuda:
+            raise RuntimeError("isosurface: the extraction runs on the ROCm device only (got a host tensor); move the inputs to 'cuda'")
+    nx, ny, nz = field.shape
+    s = field.stride(2)
+    if not (field.dtype == torch.float32 and 1 <= s < 2 ** 31 and field.stride() == (ny * nz * s, nz * s, s)):
+        field, s = f32c(field), 1
+    xs, ys, zs = xs.contiguous(), ys.contiguous(), zs.contiguous()
+    nbytes = int(lib().dn_isosurface_workspace_bytes(nx, ny, nz))
+    if nbytes == 0:
+        raise ValueError(f"isosurface: a {nx} x {ny} x {nz} grid is past the extraction's maximum ({_hip.ISO_MAX_GRID_VERTICES} grid "
+                         "vertices, 12 * cells < 2^31)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=field.device)
+    out = IsosurfaceCount(field, int(s), xs, ys, zs, level, ws, torch.empty(4, dtype=torch.int32, device=field.device))
+    check(lib().dn_isosurface_count(*out._grid_args(), ptr(out.counts), stream()), "dn_isosurface_count")
+    return out
+
+
+def isosurface_emit(counted, max_vertices, max_triangles, vertices=None, triangles=None):
+    """dn_isosurface_emit on an IsosurfaceCount: rows below the capacities are written into `vertices` (>= max_vertices, 3) fp32 and
+    `triangles` (>= max_triangles, 3) int32 (allocated at the capacities when not given) -> (vertices, triangles)."""
+    dev = counted.field.device
+    max_vertices, max_triangles = int(max_vertices), int(max_triangles)
+    if vertices is None:
+        vertices = torch.empty((max(max_vertices, 0), 3), dtype=torch.float32, device=dev)
+    if triangles is None:
+        triangles = torch.empty((max(max_triangles, 0), 3), dtype=torch.int32, device=dev)
+    assert vertices.dtype == torch.float32 and vertices.shape[0] >= max_vertices and vertices.shape[1:] == (3,)
+    assert triangles.dtype == torch.int32 and triangles.shape[0] >= max_triangles and triangles.shape[1:] == (3,)
+    check(lib().dn_isosurface_emit(*counted._grid_args(), max_vertices, max_triangles, ptr(vertices) if max_vertices > 0 else None,
+                                   ptr(triangles) if max_triangles > 0 else None, stream()), "dn_isosurface_emit")
+    return vertices, triangles
+
+
+def isosurface(field, xs, ys, zs, level):
+    """The surface {f > level} of a sampled field as an indexed triangle mesh (marching tetrahedra on the Kuhn triangulation of the
+    grid; the definition, the vertex and triangle order and the orientation - normals toward decreasing f - are those of
+    include/dexnerf_hip_mesh.h) -> (vertices (V,3) fp32, triangles (T,3) int32, n_nonfinite).  One host read between count and emit
+    sizes the outputs; an empty surface gives (0,3) tensors."""
+    counted = isosurface_count(field, xs, ys, zs, level)
+    n_v, n_t, n_bad = counted.totals()
+    vertices, triangles = isosurface_emit(counted, n_v, n_t)
+    return vertices, triangles, n_bad

@@ -571,3 +571,110 @@ def render_dex_normals(height, width, focal_length, model_coarse, model_fine, ra
         maps = _to_image(maps, [flat, flat, vec] + [flat] * len(thres) + [vec] * len(thres))
     k = len(thres)
     return DexNormals(maps[0], maps[1], maps[2], tuple(maps[3:3 + k]), tuple(maps[3 + k:3 + 2 * k]))
+
+
+# ---- the Dex threshold surface as a triangle mesh -------------------------------------------------------------------------------------
+DexMesh = collections.namedtuple("DexMesh", "vertices triangles normals n_nonfinite")
+
+
+def _grid_axes(bounds, resolution, who):
+    """bounds (x0,y0,z0,x1,y1,z1) and resolution N | (nx,ny,nz) -> three host fp32 coordinate tensors (float64 linspace, rounded once),
+    checked by the rule of the extraction (finite, strictly increasing, >= 2 per axis)."""
+    b = [float(v) for v in bounds]
+    res = [int(resolution)] * 3 if isinstance(resolution, (int, np.integer)) else [int(r) for r in resolution]
+    if len(b) != 6 or len(res) != 3:
+        raise ValueError(f"{who}: bounds are (x0, y0, z0, x1, y1, z1) and resolution is N or (nx, ny, nz)")
+    if min(res) < 2 or not all(np.isfinite(b)):
+        raise ValueError(f"{who}: needs finite bounds and at least 2 grid points per axis")
+    axes = [torch.from_numpy(np.linspace(b[a], b[a + 3], res[a]).astype(np.float32)) for a in range(3)]
+    _ops.check_isosurface_grid(*axes, 0.0, who)
+    return axes
+
+
+def _density_pack(model, encode_position_fn, who):
+    """The guards of density_gradient, then the density pack in nerf.set_precision's mode."""
+    prec = _normals_precision(who)
+    if _wants_grad(model):
+        raise RuntimeError(f"{who} is a no-grad evaluation: call it under torch.no_grad() (or with parameters that do not require grad)")
+    _require_density_net(model, encode_position_fn, who)
+    return model.packed_density(encode_position_fn.log_sampling, True, precision=prec)
+
+
+def density_grid(model, encode_position_fn, bounds, resolution, max_points=1 << 24):
+    """The network's RAW density (before noise and ReLU: what the Dex readout compares with m_thres) on a regular grid:
+    (field (nx,ny,nz) fp32, xs (nx), ys (ny), zs (nz)) on the model's device, field[i,j,k] = sigma_raw(xs[i], ys[j], zs[k]).  bounds =
+    (x0, y0, z0, x1, y1, z1), resolution = N or (nx, ny, nz); the coordinates are float64 linspaces rounded to fp32 once, end points
+    included.  The density pack (FlexibleNeRFModel.packed_density) runs through dn_run_network on explicit points - every grid point
+    fed to the network is bit-exactly (xs[i], ys[j], zs[k]) - in slabs of at most `max_points` points written into one dense field; points
+    are independent, so the field does not depend on the slabs.  The grid lives in the network's input space: world space, or NDC
+    space for forward-facing scenes; nothing converts it.  Runs in nerf.set_precision's mode, 'fp32' or bf16; 'fp16' raises, as in
+    density_gradient.  No-grad only, device tensors only, networks the fused kernels cover only: anything else raises."""
+    pack = _density_pack(model, encode_position_fn, "density_grid")
+    max_points = int(max_points)
+    if max_points < 1:
+        raise ValueError("density_grid: max_points must be at least 1")
+    dev = model.layer1.weight.device
+    xs, ys, zs = (a.to(dev) for a in _grid_axes(bounds, resolution, "density_grid"))
+    nx, ny, nz = xs.numel(), ys.numel(), zs.numel()
+    total = nx * ny * nz
+    field = torch.empty(total, dtype=torch.float32, device=dev)
+    with torch.no_grad():
+        for p0 in range(0, total, max_points):
+            idx = torch.arange(p0, min(p0 + max_points, total), dtype=torch.int64, device=dev)
+            plane = torch.div(idx, nz, rounding_mode="floor")
+            pts = torch.stack([xs[torch.div(plane, ny, rounding_mode="floor")], ys[plane % ny], zs[idx % nz]], dim=-1)
+            field[p0:p0 + pts.shape[0]] = _ops.run_network_pts(pack, pts, None, 1)[:, 3]
+    return field.view(nx, ny, nz), xs, ys, zs
+
+
+def extract_dex_mesh(model, encode_position_fn, bounds, resolution, m_thres, normals=True, max_points=1 << 24):
+    """The Dex surface as one object: the boundary of {x : sigma_raw(x) > m_thres} - the region whose samples the Dex depth readout
+    calls "hit" - as an indexed, watertight, consistently oriented triangle mesh, DexMesh(vertices (V,3) fp32, triangles (T,3) int32,
+    normals (V,3) fp32 | None, n_nonfinite).  density_grid samples the field, _ops.isosurface extracts it on the device (marching
+    tetrahedra; the definition, the fixed vertex and triangle order and the orientation - geometric normals toward decreasing density
+    - are those of include/dexnerf_hip_mesh.h).  normals=True adds the analytic vertex normals -g/|g| with g = d sigma_raw / d x at
+    the vertices (_ops.density_gradient, in chunks), by composite_normals' conventions: |g| formed in fp64, the zero vector where |g| is
+    zero or not finite.  n_nonfinite counts the grid samples that were not finite (they emit nothing).  The mesh lives in the network's
+    input space: world space, or NDC space for forward-facing scenes; nothing converts it.  An empty surface is a valid result: (0,3)
+    tensors.  Precision and guards as density_grid; other thresholds on the same field: call _ops.isosurface on density_grid's result."""
+    level = float(m_thres)
+    if not np.isfinite(np.float32(level)):
+        raise ValueError(f"extract_dex_mesh: m_thres must be finite as fp32, got {m_thres!r}")
+    pack = _density_pack(model, encode_position_fn, "extract_dex_mesh")
+    field, xs, ys, zs = density_grid(model, encode_position_fn, bounds, resolution, max_points=max_points)
+    vertices, triangles, n_bad = _ops.isosurface(field, xs, ys, zs, level)
+    vertex_normals = None
+    if normals:
+        streams = model.packed_density_grad(encode_position_fn.log_sampling, True, precision=pack.precision)
+        parts = [_ops.density_gradient(pack, streams, pts=batch)[1] for batch in get_minibatches(vertices, chunksize=1 << 16)]
+        g = (torch.cat(parts, dim=0) if parts else vertices.new_zeros((0, 3))).double()
+        length = torch.sqrt(g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1] + g[:, 2] * g[:, 2])
+        ok = torch.isfinite(length) & (length > 0)
+        vertex_normals = torch.where(ok[:, None], -g / torch.where(ok, length, torch.ones_like(length))[:, None], torch.zeros_like(g)).float()
+    return DexMesh(vertices, triangles, vertex_normals, n_bad)
+
+
+def save_ply(path, mesh):
+    """Binary little-endian PLY of a DexMesh (or anything with .vertices (V,3), .triangles (T,3) and optional .normals (V,3); tensors
+    or arrays): x y z [nx ny nz] as float32, faces as a uchar count and three int32 indices.  Host code, no dependency."""
+    def host(a):
+        return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    v = np.ascontiguousarray(host(mesh.vertices), dtype="<f4").reshape(-1, 3)
+    t = np.ascontiguousarray(host(mesh.triangles), dtype="<i4").reshape(-1, 3)
+    n = getattr(mesh, "normals", None)
+    props = ["x", "y", "z"]
+    if n is not None:
+        n = np.ascontiguousarray(host(n), dtype="<f4").reshape(-1, 3)
+        if n.shape != v.shape:
+            raise ValueError("save_ply: normals must match the vertices")
+        v = np.concatenate([v, n], axis=1)
+        props += ["nx", "ny", "nz"]
+    header = ["ply", "format binary_little_endian 1.0", "comment Dex threshold surface", f"element vertex {len(v)}"]
+    header += [f"property float {p}" for p in props]
+    header += [f"element face {len(t)}", "property list uchar int vertex_indices", "end_header"]
+    faces = np.empty(len(t), dtype=[("n", "u1"), ("v", "<i4", (3,))])
+    faces["n"], faces["v"] = 3, t
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(header) + "\n").encode("ascii"))
+        fh.write(v.astype("<f4").tobytes())
+        fh.write(faces.tobytes())
