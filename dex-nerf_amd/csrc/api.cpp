@@ -52,63 +52,50 @@ int device_cus() {
 
 static size_t align256(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
 
+// Every workspace is a run of regions, each rounded up to 256 bytes; a NULL base carves nothing and only counts (the *_bytes answers)
+struct Carver {
+  void* base;
+  size_t off = 0;
+  void* take(size_t bytes) {
+    void* p = base ? static_cast<void*>(static_cast<char*>(base) + off) : nullptr;
+    off += align256(bytes);
+    return p;
+  }
+  float* floats(size_t count) { return static_cast<float*>(take(count * sizeof(float))); }
+};
+
 struct Workspace {
   float *z_c, *rf_c, *w_c, *z_f, *rf_f, *g_rf;
   unsigned* absmax_part;   // training: one word per workgroup of the compositing backward (largest |gradient| it stored)
   unsigned* status;   // the last 256 bytes: word 0 = non-finite raw radiance-field values met by this call's compositing
   size_t bytes;
 };
+// kDepth: dn_render_rays_depth's and the normal render's - depths and raw rows only, the coarse weights stay inside
+// density_resample_kernel (no w_c region); kTrain: the render's regions, then g_rf and absmax_part
+enum WorkspaceKind { kRender, kTrain, kDepth };
 // Words of the status block (zeroed by the one hipMemsetAsync at the top of a render call): 0 and 1 are what Python reads and sums
 // (non-finite count, fp16 range flag).  dn_render_rays hands two more to its network launches as tile counters (mlp_geo48.h
 // G48Params::tile_counter), 64 bytes apart: the coarse launch's and the fine launch's.  The depth, quantile and normal renders run the
 // density instances, which do not claim tiles: they pass none.
 constexpr int kStatusTilesCoarse = 16, kStatusTilesFine = 32;
 
-static Workspace carve(void* base, int64_t n, int nc, int nf, bool train = false) {
+static Workspace carve(void* base, int64_t n, int nc, int nf, WorkspaceKind kind = kRender) {
   Workspace w{};
-  size_t off = 0;
-  auto take = [&](size_t floats) {
-    float* p = base ? reinterpret_cast<float*>(static_cast<char*>(base) + off) : nullptr;
-    off += align256(floats * sizeof(float));
-    return p;
-  };
-  w.z_c = take(static_cast<size_t>(n) * nc);
-  w.rf_c = take(static_cast<size_t>(n) * nc * 4);
-  w.w_c = take(static_cast<size_t>(n) * nc);
+  Carver c{base};
+  const size_t rays = static_cast<size_t>(n);
+  w.z_c = c.floats(rays * nc);
+  w.rf_c = c.floats(rays * nc * 4);
+  if (kind != kDepth) w.w_c = c.floats(rays * nc);
   if (nf > 0) {
-    w.z_f = take(static_cast<size_t>(n) * (nc + nf));
-    w.rf_f = take(static_cast<size_t>(n) * (nc + nf) * 4);
+    w.z_f = c.floats(rays * (nc + nf));
+    w.rf_f = c.floats(rays * (nc + nf) * 4);
   }
-  if (train) w.g_rf = take(static_cast<size_t>(n) * (nc + nf) * 4);   // d loss / d raw radiance field, one network at a time
-  if (train) w.absmax_part = reinterpret_cast<unsigned*>(take(static_cast<size_t>((n + 3) / 4)));
-  w.status = reinterpret_cast<unsigned*>(take(64));
-  w.bytes = off;
-  return w;
-}
-
-// dn_render_rays_depth: depths and raw rows only - the coarse weights stay inside density_resample_kernel
-struct DepthWorkspace {
-  float *z_c, *rf_c, *z_f, *rf_f;
-  unsigned* status;   // the last 256 bytes, as in Workspace
-  size_t bytes;
-};
-
-static DepthWorkspace carve_depth(void* base, int64_t n, int nc, int nf) {
-  DepthWorkspace w{};
-  size_t off = 0;
-  auto take = [&](size_t floats) {
-    float* p = base ? reinterpret_cast<float*>(static_cast<char*>(base) + off) : nullptr;
-    off += align256(floats * sizeof(float));
-    return p;
-  };
-  w.z_c = take(static_cast<size_t>(n) * nc);
-  w.rf_c = take(static_cast<size_t>(n) * nc * 4);
-  if (nf > 0) {
-    w.z_f = take(static_cast<size_t>(n) * (nc + nf));
-    w.rf_f = take(static_cast<size_t>(n) * (nc + nf) * 4);
+  if (kind == kTrain) {
+    w.g_rf = c.floats(rays * (nc + nf) * 4);   // d loss / d raw radiance field, one network at a time
+    w.absmax_part = static_cast<unsigned*>(c.take(static_cast<size_t>((n + 3) / 4) * sizeof(unsigned)));
   }
-  w.status = reinterpret_cast<unsigned*>(take(64));
-  w.bytes = off;
+  w.status = static_cast<unsigned*>(c.take(256));
+  w.bytes = c.off;
   return w;
 }
 
@@ -122,18 +109,53 @@ struct RegWorkspace {
 
 static RegWorkspace carve_reg(void* base, int64_t n, int nc, int nf) {
   RegWorkspace w{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    void* p = base ? static_cast<void*>(static_cast<char*>(base) + off) : nullptr;
-    off += align256(bytes);
-    return p;
-  };
+  Carver c{base};
   const size_t samples = static_cast<size_t>(n) * (nc + nf);
-  w.weights = static_cast<float*>(take(samples * sizeof(float)));
-  w.g_weights = static_cast<float*>(take(samples * sizeof(float)));
-  w.ray_loss = static_cast<double*>(take(static_cast<size_t>(n) * sizeof(double)));
-  w.bytes = off;
+  w.weights = c.floats(samples);
+  w.g_weights = c.floats(samples);
+  w.ray_loss = static_cast<double*>(c.take(static_cast<size_t>(n) * sizeof(double)));
+  w.bytes = c.off;
   return w;
+}
+
+// ---- what the density renders (depth, quantile depth, normals) share: refusals, the status block, the passes before the last ----------
+// The refusals every density render makes before any GPU work, under the entry point's name; `extras`: whether the entry point's own
+// required pointers are there (they belong to its "bad arguments").  The "thresholds given without ..." line differs: it follows in
+// the caller.
+static int check_density_render(const char* who, const dn_mlp_desc* desc_coarse, const void* packed_coarse, const dn_mlp_desc* desc_fine,
+                                const void* packed_fine, const float* rays, int ray_stride, int64_t n_rays, int num_coarse, int num_fine,
+                                int n_thres, const void* workspace, bool extras = true) {
+  DN_REQUIRE(desc_coarse && packed_coarse && extras && rays && workspace && n_rays >= 0, "%s: bad arguments", who);
+  DN_REQUIRE(num_coarse >= 1 && num_fine >= 0 && ray_stride >= 8, "%s: bad sample counts / ray stride", who);
+  DN_REQUIRE(num_fine == 0 || (desc_fine && packed_fine), "%s: fine pass requested without a fine net", who);
+  DN_REQUIRE(n_thres >= 0, "%s: negative threshold count", who);
+  DN_REQUIRE(!desc_coarse->use_viewdirs && (num_fine == 0 || !desc_fine->use_viewdirs),
+             "%s: takes density sub-networks (dn_mlp_density_desc / dn_mlp_pack_density): use_viewdirs must be 0", who);
+  DN_REQUIRE(num_fine == 0 || (num_coarse >= 10 && num_coarse <= 512 && num_coarse + num_fine <= 2048),
+             "%s: need 10 <= num_coarse <= 512 and num_coarse + num_fine <= 2048", who);
+  DN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "%s: workspace must be 256-byte aligned", who);
+  return 0;
+}
+
+static int zero_status(const char* who, unsigned* status, dn_stream_t stream) {
+  hipError_t e = hipMemsetAsync(status, 0, 256, as_stream(stream));
+  if (e != hipSuccess) { set_error("%s: hipMemsetAsync: %s", who, hipGetErrorString(e)); return -static_cast<int>(e); }
+  return 0;
+}
+
+// The passes before the last one, into a kDepth workspace: the coarse depths and, with a fine pass, the coarse density network and its
+// compositing fused with the resampling (w.z_f; depth_c / acc_c).  Without a fine pass the coarse network IS the last pass: the caller's.
+static int density_coarse_pass(const dn_mlp_desc* desc_coarse, const void* packed_coarse, int precision, const float* rays, int ray_stride,
+                               int64_t n_rays, int num_coarse, int num_fine, int lindisp, float noise_std, const float* t_rand,
+                               const float* noise_c, const float* u, float* depth_c, float* acc_c, const Workspace& w, dn_stream_t stream) {
+  int rc;
+  if ((rc = dn_coarse_depths(rays, ray_stride, n_rays, num_coarse, lindisp, t_rand, w.z_c, stream))) return rc;
+  if (num_fine == 0) return 0;
+  if ((rc = run_network_flagged(desc_coarse, precision, packed_coarse, nullptr, nullptr, rays, ray_stride, w.z_c, n_rays, num_coarse, w.rf_c,
+                                w.status + 1, stream)))
+    return rc;
+  return density_resample_counting(w.rf_c, w.z_c, rays + 3, ray_stride, noise_c, noise_std, u, n_rays, num_coarse, num_fine, depth_c, acc_c,
+                                   w.z_f, w.status, stream);
 }
 
 }  // namespace dn
@@ -162,10 +184,7 @@ extern "C" int dn_render_rays(const dn_mlp_desc* desc_coarse, const void* packed
   DN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "dn_render_rays: workspace must be 256-byte aligned");
   Workspace w = carve(workspace, n_rays, num_coarse, num_fine);
   int rc;
-  {
-    hipError_t e = hipMemsetAsync(w.status, 0, 256, as_stream(stream));
-    if (e != hipSuccess) { set_error("dn_render_rays: hipMemsetAsync: %s", hipGetErrorString(e)); return -static_cast<int>(e); }
-  }
+  if ((rc = zero_status("dn_render_rays", w.status, stream))) return rc;
   if ((rc = dn_coarse_depths(rays, ray_stride, n_rays, num_coarse, lindisp, t_rand, w.z_c, stream))) return rc;
   const bool fine = num_fine > 0;
   DN_REQUIRE(n_thres >= 0 && n_thres <= kMaxThres, "dn_render_rays: at most %d Dex thresholds", kMaxThres);
@@ -209,7 +228,7 @@ extern "C" int dn_render_rays(const dn_mlp_desc* desc_coarse, const void* packed
 // ---- the depth-only render: density sub-networks + sigma-only compositing (depth, acc, Dex depths; no colour) -----------------
 extern "C" size_t dn_render_depth_workspace_bytes(int64_t n_rays, int num_coarse, int num_fine) {
   if (n_rays < 0 || num_coarse < 1 || num_fine < 0) return 0;
-  return carve_depth(nullptr, n_rays, num_coarse, num_fine).bytes;
+  return carve(nullptr, n_rays, num_coarse, num_fine, kDepth).bytes;
 }
 
 // the one driver of dn_render_rays_depth and dn_render_rays_depth_quantiles (`who`: the entry point, for messages): with n_quant > 0
@@ -221,46 +240,31 @@ static int render_rays_depth_impl(const char* who, const dn_mlp_desc* desc_coars
                                   float* acc_c, float* depth_f, float* acc_f, float* dex_f, const float* d_quantiles, int n_quant,
                                   int interp, float* qdepth, void* workspace, dn_stream_t stream) {
   // every argument is judged before any GPU work
-  DN_REQUIRE(desc_coarse && packed_coarse && rays && workspace && n_rays >= 0, "%s: bad arguments", who);
-  DN_REQUIRE(num_coarse >= 1 && num_fine >= 0 && ray_stride >= 8, "%s: bad sample counts / ray stride", who);
-  DN_REQUIRE(num_fine == 0 || (desc_fine && packed_fine), "%s: fine pass requested without a fine net", who);
-  DN_REQUIRE(n_thres >= 0, "%s: negative threshold count", who);
-  DN_REQUIRE(n_thres == 0 || (d_m_thres && dex_f), "%s: thresholds given without dex output", who);
-  DN_REQUIRE(!desc_coarse->use_viewdirs && (num_fine == 0 || !desc_fine->use_viewdirs),
-             "%s: takes density sub-networks (dn_mlp_density_desc / dn_mlp_pack_density): use_viewdirs must be 0", who);
-  DN_REQUIRE(num_fine == 0 || (num_coarse >= 10 && num_coarse <= 512 && num_coarse + num_fine <= 2048),
-             "%s: need 10 <= num_coarse <= 512 and num_coarse + num_fine <= 2048", who);
-  DN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "%s: workspace must be 256-byte aligned", who);
   int rc;
+  if ((rc = check_density_render(who, desc_coarse, packed_coarse, desc_fine, packed_fine, rays, ray_stride, n_rays, num_coarse, num_fine, n_thres,
+                                 workspace)))
+    return rc;
+  DN_REQUIRE(n_thres == 0 || (d_m_thres && dex_f), "%s: thresholds given without dex output", who);
   if ((rc = quantile_args_check(who, d_quantiles, n_quant, interp, qdepth))) return rc;
   if ((rc = validate_desc(desc_coarse, precision))) return rc;
   if (num_fine > 0 && (rc = validate_desc(desc_fine, precision))) return rc;
   if (n_rays == 0) return 0;
-  DepthWorkspace w = carve_depth(workspace, n_rays, num_coarse, num_fine);
-  {
-    hipError_t e = hipMemsetAsync(w.status, 0, 256, as_stream(stream));
-    if (e != hipSuccess) { set_error("%s: hipMemsetAsync: %s", who, hipGetErrorString(e)); return -static_cast<int>(e); }
-  }
-  if ((rc = dn_coarse_depths(rays, ray_stride, n_rays, num_coarse, lindisp, t_rand, w.z_c, stream))) return rc;
-  if ((rc = run_network_flagged(desc_coarse, precision, packed_coarse, nullptr, nullptr, rays, ray_stride, w.z_c, n_rays, num_coarse,
-                                w.rf_c, w.status + 1, stream)))
+  const Workspace w = carve(workspace, n_rays, num_coarse, num_fine, kDepth);
+  if ((rc = zero_status(who, w.status, stream))) return rc;
+  if ((rc = density_coarse_pass(desc_coarse, packed_coarse, precision, rays, ray_stride, n_rays, num_coarse, num_fine, lindisp, noise_std, t_rand,
+                                noise_c, u, depth_c, acc_c, w, stream)))
     return rc;
-  // Dex depths come from the fine pass (train_utils.py:199-201); coarse-only renders report the coarse ones.
-  auto composite_last = [&](const float* rf, const float* z, const float* noise, int samples, float* depth, float* acc) {
-    if (n_quant > 0)
-      return composite_quantile_counting(rf, z, rays + 3, ray_stride, noise, noise_std, d_m_thres, n_thres, d_quantiles, n_quant, interp,
-                                         n_rays, samples, depth, acc, dex_f, qdepth, w.status, stream);
-    return composite_density_counting(rf, z, rays + 3, ray_stride, noise, noise_std, d_m_thres, n_thres, n_rays, samples, depth, acc, dex_f,
-                                      w.status, stream);
-  };
-  if (num_fine == 0) return composite_last(w.rf_c, w.z_c, noise_c, num_coarse, depth_c, acc_c);
-  if ((rc = density_resample_counting(w.rf_c, w.z_c, rays + 3, ray_stride, noise_c, noise_std, u, n_rays, num_coarse, num_fine, depth_c,
-                                      acc_c, w.z_f, w.status, stream)))
+  // the last pass: the fine one, or the coarse one of a coarse-only render - the Dex depths are its (train_utils.py:199-201)
+  const bool fine = num_fine > 0;
+  const int samples = num_coarse + num_fine;
+  const float* z_last = fine ? w.z_f : w.z_c;
+  float* rf_last = fine ? w.rf_f : w.rf_c;
+  if ((rc = run_network_flagged(fine ? desc_fine : desc_coarse, precision, fine ? packed_fine : packed_coarse, nullptr, nullptr, rays, ray_stride,
+                                z_last, n_rays, samples, rf_last, w.status + 1, stream)))
     return rc;
-  if ((rc = run_network_flagged(desc_fine, precision, packed_fine, nullptr, nullptr, rays, ray_stride, w.z_f, n_rays,
-                                num_coarse + num_fine, w.rf_f, w.status + 1, stream)))
-    return rc;
-  return composite_last(w.rf_f, w.z_f, noise_f, num_coarse + num_fine, depth_f, acc_f);
+  const SigmaCompositeArgs last{rf_last, z_last, rays + 3, ray_stride, fine ? noise_f : noise_c, noise_std, d_m_thres, n_thres, n_rays, samples,
+                                fine ? depth_f : depth_c, fine ? acc_f : acc_c, dex_f, w.status, d_quantiles, n_quant, interp, qdepth};
+  return n_quant > 0 ? composite_quantile_counting(last, stream) : composite_density_counting(last, stream);
 }
 
 extern "C" int dn_render_rays_depth(const dn_mlp_desc* desc_coarse, const void* packed_coarse, const dn_mlp_desc* desc_fine,
@@ -288,10 +292,10 @@ extern "C" int dn_render_rays_depth_quantiles(const dn_mlp_desc* desc_coarse, co
 
 // ---- the normal render (include/dexnerf_hip_normals.h): dn_render_rays_depth with the last pass differentiated ---------------------
 namespace dn {
-// carve_depth's regions, then what the differentiated pass keeps: the training forward's saved tensors, the gradient records, the seed
+// the kDepth regions, then what the differentiated pass keeps: the training forward's saved tensors, the gradient records, the seed
 // and the per-point gradient
 struct NormalsWorkspace {
-  DepthWorkspace d;
+  Workspace d;
   void *act, *masks, *grads;
   float *g_out, *g_pts;
   size_t bytes;   // 0: the differentiated network's descriptor / precision is not covered
@@ -299,20 +303,15 @@ struct NormalsWorkspace {
 
 static NormalsWorkspace carve_normals(void* base, const dn_mlp_desc* desc_last, int precision, int64_t n, int nc, int nf) {
   NormalsWorkspace w{};
-  w.d = carve_depth(base, n, nc, nf);
+  w.d = carve(base, n, nc, nf, kDepth);
   const int64_t points = n * (nc + nf);
   size_t act = 0, masks = 0, grads = 0;
   if (dn_mlp_train_sizes(desc_last, precision, points, &act, &masks, &grads)) return w;
-  size_t off = w.d.bytes;
-  auto take = [&](size_t bytes) {
-    void* p = base ? static_cast<void*>(static_cast<char*>(base) + off) : nullptr;
-    off += align256(bytes);
-    return p;
-  };
-  w.act = take(act); w.masks = take(masks); w.grads = take(grads);
-  w.g_out = static_cast<float*>(take(static_cast<size_t>(points) * 4 * sizeof(float)));
-  w.g_pts = static_cast<float*>(take(static_cast<size_t>(points) * 3 * sizeof(float)));
-  w.bytes = off;
+  Carver c{base, w.d.bytes};
+  w.act = c.take(act); w.masks = c.take(masks); w.grads = c.take(grads);
+  w.g_out = c.floats(static_cast<size_t>(points) * 4);
+  w.g_pts = c.floats(static_cast<size_t>(points) * 3);
+  w.bytes = c.off;
   return w;
 }
 }  // namespace dn
@@ -335,44 +334,28 @@ extern "C" int dn_render_rays_normals(const dn_mlp_desc* desc_coarse, const void
                                       float* dex, float* normal, float* dex_normal, void* workspace, size_t workspace_bytes,
                                       dn_stream_t stream) {
   // every argument is judged before any GPU work
-  DN_REQUIRE(desc_coarse && packed_coarse && packed_bwd && packed_ig && rays && workspace && n_rays >= 0, "dn_render_rays_normals: bad arguments");
-  DN_REQUIRE(num_coarse >= 1 && num_fine >= 0 && ray_stride >= 8, "dn_render_rays_normals: bad sample counts / ray stride");
-  DN_REQUIRE(num_fine == 0 || (desc_fine && packed_fine), "dn_render_rays_normals: fine pass requested without a fine net");
-  DN_REQUIRE(n_thres >= 0, "dn_render_rays_normals: negative threshold count");
+  const char* who = "dn_render_rays_normals";
+  int rc;
+  if ((rc = check_density_render(who, desc_coarse, packed_coarse, desc_fine, packed_fine, rays, ray_stride, n_rays, num_coarse, num_fine, n_thres,
+                                 workspace, packed_bwd && packed_ig)))
+    return rc;
   DN_REQUIRE(n_thres == 0 || (d_m_thres && (dex || dex_normal)), "dn_render_rays_normals: thresholds given without dex or dex_normal output");
-  DN_REQUIRE(!desc_coarse->use_viewdirs && (num_fine == 0 || !desc_fine->use_viewdirs),
-             "dn_render_rays_normals: takes density sub-networks (dn_mlp_density_desc / dn_mlp_pack_density): use_viewdirs must be 0");
-  DN_REQUIRE(num_fine == 0 || (num_coarse >= 10 && num_coarse <= 512 && num_coarse + num_fine <= 2048),
-             "dn_render_rays_normals: need 10 <= num_coarse <= 512 and num_coarse + num_fine <= 2048");
-  DN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "dn_render_rays_normals: workspace must be 256-byte aligned");
   DN_REQUIRE(((reinterpret_cast<uintptr_t>(packed_bwd) | reinterpret_cast<uintptr_t>(packed_ig)) & 15) == 0,
              "dn_render_rays_normals: the backward and input-gradient streams must be 16-byte aligned");
   const bool fine = num_fine > 0;
   const dn_mlp_desc* last = fine ? desc_fine : desc_coarse;
-  int rc;
-  if ((rc = input_grad_check(last, precision, "dn_render_rays_normals"))) return rc;   // F32, or BF16 with 16-bit saves; L_xyz in {6, 10}
+  if ((rc = input_grad_check(last, precision, who))) return rc;   // F32, or BF16 with 16-bit saves; L_xyz in {6, 10}
   if (fine && (rc = validate_desc(desc_coarse, precision))) return rc;
   const NormalsWorkspace w = carve_normals(workspace, last, precision, n_rays, num_coarse, num_fine);
   DN_REQUIRE(w.bytes != 0 && workspace_bytes >= w.bytes, "dn_render_rays_normals: workspace too small (%zu bytes needed)", w.bytes);
   if (n_rays == 0) return 0;
-  {
-    hipError_t e = hipMemsetAsync(w.d.status, 0, 256, as_stream(stream));
-    if (e != hipSuccess) { set_error("dn_render_rays_normals: hipMemsetAsync: %s", hipGetErrorString(e)); return -static_cast<int>(e); }
-  }
-  if ((rc = dn_coarse_depths(rays, ray_stride, n_rays, num_coarse, lindisp, t_rand, w.d.z_c, stream))) return rc;
-  const float* z_last = w.d.z_c;
-  float* rf_last = w.d.rf_c;
+  if ((rc = zero_status(who, w.d.status, stream))) return rc;
+  if ((rc = density_coarse_pass(desc_coarse, packed_coarse, precision, rays, ray_stride, n_rays, num_coarse, num_fine, lindisp, noise_std, t_rand,
+                                noise_c, u, depth_c, acc_c, w.d, stream)))
+    return rc;
   const int samples = num_coarse + num_fine;
-  if (fine) {
-    if ((rc = run_network_flagged(desc_coarse, precision, packed_coarse, nullptr, nullptr, rays, ray_stride, w.d.z_c, n_rays, num_coarse,
-                                  w.d.rf_c, w.d.status + 1, stream)))
-      return rc;
-    if ((rc = density_resample_counting(w.d.rf_c, w.d.z_c, rays + 3, ray_stride, noise_c, noise_std, u, n_rays, num_coarse, num_fine, depth_c,
-                                        acc_c, w.d.z_f, w.d.status, stream)))
-      return rc;
-    z_last = w.d.z_f;
-    rf_last = w.d.rf_f;
-  }
+  const float* z_last = fine ? w.d.z_f : w.d.z_c;
+  float* rf_last = fine ? w.d.rf_f : w.d.rf_c;
   // the differentiated pass: training forward (saves kept), seed, backward-data chain, per-point input gradient, compositing
   if ((rc = dn_run_network_train(last, precision, fine ? packed_fine : packed_coarse, nullptr, nullptr, rays, ray_stride, z_last, n_rays,
                                  samples, rf_last, w.act, w.masks, stream)))
@@ -381,15 +364,17 @@ extern "C" int dn_render_rays_normals(const dn_mlp_desc* desc_coarse, const void
   if ((rc = density_seed(w.g_out, points, stream))) return rc;
   if ((rc = dn_mlp_backward_data(last, precision, packed_bwd, w.g_out, w.masks, points, w.grads, stream))) return rc;
   if ((rc = input_grad_points_from_rays(last, precision, packed_ig, w.grads, rays, ray_stride, z_last, n_rays, samples, w.g_pts, stream))) return rc;
-  return composite_normals_counting(rf_last, z_last, rays + 3, ray_stride, fine ? noise_f : noise_c, noise_std, w.g_pts, d_m_thres, n_thres, n_rays,
-                                    samples, depth, acc, dex, normal, dex_normal, w.d.status, stream);
+  SigmaCompositeArgs c{rf_last, z_last, rays + 3, ray_stride, fine ? noise_f : noise_c, noise_std, d_m_thres, n_thres, n_rays, samples, depth, acc,
+                       dex, w.d.status};
+  c.g_pts = w.g_pts; c.normal = normal; c.dex_normal = dex_normal;
+  return composite_normals_counting(c, stream);
 }
 
 // ---- predict_and_render_radiance under autograd (reference nerf/train_utils.py:92-202 + loss.backward(),
 // train_dexnerf_rgb.py:278): one call forward, one call backward -------------------------------------------------------
 extern "C" size_t dn_render_train_workspace_bytes(int64_t n_rays, int num_coarse, int num_fine) {
   if (n_rays < 0 || num_coarse < 1 || num_fine < 0) return 0;
-  return carve(nullptr, n_rays, num_coarse, num_fine, true).bytes;
+  return carve(nullptr, n_rays, num_coarse, num_fine, kTrain).bytes;
 }
 
 extern "C" int dn_render_rays_train(const dn_mlp_desc* desc_coarse, const void* packed_coarse, const dn_mlp_desc* desc_fine,
@@ -420,7 +405,7 @@ extern "C" int dn_render_rays_train_geom(const dn_mlp_desc* desc_coarse, const v
   DN_REQUIRE(num_fine == 0 || (desc_fine && packed_fine && act_f && masks_f), "dn_render_rays_train: fine pass requested without a fine net / its buffers");
   DN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "dn_render_rays_train: workspace must be 256-byte aligned");
   if (n_rays == 0) return 0;
-  Workspace w = carve(workspace, n_rays, num_coarse, num_fine, true);
+  Workspace w = carve(workspace, n_rays, num_coarse, num_fine, kTrain);
   int rc;
   // a NULL draw with an RNG state: drawn in the kernels (dn_rng.h) - jitter / resampling u only when `perturb`, density noise
   // whenever noise_std > 0; explicit draws win (parity tests inject the reference's)
@@ -456,27 +441,21 @@ struct GeomWorkspace {
 
 static GeomWorkspace carve_geom(void* base, const dn_mlp_desc* desc_c, const dn_mlp_desc* desc_f, int64_t n, int stride, int nc, int nf) {
   GeomWorkspace w{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    void* p = base ? static_cast<void*>(static_cast<char*>(base) + off) : nullptr;
-    off += align256(bytes);
-    return p;
-  };
-  auto floats = [&](size_t count) { return static_cast<float*>(take(count * sizeof(float))); };
+  Carver c{base};
   const size_t rays = static_cast<size_t>(n);
   if (nf > 0) {
-    w.g_z_f = floats(rays * (nc + nf)); w.g_rd_f = floats(rays * 3); w.d_rays_f = floats(rays * stride); w.d_z_f = floats(rays * (nc + nf));
-    w.gathered = floats(rays * nc);
+    w.g_z_f = c.floats(rays * (nc + nf)); w.g_rd_f = c.floats(rays * 3); w.d_rays_f = c.floats(rays * stride); w.d_z_f = c.floats(rays * (nc + nf));
+    w.gathered = c.floats(rays * nc);
   }
-  w.g_z_c = floats(rays * nc); w.g_rd_c = floats(rays * 3); w.d_rays_c = floats(rays * stride); w.d_z_c = floats(rays * nc);
-  w.g_near_far = floats(rays * 2);
+  w.g_z_c = c.floats(rays * nc); w.g_rd_c = c.floats(rays * 3); w.d_rays_c = c.floats(rays * stride); w.d_z_c = c.floats(rays * nc);
+  w.g_near_far = c.floats(rays * 2);
   w.input_grad_bytes = dn_mlp_backward_input_workspace_bytes(desc_c, n * nc, 1);
   if (nf > 0) {
     const size_t fine = dn_mlp_backward_input_workspace_bytes(desc_f, n * (nc + nf), 1);
     if (fine > w.input_grad_bytes) w.input_grad_bytes = fine;
   }
-  w.input_grad = take(w.input_grad_bytes);
-  w.bytes = off;
+  w.input_grad = c.take(w.input_grad_bytes);
+  w.bytes = c.off;
   return w;
 }
 
@@ -518,7 +497,7 @@ static int render_rays_backward(const RenderBackwardArgs& a) {
   const bool geom = a.d_rays != nullptr, fine = a.num_fine > 0;
   const int64_t n_rays = a.n_rays;
   const int nc = a.num_coarse, nf = a.num_fine;
-  const Workspace w = carve(a.workspace, n_rays, nc, nf, true);
+  const Workspace w = carve(a.workspace, n_rays, nc, nf, kTrain);
   const GeomWorkspace g = geom ? carve_geom(a.geom_workspace, a.coarse.desc, a.fine.desc, n_rays, a.ray_stride, nc, nf) : GeomWorkspace{};
   const RegWorkspace reg = carve_reg(a.reg_workspace, n_rays, nc, nf);
   int rc;

@@ -65,23 +65,30 @@ int density_resample_counting(const float* rf, const float* z, const float* rd, 
   DN_REQUIRE((reinterpret_cast<uintptr_t>(rf) & 15) == 0, "dn_density_resample: rf must be 16-byte aligned");
   const int sort_len = next_pow2(num_coarse + num_fine);
   const size_t lds = static_cast<size_t>(kSamplerWaves) * (3 * num_coarse + sort_len) * sizeof(float);
-  const unsigned grid = static_cast<unsigned>((n_rays + kSamplerWaves - 1) / kSamplerWaves);
-  hipLaunchKernelGGL(density_resample_kernel, dim3(grid), dim3(256), lds, as_stream(stream), reinterpret_cast<const float4*>(rf), z, rd,
+  hipLaunchKernelGGL(density_resample_kernel, dim3(ray_grid(n_rays)), dim3(256), lds, as_stream(stream), reinterpret_cast<const float4*>(rf), z, rd,
                      rd_stride, noise, noise_std, u, n_rays, num_coarse, num_fine, depth, acc, z_fine, sort_len, nonfinite);
   return check_launch("dn_density_resample");
 }
 
-int composite_density_counting(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise, float noise_std,
-                               const float* d_m_thres, int n_thres, int64_t n_rays, int n_samples, float* depth, float* acc, float* dex,
-                               unsigned* nonfinite, dn_stream_t stream) {
-  if (n_rays == 0) return 0;
-  DN_REQUIRE(rf && z && rd && n_rays >= 0 && n_samples >= 1 && rd_stride >= 3, "dn_composite_density: bad arguments");
-  DN_REQUIRE(n_thres >= 0, "dn_composite_density: negative threshold count");
-  DN_REQUIRE(n_thres == 0 || (d_m_thres && dex), "dn_composite_density: thresholds given without dex output");
-  DN_REQUIRE((reinterpret_cast<uintptr_t>(rf) & 15) == 0, "dn_composite_density: rf must be 16-byte aligned");
-  const unsigned grid = static_cast<unsigned>((n_rays + kSamplerWaves - 1) / kSamplerWaves);
-  hipLaunchKernelGGL(composite_density_kernel, dim3(grid), dim3(256), 0, as_stream(stream), reinterpret_cast<const float4*>(rf), z, rd,
-                     rd_stride, noise, noise_std, d_m_thres, n_thres, n_rays, n_samples, depth, acc, n_thres > 0 ? dex : nullptr, nonfinite);
+int sigma_composite_check(const char* who, const SigmaCompositeArgs& a, bool normals) {
+  DN_REQUIRE(a.rf && a.z && a.rd && (!normals || a.g_pts) && a.n_rays >= 0 && a.n_samples >= 1 && a.rd_stride >= 3, "%s: bad arguments", who);
+  DN_REQUIRE(a.n_thres >= 0, "%s: negative threshold count", who);
+  if (normals)
+    DN_REQUIRE(a.n_thres == 0 || (a.d_m_thres && (a.dex || a.dex_normal)), "%s: thresholds given without dex or dex_normal output", who);
+  else
+    DN_REQUIRE(a.n_thres == 0 || (a.d_m_thres && a.dex), "%s: thresholds given without dex output", who);
+  if (int rc = quantile_args_check(who, a.d_quantiles, a.n_quant, a.interp, a.qdepth)) return rc;   // (n_quant == 0, interp == 0: passes)
+  DN_REQUIRE((reinterpret_cast<uintptr_t>(a.rf) & 15) == 0, "%s: rf must be 16-byte aligned", who);
+  return 0;
+}
+static_assert(kSamplerWaves == 4, "ray_grid (dn_common.h) counts four rays per workgroup");
+
+int composite_density_counting(const SigmaCompositeArgs& a, dn_stream_t stream) {
+  if (a.n_rays == 0) return 0;   // (before the checks, as ever: empty tensors carry NULL data pointers - _ops.composite_density)
+  if (int rc = sigma_composite_check("dn_composite_density", a)) return rc;
+  hipLaunchKernelGGL(composite_density_kernel, dim3(ray_grid(a.n_rays)), dim3(256), 0, as_stream(stream), reinterpret_cast<const float4*>(a.rf),
+                     a.z, a.rd, a.rd_stride, a.noise, a.noise_std, a.d_m_thres, a.n_thres, a.n_rays, a.n_samples, a.depth, a.acc,
+                     a.n_thres > 0 ? a.dex : nullptr, a.nonfinite);
   return check_launch("dn_composite_density");
 }
 
@@ -98,5 +105,5 @@ extern "C" int dn_density_resample(const float* rf, const float* z, const float*
 extern "C" int dn_composite_density(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise,
                                     float noise_std, const float* d_m_thres, int n_thres, int64_t n_rays, int n_samples,
                                     float* depth, float* acc, float* dex, dn_stream_t stream) {
-  return composite_density_counting(rf, z, rd, rd_stride, noise, noise_std, d_m_thres, n_thres, n_rays, n_samples, depth, acc, dex, nullptr, stream);
+  return composite_density_counting({rf, z, rd, rd_stride, noise, noise_std, d_m_thres, n_thres, n_rays, n_samples, depth, acc, dex}, stream);
 }

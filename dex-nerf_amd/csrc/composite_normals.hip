@@ -76,25 +76,12 @@ int density_seed(float* g_out, int64_t n_points, dn_stream_t stream) {
   return check_launch("density_seed");
 }
 
-static int composite_normals_check(const float* rf, const float* z, const float* rd, int rd_stride, const float* g_pts,
-                                   const float* d_m_thres, int n_thres, int64_t n_rays, int n_samples, const float* dex,
-                                   const float* dex_normal) {
-  DN_REQUIRE(rf && z && rd && g_pts && n_rays >= 0 && n_samples >= 1 && rd_stride >= 3, "dn_composite_normals: bad arguments");
-  DN_REQUIRE(n_thres >= 0, "dn_composite_normals: negative threshold count");
-  DN_REQUIRE(n_thres == 0 || (d_m_thres && (dex || dex_normal)), "dn_composite_normals: thresholds given without dex or dex_normal output");
-  DN_REQUIRE((reinterpret_cast<uintptr_t>(rf) & 15) == 0, "dn_composite_normals: rf must be 16-byte aligned");
-  return 0;
-}
-
-int composite_normals_counting(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise, float noise_std,
-                               const float* g_pts, const float* d_m_thres, int n_thres, int64_t n_rays, int n_samples, float* depth,
-                               float* acc, float* dex, float* normal, float* dex_normal, unsigned* nonfinite, dn_stream_t stream) {
-  if (int rc = composite_normals_check(rf, z, rd, rd_stride, g_pts, d_m_thres, n_thres, n_rays, n_samples, dex, dex_normal)) return rc;
-  if (n_rays == 0) return 0;
-  const unsigned grid = static_cast<unsigned>((n_rays + kSamplerWaves - 1) / kSamplerWaves);
-  hipLaunchKernelGGL(composite_normals_kernel, dim3(grid), dim3(256), 0, as_stream(stream), reinterpret_cast<const float4*>(rf), z, rd,
-                     rd_stride, noise, noise_std, g_pts, d_m_thres, n_thres, n_rays, n_samples, depth, acc, n_thres > 0 ? dex : nullptr, normal,
-                     n_thres > 0 ? dex_normal : nullptr, nonfinite);
+int composite_normals_counting(const SigmaCompositeArgs& a, dn_stream_t stream) {
+  if (int rc = sigma_composite_check("dn_composite_normals", a, true)) return rc;
+  if (a.n_rays == 0) return 0;
+  hipLaunchKernelGGL(composite_normals_kernel, dim3(ray_grid(a.n_rays)), dim3(256), 0, as_stream(stream), reinterpret_cast<const float4*>(a.rf),
+                     a.z, a.rd, a.rd_stride, a.noise, a.noise_std, a.g_pts, a.d_m_thres, a.n_thres, a.n_rays, a.n_samples, a.depth, a.acc,
+                     a.n_thres > 0 ? a.dex : nullptr, a.normal, a.n_thres > 0 ? a.dex_normal : nullptr, a.nonfinite);
   return check_launch("dn_composite_normals");
 }
 
@@ -105,6 +92,7 @@ using namespace dn;
 extern "C" int dn_composite_normals(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise, float noise_std,
                                     const float* g_pts, const float* d_m_thres, int n_thres, int64_t n_rays, int n_samples, float* depth,
                                     float* acc, float* dex, float* normal, float* dex_normal, dn_stream_t stream) {
-  return composite_normals_counting(rf, z, rd, rd_stride, noise, noise_std, g_pts, d_m_thres, n_thres, n_rays, n_samples, depth, acc, dex,
-                                    normal, dex_normal, nullptr, stream);
+  SigmaCompositeArgs a{rf, z, rd, rd_stride, noise, noise_std, d_m_thres, n_thres, n_rays, n_samples, depth, acc, dex};
+  a.g_pts = g_pts; a.normal = normal; a.dex_normal = dex_normal;
+  return composite_normals_counting(a, stream);
 }

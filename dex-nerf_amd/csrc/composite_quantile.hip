@@ -35,20 +35,12 @@ int quantile_args_check(const char* who, const float* d_quantiles, int n_quant, 
   return 0;
 }
 
-int composite_quantile_counting(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise, float noise_std,
-                                const float* d_m_thres, int n_thres, const float* d_quantiles, int n_quant, int interp, int64_t n_rays,
-                                int n_samples, float* depth, float* acc, float* dex, float* qdepth, unsigned* nonfinite,
-                                dn_stream_t stream) {
-  DN_REQUIRE(rf && z && rd && n_rays >= 0 && n_samples >= 1 && rd_stride >= 3, "dn_composite_density_quantiles: bad arguments");
-  DN_REQUIRE(n_thres >= 0, "dn_composite_density_quantiles: negative threshold count");
-  DN_REQUIRE(n_thres == 0 || (d_m_thres && dex), "dn_composite_density_quantiles: thresholds given without dex output");
-  if (int rc = quantile_args_check("dn_composite_density_quantiles", d_quantiles, n_quant, interp, qdepth)) return rc;
-  DN_REQUIRE((reinterpret_cast<uintptr_t>(rf) & 15) == 0, "dn_composite_density_quantiles: rf must be 16-byte aligned");
-  if (n_rays == 0) return 0;
-  const unsigned grid = static_cast<unsigned>((n_rays + kSamplerWaves - 1) / kSamplerWaves);
-  hipLaunchKernelGGL(composite_quantile_kernel, dim3(grid), dim3(256), 0, as_stream(stream), reinterpret_cast<const float4*>(rf), z, rd,
-                     rd_stride, noise, noise_std, d_m_thres, n_thres, d_quantiles, n_quant, interp, n_rays, n_samples, depth, acc,
-                     n_thres > 0 ? dex : nullptr, n_quant > 0 ? qdepth : nullptr, nonfinite);
+int composite_quantile_counting(const SigmaCompositeArgs& a, dn_stream_t stream) {
+  if (int rc = sigma_composite_check("dn_composite_density_quantiles", a)) return rc;
+  if (a.n_rays == 0) return 0;
+  hipLaunchKernelGGL(composite_quantile_kernel, dim3(ray_grid(a.n_rays)), dim3(256), 0, as_stream(stream), reinterpret_cast<const float4*>(a.rf),
+                     a.z, a.rd, a.rd_stride, a.noise, a.noise_std, a.d_m_thres, a.n_thres, a.d_quantiles, a.n_quant, a.interp, a.n_rays,
+                     a.n_samples, a.depth, a.acc, a.n_thres > 0 ? a.dex : nullptr, a.n_quant > 0 ? a.qdepth : nullptr, a.nonfinite);
   return check_launch("dn_composite_density_quantiles");
 }
 
@@ -60,6 +52,6 @@ extern "C" int dn_composite_density_quantiles(const float* rf, const float* z, c
                                               float noise_std, const float* d_m_thres, int n_thres, const float* d_quantiles, int n_quant,
                                               int interp, int64_t n_rays, int n_samples, float* depth, float* acc, float* dex, float* qdepth,
                                               dn_stream_t stream) {
-  return composite_quantile_counting(rf, z, rd, rd_stride, noise, noise_std, d_m_thres, n_thres, d_quantiles, n_quant, interp, n_rays,
-                                     n_samples, depth, acc, dex, qdepth, nullptr, stream);
+  return composite_quantile_counting({rf, z, rd, rd_stride, noise, noise_std, d_m_thres, n_thres, n_rays, n_samples, depth, acc, dex, nullptr,
+                                      d_quantiles, n_quant, interp, qdepth}, stream);
 }

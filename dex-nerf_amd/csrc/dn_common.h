@@ -39,26 +39,41 @@ int volume_render_counting(const float* rf, const float* z, const float* rd, int
                            float* disp, float* acc, float* weights, float* depth, float* dex, unsigned* nonfinite,
                            dn_stream_t stream, const uint32_t* rng_state = nullptr, uint32_t rng_stream = 0);
 
-// composite_density.hip: the sigma-only kernels of dn_render_rays_depth, counting non-finite raw sigma like volume_render_counting
+// The sigma-only compositing passes (composite_density.hip, composite_quantile.hip, composite_normals.hip): one record for the three
+// launchers.  nonfinite: the device word that counts non-finite raw sigma like volume_render_counting (NULL = do not count).
+struct SigmaCompositeArgs {
+  const float *rf, *z, *rd;
+  int rd_stride;
+  const float* noise;
+  float noise_std;
+  const float* d_m_thres;
+  int n_thres;
+  int64_t n_rays;
+  int n_samples;
+  float *depth, *acc, *dex;
+  unsigned* nonfinite;
+  // the quantile pass alone (n_quant == 0: none)
+  const float* d_quantiles;
+  int n_quant, interp;
+  float* qdepth;
+  // the normals pass alone
+  const float* g_pts;
+  float *normal, *dex_normal;
+};
+// composite_density.hip: the launchers' shared refusals under the entry point's name (`normals`: g_pts is required and dex_normal may
+// stand for dex), the quantile arguments' rule among them, and their grid - one wave per ray, four rays per workgroup
+int sigma_composite_check(const char* who, const SigmaCompositeArgs& a, bool normals = false);
+inline unsigned ray_grid(int64_t n_rays) { return static_cast<unsigned>((n_rays + 3) / 4); }
+int composite_density_counting(const SigmaCompositeArgs& a, dn_stream_t stream);
+// the coarse pass fused with the fine-depth generation (its own checks and LDS sizing)
 int density_resample_counting(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise, float noise_std,
                               const float* u, int64_t n_rays, int num_coarse, int num_fine, float* depth, float* acc, float* z_fine,
                               unsigned* nonfinite, dn_stream_t stream);
-int composite_density_counting(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise, float noise_std,
-                               const float* d_m_thres, int n_thres, int64_t n_rays, int n_samples, float* depth, float* acc, float* dex,
-                               unsigned* nonfinite, dn_stream_t stream);
-
-// composite_quantile.hip: the quantile arguments' rule (`who`: the entry point, for messages) and dn_composite_density_quantiles with
-// the non-finite count
+// composite_quantile.hip: the quantile arguments' rule (`who`: the entry point, for messages) and dn_composite_density_quantiles
 int quantile_args_check(const char* who, const float* d_quantiles, int n_quant, int interp, const float* qdepth);
-int composite_quantile_counting(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise, float noise_std,
-                                const float* d_m_thres, int n_thres, const float* d_quantiles, int n_quant, int interp, int64_t n_rays,
-                                int n_samples, float* depth, float* acc, float* dex, float* qdepth, unsigned* nonfinite,
-                                dn_stream_t stream);
-
-// composite_normals.hip: dn_composite_normals with the non-finite count; the density gradient's seed g_out = (0,0,0,1) per point
-int composite_normals_counting(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise, float noise_std,
-                               const float* g_pts, const float* d_m_thres, int n_thres, int64_t n_rays, int n_samples, float* depth,
-                               float* acc, float* dex, float* normal, float* dex_normal, unsigned* nonfinite, dn_stream_t stream);
+int composite_quantile_counting(const SigmaCompositeArgs& a, dn_stream_t stream);
+// composite_normals.hip: dn_composite_normals; the density gradient's seed g_out = (0,0,0,1) per point
+int composite_normals_counting(const SigmaCompositeArgs& a, dn_stream_t stream);
 int density_seed(float* g_out, int64_t n_points, dn_stream_t stream);
 // mlp_input_grad.hip: dn_mlp_backward_input's descriptor / precision rule, and its first launch alone - the per-point d_pts (P,3) of a
 // no-view-direction network from rays + z into the caller's buffer

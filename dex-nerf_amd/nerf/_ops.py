@@ -3,6 +3,7 @@
 Every function here requires ROCm device tensors and calls straight into libdexnerf_hip.so; there is
 no alternative implementation behind them.
 """
+import collections
 import ctypes
 import math
 import types
@@ -182,6 +183,54 @@ def _draw_tensors(draws):
 
 def _empty(dev, *shape):
     return torch.empty(shape, dtype=torch.float32, device=dev)
+
+
+def _net_args(packed_c, packed_f, fine, attr="buffer", key=None):
+    """The four (descriptor, packed stream) arguments of a render entry point: coarse pair, fine pair (NULLs without a fine pass).
+    The stream is the pack's `attr` (the inference stream by default), or its entry `key` when that is a dict (buffers_bwd[prec])."""
+    def pair(packed):
+        buf = getattr(packed, attr)
+        return [ctypes.byref(packed.desc), ptr(buf if key is None else buf[key])]
+    return pair(packed_c) + (pair(packed_f) if fine else [None, None])
+
+
+_RenderCall = collections.namedtuple("_RenderCall", "rays n dev fine nf k draws net_args")
+
+
+def _render_call(packed_c, packed_f, rays, num_fine, m_thres, draws):
+    """The prelude of the render wrappers: fp32-contiguous ray rows, their count and device, whether a fine pass runs and its sample
+    count, the number of thresholds (a list, a device tensor or None), the four draw tensors in argument order (_draw_tensors) and
+    the four network arguments on the inference streams (_net_args)."""
+    rays = f32c(rays)
+    fine = num_fine > 0 and packed_f is not None
+    k = 0 if m_thres is None else (int(m_thres.numel()) if torch.is_tensor(m_thres) else len(m_thres))
+    return _RenderCall(rays, rays.shape[0], rays.device, fine, num_fine if fine else 0, k, _draw_tensors(draws),
+                       _net_args(packed_c, packed_f, fine))
+
+
+def _pass_maps(dev, n, present=True, rgb=False):
+    """The output buffers of one pass: (depth, acc), led by rgb (n,3) when asked; a None each for a pass that does not run."""
+    shapes = ([(n, 3)] if rgb else []) + [(n,), (n,)]
+    return tuple(_empty(dev, *shape) if present else None for shape in shapes)
+
+
+_SigmaCall = collections.namedtuple("_SigmaCall", "n s dev head thres k keep")
+
+
+def _sigma_call(rf, z, rd, noise, noise_std, m_thres=None):
+    """What the sigma-compositing wrappers prepare: rf (N,S,4) and z (N,S) fp32-contiguous, the direction rows (_dir_rows), the noise
+    tensor only when noise_std > 0, the thresholds - a list or a device tensor - as a device tensor (None for none).  head: the six
+    leading arguments of their entry points (rf, z, rd, rd_stride, noise, noise_std); keep: the tensors behind its pointers."""
+    rf, z = f32c(rf), f32c(z)
+    n, s = z.shape
+    dev = rf.device
+    rd_ptr, rd_stride, rd = _dir_rows(rd)
+    nz = None if (noise is None or noise_std <= 0.0) else f32c(noise)
+    th = m_thres
+    if th is not None and not torch.is_tensor(th):
+        th = torch.tensor([float(m) for m in th], dtype=torch.float32, device=dev) if len(th) else None
+    k = 0 if th is None else int(th.numel())
+    return _SigmaCall(n, s, dev, [ptr(rf), ptr(z), rd_ptr, rd_stride, ptr(nz), float(noise_std)], th if k else None, k, (rf, z, rd, nz))
 
 
 def _grads_buf(packed, n_points, prec, dev):
@@ -1196,42 +1245,23 @@ def render_rays(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, noise_s
     packed_c.require_fresh_inference_stream("render_rays")
     if packed_f is not None:
         packed_f.require_fresh_inference_stream("render_rays")
-    rays = f32c(rays)
-    n = rays.shape[0]
-    dev = rays.device
-    k = len(m_thres)
-    fine = num_fine > 0 and packed_f is not None
-    nf = num_fine if fine else 0
-    ws = _render_workspace(dev, lib().dn_render_workspace_bytes(n, num_coarse, nf))
-    rgb_c, depth_c, acc_c = _empty(dev, n, 3), _empty(dev, n), _empty(dev, n)
-    rgb_f, depth_f, acc_f = (_empty(dev, n, 3), _empty(dev, n), _empty(dev, n)) if fine else (None, None, None)
-    dex = _empty(dev, k, n) if k else None
-    prec = packed_c.precision
-    t_rand, noise_c, u, noise_f = _draw_tensors(draws)
+    c = _render_call(packed_c, packed_f, rays, num_fine, m_thres, draws)
+    n, dev = c.n, c.dev
+    ws = _render_workspace(dev, lib().dn_render_workspace_bytes(n, num_coarse, c.nf))
+    maps = _pass_maps(dev, n, rgb=True) + _pass_maps(dev, n, c.fine, rgb=True) + (_empty(dev, c.k, n) if c.k else None,)
     check(lib().dn_render_rays(
-        ctypes.byref(packed_c.desc), ptr(packed_c.buffer),
-        ctypes.byref(packed_f.desc) if fine else None, ptr(packed_f.buffer) if fine else None, prec,
-        ptr(rays), rays.shape[1], n, num_coarse, nf, int(bool(lindisp)), float(noise_std), int(bool(white)),
-        host_floats(m_thres), k, ptr(t_rand), ptr(noise_c), ptr(u), ptr(noise_f),
-        ptr(rgb_c), ptr(depth_c), ptr(acc_c), ptr(rgb_f), ptr(depth_f), ptr(acc_f), ptr(dex), ptr(ws), stream()),
+        *c.net_args, packed_c.precision, ptr(c.rays), c.rays.shape[1], n, num_coarse, c.nf, int(bool(lindisp)), float(noise_std),
+        int(bool(white)), host_floats(m_thres), c.k, *[ptr(d) for d in c.draws], *[ptr(m) for m in maps], ptr(ws), stream()),
         "dn_render_rays")
-    return rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f, dex
+    return maps
 
 
 def composite_density(rf, z, rd, noise, noise_std, m_thres):
     """dn_composite_density: (depth, acc, dex (K,N) or None) from the sigma column of rf (N,S,4); any number of thresholds."""
-    rf, z = f32c(rf), f32c(z)
-    n, s = z.shape
-    dev = rf.device
-    rd_ptr, rd_stride, rd = _dir_rows(rd)
-    k = len(m_thres)
-    depth = torch.empty((n,), dtype=torch.float32, device=dev)
-    acc = torch.empty_like(depth)
-    dex = torch.empty((k, n), dtype=torch.float32, device=dev) if k else None
-    th = torch.tensor([float(m) for m in m_thres], dtype=torch.float32, device=dev) if k else None
-    nz = None if (noise is None or noise_std <= 0.0) else f32c(noise)
-    check(lib().dn_composite_density(ptr(rf), ptr(z), rd_ptr, rd_stride, ptr(nz), float(noise_std), ptr(th), k, n, s, ptr(depth),
-                                     ptr(acc), ptr(dex), stream()), "dn_composite_density")
+    c = _sigma_call(rf, z, rd, noise, noise_std, m_thres)
+    depth, acc = _pass_maps(c.dev, c.n)
+    dex = _empty(c.dev, c.k, c.n) if c.k else None
+    check(lib().dn_composite_density(*c.head, ptr(c.thres), c.k, c.n, c.s, ptr(depth), ptr(acc), ptr(dex), stream()), "dn_composite_density")
     return depth, acc, dex
 
 
@@ -1254,37 +1284,24 @@ def composite_density_quantiles(rf, z, rd, noise, noise_std, m_thres, quantiles,
     """dn_composite_density_quantiles: composite_density's (depth, acc, dex (K,N) or None) and qdepth (Q,N) or None - the depth at
     which the accumulated opacity first reaches each quantile (interp: the piecewise-linear inversion instead of the sample's z)."""
     qs = check_quantiles(quantiles, "composite_density_quantiles")
-    rf, z = f32c(rf), f32c(z)
-    n, s = z.shape
-    dev = rf.device
-    rd_ptr, rd_stride, rd = _dir_rows(rd)
-    k, nq = len(m_thres), len(qs)
-    depth = torch.empty((n,), dtype=torch.float32, device=dev)
-    acc = torch.empty_like(depth)
-    dex = torch.empty((k, n), dtype=torch.float32, device=dev) if k else None
-    qdepth = torch.empty((nq, n), dtype=torch.float32, device=dev) if nq else None
-    th = torch.tensor([float(m) for m in m_thres], dtype=torch.float32, device=dev) if k else None
-    qt = torch.tensor(qs, dtype=torch.float32, device=dev) if nq else None
-    nz = None if (noise is None or noise_std <= 0.0) else f32c(noise)
-    check(lib().dn_composite_density_quantiles(ptr(rf), ptr(z), rd_ptr, rd_stride, ptr(nz), float(noise_std), ptr(th), k, ptr(qt), nq,
-                                               int(bool(interp)), n, s, ptr(depth), ptr(acc), ptr(dex), ptr(qdepth), stream()),
-          "dn_composite_density_quantiles")
+    c = _sigma_call(rf, z, rd, noise, noise_std, m_thres)
+    nq = len(qs)
+    depth, acc = _pass_maps(c.dev, c.n)
+    dex = _empty(c.dev, c.k, c.n) if c.k else None
+    qdepth = _empty(c.dev, nq, c.n) if nq else None
+    qt = torch.tensor(qs, dtype=torch.float32, device=c.dev) if nq else None
+    check(lib().dn_composite_density_quantiles(*c.head, ptr(c.thres), c.k, ptr(qt), nq, int(bool(interp)), c.n, c.s, ptr(depth), ptr(acc),
+                                               ptr(dex), ptr(qdepth), stream()), "dn_composite_density_quantiles")
     return depth, acc, dex, qdepth
 
 
 def density_resample(rf, z, rd, num_fine, noise=None, noise_std=0.0, u=None):
     """dn_density_resample: coarse sigma compositing fused with fine_depths -> (depth_c, acc_c, z_fine)."""
-    rf, z = f32c(rf), f32c(z)
-    n, nc = z.shape
-    dev = rf.device
-    rd_ptr, rd_stride, rd = _dir_rows(rd)
-    depth = torch.empty((n,), dtype=torch.float32, device=dev)
-    acc = torch.empty_like(depth)
-    z_fine = torch.empty((n, nc + num_fine), dtype=torch.float32, device=dev)
-    nz = None if (noise is None or noise_std <= 0.0) else f32c(noise)
+    c = _sigma_call(rf, z, rd, noise, noise_std)
+    depth, acc = _pass_maps(c.dev, c.n)
+    z_fine = _empty(c.dev, c.n, c.s + num_fine)
     uu = None if u is None else f32c(u)
-    check(lib().dn_density_resample(ptr(rf), ptr(z), rd_ptr, rd_stride, ptr(nz), float(noise_std), ptr(uu), n, nc, num_fine,
-                                    ptr(depth), ptr(acc), ptr(z_fine), stream()), "dn_density_resample")
+    check(lib().dn_density_resample(*c.head, ptr(uu), c.n, c.s, num_fine, ptr(depth), ptr(acc), ptr(z_fine), stream()), "dn_density_resample")
     return depth, acc, z_fine
 
 
@@ -1295,37 +1312,22 @@ def render_rays_depth(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, n
     quantiles: a device tensor of Q <= 64 opacity quantiles the caller has validated (check_quantiles) - the call then goes to
     dn_render_rays_depth_quantiles (same launches, the last pass composited by the quantile kernel) and returns qdepth (Q,N) as a
     sixth value; None: the call and the return are what they were."""
-    rays = f32c(rays)
-    n = rays.shape[0]
-    dev = rays.device
-    k = 0 if m_thres is None else int(m_thres.numel())
-    fine = num_fine > 0 and packed_f is not None
-    nf = num_fine if fine else 0
-    ws = _render_workspace(dev, lib().dn_render_depth_workspace_bytes(n, num_coarse, nf))
-    depth_c, acc_c = _empty(dev, n), _empty(dev, n)
-    depth_f, acc_f = (_empty(dev, n), _empty(dev, n)) if fine else (None, None)
-    dex = _empty(dev, k, n) if k else None
-    t_rand, noise_c, u, noise_f = _draw_tensors(draws)
-    if quantiles is not None:
-        nq = int(quantiles.numel())
-        if not 1 <= nq <= _hip.MAX_QUANTILES or quantiles.dtype != torch.float32:
-            raise ValueError(f"render_rays_depth: quantiles must be a float32 device tensor of 1 .. {_hip.MAX_QUANTILES} values")
-        qdepth = _empty(dev, nq, n)
-        check(lib().dn_render_rays_depth_quantiles(
-            ctypes.byref(packed_c.desc), ptr(packed_c.buffer),
-            ctypes.byref(packed_f.desc) if fine else None, ptr(packed_f.buffer) if fine else None, packed_c.precision,
-            ptr(rays), rays.shape[1], n, num_coarse, nf, int(bool(lindisp)), float(noise_std),
-            ptr(m_thres) if k else None, k, ptr(t_rand), ptr(noise_c), ptr(u), ptr(noise_f),
-            ptr(depth_c), ptr(acc_c), ptr(depth_f), ptr(acc_f), ptr(dex), ptr(quantiles), nq, int(bool(interp)), ptr(qdepth),
-            ptr(ws), stream()), "dn_render_rays_depth_quantiles")
-        return depth_c, acc_c, depth_f, acc_f, dex, qdepth
-    check(lib().dn_render_rays_depth(
-        ctypes.byref(packed_c.desc), ptr(packed_c.buffer),
-        ctypes.byref(packed_f.desc) if fine else None, ptr(packed_f.buffer) if fine else None, packed_c.precision,
-        ptr(rays), rays.shape[1], n, num_coarse, nf, int(bool(lindisp)), float(noise_std),
-        ptr(m_thres) if k else None, k, ptr(t_rand), ptr(noise_c), ptr(u), ptr(noise_f),
-        ptr(depth_c), ptr(acc_c), ptr(depth_f), ptr(acc_f), ptr(dex), ptr(ws), stream()), "dn_render_rays_depth")
-    return depth_c, acc_c, depth_f, acc_f, dex
+    c = _render_call(packed_c, packed_f, rays, num_fine, m_thres, draws)
+    n, dev = c.n, c.dev
+    ws = _render_workspace(dev, lib().dn_render_depth_workspace_bytes(n, num_coarse, c.nf))
+    maps = _pass_maps(dev, n) + _pass_maps(dev, n, c.fine) + (_empty(dev, c.k, n) if c.k else None,)
+    args = [*c.net_args, packed_c.precision, ptr(c.rays), c.rays.shape[1], n, num_coarse, c.nf, int(bool(lindisp)), float(noise_std),
+            ptr(m_thres) if c.k else None, c.k, *[ptr(d) for d in c.draws], *[ptr(m) for m in maps]]
+    if quantiles is None:
+        check(lib().dn_render_rays_depth(*args, ptr(ws), stream()), "dn_render_rays_depth")
+        return maps
+    nq = int(quantiles.numel())
+    if not 1 <= nq <= _hip.MAX_QUANTILES or quantiles.dtype != torch.float32:
+        raise ValueError(f"render_rays_depth: quantiles must be a float32 device tensor of 1 .. {_hip.MAX_QUANTILES} values")
+    qdepth = _empty(dev, nq, n)
+    check(lib().dn_render_rays_depth_quantiles(*args, ptr(quantiles), nq, int(bool(interp)), ptr(qdepth), ptr(ws), stream()),
+          "dn_render_rays_depth_quantiles")
+    return maps + (qdepth,)
 
 
 # ---- density-gradient surface normals (include/dexnerf_hip_normals.h) ---------------------------------------------------------------
@@ -1358,20 +1360,14 @@ def composite_normals(rf, z, rd, g_pts, noise, noise_std, m_thres, want_dex=True
     """dn_composite_normals: (depth, acc, dex (K,N) | None, normal (N,3), dex_normal (K,N,3) | None) from the sigma column of rf (N,S,4)
     and the per-sample density gradients g_pts (N,S,3).  m_thres: a list of K thresholds or a device tensor of them (any K);
     want_dex=False leaves the Dex depths out (the Dex normals alone)."""
-    rf, z, g_pts = f32c(rf), f32c(z), f32c(g_pts)
-    n, s = z.shape
-    dev = rf.device
-    rd_ptr, rd_stride, rd = _dir_rows(rd)
-    th = m_thres
-    if th is not None and not torch.is_tensor(th):
-        th = torch.tensor([float(m) for m in th], dtype=torch.float32, device=dev) if len(th) else None
-    k = 0 if th is None else int(th.numel())
-    depth, acc, normal = _empty(dev, n), _empty(dev, n), _empty(dev, n, 3)
+    c = _sigma_call(rf, z, rd, noise, noise_std, m_thres)
+    g_pts = f32c(g_pts)
+    n, dev, k = c.n, c.dev, c.k
+    (depth, acc), normal = _pass_maps(dev, n), _empty(dev, n, 3)
     dex = _empty(dev, k, n) if (k and want_dex) else None
     dex_normal = _empty(dev, k, n, 3) if k else None
-    nz = None if (noise is None or noise_std <= 0.0) else f32c(noise)
-    check(lib().dn_composite_normals(ptr(rf), ptr(z), rd_ptr, rd_stride, ptr(nz), float(noise_std), ptr(g_pts), ptr(th) if k else None, k, n, s,
-                                     ptr(depth), ptr(acc), ptr(dex), ptr(normal), ptr(dex_normal), stream()), "dn_composite_normals")
+    check(lib().dn_composite_normals(*c.head, ptr(g_pts), ptr(c.thres), k, n, c.s, ptr(depth), ptr(acc), ptr(dex), ptr(normal),
+                                     ptr(dex_normal), stream()), "dn_composite_normals")
     return depth, acc, dex, normal, dex_normal
 
 
@@ -1425,30 +1421,19 @@ def render_rays_normals(packed_c, packed_f, streams, rays, num_coarse, num_fine,
     DensityGradStreams of the last pass's network (the fine one; the coarse one with num_fine == 0).  m_thres: a device tensor of K
     thresholds (any K) or None.  Returns (depth_c, acc_c, depth, acc, dex (K,N) | None, normal (N,3), dex_normal (K,N,3) | None);
     depth_c / acc_c are None without a fine pass."""
-    rays = f32c(rays)
-    n = rays.shape[0]
-    dev = rays.device
-    k = 0 if m_thres is None else int(m_thres.numel())
-    fine = num_fine > 0 and packed_f is not None
-    nf = num_fine if fine else 0
-    nbytes = _sized(render_normals_workspace_bytes(packed_c, packed_f, n, num_coarse, nf), "dn_render_normals_workspace_bytes")
+    c = _render_call(packed_c, packed_f, rays, num_fine, m_thres, draws)
+    n, dev, k = c.n, c.dev, c.k
+    nbytes = _sized(render_normals_workspace_bytes(packed_c, packed_f, n, num_coarse, c.nf), "dn_render_normals_workspace_bytes")
     # (a stream-ordered allocation per call, not the cached render workspace: the saved tensors make it large, and its status
     # block is not where render_status_words looks)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    depth_c, acc_c = (_empty(dev, n), _empty(dev, n)) if fine else (None, None)
-    depth, acc, normal = _empty(dev, n), _empty(dev, n), _empty(dev, n, 3)
-    dex = _empty(dev, k, n) if k else None
-    dex_normal = _empty(dev, k, n, 3) if k else None
-    t_rand, noise_c, u, noise_f = _draw_tensors(draws)
+    maps = _pass_maps(dev, n, c.fine) + _pass_maps(dev, n) + (_empty(dev, k, n) if k else None, _empty(dev, n, 3),
+                                                              _empty(dev, k, n, 3) if k else None)
     check(lib().dn_render_rays_normals(
-        ctypes.byref(packed_c.desc), ptr(packed_c.buffer),
-        ctypes.byref(packed_f.desc) if fine else None, ptr(packed_f.buffer) if fine else None,
-        ptr(streams.buffer_bwd), ptr(streams.buffer_ig), packed_c.precision,
-        ptr(rays), rays.shape[1], n, num_coarse, nf, int(bool(lindisp)), float(noise_std),
-        ptr(m_thres) if k else None, k, ptr(t_rand), ptr(noise_c), ptr(u), ptr(noise_f),
-        ptr(depth_c), ptr(acc_c), ptr(depth), ptr(acc), ptr(dex), ptr(normal), ptr(dex_normal), ptr(ws), nbytes, stream()),
-        "dn_render_rays_normals")
-    return depth_c, acc_c, depth, acc, dex, normal, dex_normal
+        *c.net_args, ptr(streams.buffer_bwd), ptr(streams.buffer_ig), packed_c.precision, ptr(c.rays), c.rays.shape[1], n, num_coarse, c.nf,
+        int(bool(lindisp)), float(noise_std), ptr(m_thres) if k else None, k, *[ptr(d) for d in c.draws], *[ptr(m) for m in maps],
+        ptr(ws), nbytes, stream()), "dn_render_rays_normals")
+    return maps
 
 
 def render_status_words(ws=None):
@@ -1472,12 +1457,8 @@ def render_rays_train(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, n
     """dn_render_rays_train: the training forward of a whole ray chunk.  Returns (maps, saved): maps = (rgb_c, depth_c, acc_c,
     rgb_f, depth_f, acc_f, dex), saved = what dn_render_rays_backward needs (workspace, per-network act / masks, the draws).
     geom=True: dn_render_rays_train_geom - saved also holds the fine pass's resamples and what render_rays_backward_geom needs."""
-    rays = f32c(rays)
-    n = rays.shape[0]
-    dev = rays.device
-    k = len(m_thres)
-    fine = num_fine > 0 and packed_f is not None
-    nf = num_fine if fine else 0
+    c = _render_call(packed_c, packed_f, rays, num_fine, m_thres, draws)
+    rays, n, dev, fine, nf, k = c.rays, c.n, c.dev, c.fine, c.nf, c.k
     ws = torch.empty(max(lib().dn_render_train_workspace_bytes(n, num_coarse, nf), 1), dtype=torch.uint8, device=dev)
     prec = train_precision(packed_c) if prec is None else prec
 
@@ -1486,15 +1467,10 @@ def render_rays_train(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, n
         return torch.empty(a, dtype=torch.uint8, device=dev), torch.empty(m, dtype=torch.uint8, device=dev)
     act_c, masks_c = bufs(packed_c, n * num_coarse)
     act_f, masks_f = bufs(packed_f, n * (num_coarse + nf)) if fine else (None, None)
-    rgb_c, depth_c, acc_c = _empty(dev, n, 3), _empty(dev, n), _empty(dev, n)
-    rgb_f, depth_f, acc_f = (_empty(dev, n, 3), _empty(dev, n), _empty(dev, n)) if fine else (None, None, None)
-    dex = _empty(dev, k, n) if k else None
-    t_rand, noise_c, u, noise_f = _draw_tensors(draws)
-    args = [ctypes.byref(packed_c.desc), ptr(packed_c.buffer),
-            ctypes.byref(packed_f.desc) if fine else None, ptr(packed_f.buffer) if fine else None, prec,
-            ptr(rays), rays.shape[1], n, num_coarse, nf, int(bool(lindisp)), float(noise_std), int(bool(white)),
-            host_floats(m_thres), k, ptr(t_rand), ptr(noise_c), ptr(u), ptr(noise_f),
-            ptr(rgb_c), ptr(depth_c), ptr(acc_c), ptr(rgb_f), ptr(depth_f), ptr(acc_f), ptr(dex), ptr(ws),
+    maps = _pass_maps(dev, n, rgb=True) + _pass_maps(dev, n, fine, rgb=True) + (_empty(dev, k, n) if k else None,)
+    t_rand, noise_c, _, noise_f = c.draws
+    args = [*c.net_args, prec, ptr(rays), rays.shape[1], n, num_coarse, nf, int(bool(lindisp)), float(noise_std), int(bool(white)),
+            host_floats(m_thres), k, *[ptr(d) for d in c.draws], *[ptr(m) for m in maps], ptr(ws),
             ptr(act_c), ptr(masks_c), ptr(act_f), ptr(masks_f), ptr(rng_state), int(bool(perturb))]
     saved = dict(rays=rays, ws=ws, act_c=act_c, masks_c=masks_c, act_f=act_f, masks_f=masks_f, noise_c=noise_c,
                  noise_f=noise_f, n=n, nc=num_coarse, nf=nf, noise_std=float(noise_std), white=bool(white), prec=prec,
@@ -1505,7 +1481,7 @@ def render_rays_train(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, n
         saved.update(t_rand=t_rand, z_samples=z_samples, lindisp=bool(lindisp), perturb=bool(perturb))
     else:
         check(lib().dn_render_rays_train(*args, stream()), "dn_render_rays_train")
-    return (rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f, dex), saved
+    return maps, saved
 
 
 def _backward_args(packed_c, packed_f, saved, g_c, g_f, views_c, views_f, nets, wgrad):
@@ -1532,8 +1508,7 @@ def render_rays_backward(packed_c, packed_f, saved, g_c, g_f, views_c, views_f, 
     ([coarse, fine]; a half writes its own word)."""
     n, nc, nf, prec = saved["n"], saved["nc"], saved["nf"], saved["prec"]
     fine, grads_c, grads_f, ptrs, gs, (scratch, scratch_bytes) = _backward_args(packed_c, packed_f, saved, g_c, g_f, views_c, views_f, nets, True)
-    args = [ctypes.byref(packed_c.desc), ptr(packed_c.buffers_bwd[prec]),
-            ctypes.byref(packed_f.desc) if fine else None, ptr(packed_f.buffers_bwd[prec]) if fine else None, prec,
+    args = [*_net_args(packed_c, packed_f, fine, "buffers_bwd", prec), prec,
             ptr(saved["rays"]), saved["rays"].shape[1], n, nc, nf, saved["noise_std"], int(saved["white"]),
             ptr(saved["noise_c"]), ptr(saved["noise_f"]), *[ptr(g) for g in gs],
             ptr(saved["ws"]), ptr(saved["act_c"]), ptr(saved["masks_c"]), ptr(grads_c), ptr(saved["act_f"]), ptr(saved["masks_f"]),

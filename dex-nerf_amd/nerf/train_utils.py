@@ -369,6 +369,50 @@ def _threshold_tensor(thres, dev):
     return t
 
 
+def _require_density_net(model, encode_position_fn, who):
+    if not _fusable(model, encode_position_fn, None, density=True):
+        raise RuntimeError(f"{who}: needs FlexibleNeRFModel networks the fused HIP kernels cover (fused_ok()) and this package's "
+                           "position embedder with the network's encoding; there is no fallback")
+    _require_device(model.layer1.weight, who)
+
+
+_DensityRender = collections.namedtuple("_DensityRender", "rays img_shape dev nc nf fine models lindisp std perturb lx m_thres")
+
+
+def _density_render_setup(who, instead, height, width, focal_length, model_coarse, model_fine, ray_origins, ray_directions, options, mode,
+                          encode_position_fn, m_thres_cand):
+    """What the density renders (render_dex_depth, render_dex_normals) settle before their chunk loops, every refusal before any GPU
+    work: no autograd (`instead`: where the message sends the caller), device rays, density networks the fused kernels cover; then
+    the NDC warp, the ray rows without view-direction columns (the density sub-network does not read them), the mode's options and
+    the thresholds on the device.  nf is 0 without a fine pass."""
+    opt = getattr(options.nerf, mode)
+    nc, nf = int(opt.num_coarse), int(opt.num_fine)
+    fine = nf > 0 and bool(model_fine)
+    models = [model_coarse] + ([model_fine] if fine else [])
+    if _wants_grad(*models) or inputs_need_grad(ray_origins, ray_directions):
+        raise RuntimeError(f"{who} is a no-grad render: call it under torch.no_grad() (or with parameters and rays that do "
+                           f"not require grad); {instead}")
+    _require_device(ray_directions, who)
+    _require_device(ray_origins, who)
+    for m in models:
+        _require_density_net(m, encode_position_fn, who)
+    dev = ray_directions.device
+    if options.dataset.no_ndc is False:
+        ro, rd = ndc_rays(height, width, focal_length, 1.0, ray_origins, ray_directions)
+    else:
+        ro, rd = ray_origins, ray_directions
+    ro, rd = ro.reshape((-1, 3)).float(), rd.reshape((-1, 3)).float()
+    rays = _ops.pack_ray_rows(ro.contiguous(), rd.contiguous(), None, options.dataset.near, options.dataset.far)
+    return _DensityRender(rays, ray_directions.shape, dev, nc, nf if fine else 0, fine, models, bool(opt.lindisp),
+                          float(opt.radiance_field_noise_std), bool(opt.perturb), encode_position_fn.log_sampling,
+                          _threshold_tensor(_thresholds(m_thres_cand), dev))
+
+
+def _density_packs(r, prec):
+    """(coarse, fine | None) density packs of a _DensityRender's networks in precision `prec`."""
+    return tuple(m.packed_density(r.lx, True, precision=prec) for m in r.models) + (() if r.fine else (None,))
+
+
 def render_dex_depth(height, width, focal_length, model_coarse, model_fine, ray_origins, ray_directions, options,
                      mode="validation", encode_position_fn=None, encode_direction_fn=None, m_thres_cand=None, quantiles=None,
                      quantile_interp=False):
@@ -389,37 +433,10 @@ def render_dex_depth(height, width, focal_length, model_coarse, model_fine, ray_
     whose accumulation stays below q reports its LAST sample's depth (it went through) - not z[0] like a Dex depth without a crossing.
     quantiles=None: the launches and the return are what they were."""
     qs = None if quantiles is None else _ops.check_quantiles(quantiles, "render_dex_depth: quantiles")
-    _require_device(ray_directions, "render_dex_depth")
-    _require_device(ray_origins, "render_dex_depth")
-    opt = getattr(options.nerf, mode)
-    nc, nf = int(opt.num_coarse), int(opt.num_fine)
-    fine = nf > 0 and bool(model_fine)
-    models = [model_coarse] + ([model_fine] if fine else [])
-    for m in models:
-        if not _fusable(m, encode_position_fn, None, density=True):
-            raise RuntimeError("render_dex_depth: needs FlexibleNeRFModel networks the fused HIP kernels cover (fused_ok()) and this "
-                               "package's position embedder with the network's encoding; there is no fallback")
-        _require_device(m.layer1.weight, "render_dex_depth")
-    if _wants_grad(*models) or inputs_need_grad(ray_origins, ray_directions):
-        raise RuntimeError("render_dex_depth is a no-grad render: call it under torch.no_grad() (or with parameters and rays that do "
-                           "not require grad); differentiable renders go through run_one_iter_of_nerf")
-    thres = _thresholds(m_thres_cand)
-    dev = ray_directions.device
-    img_shape = ray_directions.shape
-    if options.dataset.no_ndc is False:
-        ro, rd = ndc_rays(height, width, focal_length, 1.0, ray_origins, ray_directions)
-    else:
-        ro, rd = ray_origins, ray_directions
-    ro, rd = ro.reshape((-1, 3)).float(), rd.reshape((-1, 3)).float()
-    # ray rows without the view-direction columns: the density sub-network does not read them
-    rays = _ops.pack_ray_rows(ro.contiguous(), rd.contiguous(), None, options.dataset.near, options.dataset.far)
-    perturb = bool(opt.perturb)
-    std = float(opt.radiance_field_noise_std)
-    lindisp = bool(opt.lindisp)
-    lx = encode_position_fn.log_sampling
-    m_thres = _threshold_tensor(thres, dev)
-    q_dev = _threshold_tensor(qs, dev) if qs else None   # (the same cache: one host-to-device copy per quantile set)
-    guard = _fp16_guard(models, density=True)
+    r = _density_render_setup("render_dex_depth", "differentiable renders go through run_one_iter_of_nerf", height, width, focal_length,
+                              model_coarse, model_fine, ray_origins, ray_directions, options, mode, encode_position_fn, m_thres_cand)
+    q_dev = _threshold_tensor(qs, r.dev) if qs else None   # (the same cache: one host-to-device copy per quantile set)
+    guard = _fp16_guard(r.models, density=True)
     # precision code -> the density packs: fetched once per pass over the chunks, not per chunk (a pass runs in one precision, and
     # the re-render after a trip in another - the configured one is never the guarded one - so it fetches its own)
     packs = {}
@@ -427,24 +444,18 @@ def render_dex_depth(height, width, focal_length, model_coarse, model_fine, ray_
     def render_chunk(batch, status):
         prec, guarded = guard if status is not None else (_ops._precision, False)
         if prec not in packs:
-            packs[prec] = (model_coarse.packed_density(lx, True, precision=prec),
-                           model_fine.packed_density(lx, True, precision=prec) if fine else None)
-        draws = _draws(batch.shape[0], nc, nf, fine, perturb, std, dev)
-        if q_dev is None:
-            depth_c, acc_c, depth_f, acc_f, dex = _ops.render_rays_depth(*packs[prec], batch, nc, nf if fine else 0, lindisp, std, m_thres,
-                                                                        draws)
-            qdepth = None
-        else:
-            depth_c, acc_c, depth_f, acc_f, dex, qdepth = _ops.render_rays_depth(*packs[prec], batch, nc, nf if fine else 0, lindisp, std,
-                                                                                m_thres, draws, quantiles=q_dev, interp=quantile_interp)
+            packs[prec] = _density_packs(r, prec)
+        draws = _draws(batch.shape[0], r.nc, r.nf, r.fine, r.perturb, r.std, r.dev)
+        depth_c, acc_c, depth_f, acc_f, dex, *qdepth = _ops.render_rays_depth(*packs[prec], batch, r.nc, r.nf, r.lindisp, r.std, r.m_thres, draws,
+                                                                              quantiles=q_dev, interp=quantile_interp)
         maps = [depth_c, acc_c, depth_f, acc_f] + ([] if dex is None else [dex[k] for k in range(dex.shape[0])])
-        maps += [] if qdepth is None else [qdepth[k] for k in range(qdepth.shape[0])]
+        maps += [qdepth[0][k] for k in range(qdepth[0].shape[0])] if qdepth else []
         words = _ops.render_status_words()   # (copied for unguarded chunks too, as it always was: same launches on every path)
         if guarded:
             status.append(words)
         return maps
-    maps = _render_chunks(rays, opt.chunksize, render_chunk)
-    return _to_image(maps, [img_shape[:-1]] * len(maps)) if mode == "validation" else tuple(maps)
+    maps = _render_chunks(r.rays, getattr(options.nerf, mode).chunksize, render_chunk)
+    return _to_image(maps, [r.img_shape[:-1]] * len(maps)) if mode == "validation" else tuple(maps)
 
 
 # ---- density-gradient surface normals ------------------------------------------------------------------------------------------------
@@ -458,13 +469,6 @@ def _normals_precision(who):
         raise RuntimeError(f"{who}: the density gradient runs on the training kernels, which exist for fp32 and bf16 - not under "
                            "nerf.set_precision('fp16')")
     return _ops._precision
-
-
-def _require_density_net(model, encode_position_fn, who):
-    if not _fusable(model, encode_position_fn, None, density=True):
-        raise RuntimeError(f"{who}: needs FlexibleNeRFModel networks the fused HIP kernels cover (fused_ok()) and this package's "
-                           "position embedder with the network's encoding; there is no fallback")
-    _require_device(model.layer1.weight, who)
 
 
 def density_gradient(model, pts, encode_position_fn, chunksize=1 << 16):
@@ -524,52 +528,30 @@ def render_dex_normals(height, width, focal_length, model_coarse, model_fine, ra
     fp16 render policy (nerf.set_render_policy) and its range guard do not apply here.  The last pass's sigma comes from the
     training-forward kernel: depth may differ from render_dex_depth's in the last bits."""
     prec = _normals_precision("render_dex_normals")
-    opt = getattr(options.nerf, mode)
-    nc, nf = int(opt.num_coarse), int(opt.num_fine)
-    fine = nf > 0 and bool(model_fine)
-    nf = nf if fine else 0
-    models = [model_coarse] + ([model_fine] if fine else [])
-    if _wants_grad(*models) or inputs_need_grad(ray_origins, ray_directions):
-        raise RuntimeError("render_dex_normals is a no-grad render: call it under torch.no_grad() (or with parameters and rays that do "
-                           "not require grad); gradients through the normals are second order and not provided")
-    _require_device(ray_directions, "render_dex_normals")
-    _require_device(ray_origins, "render_dex_normals")
-    for m in models:
-        _require_density_net(m, encode_position_fn, "render_dex_normals")
-    thres = _thresholds(m_thres_cand)
-    dev = ray_directions.device
-    img_shape = ray_directions.shape
-    if options.dataset.no_ndc is False:
-        ro, rd = ndc_rays(height, width, focal_length, 1.0, ray_origins, ray_directions)
-    else:
-        ro, rd = ray_origins, ray_directions
-    ro, rd = ro.reshape((-1, 3)).float(), rd.reshape((-1, 3)).float()
-    rays = _ops.pack_ray_rows(ro.contiguous(), rd.contiguous(), None, options.dataset.near, options.dataset.far)
-    perturb = bool(opt.perturb)
-    std = float(opt.radiance_field_noise_std)
-    lindisp = bool(opt.lindisp)
-    lx = encode_position_fn.log_sampling
-    m_thres = _threshold_tensor(thres, dev)
-    packs = (model_coarse.packed_density(lx, True, precision=prec), model_fine.packed_density(lx, True, precision=prec) if fine else None)
-    streams = models[-1].packed_density_grad(lx, True, precision=prec)
+    r = _density_render_setup("render_dex_normals", "gradients through the normals are second order and not provided", height, width,
+                              focal_length, model_coarse, model_fine, ray_origins, ray_directions, options, mode, encode_position_fn,
+                              m_thres_cand)
+    nc, nf = r.nc, r.nf
+    k = 0 if r.m_thres is None else int(r.m_thres.numel())
+    packs = _density_packs(r, prec)
+    streams = r.models[-1].packed_density_grad(r.lx, True, precision=prec)
     max_bytes = int(max_workspace_bytes)
 
     def render_chunk(batch):
         n = batch.shape[0]
-        draws = _draws(n, nc, nf, fine, perturb, std, dev)
+        draws = _draws(n, nc, nf, r.fine, r.perturb, r.std, r.dev)
         step = _rays_within_workspace(packs, n, nc, nf, max_bytes)
         pieces = []
         for r0 in range(0, n, step):
             rows = slice(r0, min(r0 + step, n))
             _, _, depth, acc, dex, normal, dex_normal = _ops.render_rays_normals(
-                *packs, streams, batch[rows], nc, nf, lindisp, std, m_thres, {name: d[rows] for name, d in draws.items()})
-            pieces.append([depth, acc, normal] + [dex[k] for k in range(len(thres))] + [dex_normal[k] for k in range(len(thres))])
+                *packs, streams, batch[rows], nc, nf, r.lindisp, r.std, r.m_thres, {name: d[rows] for name, d in draws.items()})
+            pieces.append([depth, acc, normal] + [dex[i] for i in range(k)] + [dex_normal[i] for i in range(k)])
         return _join_chunks(pieces)
-    maps = _join_chunks([render_chunk(batch) for batch in get_minibatches(rays, chunksize=opt.chunksize)])
+    maps = _join_chunks([render_chunk(batch) for batch in get_minibatches(r.rays, chunksize=getattr(options.nerf, mode).chunksize)])
     if mode == "validation":
-        flat, vec = img_shape[:-1], img_shape
-        maps = _to_image(maps, [flat, flat, vec] + [flat] * len(thres) + [vec] * len(thres))
-    k = len(thres)
+        flat, vec = r.img_shape[:-1], r.img_shape
+        maps = _to_image(maps, [flat, flat, vec] + [flat] * k + [vec] * k)
     return DexNormals(maps[0], maps[1], maps[2], tuple(maps[3:3 + k]), tuple(maps[3 + k:3 + 2 * k]))
 
 

@@ -18,8 +18,12 @@ The one-body refactor of the loss heads and the forward compositing added loss_h
 list the cases): dn_mse2_loss, dn_render_loss and dn_render_loss_exposure at 1, 65 and 1025 rays, and on 5 rays dn_volume_render,
 dn_composite_density(_quantiles), dn_composite_normals, dn_density_resample, dn_volume_render_backward(_geom), a training render that
 draws its density noise in the compositing kernel and a render with DEXNERF_FUSED_COMPOSITE=1.  Their thousands of small outputs are
-folded into one digest per group of cases (fold_into)."""
+folded into one digest per group of cases (fold_into).
+
+The pass that gave the density renders one driver per layer added density_renders() (its docstring lists the cases;
+--density-renders runs it alone): profiles/density_render_refactor_bits_{parent,change}.json."""
 import argparse
+import ctypes
 import hashlib
 import json
 import os
@@ -45,11 +49,13 @@ V = 3
 NDC_FOCAL = 14.0
 OUT = {}
 FOLD = []
+TENSORS = [0]     # tensors hashed (the outputs a call does not produce, None, are not counted)
 
 
 def record(name, *tensors):
     """sha256 of each tensor's bytes (None: "-") under name, name.1, ...; after fold_into(label) the bytes go, in call order, into the
     one digest kept under the label instead."""
+    TENSORS[0] += sum(t is not None for t in tensors)
     if FOLD:
         for t in tensors:
             FOLD[-1][1].update(b"-" if t is None else t.detach().contiguous().cpu().numpy().tobytes())
@@ -347,30 +353,163 @@ def forward_compositing(dev):
         nerf.set_precision("fp32")
 
 
+def density_renders(dev):
+    """The density renders and what stands beside them, for the pass that gave them one driver per layer.  Two seeded 4 x 128 networks
+    (L_xyz = 10; full packs for render_rays, density packs for the rest).  5 and 37 rays (0 where the wrapper allows it: elsewhere the
+    refusal's text is recorded), 16 + 16 samples and coarse-only; (K, noise_std, lindisp) in (0, 0, off), (1, 0.3, on), (65, 0.3, off)
+    with given noise tensors (render_rays: K = 64, the host limit); fp32 and bf16, render_rays also in the fp16-guarded default;
+    Q = 1 and 64 quantiles with interp 0 and 1; the status words after every render.  The standalone compositing calls at 130
+    samples (a third chunk).  render_dex_depth (with and without quantiles) and render_dex_normals on a 6 x 7 image in validation
+    mode with chunksize 16 (three chunks, a short last one), world and NDC.  The answers of seven *_workspace_bytes functions.
+    One digest per group of cases (fold_into); the refusals are kept as text."""
+    import nerf
+    from nerf import _hip, _ops
+    lib = _hip.lib()
+    mc, mf = models_on(dev)
+    thres = lambda k: [0.05 + 2.5 * i / max(k, 1) for i in range(k)]
+    quants = lambda q: [(i + 1.0) / (q + 1.0) for i in range(q)]
+    on_dev = lambda values: torch.tensor(values, dtype=torch.float32, device=dev) if values else None
+
+    def refusal(name, fn):
+        try:
+            fn()
+        except (RuntimeError, ValueError) as e:
+            OUT[name] = f"refused: {e}"
+        else:
+            OUT[name] = "accepted"
+
+    def rows_of(n):
+        rd = rand(70 + n, n, 3, normal=True)
+        return torch.cat([rand(80 + n, n, 3) - 0.5, rd, torch.full((n, 1), 2.0, device=dev), torch.full((n, 1), 6.0, device=dev),
+                          torch.nn.functional.normalize(rd, dim=-1)], dim=1).contiguous()
+
+    def draws_of(n, nf, std):
+        d = dict(t_rand=rand(90, n, 16), u=rand(91, n, nf) if nf else None)
+        if std:
+            d.update(noise_c=rand(92, n, 16, normal=True), noise_f=rand(93, n, 16 + nf, normal=True) if nf else None)
+        return d
+    settings = ((0, 0.0, False), (1, 0.3, True), (65, 0.3, False))
+    nerf.set_precision("bf16")
+    guarded = _ops.render_precision()
+    nerf.set_precision("fp32")
+    for pname, prec in (("fp32", _hip.PREC_F32), ("bf16", _hip.PREC_BF16), ("guarded", guarded)):
+        full = (mc.packed(precision=prec), mf.packed(precision=prec))
+        for n in (0, 5, 37):
+            fold_into(f"render_rays {pname} n={n}")
+            for nf in (16, 0):
+                for k, std, lindisp in settings:
+                    what = f"{pname} n={n} 16+{nf} K={k} noise={std} lindisp={lindisp}"
+                    maps = _ops.render_rays(*full, rows_of(n), 16, nf, lindisp, std, k == 1, thres(min(k, 64)), draws_of(n, nf, std))
+                    # (an empty call returns before the status block is zeroed: its words are not this call's)
+                    record(f"render_rays {what}", *maps, _ops.render_status_words() if n else None)
+        if pname == "guarded":
+            continue
+        dens = (mc.packed_density(True, True, precision=prec), mf.packed_density(True, True, precision=prec))
+        streams = (mc.packed_density_grad(True, True, precision=prec), mf.packed_density_grad(True, True, precision=prec))
+        for nf in (16, 0):
+            refusal(f"render_rays_depth {pname} n=0 16+{nf}", lambda: _ops.render_rays_depth(*dens, rows_of(0), 16, nf, False, 0.0, None))
+            refusal(f"render_rays_normals {pname} n=0 16+{nf}",
+                    lambda: _ops.render_rays_normals(*dens, streams[1 if nf else 0], rows_of(0), 16, nf, False, 0.0, None))
+        for n in (5, 37):
+            fold_into(f"render_rays_depth (also with quantiles), render_rays_normals {pname} n={n}")
+            for nf in (16, 0):
+                for k, std, lindisp in settings:
+                    what = f"{pname} n={n} 16+{nf} K={k} noise={std} lindisp={lindisp}"
+                    args = (rows_of(n)[:, :8].contiguous(), 16, nf, lindisp, std, on_dev(thres(k)), draws_of(n, nf, std))
+                    record(f"render_rays_depth {what}", *_ops.render_rays_depth(*dens, *args), _ops.render_status_words())
+                    for q in (1, 64):
+                        for interp in (False, True):
+                            record(f"render_rays_depth {what} Q={q} interp={interp}",
+                                   *_ops.render_rays_depth(*dens, *args, quantiles=on_dev(quants(q)), interp=interp), _ops.render_status_words())
+                    record(f"render_rays_normals {what}", *_ops.render_rays_normals(*dens, streams[1 if nf else 0], *args))
+    # the standalone compositing calls: a third 64-sample chunk
+    s = 130
+    for n in (0, 5, 37):
+        rd = rand(100 + n, n, 3, normal=True)
+        rf = rand(101, n, s, 4, normal=True)
+        z = torch.sort(2.0 + 4.0 * rand(102, n, s), dim=1).values
+        g_pts = rand(103, n, s, 3, normal=True)
+        fold_into(f"standalone compositing n={n} s={s}")
+        for k, std, _ in settings:
+            noise = rand(104, n, s, normal=True) if std else None
+            what = f"n={n} s={s} K={k} noise={std}"
+            if n == 0:
+                refusal(f"composite_density_quantiles {what}", lambda: _ops.composite_density_quantiles(rf, z, rd, noise, std, thres(k), quants(1)))
+                refusal(f"composite_normals {what}", lambda: _ops.composite_normals(rf, z, rd, g_pts, noise, std, thres(k)))
+            else:
+                for q in (1, 64):
+                    for interp in (False, True):
+                        record(f"composite_density_quantiles {what} Q={q} interp={interp}",
+                               *_ops.composite_density_quantiles(rf, z, rd, noise, std, thres(k), quants(q), interp))
+                record(f"composite_normals {what}", *_ops.composite_normals(rf, z, rd, g_pts, noise, std, thres(k)))
+                record(f"composite_normals no dex {what}", *_ops.composite_normals(rf, z, rd, g_pts, noise, std, on_dev(thres(k)), want_dex=False))
+            record(f"composite_density {what}", *_ops.composite_density(rf, z, rd, noise, std, thres(k)))
+            record(f"density_resample {what}", *_ops.density_resample(rf, z, rd, 65, noise, std, rand(105, n, 65)))
+    # the image-level renders: 6 x 7, validation mode, three chunks of 16, 16, 10 rays
+    from nerf import synthetic as syn
+    h, w = 6, 7
+    mode = dict(chunksize=16, lindisp=False, num_coarse=16, num_fine=16, perturb=False, radiance_field_noise_std=0.0, white_background=False)
+    ex = nerf.get_embedding_function(10, True, True)
+    k_mat = torch.from_numpy(syn.intrinsic(h, w)).to(dev)
+    focal = float(k_mat[0, 0])
+    ro, rd = nerf.get_ray_bundle(h, w, focal, torch.from_numpy(syn.scene_pose(3)).to(dev), k_mat)
+    for space, dataset in (("world", dict(near=2.0, far=6.0, no_ndc=True)), ("ndc", dict(near=0.0, far=1.0, no_ndc=False))):
+        for nf in (16, 0):
+            cfg = nerf.CfgNode(dict(dataset=dataset, nerf=dict(use_viewdirs=True, train=dict(mode, num_fine=nf), validation=dict(mode, num_fine=nf))))
+            for precision in ("fp32", "bf16"):
+                nerf.set_precision(precision)
+                what = f"{space} 16+{nf} {precision}"
+                fold_into(f"render_dex_depth (also with quantiles), render_dex_normals 6 x 7 {what}")
+                with torch.no_grad():
+                    for qs in (None, (0.1, 0.5, 0.9)):
+                        maps = nerf.render_dex_depth(h, w, focal, mc, mf, ro, rd, cfg, mode="validation", encode_position_fn=ex,
+                                                     m_thres_cand=thres(2), quantiles=qs, quantile_interp=qs is not None)
+                        record(f"render_dex_depth {what} quantiles={qs}", *maps, _ops.render_status_words())
+                    out = nerf.render_dex_normals(h, w, focal, mc, mf, ro, rd, cfg, mode="validation", encode_position_fn=ex, m_thres_cand=thres(2))
+                    record(f"render_dex_normals {what}", out.depth, out.acc, out.normal, *out.dex_depth, *out.dex_normal)
+    nerf.set_precision("fp32")
+    fold_into(None)
+    # the workspace sizes
+    full_desc, dens_desc = mc.packed(precision=_hip.PREC_F32).desc, mc.packed_density(True, True, precision=_hip.PREC_F32).desc
+    sizes = []
+    for n in (0, 1, 5, 4097):
+        for nc, nf in ((16, 0), (16, 16), (64, 128)):
+            d, f = ctypes.byref(dens_desc), ctypes.byref(full_desc)
+            sizes.append([lib.dn_render_workspace_bytes(n, nc, nf), lib.dn_render_depth_workspace_bytes(n, nc, nf),
+                          lib.dn_render_train_workspace_bytes(n, nc, nf), lib.dn_render_reg_workspace_bytes(n, nc, nf),
+                          lib.dn_render_normals_workspace_bytes(d, d if nf else None, _hip.PREC_F32, n, nc, nf),
+                          lib.dn_render_normals_workspace_bytes(d, d if nf else None, _hip.PREC_BF16, n, nc, nf),
+                          lib.dn_render_backward_geom_workspace_bytes(f, f if nf else None, n, 11, nc, nf)])
+    OUT["workspace bytes (render, depth, train, reg, normals fp32, normals bf16, backward_geom) over n x (nc, nf)"] = json.dumps(sizes)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tree", default="", help="import the package of this checkout (built there) instead of this script's")
     ap.add_argument("--out", required=True)
+    ap.add_argument("--density-renders", action="store_true", help="the density_renders() group alone")
     args = ap.parse_args()
     from nerf import _ops, synthetic as syn
     dev = torch.device("cuda:0")
-    e0 = torch.stack([torch.from_numpy(syn.scene_pose(v, n_views=8)) for v in range(V)]).to(dev)
-    k = torch.from_numpy(syn.intrinsic(H, W)).to(dev)
-    xi = torch.zeros(V, 6, device=dev)
-    cams, cams_ndc = _ops.pose_records(xi, e0, k), _ops.pose_records(xi, e0, k, ndc_focal=NDC_FOCAL)
-    images = rand(1, V, H, W, 3)
-    batches = selection(dev, cams, cams_ndc, images)
-    render(dev, batches)
-    compositing(dev, batches)
-    moved(dev, batches, cams, cams_ndc)
-    loss_heads(dev)
-    fold_into(None)
-    forward_compositing(dev)
+    if not args.density_renders:
+        e0 = torch.stack([torch.from_numpy(syn.scene_pose(v, n_views=8)) for v in range(V)]).to(dev)
+        k = torch.from_numpy(syn.intrinsic(H, W)).to(dev)
+        xi = torch.zeros(V, 6, device=dev)
+        cams, cams_ndc = _ops.pose_records(xi, e0, k), _ops.pose_records(xi, e0, k, ndc_focal=NDC_FOCAL)
+        images = rand(1, V, H, W, 3)
+        batches = selection(dev, cams, cams_ndc, images)
+        render(dev, batches)
+        compositing(dev, batches)
+        moved(dev, batches, cams, cams_ndc)
+        loss_heads(dev)
+        fold_into(None)
+        forward_compositing(dev)
+    density_renders(dev)
     torch.cuda.synchronize()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as fh:
-        json.dump(dict(device=torch.cuda.get_device_name(0), sha256=OUT), fh, indent=1, sort_keys=True)
-    print(f"{len(OUT)} tensors hashed -> {args.out}")
+        json.dump(dict(device=torch.cuda.get_device_name(0), sha256=OUT, tensors=TENSORS[0]), fh, indent=1, sort_keys=True)
+    print(f"{TENSORS[0]} tensors hashed into {len(OUT)} entries -> {args.out}")
 
 
 if __name__ == "__main__":
