@@ -20,15 +20,15 @@
 // hits) and writes 2 B; the scan passes read 2 B twice and write 8 B; emit reads 2 B per vertex and touches the field and the prefixes
 // only at surface cells.
 #include "../../include/dexnerf_hip_mesh.h"
-#include "dn_common.h"
+#include "scan_blocks.h"
 
 namespace dn {
 namespace iso {
 
-constexpr int kThreads = 256;
-constexpr int kPerThread = 4;
+constexpr int kThreads = kScanThreads;
+constexpr int kPerThread = kScanPerThread;
 constexpr int kScanBlock = DN_ISO_SCAN_BLOCK;   // elements per workgroup at every scan level
-static_assert(kScanBlock == kThreads * kPerThread, "a workgroup scans 256 x 4 elements");
+static_assert(kScanBlock == kScanElems && kScanBlock == kThreads * kPerThread, "a workgroup scans 256 x 4 elements (scan_blocks.h)");
 constexpr int64_t kMaxVertices = DN_ISO_MAX_GRID_VERTICES;
 // the top scan level is one workgroup; 7 mesh vertices per grid vertex stay inside int32
 static_assert(kMaxVertices <= static_cast<int64_t>(kScanBlock) * kScanBlock * kScanBlock && 7 * kMaxVertices < (int64_t{1} << 31), "limits");
@@ -144,34 +144,6 @@ __device__ __forceinline__ unsigned tet_case(unsigned fin, unsigned ins, int p) 
   return (ins & 1) | ((ins >> c1) & 1) << 1 | ((ins >> c2) & 1) << 2 | ((ins >> 7) & 1) << 3;
 }
 
-__device__ __forceinline__ unsigned wave_scan_add(unsigned v) {
-  const int l = lane_id();
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned t = __shfl_up(v, o, 64);
-    if (l >= o) v += t;
-  }
-  return v;
-}
-
-// Exclusive prefix of one value per thread over the 256 threads of the workgroup, in thread order; `total`: the workgroup's sum.
-// `lds`: 4 words of this call's own.
-__device__ __forceinline__ unsigned block_scan_exclusive(unsigned x, unsigned* lds, unsigned& total) {
-  const unsigned inc = wave_scan_add(x);
-  const int w = threadIdx.x >> 6;
-  if (lane_id() == kWave - 1) lds[w] = inc;
-  __syncthreads();
-  unsigned before = 0, all = 0;
-#pragma unroll
-  for (int q = 0; q < kThreads / kWave; ++q) {
-    const unsigned s = lds[q];
-    before += q < w ? s : 0u;
-    all += s;
-  }
-  total = all;
-  return before + inc - x;
-}
-
 __device__ __forceinline__ unsigned edges_of(unsigned word) { return __popc(word & 0x7Fu); }
 __device__ __forceinline__ unsigned triangles_of(unsigned word) { return (word >> 8) & 0xFu; }
 
@@ -220,20 +192,7 @@ __global__ __launch_bounds__(kThreads) void block_totals_kernel(const uint16_t* 
   if (threadIdx.x == 0) { tot_v[blockIdx.x] = av; tot_t[blockIdx.x] = at; tot_n[blockIdx.x] = an; }
 }
 
-// a[0 .. n) -> its exclusive prefix inside every block of 1024, in place; up[b]: the sum of block b
-__device__ __forceinline__ void scan_row(unsigned* __restrict__ a, unsigned n, unsigned* __restrict__ up, unsigned* lds) {
-  const unsigned e0 = blockIdx.x * kScanBlock + threadIdx.x * kPerThread;
-  unsigned x[kPerThread], s = 0;
-#pragma unroll
-  for (int q = 0; q < kPerThread; ++q) { x[q] = e0 + q < n ? a[e0 + q] : 0u; s += x[q]; }
-  unsigned all, run = block_scan_exclusive(s, lds, all);
-#pragma unroll
-  for (int q = 0; q < kPerThread; ++q) {
-    if (e0 + q < n) a[e0 + q] = run;
-    run += x[q];
-  }
-  if (threadIdx.x == 0) up[blockIdx.x] = all;
-}
+// (scan_row of scan_blocks.h: a row's exclusive prefix inside every block of 1024, in place, and the blocks' sums one level up)
 __global__ __launch_bounds__(kThreads) void scan_totals_kernel(unsigned* __restrict__ a_v, unsigned* __restrict__ a_t, unsigned* __restrict__ a_n,
                                                                unsigned n, unsigned* __restrict__ up_v, unsigned* __restrict__ up_t,
                                                                unsigned* __restrict__ up_n, unsigned* __restrict__ reserved) {
@@ -353,8 +312,6 @@ struct Layout {
   size_t cls, vbase, tbase, tot0, tot1, bytes;      // byte offsets of the regions; tot0 / tot1 hold three rows of row0 / row1 words
   size_t row0, row1;
 };
-
-constexpr size_t up256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
 
 // false: a grid the entry points refuse
 bool layout_of(int nx, int ny, int nz, Layout& l) {

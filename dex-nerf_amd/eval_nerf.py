@@ -5,6 +5,9 @@ poses in validation mode, optionally save RGB / disparity-style depth PNGs, and 
 `--depth-only --m-thres M` renders the depth and Dex depth maps alone (nerf.render_dex_depth): no colour is evaluated, no RGB PNG
 is written, and the maps go to dex_<view>.npz beside depth_<view>.png.  `--depth-quantiles 0.1,0.5,0.9 [--quantile-interp]` adds the
 opacity-quantile depth maps (0.5: the median depth) to the same render and the same file (quantiles / qdepth), with or without --m-thres.
+`--depth-only --occupancy N[,N,N] [--occupancy-bounds x0 y0 z0 x1 y1 z1] [--occupancy-level L] [--occupancy-dilate D]` builds an
+occupancy grid of the two networks (nerf.OccupancyGrid.from_networks) and renders with the networks evaluated only on the samples in
+set cells; `--occupancy-check` renders every view both ways and reports, per threshold, the share of equal Dex depths.
 `--normals` renders density-gradient surface normals (nerf.render_dex_normals) instead: normal_<view>.npy holds the expected normal
 (H,W,3) (not renormalised: its length is a confidence), normal_<view>.png shows (n/|n| + 1)/2, black where n = 0; with `--m-thres M` the
 same pair per threshold, dex_normal_<view>_m<threshold>.npy / .png - the normal at the sample the Dex depth reports.
@@ -78,6 +81,20 @@ def main(argv=None):
     ap.add_argument("--mesh-bounds", default="", metavar="x0,y0,z0,x1,y1,z1", help="--mesh: the box the grid spans, in the network's input space (write --mesh-bounds=-1,... when it starts with a minus)")
     ap.add_argument("--mesh-resolution", default="128", metavar="N[,N,N]", help="--mesh: grid points per axis (one number, or nx,ny,nz)")
     ap.add_argument("--mesh-thres", type=float, default=None, metavar="T", help="--mesh: the Dex threshold m_thres on the raw density")
+    ap.add_argument("--occupancy", default="", metavar="N[,N,N]",
+                    help="--depth-only: cull the ray samples against an occupancy grid of this many cells per axis (nerf.OccupancyGrid."
+                         "from_networks on the coarse and the fine network) - the density networks run only where a cell is set; not with "
+                         "--precision fp16")
+    ap.add_argument("--occupancy-bounds", type=float, nargs=6, default=None, metavar=("x0", "y0", "z0", "x1", "y1", "z1"),
+                    help="--occupancy: the grid's box in the network's input space (default: the box around every rendered camera's corner "
+                         "rays between near and far)")
+    ap.add_argument("--occupancy-level", type=float, default=0.0, metavar="L",
+                    help="--occupancy: a cell is set when the raw density at one of its corners exceeds L (default 0: what a ReLU passes)")
+    ap.add_argument("--occupancy-dilate", type=int, default=1, metavar="D", help="--occupancy: also set the cells within D cells of a set one (0..8)")
+    ap.add_argument("--occupancy-check", action="store_true",
+                    help="--occupancy: render every view with and without the grid (both in the configured precision) and print, per "
+                         "threshold, the share of pixels with equal Dex depth and the largest depth difference - how to find the cells and "
+                         "the dilation a scene needs")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"])
     ap.add_argument("--savedir", default="")
     ap.add_argument("--quiet", action="store_true")
@@ -125,6 +142,31 @@ def main(argv=None):
         mesh_res = mesh_res * 3 if len(mesh_res) == 1 else mesh_res
     elif args.mesh_bounds or args.mesh_thres is not None:
         ap.error("--mesh-bounds / --mesh-thres belong to --mesh")
+    occ_cells = None
+    if args.occupancy:
+        if not args.depth_only:
+            ap.error("--occupancy culls the depth-only render: it needs --depth-only")
+        if args.precision == "fp16":
+            ap.error("--occupancy evaluates explicit points, which run in fp32 or bf16: not with --precision fp16")
+        try:
+            occ_cells = [int(v) for v in args.occupancy.split(",") if v.strip()]
+        except ValueError as e:
+            ap.error(f"--occupancy: {e}")
+        if len(occ_cells) not in (1, 3):
+            ap.error("--occupancy takes N or cx,cy,cz")
+        occ_cells = occ_cells * 3 if len(occ_cells) == 1 else occ_cells
+        try:
+            _ops.check_occupancy_grid(args.occupancy_bounds or (0, 0, 0, 1, 1, 1), occ_cells, "--occupancy")
+        except ValueError as e:
+            ap.error(str(e))
+        if not np.isfinite(np.float32(args.occupancy_level)):
+            ap.error("--occupancy-level must be finite")
+        if not 0 <= args.occupancy_dilate <= 8:
+            ap.error("--occupancy-dilate must be 0..8")
+        if args.occupancy_check and args.m_thres <= 0:
+            ap.error("--occupancy-check compares Dex depths: it needs --m-thres > 0")
+    elif args.occupancy_bounds is not None or args.occupancy_check or args.occupancy_level != 0.0 or args.occupancy_dilate != 1:
+        ap.error("--occupancy-bounds / --occupancy-level / --occupancy-dilate / --occupancy-check belong to --occupancy")
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     nerf.set_precision(args.precision)
     ck = torch.load(args.checkpoint, map_location="cpu")
@@ -174,6 +216,31 @@ def main(argv=None):
             ap.error("--apply-exposure: the checkpoint carries no exposure rows (train_dexnerf.py --refine-exposure writes them)")
     else:
         cameras = [(torch.from_numpy(syn.scene_pose(i, n_views=args.views)).to(dev), k_mat) for i in range(args.views)]
+    grid, cull, check = None, dict(kept=[0, 0], total=[0, 0], nonfinite=0), []
+    if occ_cells:
+        bounds = args.occupancy_bounds
+        if bounds is None:      # the box around the corner rays of every camera between near and far: it holds every sample
+            corners = []
+            for pose, k_cam in cameras:
+                ro, rd = nerf.get_ray_bundle(size, size, float(k_cam[0, 0]), pose, k_cam)
+                ro, rd = ro[[0, 0, -1, -1], [0, -1, 0, -1]].double(), rd[[0, 0, -1, -1], [0, -1, 0, -1]].double()
+                corners += [ro + rd * args.near, ro + rd * args.far]
+            pts = torch.cat(corners).cpu().numpy()
+            lo, hi = pts.min(axis=0), pts.max(axis=0)
+            pad = 1e-3 * np.maximum(hi - lo, 1e-6)
+            bounds = list(lo - pad) + list(hi + pad)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            grid = nerf.OccupancyGrid.from_networks([coarse, fine], ex, bounds, occ_cells, level=args.occupancy_level,
+                                                    dilate=args.occupancy_dilate)
+        torch.cuda.synchronize()
+        if args.occupancy_check and args.precision == "bf16":
+            nerf.set_render_policy("bf16")      # the culled render runs in bf16: compare it with a bf16 full render, not the guarded fp16 one
+        if not args.quiet:
+            print(f"occupancy grid {occ_cells[0]}x{occ_cells[1]}x{occ_cells[2]} over {[round(float(b), 4) for b in grid.bounds]}: "
+                  f"{100 * grid.occupied_fraction():.2f} % of the cells set (level {args.occupancy_level:g}, dilate {args.occupancy_dilate}) "
+                  f"in {time.perf_counter() - t0:.3f} s", flush=True)
     for i, (pose, k_mat) in enumerate(cameras):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -203,9 +270,21 @@ def main(argv=None):
                 ro, rd = nerf.get_ray_bundle(size, size, float(k_mat[0, 0]), pose, k_mat)
                 out = nerf.render_dex_depth(size, size, float(k_mat[0, 0]), coarse, fine, ro, rd, cfg, mode="validation",
                                             encode_position_fn=ex, encode_direction_fn=ed, m_thres_cand=thres,
-                                            quantiles=quantiles or None, quantile_interp=args.quantile_interp)
+                                            quantiles=quantiles or None, quantile_interp=args.quantile_interp, occupancy=grid,
+                                            cull_stats=grid is not None)
             torch.cuda.synchronize()
             times.append(time.perf_counter() - t0)
+            if grid is not None:
+                *out, stats = out
+                for p in range(2):
+                    cull["kept"][p] += stats["kept"][p]
+                    cull["total"][p] += stats["total"][p]
+                cull["nonfinite"] += stats["nonfinite"]
+                if args.occupancy_check and thres is not None:
+                    with torch.no_grad():
+                        full = nerf.render_dex_depth(size, size, float(k_mat[0, 0]), coarse, fine, ro, rd, cfg, mode="validation",
+                                                     encode_position_fn=ex, encode_direction_fn=ed, m_thres_cand=thres)
+                    check.append([(float((a == b).float().mean()), float((a - b).abs().max())) for a, b in zip(out[4:4 + len(thres)], full[4:])])
             depth = out[2] if fine is not None else out[0]
             n_dex = 0 if thres is None else len(thres)
             dex_maps, q_maps = out[4:4 + n_dex], out[4 + n_dex:]
@@ -244,7 +323,21 @@ def main(argv=None):
     avg = float(np.mean(times[1:])) if len(times) > 1 else float(times[0])
     if not args.quiet:
         print(f"Avg time per image: {avg:.4f} s ({size}x{size}, {size * size / avg:.0f} rays/s, {args.precision})", flush=True)
-    return dict(avg_seconds=avg, frames=frames, times=times)
+    result = dict(avg_seconds=avg, frames=frames, times=times)
+    if grid is not None:
+        result.update(occupancy=grid, cull=cull)
+        if not args.quiet:
+            shares = [f"{100 * k / max(t, 1):.2f} % of {t}" for k, t in zip(cull["kept"], cull["total"])]
+            print(f"occupancy: kept {shares[0]} coarse samples, {shares[1]} fine samples; {cull['nonfinite']} non-finite sigma", flush=True)
+        if check:
+            # per threshold over all views: the share of pixels with equal Dex depth, the largest depth difference
+            equal = np.mean([[e for e, _ in view] for view in check], axis=0)
+            worst = np.max([[d for _, d in view] for view in check], axis=0)
+            result.update(occupancy_check=dict(m_thres=[float(m) for m in thres], equal=equal.tolist(), max_diff=worst.tolist()))
+            if not args.quiet:
+                for m, e, d in zip(thres, equal, worst):
+                    print(f"occupancy check m_thres {int(m):3d}: {100 * e:.3f} % of the pixels equal, max |depth difference| {d:.5f}", flush=True)
+    return result
 
 
 if __name__ == "__main__":

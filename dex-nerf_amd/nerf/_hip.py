@@ -65,6 +65,17 @@ MESH_EXPORTS = ("dn_isosurface_workspace_bytes", "dn_isosurface_count", "dn_isos
 ISO_SCAN_BLOCK = 1024               # DN_ISO_SCAN_BLOCK: elements per workgroup at each of the three scan levels
 ISO_MAX_GRID_VERTICES = 1 << 28     # DN_ISO_MAX_GRID_VERTICES
 
+# include/dexnerf_hip_occupancy.h: an occupancy bit grid and the compaction of ray samples against it (nerf.OccupancyGrid,
+# nerf.render_dex_depth(occupancy=...))
+OCCUPANCY_EXPORTS = ("dn_occupancy_words", "dn_occupancy_build", "dn_occupancy_compact_workspace_bytes", "dn_occupancy_compact_count",
+                     "dn_occupancy_compact_emit", "dn_occupancy_gather")
+OCC_MAX_AXIS_CELLS = 1 << 24        # DN_OCC_MAX_AXIS_CELLS
+OCC_MAX_CELLS = 1 << 30             # DN_OCC_MAX_CELLS
+OCC_MAX_DILATE = 8                  # DN_OCC_MAX_DILATE
+OCC_MAX_SAMPLES = 1 << 30           # DN_OCC_MAX_SAMPLES
+OCC_MAX_SAMPLES_PER_RAY = 2048      # DN_OCC_MAX_SAMPLES_PER_RAY
+OCC_FILL = -3.4028234663852886e+38  # DN_OCC_FILL: -FLT_MAX
+
 
 class MlpDesc(ctypes.Structure):
     """dn_mlp_desc (mirrors FlexibleNeRFModel.__init__, reference nerf/models.py:186-196)."""
@@ -236,6 +247,19 @@ def _declare(lib):
     lib.dn_isosurface_count.restype = c_int
     lib.dn_isosurface_emit.argtypes = [fp, c_int, fp, fp, fp, c_int, c_int, c_int, c_float, vp, c_int64, c_int64, fp, vp, vp]
     lib.dn_isosurface_emit.restype = c_int
+    # the occupancy header
+    lib.dn_occupancy_words.argtypes = [c_int, c_int, c_int]
+    lib.dn_occupancy_words.restype = c_int64
+    lib.dn_occupancy_build.argtypes = [fp, c_int, c_int, c_int, c_int, c_float, c_int, c_int, vp, vp, vp]
+    lib.dn_occupancy_build.restype = c_int
+    lib.dn_occupancy_compact_workspace_bytes.argtypes = [c_int64, c_int]
+    lib.dn_occupancy_compact_workspace_bytes.restype = c_size_t
+    lib.dn_occupancy_compact_count.argtypes = [fp, c_int, fp, c_int64, c_int, vp, c_int, c_int, c_int] + [c_float] * 9 + [vp, vp, vp, vp]
+    lib.dn_occupancy_compact_count.restype = c_int
+    lib.dn_occupancy_compact_emit.argtypes = [fp, c_int, fp, c_int64, c_int, vp, c_int64, fp, vp]
+    lib.dn_occupancy_compact_emit.restype = c_int
+    lib.dn_occupancy_gather.argtypes = [vp, fp, c_int64, c_int64, fp, vp, vp, vp]
+    lib.dn_occupancy_gather.restype = c_int
 
 
 def lib():

@@ -1747,3 +1747,166 @@ def isosurface(field, xs, ys, zs, level):
     n_v, n_t, n_bad = counted.totals()
     vertices, triangles = isosurface_emit(counted, n_v, n_t)
     return vertices, triangles, n_bad
+
+
+# ---- occupancy-grid culling of the depth-only render (include/dexnerf_hip_occupancy.h) ---------------------------------------------------
+def check_occupancy_grid(bounds, cells, who="occupancy"):
+    """The host-side rule of an occupancy grid: bounds (x0,y0,z0,x1,y1,z1) finite as fp32 with x1 > x0, y1 > y0, z1 > z0; cells N or
+    (cx,cy,cz), each 1 .. 2^24, their product at most 2^30.  Returns (bounds as the Python floats of their fp32 values, (cx,cy,cz), the
+    three scales cells / (b1 - b0): formed in float64 from the fp32 bounds and rounded to fp32 once, as the header asks).  Raises
+    ValueError before any GPU work."""
+    import numbers
+    try:
+        b = [float(v) for v in bounds]
+        c = [int(cells)] * 3 if isinstance(cells, numbers.Integral) else [int(v) for v in cells]
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"{who}: bounds are six numbers and cells is N or (cx, cy, cz): {e}") from None
+    if len(b) != 6 or len(c) != 3:
+        raise ValueError(f"{who}: bounds are (x0, y0, z0, x1, y1, z1) and cells is N or (cx, cy, cz)")
+    if not all(math.isfinite(v) for v in b):
+        raise ValueError(f"{who}: the bounds must be finite, got {b}")
+    b = [ctypes.c_float(v).value for v in b]
+    if not all(math.isfinite(v) for v in b) or any(b[a + 3] <= b[a] for a in range(3)):
+        raise ValueError(f"{who}: the bounds must be finite as fp32 with x1 > x0, y1 > y0, z1 > z0, got {b}")
+    if min(c) < 1 or max(c) > _hip.OCC_MAX_AXIS_CELLS or c[0] * c[1] * c[2] > _hip.OCC_MAX_CELLS:
+        raise ValueError(f"{who}: every axis needs 1 .. {_hip.OCC_MAX_AXIS_CELLS} cells and the grid at most {_hip.OCC_MAX_CELLS}, got {c}")
+    scale = [ctypes.c_float(c[a] / (b[a + 3] - b[a])).value for a in range(3)]
+    if not all(math.isfinite(s) and s > 0.0 for s in scale):
+        raise ValueError(f"{who}: cells / (b1 - b0) must be finite and > 0 as fp32, got {scale}")
+    return tuple(b), tuple(c), tuple(scale)
+
+
+def occupancy_words(cells):
+    return (int(cells[0]) * int(cells[1]) * int(cells[2]) + 31) // 32
+
+
+def occupancy_build(field, cells, level, dilate=0, bits=None, accumulate=False):
+    """dn_occupancy_build: the bit grid (int32 words, cell c = bit c & 31 of word c >> 5) of the cells (cx,cy,cz) from the vertex field
+    (cx+1, cy+1, cz+1) fp32 - dense, or a strided view read in place like isosurface_count's.  A cell is set iff one of its corners is
+    non-finite or > level, dilated by `dilate` cells (Chebyshev).  bits given and accumulate: OR-ed into it."""
+    cells = tuple(int(c) for c in cells)
+    level = float(level)
+    l32 = ctypes.c_float(level).value if math.isfinite(level) else level
+    if not math.isfinite(l32):
+        raise ValueError(f"occupancy_build: the level must be finite as fp32, got {level!r}")
+    dilate = int(dilate)
+    if not 0 <= dilate <= _hip.OCC_MAX_DILATE:
+        raise ValueError(f"occupancy_build: dilate must be 0 .. {_hip.OCC_MAX_DILATE}, got {dilate}")
+    if not (torch.is_tensor(field) and field.dim() == 3 and tuple(field.shape) == tuple(c + 1 for c in cells)):
+        raise ValueError("occupancy_build: the field must be (cx+1, cy+1, cz+1): the density at the cells' corners")
+    if not field.is_cuda:
+        raise RuntimeError("occupancy_build: runs on the ROCm device only (got a host tensor); move the field to 'cuda'")
+    n_words = int(lib().dn_occupancy_words(*cells))
+    if n_words == 0:
+        raise ValueError(f"occupancy_build: cells {cells} are past the grid's maximum")
+    ny, nz = field.shape[1:]
+    s = field.stride(2)
+    if not (field.dtype == torch.float32 and 1 <= s < 2 ** 31 and field.stride() == (ny * nz * s, nz * s, s)):
+        field, s = f32c(field), 1
+    dev = field.device
+    if bits is None:
+        if accumulate:
+            raise ValueError("occupancy_build: accumulate needs the bits to accumulate into")
+        bits = torch.empty(n_words, dtype=torch.int32, device=dev)
+    assert bits.dtype == torch.int32 and bits.numel() == n_words and bits.device == dev
+    scratch = torch.empty(n_words, dtype=torch.int32, device=dev) if dilate > 0 else None
+    check(lib().dn_occupancy_build(c_void_p(field.data_ptr()), int(s), *cells, l32, dilate, int(bool(accumulate)), ptr(scratch), ptr(bits),
+                                   stream()), "dn_occupancy_build")
+    return bits
+
+
+def occupancy_compact_count(rays, z, grid):
+    """dn_occupancy_compact_count of the samples rays (N, >= 8) x z (N,S) against `grid` (bits, cells, bounds, scale: an
+    nerf.OccupancyGrid) -> (slot (N,S) int32: the rank among the kept samples or -1, record int32 x 4 on the device: n_kept, N*S, 0, 0,
+    the workspace - a counting occupancy_gather reuses it)."""
+    rays, z = f32c(rays), f32c(z)
+    n, s = z.shape
+    nbytes = int(lib().dn_occupancy_compact_workspace_bytes(n, s))
+    if nbytes == 0:
+        raise ValueError(f"occupancy: {n} rays x {s} samples are outside the compaction (1 .. {_hip.OCC_MAX_SAMPLES_PER_RAY} samples per ray, "
+                         f"at most {_hip.OCC_MAX_SAMPLES} in all)")
+    dev = z.device
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    slot = torch.empty((n, s), dtype=torch.int32, device=dev)
+    record = torch.empty(4, dtype=torch.int32, device=dev)
+    check(lib().dn_occupancy_compact_count(ptr(rays), rays.shape[1], ptr(z), n, s, ptr(grid.bits), *grid.cells, *grid.bounds, *grid.scale,
+                                           ptr(ws), ptr(slot), ptr(record), stream()), "dn_occupancy_compact_count")
+    return slot, record, ws
+
+
+def occupancy_compact_emit(rays, z, slot, max_points, pts=None):
+    """dn_occupancy_compact_emit: pts (max_points,3), row slot[p] = ro + rd * z of sample p; rows at or past max_points are not written."""
+    rays, z = f32c(rays), f32c(z)
+    n, s = z.shape
+    max_points = int(max_points)
+    if pts is None:
+        pts = torch.empty((max(max_points, 0), 3), dtype=torch.float32, device=z.device)
+    assert pts.dtype == torch.float32 and pts.shape[0] >= max_points and pts.shape[1:] == (3,)
+    check(lib().dn_occupancy_compact_emit(ptr(rays), rays.shape[1], ptr(z), n, s, ptr(slot), max_points, ptr(pts) if max_points > 0 else None,
+                                          stream()), "dn_occupancy_compact_emit")
+    return pts
+
+
+def occupancy_gather(slot, net_out, rf, ws=None, record=None):
+    """dn_occupancy_gather: rf[p][3] = net_out[slot[p]][3], or the fill value (-FLT_MAX) for a culled sample; net_out (n_rows,4) or None
+    (no sample kept).  ws and record (occupancy_compact_count's) given: word 2 of the record becomes the number of non-finite values."""
+    n_rows = 0 if net_out is None else int(net_out.shape[0])
+    assert rf.dtype == torch.float32 and rf.is_contiguous() and rf.shape[-1] == 4 and rf.numel() == 4 * slot.numel()
+    check(lib().dn_occupancy_gather(ptr(slot), ptr(net_out) if n_rows else None, n_rows, slot.numel(), ptr(rf), ptr(ws), ptr(record), stream()),
+          "dn_occupancy_gather")
+    return rf
+
+
+def _culled_pass(packed, rays, z, grid, count_nonfinite):
+    """One network pass of the culled render: (rf (N,S,4) whose sigma column alone is written, n_kept, record)."""
+    slot, record, ws = occupancy_compact_count(rays, z, grid)
+    n_kept = int(record[0].item())   # the host read: the kept count sizes the network launch
+    net_out = run_network_pts(packed, occupancy_compact_emit(rays, z, slot, n_kept), None, 1) if n_kept else None
+    rf = torch.empty(tuple(z.shape) + (4,), dtype=torch.float32, device=z.device)
+    occupancy_gather(slot, net_out, rf, *((ws, record) if count_nonfinite else ()))
+    return rf, n_kept, record
+
+
+def render_rays_depth_culled(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, noise_std, m_thres, occupancy, draws=None, quantiles=None,
+                             interp=False, count_nonfinite=False):
+    """render_rays_depth with the network evaluated only on the samples whose occupancy cell is set, as a chain of entry points on the
+    current stream: dn_coarse_depths, dn_occupancy_compact_count, a host read of the kept count, dn_occupancy_compact_emit,
+    dn_run_network on the kept points (explicit points, one sample per "ray"; skipped when nothing is kept), dn_occupancy_gather
+    (culled samples get -FLT_MAX: no opacity, no threshold crossing), dn_density_resample, the same compaction on the fine depths for
+    the fine network, dn_composite_density or its quantile variant.  num_fine == 0 (or no fine pack) ends after a dn_composite_density
+    of the coarse pass.
+
+    Returns (render_rays_depth's maps, stats): stats = dict(kept=(coarse, fine), total=(coarse, fine), records=[the passes' device
+    records]) - the fine entries 0 without a fine pass.  Two host reads per chunk (one per network pass: the kept count sizes the
+    network launch) - the chain cannot be captured into a HIP graph.  The network runs in the packs' precision; an explicit-points
+    launch carries no fp16 range status, so the guarded-fp16 render policy does not apply here."""
+    packed_c.require_fresh_inference_stream("render_rays_depth_culled")
+    rays = f32c(rays)
+    fine = num_fine > 0 and packed_f is not None
+    if fine:
+        packed_f.require_fresh_inference_stream("render_rays_depth_culled")
+    t_rand, noise_c, u, noise_f = _draw_tensors(draws)
+    rd = rays[:, 3:6]
+    z = coarse_depths(rays, num_coarse, lindisp, t_rand)
+    rf, kept_c, rec_c = _culled_pass(packed_c, rays, z, occupancy, count_nonfinite)
+    kept, total, records = [kept_c, 0], [z.numel(), 0], [rec_c]
+    if fine:
+        depth_c, acc_c, z = density_resample(rf, z, rd, num_fine, noise_c, noise_std, u)
+        rf, kept[1], rec_f = _culled_pass(packed_f, rays, z, occupancy, count_nonfinite)
+        total[1] = z.numel()
+        records.append(rec_f)
+    noise = noise_f if fine else noise_c
+    if quantiles is None:
+        last = composite_density(rf, z, rd, noise, noise_std, m_thres)
+    else:
+        nq = int(quantiles.numel())
+        if not 1 <= nq <= _hip.MAX_QUANTILES or quantiles.dtype != torch.float32:
+            raise ValueError(f"render_rays_depth_culled: quantiles must be a float32 device tensor of 1 .. {_hip.MAX_QUANTILES} values")
+        # (composite_density_quantiles with the validated quantiles already on the device: no host read, no copy per chunk)
+        c = _sigma_call(rf, z, rd, noise, noise_std, m_thres)
+        last = _pass_maps(c.dev, c.n) + (_empty(c.dev, c.k, c.n) if c.k else None, _empty(c.dev, nq, c.n))
+        check(lib().dn_composite_density_quantiles(*c.head, ptr(c.thres), c.k, ptr(quantiles), nq, int(bool(interp)), c.n, c.s,
+                                                   *[ptr(m) for m in last], stream()), "dn_composite_density_quantiles")
+    depth, acc, dex, *qdepth = last
+    maps = ((depth_c, acc_c, depth, acc, dex) if fine else (depth, acc, None, None, dex)) + tuple(qdepth)
+    return maps, dict(kept=tuple(kept), total=tuple(total), records=records)

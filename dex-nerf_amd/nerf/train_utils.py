@@ -413,9 +413,34 @@ def _density_packs(r, prec):
     return tuple(m.packed_density(r.lx, True, precision=prec) for m in r.models) + (() if r.fine else (None,))
 
 
+def _render_dex_depth_culled(r, prec, occupancy, q_dev, interp, cull_stats, chunksize, mode):
+    """render_dex_depth's chunk loop on _ops.render_rays_depth_culled: the draws of every chunk from _draws, as without a grid; the
+    per-pass kept / total counts summed on the host (the chain reads them anyway), the non-finite counts summed on the device and
+    read once at the end, only when the stats are asked for."""
+    packs = _density_packs(r, prec)
+    kept, total, records = [0, 0], [0, 0], []
+
+    def render_chunk(batch):
+        draws = _draws(batch.shape[0], r.nc, r.nf, r.fine, r.perturb, r.std, r.dev)
+        (depth_c, acc_c, depth_f, acc_f, dex, *qdepth), stats = _ops.render_rays_depth_culled(
+            *packs, batch, r.nc, r.nf, r.lindisp, r.std, r.m_thres, occupancy, draws, quantiles=q_dev, interp=interp,
+            count_nonfinite=cull_stats)
+        for p in range(2):
+            kept[p] += stats["kept"][p]
+            total[p] += stats["total"][p]
+        records.extend(stats["records"])
+        maps = [depth_c, acc_c, depth_f, acc_f] + ([] if dex is None else [dex[k] for k in range(dex.shape[0])])
+        return maps + ([qdepth[0][k] for k in range(qdepth[0].shape[0])] if qdepth else [])
+    maps = _join_chunks([render_chunk(batch) for batch in get_minibatches(r.rays, chunksize=chunksize)])
+    out = _to_image(maps, [r.img_shape[:-1]] * len(maps)) if mode == "validation" else tuple(maps)
+    if cull_stats:
+        out += (dict(kept=tuple(kept), total=tuple(total), nonfinite=int(torch.stack(records)[:, 2].sum().item())),)
+    return out
+
+
 def render_dex_depth(height, width, focal_length, model_coarse, model_fine, ray_origins, ray_directions, options,
                      mode="validation", encode_position_fn=None, encode_direction_fn=None, m_thres_cand=None, quantiles=None,
-                     quantile_interp=False):
+                     quantile_interp=False, occupancy=None, cull_stats=False):
     """The depth half of run_one_iter_of_nerf and nothing else: expected depth, accumulation and the Dex first-crossing depths
     depend on sigma alone (reference nerf/volume_rendering_utils.py:33-58), so this render evaluates only the density
     sub-networks (trunk + fc_alpha: FlexibleNeRFModel.packed_density) and composites no colour (dn_render_rays_depth).
@@ -431,11 +456,35 @@ def render_dex_depth(height, width, focal_length, model_coarse, model_fine, ray_
     depth confidence), from the same pass (dn_render_rays_depth_quantiles: the same launches).  quantile_interp=False gives the z of
     the crossing sample, the convention of the Dex depth; True the piecewise-linear CDF inversion the fine-depth sampler uses.  A ray
     whose accumulation stays below q reports its LAST sample's depth (it went through) - not z[0] like a Dex depth without a crossing.
-    quantiles=None: the launches and the return are what they were."""
+    quantiles=None: the launches and the return are what they were.
+
+    occupancy: an nerf.OccupancyGrid on the rays' device - each chunk then goes through _ops.render_rays_depth_culled: the samples of
+    both passes are classified against the grid, the density networks run only on the kept ones, and a culled sample composites as
+    empty space (sigma = -FLT_MAX).  The grid lives in the space of the sampled points (after the NDC warp where there is one).  With
+    level 0 and no density noise a correctly classified culled sample contributes exactly nothing; a level above 0 changes the coarse
+    weights and with them the fine samples; with noise the full render can revive a negative sigma and the culled one cannot.  The
+    draws are made as without a grid, so the generator ends where the full render leaves it; quantiles are supported.  The culled
+    render runs in nerf.set_precision's mode - 'fp32', or bf16 for 'bf16' and 'bf16-s16'; 'fp16' raises, as in density_grid - and does
+    NOT follow the guarded-fp16 render policy: the network runs on explicit points, a launch that carries no range status (the
+    guarded-fp16 policy on this path is a follow-up).  It reads the kept count back once per network pass - two host reads per chunk -
+    and cannot be captured into a HIP graph.  cull_stats=True (with a grid only) appends one more value to the return: dict(kept=
+    (coarse, fine), total=(coarse, fine), nonfinite=...) summed over the chunks - nonfinite: the non-finite raw sigma values the kept
+    samples produced.  occupancy=None: the launches and the return are what they were."""
     qs = None if quantiles is None else _ops.check_quantiles(quantiles, "render_dex_depth: quantiles")
+    if occupancy is None and cull_stats:
+        raise ValueError("render_dex_depth: cull_stats reports on a culled render: give occupancy=")
+    if occupancy is not None:
+        # every refusal of the culled path before any GPU work: the precision, the grid's device, then the setup's own
+        prec = _ops._precision
+        if prec == _ops._hip.PREC_F16:
+            raise RuntimeError("render_dex_depth(occupancy=...): the culled render evaluates explicit points, which carry no fp16 range "
+                               "status - it runs in 'fp32' or bf16, not under nerf.set_precision('fp16')")
+        occupancy.check_render(ray_directions.device, "render_dex_depth")
     r = _density_render_setup("render_dex_depth", "differentiable renders go through run_one_iter_of_nerf", height, width, focal_length,
                               model_coarse, model_fine, ray_origins, ray_directions, options, mode, encode_position_fn, m_thres_cand)
     q_dev = _threshold_tensor(qs, r.dev) if qs else None   # (the same cache: one host-to-device copy per quantile set)
+    if occupancy is not None:
+        return _render_dex_depth_culled(r, prec, occupancy, q_dev, quantile_interp, cull_stats, getattr(options.nerf, mode).chunksize, mode)
     guard = _fp16_guard(r.models, density=True)
     # precision code -> the density packs: fetched once per pass over the chunks, not per chunk (a pass runs in one precision, and
     # the re-render after a trip in another - the configured one is never the guarded one - so it fetches its own)
