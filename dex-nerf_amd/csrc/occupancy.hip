@@ -11,9 +11,15 @@
 //   gather_kernel          rf[p][3] = net_out[slot[p]][3] or the fill value; optionally the workgroup's count of non-finite values
 //   sum_partials_kernel    one workgroup: the sum of those counts, in a fixed order
 //
+// and the two kernels of include/dexnerf_hip_cull.h, for culled renders that read more than sigma:
+//
+//   emit_kernel<true>      also dirs[slot[p]] = columns 8..10 of the sample's ray row, in the same launch
+//   gather_rows_kernel     dst[p][c] = src[slot[p]][c] or fill_c for c < width, as 32-bit words; a thread owns 4 consecutive dst rows, so
+//                          kept rows are read in ascending order; rows of 16 aligned bytes move as one dwordx4 load and store
+//
 // No workgroup waits on another, no atomics, plain vector stores: the output is a function of the input.  Memory: the sample kernels
 // touch about 40 B per sample (z twice, slot written twice and read three times, 12 B per kept point, one 16-byte line share of rf).
-#include "../../include/dexnerf_hip_occupancy.h"
+#include "../../include/dexnerf_hip_cull.h"
 #include "scan_blocks.h"
 
 namespace dn {
@@ -178,7 +184,9 @@ __global__ __launch_bounds__(kThreads) void scan_slots_kernel(int64_t n, const u
   }
 }
 
-__global__ __launch_bounds__(kThreads) void emit_kernel(Samples a, const int* __restrict__ slot, int64_t max_points, float* __restrict__ pts) {
+template <bool DIRS>
+__global__ __launch_bounds__(kThreads) void emit_kernel(Samples a, const int* __restrict__ slot, int64_t max_points, float* __restrict__ pts,
+                                                        float* __restrict__ dirs) {
   const int64_t e0 = static_cast<int64_t>(blockIdx.x) * kScanElems + threadIdx.x * kPerThread;
 #pragma unroll
   for (int q = 0; q < kPerThread; ++q) {
@@ -190,6 +198,11 @@ __global__ __launch_bounds__(kThreads) void emit_kernel(Samples a, const int* __
     point_of(a, p, x);
     float* row = pts + s * 3;
     row[0] = x[0]; row[1] = x[1]; row[2] = x[2];
+    if (DIRS) {
+      const float* ray = a.rays + (p / a.s) * a.ray_stride;
+      float* d = dirs + s * 3;
+      d[0] = ray[8]; d[1] = ray[9]; d[2] = ray[10];
+    }
   }
 }
 
@@ -210,6 +223,54 @@ __global__ __launch_bounds__(kThreads) void gather_kernel(const int* __restrict_
       if (COUNT) bad += (__builtin_bit_cast(unsigned, v) & 0x7F800000u) == 0x7F800000u;
     }
     rf[p * 4 + 3] = v;
+  }
+  if (COUNT) {
+    unsigned all;
+    block_scan_exclusive(bad, lds, all);
+    if (threadIdx.x == 0) partial[blockIdx.x] = all;
+  }
+}
+
+struct Fills {
+  unsigned v[DN_CULL_MAX_WIDTH];
+};
+
+// W: the row width; VEC: rows of 16 aligned bytes on both sides (W == 4, both strides 4).  Words, not floats: a copy of bits.
+template <int W, bool VEC, bool COUNT>
+__global__ __launch_bounds__(kThreads) void gather_rows_kernel(const int* __restrict__ slot, const unsigned* __restrict__ src, int64_t src_stride,
+                                                               int64_t n_rows, int64_t n, Fills fill, unsigned* __restrict__ dst,
+                                                               int64_t dst_stride, unsigned* __restrict__ partial) {
+  static_assert(!VEC || W == 4, "a 16-byte row is four words");
+  __shared__ unsigned lds[4];
+  const int64_t e0 = static_cast<int64_t>(blockIdx.x) * kScanElems + threadIdx.x * kPerThread;
+  unsigned bad = 0;
+#pragma unroll
+  for (int q = 0; q < kPerThread; ++q) {
+    const int64_t p = e0 + q;
+    if (p >= n) continue;
+    const int64_t s = slot[p];
+    unsigned v[W];
+#pragma unroll
+    for (int c = 0; c < W; ++c) v[c] = fill.v[c];
+    if (s >= 0 && s < n_rows) {
+      if constexpr (VEC) {
+        const uint4 r = *reinterpret_cast<const uint4*>(src + s * 4);
+        v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
+      } else {
+#pragma unroll
+        for (int c = 0; c < W; ++c) v[c] = src[s * src_stride + c];
+      }
+      if (COUNT) {
+#pragma unroll
+        for (int c = 0; c < W; ++c) bad += (v[c] & 0x7F800000u) == 0x7F800000u;
+      }
+    }
+    if constexpr (VEC) {
+      *reinterpret_cast<uint4*>(dst + p * 4) = make_uint4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+      for (int c = 0; c < W; ++c) dst[p * dst_stride + c] = v[c];
+    }
   }
   if (COUNT) {
     unsigned all;
@@ -268,6 +329,17 @@ int samples_check(const char* who, const float* rays, int ray_stride, const floa
 
 bool aligned(const void* p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) == 0; }
 bool is_finite(float x) { return x - x == 0.0f; }
+
+template <int W, bool VEC>
+void launch_gather_rows(bool count, unsigned blocks, hipStream_t s, const int* slot, const unsigned* src, int64_t src_stride, int64_t n_rows,
+                        int64_t n, const Fills& fill, unsigned* dst, int64_t dst_stride, unsigned* partial) {
+  if (count)
+    hipLaunchKernelGGL((gather_rows_kernel<W, VEC, true>), dim3(blocks), dim3(kThreads), 0, s, slot, src, src_stride, n_rows, n, fill, dst, dst_stride,
+                       partial);
+  else
+    hipLaunchKernelGGL((gather_rows_kernel<W, VEC, false>), dim3(blocks), dim3(kThreads), 0, s, slot, src, src_stride, n_rows, n, fill, dst, dst_stride,
+                       partial);
+}
 
 }  // namespace occ
 }  // namespace dn
@@ -348,7 +420,7 @@ extern "C" int dn_occupancy_compact_emit(const float* rays, int ray_stride, cons
   DN_REQUIRE(max_points == 0 || (pts && aligned(pts, 4)), "%s: a capacity without its output", who);
   if (max_points == 0) return 0;
   const Samples a{rays, ray_stride, z, l.n, n_samples};
-  hipLaunchKernelGGL(emit_kernel, dim3(l.n0), dim3(kThreads), 0, as_stream(stream), a, slot, max_points, pts);
+  hipLaunchKernelGGL(emit_kernel<false>, dim3(l.n0), dim3(kThreads), 0, as_stream(stream), a, slot, max_points, pts, static_cast<float*>(nullptr));
   return check_launch(who);
 }
 
@@ -371,5 +443,58 @@ extern "C" int dn_occupancy_gather(const int* slot, const float* net_out, int64_
   } else {
     hipLaunchKernelGGL(gather_kernel<false>, dim3(blocks), dim3(kThreads), 0, s, slot, net_out, n_rows, n_points, rf, static_cast<unsigned*>(nullptr));
   }
+  return check_launch(who);
+}
+
+// ---- include/dexnerf_hip_cull.h -----------------------------------------------------------------------------------------------------
+extern "C" int dn_occupancy_compact_emit_dirs(const float* rays, int ray_stride, const float* z, int64_t n_rays, int n_samples, const int* slot,
+                                              int64_t max_points, float* pts, float* dirs, dn_stream_t stream) {
+  const char* who = "dn_occupancy_compact_emit_dirs";
+  Layout l;
+  if (int rc = samples_check(who, rays, ray_stride, z, n_rays, n_samples, l)) return rc;
+  DN_REQUIRE(ray_stride >= 11, "%s: ray_stride must be >= 11: the view direction is columns 8..10 of a ray row (got %d)", who, ray_stride);
+  DN_REQUIRE(aligned(rays, 4) && aligned(z, 4), "%s: rays and depths must be 4-byte aligned", who);
+  DN_REQUIRE(slot && aligned(slot, 4), "%s: null or unaligned slots", who);
+  DN_REQUIRE(max_points >= 0, "%s: negative capacity", who);
+  DN_REQUIRE(max_points == 0 || (pts && dirs && aligned(pts, 4) && aligned(dirs, 4)), "%s: a capacity without both of its outputs", who);
+  DN_REQUIRE(max_points == 0 || pts != dirs, "%s: the points and the directions must not be one buffer", who);
+  if (max_points == 0) return 0;
+  const Samples a{rays, ray_stride, z, l.n, n_samples};
+  hipLaunchKernelGGL(emit_kernel<true>, dim3(l.n0), dim3(kThreads), 0, as_stream(stream), a, slot, max_points, pts, dirs);
+  return check_launch(who);
+}
+
+extern "C" int dn_occupancy_gather_rows(const int* slot, const float* src, int src_stride, int64_t n_rows, int64_t n_points, int width,
+                                        float fill0, float fill1, float fill2, float fill3, float* dst, int dst_stride, void* workspace,
+                                        unsigned* d_record, dn_stream_t stream) {
+  const char* who = "dn_occupancy_gather_rows";
+  DN_REQUIRE(slot && dst && aligned(slot, 4) && aligned(dst, 4), "%s: null or unaligned slots or destination", who);
+  DN_REQUIRE(n_points >= 1 && n_points <= kMaxSamples, "%s: n_points must be 1 .. %lld (got %lld)", who, static_cast<long long>(kMaxSamples),
+             static_cast<long long>(n_points));
+  DN_REQUIRE(n_rows >= 0 && n_rows <= n_points, "%s: n_rows must be 0 .. n_points", who);
+  DN_REQUIRE(width >= 1 && width <= DN_CULL_MAX_WIDTH, "%s: width must be 1 .. %d (got %d)", who, DN_CULL_MAX_WIDTH, width);
+  DN_REQUIRE(src_stride >= width && dst_stride >= width, "%s: the strides (%d, %d floats) must be at least the width %d", who, src_stride,
+             dst_stride, width);
+  DN_REQUIRE(n_rows == 0 || (src && aligned(src, 4)), "%s: rows without their source", who);
+  DN_REQUIRE((workspace == nullptr) == (d_record == nullptr), "%s: the count needs both the workspace and the record", who);
+  DN_REQUIRE(aligned(workspace, 256) && aligned(d_record, 4), "%s: workspace must be 256-byte aligned, the record 4-byte aligned", who);
+  const unsigned blocks = blocks_for(n_points, kScanElems);
+  hipStream_t s = as_stream(stream);
+  const float f[DN_CULL_MAX_WIDTH] = {fill0, fill1, fill2, fill3};
+  Fills fill;
+  for (int c = 0; c < DN_CULL_MAX_WIDTH; ++c) fill.v[c] = __builtin_bit_cast(unsigned, f[c]);
+  const unsigned* from = reinterpret_cast<const unsigned*>(src);
+  unsigned* to = reinterpret_cast<unsigned*>(dst);
+  unsigned* partial = static_cast<unsigned*>(workspace);   // the level-0 totals of the count: dead once the slots are written
+  const bool count = d_record != nullptr;
+  // (n_rows == 0 reads no source row: a NULL source passes as 16-byte aligned, and the vector kernel then only stores)
+  const bool vec = width == 4 && src_stride == 4 && dst_stride == 4 && aligned(src, 16) && aligned(dst, 16);
+  const int64_t ss = src_stride, ds = dst_stride;
+  if (vec) launch_gather_rows<4, true>(count, blocks, s, slot, from, ss, n_rows, n_points, fill, to, ds, partial);
+  else if (width == 4) launch_gather_rows<4, false>(count, blocks, s, slot, from, ss, n_rows, n_points, fill, to, ds, partial);
+  else if (width == 3) launch_gather_rows<3, false>(count, blocks, s, slot, from, ss, n_rows, n_points, fill, to, ds, partial);
+  else if (width == 2) launch_gather_rows<2, false>(count, blocks, s, slot, from, ss, n_rows, n_points, fill, to, ds, partial);
+  else launch_gather_rows<1, false>(count, blocks, s, slot, from, ss, n_rows, n_points, fill, to, ds, partial);
+  if (count) hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(kThreads), 0, s, partial, blocks, d_record);
   return check_launch(who);
 }

@@ -8,6 +8,9 @@ opacity-quantile depth maps (0.5: the median depth) to the same render and the s
 `--depth-only --occupancy N[,N,N] [--occupancy-bounds x0 y0 z0 x1 y1 z1] [--occupancy-level L] [--occupancy-dilate D]` builds an
 occupancy grid of the two networks (nerf.OccupancyGrid.from_networks) and renders with the networks evaluated only on the samples in
 set cells; `--occupancy-check` renders every view both ways and reports, per threshold, the share of equal Dex depths.
+`--occupancy N[,N,N] --occupancy-colour` culls the full colour render the same way (nerf.run_one_iter_of_nerf(occupancy=...)), and
+`--normals --occupancy N[,N,N]` the normal render (nerf.render_dex_normals(occupancy=...)); with `--occupancy-colour`, `--occupancy-check`
+also reports the largest |rgb| difference.
 `--normals` renders density-gradient surface normals (nerf.render_dex_normals) instead: normal_<view>.npy holds the expected normal
 (H,W,3) (not renormalised: its length is a confidence), normal_<view>.png shows (n/|n| + 1)/2, black where n = 0; with `--m-thres M` the
 same pair per threshold, dex_normal_<view>_m<threshold>.npy / .png - the normal at the sample the Dex depth reports.
@@ -91,6 +94,9 @@ def main(argv=None):
     ap.add_argument("--occupancy-level", type=float, default=0.0, metavar="L",
                     help="--occupancy: a cell is set when the raw density at one of its corners exceeds L (default 0: what a ReLU passes)")
     ap.add_argument("--occupancy-dilate", type=int, default=1, metavar="D", help="--occupancy: also set the cells within D cells of a set one (0..8)")
+    ap.add_argument("--occupancy-colour", action="store_true",
+                    help="--occupancy without --depth-only: cull the full colour render (nerf.run_one_iter_of_nerf(occupancy=...)) - both "
+                         "networks, colour heads included, run only where a cell is set; not with --depth-only or --normals")
     ap.add_argument("--occupancy-check", action="store_true",
                     help="--occupancy: render every view with and without the grid (both in the configured precision) and print, per "
                          "threshold, the share of pixels with equal Dex depth and the largest depth difference - how to find the cells and "
@@ -144,8 +150,13 @@ def main(argv=None):
         ap.error("--mesh-bounds / --mesh-thres belong to --mesh")
     occ_cells = None
     if args.occupancy:
-        if not args.depth_only:
-            ap.error("--occupancy culls the depth-only render: it needs --depth-only")
+        if not (args.depth_only or args.occupancy_colour or args.normals):
+            ap.error("--occupancy culls the depth-only render: it needs --depth-only (or --occupancy-colour for the colour render, "
+                     "--normals for the normal render)")
+        if args.occupancy_colour and (args.depth_only or args.normals):
+            ap.error("--occupancy-colour culls the full colour render: not with --depth-only or --normals")
+        if args.occupancy_check and args.normals:
+            ap.error("--occupancy-check compares depth-only or colour renders: not with --normals")
         if args.precision == "fp16":
             ap.error("--occupancy evaluates explicit points, which run in fp32 or bf16: not with --precision fp16")
         try:
@@ -163,10 +174,11 @@ def main(argv=None):
             ap.error("--occupancy-level must be finite")
         if not 0 <= args.occupancy_dilate <= 8:
             ap.error("--occupancy-dilate must be 0..8")
-        if args.occupancy_check and args.m_thres <= 0:
+        if args.occupancy_check and args.m_thres <= 0 and not args.occupancy_colour:
             ap.error("--occupancy-check compares Dex depths: it needs --m-thres > 0")
-    elif args.occupancy_bounds is not None or args.occupancy_check or args.occupancy_level != 0.0 or args.occupancy_dilate != 1:
-        ap.error("--occupancy-bounds / --occupancy-level / --occupancy-dilate / --occupancy-check belong to --occupancy")
+    elif (args.occupancy_bounds is not None or args.occupancy_check or args.occupancy_colour or args.occupancy_level != 0.0
+          or args.occupancy_dilate != 1):
+        ap.error("--occupancy-bounds / --occupancy-level / --occupancy-dilate / --occupancy-check / --occupancy-colour belong to --occupancy")
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     nerf.set_precision(args.precision)
     ck = torch.load(args.checkpoint, map_location="cpu")
@@ -216,7 +228,13 @@ def main(argv=None):
             ap.error("--apply-exposure: the checkpoint carries no exposure rows (train_dexnerf.py --refine-exposure writes them)")
     else:
         cameras = [(torch.from_numpy(syn.scene_pose(i, n_views=args.views)).to(dev), k_mat) for i in range(args.views)]
-    grid, cull, check = None, dict(kept=[0, 0], total=[0, 0], nonfinite=0), []
+    grid, cull, check, rgb_diff = None, dict(kept=[0, 0], total=[0, 0], nonfinite=0), [], []
+
+    def tally(stats):
+        for p in range(2):
+            cull["kept"][p] += stats["kept"][p]
+            cull["total"][p] += stats["total"][p]
+        cull["nonfinite"] += stats["nonfinite"]
     if occ_cells:
         bounds = args.occupancy_bounds
         if bounds is None:      # the box around the corner rays of every camera between near and far: it holds every sample
@@ -248,9 +266,13 @@ def main(argv=None):
             with torch.no_grad():
                 ro, rd = nerf.get_ray_bundle(size, size, float(k_mat[0, 0]), pose, k_mat)
                 out = nerf.render_dex_normals(size, size, float(k_mat[0, 0]), coarse, fine, ro, rd, cfg, mode="validation",
-                                              encode_position_fn=ex, encode_direction_fn=ed, m_thres_cand=thres)
+                                              encode_position_fn=ex, encode_direction_fn=ed, m_thres_cand=thres, occupancy=grid,
+                                              cull_stats=grid is not None)
             torch.cuda.synchronize()
             times.append(time.perf_counter() - t0)
+            if grid is not None:
+                out, stats = out
+                tally(stats)
             frames.append((None, out.depth, out))
             if args.savedir:   # every normal map as float32, and as a PNG of the unit normal (black: no normal)
                 from PIL import Image
@@ -276,10 +298,7 @@ def main(argv=None):
             times.append(time.perf_counter() - t0)
             if grid is not None:
                 *out, stats = out
-                for p in range(2):
-                    cull["kept"][p] += stats["kept"][p]
-                    cull["total"][p] += stats["total"][p]
-                cull["nonfinite"] += stats["nonfinite"]
+                tally(stats)
                 if args.occupancy_check and thres is not None:
                     with torch.no_grad():
                         full = nerf.render_dex_depth(size, size, float(k_mat[0, 0]), coarse, fine, ro, rd, cfg, mode="validation",
@@ -304,9 +323,20 @@ def main(argv=None):
         with torch.no_grad():
             ro, rd = nerf.get_ray_bundle(size, size, float(k_mat[0, 0]), pose, k_mat)
             out = nerf.run_one_iter_of_nerf(size, size, float(k_mat[0, 0]), coarse, fine, ro, rd, cfg, mode="validation",
-                                            encode_position_fn=ex, encode_direction_fn=ed, m_thres_cand=thres)
+                                            encode_position_fn=ex, encode_direction_fn=ed, m_thres_cand=thres, occupancy=grid,
+                                            cull_stats=grid is not None)
         torch.cuda.synchronize()
         times.append(time.perf_counter() - t0)
+        if grid is not None:
+            *out, stats = out
+            tally(stats)
+            if args.occupancy_check:
+                with torch.no_grad():
+                    full = nerf.run_one_iter_of_nerf(size, size, float(k_mat[0, 0]), coarse, fine, ro, rd, cfg, mode="validation",
+                                                     encode_position_fn=ex, encode_direction_fn=ed, m_thres_cand=thres)
+                slot = 3 if fine is not None else 0
+                rgb_diff.append(float((out[slot] - full[slot]).abs().max()))
+                check.append([(float((a == b).float().mean()), float((a - b).abs().max())) for a, b in zip(out[6:], full[6:])])
         rgb = out[3] if fine is not None else out[0]
         if args.apply_exposure:      # training view i as its camera saw it
             rgb = nerf.apply_exposure(rgb, torch.as_tensor(ck["refined_exposure"])[i], ck["refined_exposure_mode"],
@@ -329,11 +359,15 @@ def main(argv=None):
         if not args.quiet:
             shares = [f"{100 * k / max(t, 1):.2f} % of {t}" for k, t in zip(cull["kept"], cull["total"])]
             print(f"occupancy: kept {shares[0]} coarse samples, {shares[1]} fine samples; {cull['nonfinite']} non-finite sigma", flush=True)
-        if check:
+        if rgb_diff:
+            result.update(occupancy_check=dict(max_rgb_diff=max(rgb_diff)))
+            if not args.quiet:
+                print(f"occupancy check rgb: max |rgb difference| {max(rgb_diff):.3e}", flush=True)
+        if check and thres is not None:
             # per threshold over all views: the share of pixels with equal Dex depth, the largest depth difference
             equal = np.mean([[e for e, _ in view] for view in check], axis=0)
             worst = np.max([[d for _, d in view] for view in check], axis=0)
-            result.update(occupancy_check=dict(m_thres=[float(m) for m in thres], equal=equal.tolist(), max_diff=worst.tolist()))
+            result.setdefault("occupancy_check", {}).update(m_thres=[float(m) for m in thres], equal=equal.tolist(), max_diff=worst.tolist())
             if not args.quiet:
                 for m, e, d in zip(thres, equal, worst):
                     print(f"occupancy check m_thres {int(m):3d}: {100 * e:.3f} % of the pixels equal, max |depth difference| {d:.5f}", flush=True)

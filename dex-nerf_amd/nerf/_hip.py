@@ -76,6 +76,11 @@ OCC_MAX_SAMPLES = 1 << 30           # DN_OCC_MAX_SAMPLES
 OCC_MAX_SAMPLES_PER_RAY = 2048      # DN_OCC_MAX_SAMPLES_PER_RAY
 OCC_FILL = -3.4028234663852886e+38  # DN_OCC_FILL: -FLT_MAX
 
+# include/dexnerf_hip_cull.h: the emit with view directions and the gather of whole rows - the compaction for the culled colour and
+# normal renders (nerf.run_one_iter_of_nerf(occupancy=...), nerf.render_dex_normals(occupancy=...))
+CULL_EXPORTS = ("dn_occupancy_compact_emit_dirs", "dn_occupancy_gather_rows")
+CULL_MAX_WIDTH = 4                  # DN_CULL_MAX_WIDTH
+
 
 class MlpDesc(ctypes.Structure):
     """dn_mlp_desc (mirrors FlexibleNeRFModel.__init__, reference nerf/models.py:186-196)."""
@@ -260,6 +265,11 @@ def _declare(lib):
     lib.dn_occupancy_compact_emit.restype = c_int
     lib.dn_occupancy_gather.argtypes = [vp, fp, c_int64, c_int64, fp, vp, vp, vp]
     lib.dn_occupancy_gather.restype = c_int
+    # the cull header
+    lib.dn_occupancy_compact_emit_dirs.argtypes = [fp, c_int, fp, c_int64, c_int, vp, c_int64, fp, fp, vp]
+    lib.dn_occupancy_compact_emit_dirs.restype = c_int
+    lib.dn_occupancy_gather_rows.argtypes = [vp, fp, c_int, c_int64, c_int64, c_int] + [c_float] * 4 + [fp, c_int, vp, vp, vp]
+    lib.dn_occupancy_gather_rows.restype = c_int
 
 
 def lib():

@@ -1910,3 +1910,163 @@ def render_rays_depth_culled(packed_c, packed_f, rays, num_coarse, num_fine, lin
     depth, acc, dex, *qdepth = last
     maps = ((depth_c, acc_c, depth, acc, dex) if fine else (depth, acc, None, None, dex)) + tuple(qdepth)
     return maps, dict(kept=tuple(kept), total=tuple(total), records=records)
+
+
+# ---- culled colour and normal renders (include/dexnerf_hip_cull.h) --------------------------------------------------------------------------
+def occupancy_compact_emit_dirs(rays, z, slot, max_points, pts=None, dirs=None):
+    """dn_occupancy_compact_emit_dirs: occupancy_compact_emit's pts (max_points,3) and, from the same launch, dirs (max_points,3): row
+    slot[p] = columns 8..10 of sample p's ray row (rays (N, >= 11)); rows at or past max_points are not written."""
+    rays, z = f32c(rays), f32c(z)
+    n, s = z.shape
+    max_points = int(max_points)
+    if pts is None:
+        pts = torch.empty((max(max_points, 0), 3), dtype=torch.float32, device=z.device)
+    if dirs is None:
+        dirs = torch.empty((max(max_points, 0), 3), dtype=torch.float32, device=z.device)
+    for t in (pts, dirs):
+        assert t.dtype == torch.float32 and t.shape[0] >= max_points and t.shape[1:] == (3,)
+    some = max_points > 0
+    check(lib().dn_occupancy_compact_emit_dirs(ptr(rays), rays.shape[1], ptr(z), n, s, ptr(slot), max_points, ptr(pts) if some else None,
+                                               ptr(dirs) if some else None, stream()), "dn_occupancy_compact_emit_dirs")
+    return pts, dirs
+
+
+def occupancy_gather_rows(slot, src, dst, width, fills, ws=None, record=None):
+    """dn_occupancy_gather_rows: dst[p][c] = src[slot[p]][c] for c < width where slot[p] names one of src's rows, else fills[c] - copies
+    of bits.  src: (n_rows, >= width) fp32 with unit stride along a row (a column view like net_out[:, 3:] is read in place), or None
+    (no sample kept).  dst: (..., >= width) fp32 of slot.numel() rows, likewise a view with unit stride along a row and one stride
+    between rows; its other columns are not written.  fills: `width` numbers.  ws and record (occupancy_compact_count's) given: word 2
+    of the record becomes the number of non-finite copied values."""
+    width = int(width)
+    fills = [float(f) for f in fills]
+    if not 1 <= width <= _hip.CULL_MAX_WIDTH or len(fills) != width:
+        raise ValueError(f"occupancy_gather_rows: width must be 1 .. {_hip.CULL_MAX_WIDTH} with one fill per column, got {width} and {len(fills)} fills")
+    n = slot.numel()
+    rows = dst.view(n, dst.shape[-1])     # (a view or an error: never a copy the kernel would write into)
+    assert rows.dtype == torch.float32 and rows.is_cuda and rows.shape[1] >= width
+    assert (rows.stride(1) == 1 or rows.shape[1] == 1) and (rows.stride(0) >= width or n == 1)
+    n_rows = 0 if src is None else int(src.shape[0])
+    src_stride = width
+    if n_rows:
+        assert src.dtype == torch.float32 and src.is_cuda and src.dim() == 2 and src.shape[1] >= width
+        assert (src.stride(1) == 1 or src.shape[1] == 1) and (src.stride(0) >= width or n_rows == 1)
+        src_stride = max(int(src.stride(0)), width)     # (the stride of a single row is never used)
+    check(lib().dn_occupancy_gather_rows(ptr(slot), c_void_p(src.data_ptr()) if n_rows else None, src_stride, n_rows, n, width,
+                                         *(fills + [0.0] * (_hip.CULL_MAX_WIDTH - width)), c_void_p(rows.data_ptr()), max(int(rows.stride(0)), width),
+                                         ptr(ws), ptr(record), stream()), "dn_occupancy_gather_rows")
+    return dst
+
+
+def _compact(rays, z, grid, dirs):
+    """Count, the host read of the kept count (it sizes the network launch), emit -> (slot, record, ws, n_kept, pts | None,
+    view directions | None); dirs: emit a direction row per kept point from columns 8..10 of the ray rows."""
+    slot, record, ws = occupancy_compact_count(rays, z, grid)
+    n_kept = int(record[0].item())
+    pts = vd = None
+    if n_kept and dirs:
+        pts, vd = occupancy_compact_emit_dirs(rays, z, slot, n_kept)
+    elif n_kept:
+        pts = occupancy_compact_emit(rays, z, slot, n_kept)
+    return slot, record, ws, n_kept, pts, vd
+
+
+def _culled_colour_pass(packed, rays, z, grid, count_nonfinite):
+    """One network pass of the culled colour render: (rf (N,S,4): the network's rows at the kept samples, (+0, +0, +0, -FLT_MAX) at the
+    culled ones, n_kept, record)."""
+    slot, record, ws, n_kept, pts, vd = _compact(rays, z, grid, dirs=bool(packed.desc.use_viewdirs))
+    net_out = run_network_pts(packed, pts, vd, 1) if n_kept else None
+    rf = torch.empty(tuple(z.shape) + (4,), dtype=torch.float32, device=z.device)
+    occupancy_gather_rows(slot, net_out, rf, 4, (0.0, 0.0, 0.0, _hip.OCC_FILL), *((ws, record) if count_nonfinite else ()))
+    return rf, n_kept, record
+
+
+def render_rays_culled(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, noise_std, white, m_thres, occupancy, draws=None,
+                       count_nonfinite=False):
+    """render_rays with the networks evaluated only on the samples whose occupancy cell is set, as a chain of entry points on the
+    current stream, per pass: dn_occupancy_compact_count, a host read of the kept count, dn_occupancy_compact_emit_dirs (the plain emit
+    for a network without view directions), dn_run_network on the kept points - explicit points, one sample and one direction row per
+    "ray"; skipped when nothing is kept -, dn_occupancy_gather_rows of its four columns (a culled sample gets rgb +0 and sigma -FLT_MAX:
+    weight exactly 0, no threshold crossing), dn_volume_render.  dn_coarse_depths leads the coarse pass; with a fine pass the coarse one
+    is composited with its weights and without thresholds, dn_fine_depths follows, then the same pass on the fine network.
+
+    Full packs (FlexibleNeRFModel.packed).  m_thres: a list of thresholds.  Returns (render_rays' seven maps, stats): stats as
+    render_rays_depth_culled's.  Two host reads per chunk; the chain cannot be captured into a HIP graph.  The network runs in the
+    packs' precision; the guarded-fp16 render policy does not apply (an explicit-points launch carries no range status)."""
+    packed_c.require_fresh_inference_stream("render_rays_culled")
+    rays = f32c(rays)
+    fine = num_fine > 0 and packed_f is not None
+    if fine:
+        packed_f.require_fresh_inference_stream("render_rays_culled")
+    dirs = bool(packed_c.desc.use_viewdirs)
+    if rays.shape[1] < (11 if dirs else 8) or (fine and bool(packed_f.desc.use_viewdirs) != dirs):
+        raise ValueError("render_rays_culled: networks with view directions need ray rows of 11 columns, and both networks the same kind")
+    t_rand, noise_c, u, noise_f = _draw_tensors(draws)
+    rd = rays[:, 3:6]
+    thres = list(m_thres) if m_thres is not None else []
+    z = coarse_depths(rays, num_coarse, lindisp, t_rand)
+    rf, kept_c, rec_c = _culled_colour_pass(packed_c, rays, z, occupancy, count_nonfinite)
+    kept, total, records = [kept_c, 0], [z.numel(), 0], [rec_c]
+    rgb_c, _, acc_c, weights, depth_c, dex = volume_render_fwd(rf, z, rd, noise_c, noise_std, white, [] if fine else thres, want_weights=fine)
+    rgb_f = depth_f = acc_f = None
+    if fine:
+        z = fine_depths(z, weights, num_fine, u)
+        rf, kept[1], rec_f = _culled_colour_pass(packed_f, rays, z, occupancy, count_nonfinite)
+        total[1] = z.numel()
+        records.append(rec_f)
+        rgb_f, _, acc_f, _, depth_f, dex = volume_render_fwd(rf, z, rd, noise_f, noise_std, white, thres, want_weights=False)
+    return (rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f, dex), dict(kept=tuple(kept), total=tuple(total), records=records)
+
+
+def density_gradient_bytes_per_point(packed_density):
+    """Device bytes density_gradient(pts=) holds per point: the saved tensors of the training forward, the gradient chain's buffers,
+    the output rows, the seed, the points and their gradients."""
+    n = 1 << 16
+    return -(-sum(train_sizes(packed_density, n, prec=packed_density.precision)) // n) + 16 + 16 + 12 + 12
+
+
+def render_rays_normals_culled(packed_c, packed_f, streams, rays, num_coarse, num_fine, lindisp, noise_std, m_thres, occupancy, draws=None,
+                               count_nonfinite=False, max_points=None):
+    """render_rays_normals with the networks evaluated only on the samples whose occupancy cell is set.  With a fine pass the coarse
+    one is render_rays_depth_culled's (_culled_pass, dn_density_resample).  The last pass: count, host read, emit, density_gradient on
+    the kept points (the training forward, the backward-data chain and the input gradient: the most expensive evaluation per sample
+    the library has), dn_occupancy_gather_rows of its sigma (width 1, -FLT_MAX for a culled sample) and of its gradients (width 3, +0:
+    a zero gradient is dn_composite_normals' "no normal"), dn_composite_normals.  max_points: the kept points are differentiated in
+    slabs of at most that many (points are independent: the maps do not depend on the slabs).  Density packs and the
+    DensityGradStreams of the last pass's network.  Returns (render_rays_normals' maps, stats as render_rays_depth_culled's); the count of non-finite values covers
+    sigma, in both passes."""
+    packed_c.require_fresh_inference_stream("render_rays_normals_culled")
+    rays = f32c(rays)
+    fine = num_fine > 0 and packed_f is not None
+    if fine:
+        packed_f.require_fresh_inference_stream("render_rays_normals_culled")
+    t_rand, noise_c, u, noise_f = _draw_tensors(draws)
+    rd = rays[:, 3:6]
+    z = coarse_depths(rays, num_coarse, lindisp, t_rand)
+    kept, total, records = [0, 0], [z.numel(), 0], []
+    depth_c = acc_c = None
+    if fine:
+        rf, kept[0], rec_c = _culled_pass(packed_c, rays, z, occupancy, count_nonfinite)
+        records.append(rec_c)
+        depth_c, acc_c, z = density_resample(rf, z, rd, num_fine, noise_c, noise_std, u)
+        total[1] = z.numel()
+    last = packed_f if fine else packed_c
+    slot, record, ws, n_kept, pts, _ = _compact(rays, z, occupancy, dirs=False)
+    kept[1 if fine else 0] = n_kept
+    records.append(record)
+    dev = z.device
+    sigma = g = None
+    step = n_kept if max_points is None else max(1, int(max_points))
+    if 0 < n_kept <= step:
+        sigma, g = density_gradient(last, streams, pts=pts)
+        sigma = sigma.unsqueeze(-1)          # the .w column of the training forward's rows, read in place: row stride 4
+    elif n_kept:
+        sigma, g = torch.empty((n_kept, 1), dtype=torch.float32, device=dev), torch.empty((n_kept, 3), dtype=torch.float32, device=dev)
+        for p0 in range(0, n_kept, step):
+            part = density_gradient(last, streams, pts=pts[p0:p0 + step])
+            sigma[p0:p0 + step, 0], g[p0:p0 + step] = part
+    rf = torch.empty(tuple(z.shape) + (4,), dtype=torch.float32, device=dev)
+    g_pts = torch.empty(tuple(z.shape) + (3,), dtype=torch.float32, device=dev)
+    occupancy_gather_rows(slot, sigma, rf[..., 3:], 1, (_hip.OCC_FILL,), *((ws, record) if count_nonfinite else ()))
+    occupancy_gather_rows(slot, g, g_pts, 3, (0.0, 0.0, 0.0))
+    depth, acc, dex, normal, dex_normal = composite_normals(rf, z, rd, g_pts, noise_f if fine else noise_c, noise_std, m_thres)
+    return (depth_c, acc_c, depth, acc, dex, normal, dex_normal), dict(kept=tuple(kept), total=tuple(total), records=records)

@@ -312,13 +312,59 @@ def _to_image(maps, shapes):
     return tuple(m.reshape(shape) if m is not None else None for m, shape in zip(maps, shapes))
 
 
+def _culled_precision(who):
+    """Precision code of a culled render: the configured one; 'fp16' raises (explicit points carry no range status)."""
+    if _ops._precision == _ops._hip.PREC_F16:
+        raise RuntimeError(f"{who}(occupancy=...): the culled render evaluates explicit points, which carry no fp16 range status - it "
+                           "runs in 'fp32' or bf16, not under nerf.set_precision('fp16')")
+    return _ops._precision
+
+
+def _refuse_culled_colour(model_coarse, model_fine, ray_origins, ray_directions, options, mode, encode_position_fn, encode_direction_fn,
+                          occupancy):
+    """Every refusal of run_one_iter_of_nerf(occupancy=...) before any GPU work, in render_dex_depth(occupancy=...)'s order -> (the
+    precision code, whether a fine pass runs)."""
+    who = "run_one_iter_of_nerf"
+    prec = _culled_precision(who)
+    occupancy.check_render(ray_directions.device, who)
+    fine = int(getattr(options.nerf, mode).num_fine) > 0 and model_fine is not None
+    models = [model_coarse] + ([model_fine] if fine else [])
+    if _wants_grad(*models) or inputs_need_grad(ray_origins, ray_directions):
+        raise RuntimeError(f"{who}(occupancy=...) is a no-grad render: call it under torch.no_grad() (or with parameters and rays that "
+                           "do not require grad); culling in training is not provided")
+    for m in models:
+        if not _fusable(m, encode_position_fn, encode_direction_fn) or m.use_viewdirs != bool(options.nerf.use_viewdirs):
+            raise RuntimeError(f"{who}(occupancy=...): needs FlexibleNeRFModel networks the fused HIP kernels cover (fused_ok()), this "
+                               "package's embedders with the networks' encodings and nerf.use_viewdirs as the networks have it; there "
+                               "is no fallback")
+    for t in [ray_directions, ray_origins] + [m.layer1.weight for m in models]:
+        _require_device(t, who)
+    return prec, fine
+
+
 def run_one_iter_of_nerf(height, width, focal_length, model_coarse, model_fine, ray_origins, ray_directions, options,
-                         mode="train", encode_position_fn=None, encode_direction_fn=None, m_thres_cand=None):
+                         mode="train", encode_position_fn=None, encode_direction_fn=None, m_thres_cand=None, occupancy=None,
+                         cull_stats=False):
     """Pack rays, chunk, render, concatenate (reference train_utils.py:205-288).
 
     Output order: rgb_coarse, depth_coarse, acc_coarse, rgb_fine, depth_fine, acc_fine, *dex_fine[K]; flat
     (N,3)/(N,) in train mode, reshaped to the image in validation mode (slots 1/4 are depth, not disparity).
+
+    occupancy: an nerf.OccupancyGrid on the rays' device - a no-grad render whose chunks go through _ops.render_rays_culled: the
+    samples of both passes are classified against the grid, the networks run only on the kept ones (explicit points, one view
+    direction row per point), and a culled sample composites as empty space (rgb 0, sigma -FLT_MAX: weight exactly 0).  What
+    render_dex_depth says of its grid holds here: the space the grid lives in, the level, the noise, the draws (made as without a
+    grid), the precision - nerf.set_precision's, 'fp16' raises, the guarded-fp16 render policy does not apply -, two host reads per
+    chunk, no HIP-graph capture.  No-grad only, device tensors only, networks the fused kernels cover only: anything else raises before
+    any GPU work.  cull_stats=True (with a grid only) appends render_dex_depth's dict(kept=, total=, nonfinite=) to the return -
+    nonfinite counts all four columns of the kept rows.  occupancy=None: the launches and the return are what they were.
     """
+    if occupancy is None and cull_stats:
+        raise ValueError("run_one_iter_of_nerf: cull_stats reports on a culled render: give occupancy=")
+    culled = None
+    if occupancy is not None:
+        culled = _refuse_culled_colour(model_coarse, model_fine, ray_origins, ray_directions, options, mode, encode_position_fn,
+                                       encode_direction_fn, occupancy)
     _require_device(ray_directions, "run_one_iter_of_nerf")
     thres = _thresholds(m_thres_cand)
     # device rays that need no gradient: the rows are packed by one kernel (dn_pack_ray_rows), op for op what follows
@@ -346,12 +392,49 @@ def run_one_iter_of_nerf(height, width, focal_length, model_coarse, model_fine, 
     def render_chunk(batch, status):
         return _render_chunk(batch, model_coarse, model_fine, options, mode, encode_position_fn, encode_direction_fn, thres,
                              status=status, fp16_ok=status is not None)
-    images = _render_chunks(rays, getattr(options.nerf, mode).chunksize, render_chunk)
+    stats = None
+    if culled is None:
+        images = _render_chunks(rays, getattr(options.nerf, mode).chunksize, render_chunk)
+    else:
+        images, stats = _render_chunks_culled(rays, model_coarse, model_fine, options, mode, encode_position_fn, encode_direction_fn, thres,
+                                              occupancy, culled, cull_stats)
+    tail = (stats,) if cull_stats else ()
     if mode != "validation":
-        return tuple(images)
+        return tuple(images) + tail
     # rgb, depth, acc per pass (coarse-only: the reference returns the 3 maps + three Nones), then the Dex depths
     three = [img_shape, img_shape[:-1], img_shape[:-1]]
-    return _to_image(images, three + (three if model_fine else [None, None, None]) + [img_shape[:-1]] * len(thres))
+    return _to_image(images, three + (three if model_fine else [None, None, None]) + [img_shape[:-1]] * len(thres)) + tail
+
+
+def _render_chunks_culled(rays, model_coarse, model_fine, options, mode, encode_position_fn, encode_direction_fn, thres, occupancy, culled,
+                          cull_stats):
+    """run_one_iter_of_nerf's chunk loop on _ops.render_rays_culled -> (the joined maps, the stats dict | None): the draws of every
+    chunk from _draws, as without a grid; the kept / total counts summed on the host (the chain reads them anyway), the non-finite
+    counts summed on the device and read once at the end, only when the stats are asked for."""
+    prec, fine = culled
+    opt = getattr(options.nerf, mode)
+    nc, nf = int(opt.num_coarse), int(opt.num_fine) if fine else 0
+    std = float(opt.radiance_field_noise_std)
+    lx = encode_position_fn.log_sampling
+    ld = encode_direction_fn.log_sampling if model_coarse.use_viewdirs else True
+    pc = model_coarse.packed(lx, ld, precision=prec)
+    pf = model_fine.packed(lx, ld, precision=prec) if fine else None
+    kept, total, records = [0, 0], [0, 0], []
+
+    def render_chunk(batch):
+        draws = _draws(batch.shape[0], nc, nf, fine, bool(opt.perturb), std, batch.device)
+        maps, stats = _ops.render_rays_culled(pc, pf, batch, nc, nf, bool(opt.lindisp), std, bool(opt.white_background), thres, occupancy,
+                                              draws, count_nonfinite=cull_stats)
+        for p in range(2):
+            kept[p] += stats["kept"][p]
+            total[p] += stats["total"][p]
+        records.extend(stats["records"])
+        dex = maps[6]
+        return list(maps[:6]) + ([] if dex is None else [dex[k] for k in range(dex.shape[0])])
+    images = _join_chunks([render_chunk(batch) for batch in get_minibatches(rays, chunksize=opt.chunksize)])
+    if not cull_stats:
+        return images, None
+    return images, dict(kept=tuple(kept), total=tuple(total), nonfinite=int(torch.stack(records)[:, 2].sum().item()))
 
 
 _THRESHOLDS_ON_DEVICE = {}   # (thresholds, device) -> device tensor: one host-to-device copy per threshold set, none per render
@@ -557,7 +640,7 @@ def _rays_within_workspace(packs, n, nc, nf, max_bytes):
 
 def render_dex_normals(height, width, focal_length, model_coarse, model_fine, ray_origins, ray_directions, options,
                        mode="validation", encode_position_fn=None, encode_direction_fn=None, m_thres_cand=None,
-                       max_workspace_bytes=2 ** 31):
+                       max_workspace_bytes=2 ** 31, occupancy=None, cull_stats=False):
     """render_dex_depth's last pass with surface normals: the density sub-network of the last pass (the fine one; the coarse one
     without a fine pass) is differentiated w.r.t. its input points, and n = -grad sigma_raw / |grad sigma_raw| is composited beside
     the depths (dn_render_rays_normals).
@@ -575,8 +658,21 @@ def render_dex_normals(height, width, focal_length, model_coarse, model_fine, ra
     networks the fused kernels cover only: anything else raises.  Precision follows nerf.set_precision: 'fp32' runs fp32, 'bf16' and
     'bf16-s16' both run bf16 with 16-bit saved tensors, 'fp16' raises - there is no fp16 instance of the training kernels, so the
     fp16 render policy (nerf.set_render_policy) and its range guard do not apply here.  The last pass's sigma comes from the
-    training-forward kernel: depth may differ from render_dex_depth's in the last bits."""
+    training-forward kernel: depth may differ from render_dex_depth's in the last bits.
+
+    occupancy: an nerf.OccupancyGrid on the rays' device - each chunk then goes through _ops.render_rays_normals_culled: the samples of
+    both passes are classified against the grid, the coarse density network and the differentiated last pass (forward, backward-data
+    chain, input gradient) run only on the kept ones; a culled sample composites as empty space with a zero gradient, the kernel's "no
+    normal".  What render_dex_depth says of its grid holds here (space, level, noise, draws, two host reads per chunk, no HIP-graph
+    capture); max_workspace_bytes then bounds the saved tensors of the kept points, which are differentiated in slabs (points are
+    independent: the maps do not depend on the slabs), not the rays of a chunk.  cull_stats=True (with
+    a grid only) returns (DexNormals, dict(kept=, total=, nonfinite=)).  occupancy=None: the launches and the return are what they
+    were."""
+    if occupancy is None and cull_stats:
+        raise ValueError("render_dex_normals: cull_stats reports on a culled render: give occupancy=")
     prec = _normals_precision("render_dex_normals")
+    if occupancy is not None:
+        occupancy.check_render(ray_directions.device, "render_dex_normals")
     r = _density_render_setup("render_dex_normals", "gradients through the normals are second order and not provided", height, width,
                               focal_length, model_coarse, model_fine, ray_origins, ray_directions, options, mode, encode_position_fn,
                               m_thres_cand)
@@ -597,11 +693,27 @@ def render_dex_normals(height, width, focal_length, model_coarse, model_fine, ra
                 *packs, streams, batch[rows], nc, nf, r.lindisp, r.std, r.m_thres, {name: d[rows] for name, d in draws.items()})
             pieces.append([depth, acc, normal] + [dex[i] for i in range(k)] + [dex_normal[i] for i in range(k)])
         return _join_chunks(pieces)
-    maps = _join_chunks([render_chunk(batch) for batch in get_minibatches(r.rays, chunksize=getattr(options.nerf, mode).chunksize)])
+    kept, total, records = [0, 0], [0, 0], []
+    max_points = max(1, max_bytes // _ops.density_gradient_bytes_per_point(packs[1] if r.fine else packs[0])) if occupancy is not None else None
+
+    def render_chunk_culled(batch):
+        draws = _draws(batch.shape[0], nc, nf, r.fine, r.perturb, r.std, r.dev)
+        (_, _, depth, acc, dex, normal, dex_normal), stats = _ops.render_rays_normals_culled(
+            *packs, streams, batch, nc, nf, r.lindisp, r.std, r.m_thres, occupancy, draws, count_nonfinite=cull_stats, max_points=max_points)
+        for p in range(2):
+            kept[p] += stats["kept"][p]
+            total[p] += stats["total"][p]
+        records.extend(stats["records"])
+        return [depth, acc, normal] + [dex[i] for i in range(k)] + [dex_normal[i] for i in range(k)]
+    one_chunk = render_chunk if occupancy is None else render_chunk_culled
+    maps = _join_chunks([one_chunk(batch) for batch in get_minibatches(r.rays, chunksize=getattr(options.nerf, mode).chunksize)])
     if mode == "validation":
         flat, vec = r.img_shape[:-1], r.img_shape
         maps = _to_image(maps, [flat, flat, vec] + [flat] * k + [vec] * k)
-    return DexNormals(maps[0], maps[1], maps[2], tuple(maps[3:3 + k]), tuple(maps[3 + k:3 + 2 * k]))
+    out = DexNormals(maps[0], maps[1], maps[2], tuple(maps[3:3 + k]), tuple(maps[3 + k:3 + 2 * k]))
+    if cull_stats:
+        return out, dict(kept=tuple(kept), total=tuple(total), nonfinite=int(torch.stack(records)[:, 2].sum().item()))
+    return out
 
 
 # ---- the Dex threshold surface as a triangle mesh -------------------------------------------------------------------------------------
