@@ -4,7 +4,10 @@
 //                             ray forms the coarse weights in registers, drops weights[1:-1] + 1e-5 straight into the sampler's
 //                             LDS row and runs the sampler's own code on it: the (N, Nc) weights never reach HBM.
 //   composite_density_kernel: depth, acc and dex (K, N) for any K (thresholds in device memory, 64 per pass).
+//   composite_brackets_kernel: the same without noise, plus the bracket record and first midpoint of every first crossing
+//                             (include/dexnerf_hip_refine.h; the bisection and the finish are dex_refine.hip's).
 // One wave64 per ray, four rays per workgroup, like composite.hip / the sampler.
+#include "../../include/dexnerf_hip_refine.h"
 #include "composite_body.h"
 #include "sampler_body.h"
 
@@ -47,6 +50,34 @@ __global__ __launch_bounds__(256) void composite_density_kernel(const float4* __
   if (ray >= n_rays) return;  // wave-uniform exit; no block-level sync in this kernel
   forward_ray(SigmaColumn(rf + ray * S), TensorNoise{noise, noise_std, ray, S}, DeviceThres{d_thres, n_thres}, z + ray * S,
               rd + ray * rd_stride, ray, true, lane, n_rays, S, acc, depth, dex, nonfinite, [](int, bool, float, float) {});
+}
+
+// composite_density_kernel without noise whose first-crossing hook writes the bracket record (z_lo, z_hi, s_lo, s_hi) of every
+// threshold and its first midpoint (include/dexnerf_hip_refine.h).  The hook runs once per (ray, threshold) in the lane that holds the
+// threshold: two depths and two raw densities re-read from the ray's rows (L2-resident by then), one 16-byte store, one 4-byte store.
+__global__ __launch_bounds__(256) void composite_brackets_kernel(const float4* __restrict__ rf, const float* __restrict__ z,
+                                                                 const float* __restrict__ rd, int rd_stride, const float* __restrict__ d_thres,
+                                                                 int n_thres, int64_t n_rays, int S, float* __restrict__ depth,
+                                                                 float* __restrict__ acc, float* __restrict__ dex, float4* __restrict__ br,
+                                                                 float* __restrict__ z_mid, unsigned* __restrict__ nonfinite) {
+  const int lane = lane_id();
+  const int64_t ray = static_cast<int64_t>(blockIdx.x) * kSamplerWaves + (threadIdx.x >> 6);
+  if (ray >= n_rays) return;  // wave-uniform exit; no block-level sync in this kernel
+  const SigmaColumn sig(rf + ray * S);
+  const float* zr = z + ray * S;
+  forward_ray(sig, TensorNoise{nullptr, 0.0f, ray, S}, DeviceThres{d_thres, n_thres}, zr, rd + ray * rd_stride, ray, true, lane, n_rays, S, acc,
+              depth, dex, nonfinite, [](int, bool, float, float) {}, [&](int k, int idx) {
+                float4 r;
+                if (idx < 0) {
+                  r = make_float4(zr[0], zr[0], __builtin_inff(), -__builtin_inff());
+                } else {
+                  const int lo = idx > 0 ? idx - 1 : 0;
+                  r = make_float4(zr[lo], zr[idx], sig(lo), sig(idx));
+                }
+                const int64_t rec = ray * n_thres + k;
+                br[rec] = r;
+                z_mid[rec] = r.x + 0.5f * (r.y - r.x);
+              });
 }
 
 static int next_pow2(int v) {
@@ -92,9 +123,28 @@ int composite_density_counting(const SigmaCompositeArgs& a, dn_stream_t stream) 
   return check_launch("dn_composite_density");
 }
 
+int composite_brackets_counting(const SigmaCompositeArgs& a, float* br, float* z_mid, dn_stream_t stream) {
+  const char* who = "dn_composite_density_brackets";
+  if (a.n_rays == 0) return 0;   // (before the checks, like dn_composite_density: empty tensors carry NULL data pointers)
+  DN_REQUIRE(a.rf && a.z && a.rd && br && z_mid && a.n_rays >= 0 && a.n_samples >= 1 && a.rd_stride >= 3, "%s: bad arguments", who);
+  DN_REQUIRE(a.n_thres >= 1 && a.d_m_thres, "%s: needs at least one threshold", who);
+  DN_REQUIRE(((reinterpret_cast<uintptr_t>(a.rf) | reinterpret_cast<uintptr_t>(br)) & 15) == 0, "%s: rf and br must be 16-byte aligned", who);
+  hipLaunchKernelGGL(composite_brackets_kernel, dim3(ray_grid(a.n_rays)), dim3(256), 0, as_stream(stream), reinterpret_cast<const float4*>(a.rf),
+                     a.z, a.rd, a.rd_stride, a.d_m_thres, a.n_thres, a.n_rays, a.n_samples, a.depth, a.acc, a.dex, reinterpret_cast<float4*>(br),
+                     z_mid, a.nonfinite);
+  return check_launch(who);
+}
+
 }  // namespace dn
 
 using namespace dn;
+
+extern "C" int dn_composite_density_brackets(const float* rf, const float* z, const float* rd, int rd_stride, const float* d_m_thres,
+                                             int n_thres, int64_t n_rays, int n_samples, float* depth, float* acc, float* dex, float* br,
+                                             float* z_mid, dn_stream_t stream) {
+  return composite_brackets_counting({rf, z, rd, rd_stride, nullptr, 0.0f, d_m_thres, n_thres, n_rays, n_samples, depth, acc, dex}, br, z_mid,
+                                     stream);
+}
 
 extern "C" int dn_density_resample(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise,
                                    float noise_std, const float* u, int64_t n_rays, int num_coarse, int num_fine, float* depth,

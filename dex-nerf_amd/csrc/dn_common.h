@@ -69,6 +69,12 @@ int composite_density_counting(const SigmaCompositeArgs& a, dn_stream_t stream);
 int density_resample_counting(const float* rf, const float* z, const float* rd, int rd_stride, const float* noise, float noise_std,
                               const float* u, int64_t n_rays, int num_coarse, int num_fine, float* depth, float* acc, float* z_fine,
                               unsigned* nonfinite, dn_stream_t stream);
+// the refined Dex depth (include/dexnerf_hip_refine.h): dn_composite_density_brackets (composite_density.hip; a.noise is not read),
+// dn_dex_bisect and dn_dex_refine_finish (dex_refine.hip)
+int composite_brackets_counting(const SigmaCompositeArgs& a, float* br, float* z_mid, dn_stream_t stream);
+int dex_bisect_launch(float* br, const float* rf_mid, const float* d_m_thres, int n_thres, int64_t n_rays, float* z_mid, dn_stream_t stream);
+int dex_refine_finish_launch(const float* br, const float* d_m_thres, int n_thres, int64_t n_rays, float* refined, float* width,
+                             dn_stream_t stream);
 // composite_quantile.hip: the quantile arguments' rule (`who`: the entry point, for messages) and dn_composite_density_quantiles
 int quantile_args_check(const char* who, const float* d_quantiles, int n_quant, int interp, const float* qdepth);
 int composite_quantile_counting(const SigmaCompositeArgs& a, dn_stream_t stream);

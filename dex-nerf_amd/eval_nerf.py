@@ -5,6 +5,8 @@ poses in validation mode, optionally save RGB / disparity-style depth PNGs, and 
 `--depth-only --m-thres M` renders the depth and Dex depth maps alone (nerf.render_dex_depth): no colour is evaluated, no RGB PNG
 is written, and the maps go to dex_<view>.npz beside depth_<view>.png.  `--depth-quantiles 0.1,0.5,0.9 [--quantile-interp]` adds the
 opacity-quantile depth maps (0.5: the median depth) to the same render and the same file (quantiles / qdepth), with or without --m-thres.
+`--depth-only --m-thres M --dex-refine R [--dex-refine-width]` adds the refined Dex depth maps (nerf.render_dex_depth(refine_steps=R): the first
+crossing bracketed between two samples, halved R times on the density network, interpolated) as dex_refined / dex_width in the same file.
 `--depth-only --occupancy N[,N,N] [--occupancy-bounds x0 y0 z0 x1 y1 z1] [--occupancy-level L] [--occupancy-dilate D]` builds an
 occupancy grid of the two networks (nerf.OccupancyGrid.from_networks) and renders with the networks evaluated only on the samples in
 set cells; `--occupancy-check` renders every view both ways and reports, per threshold, the share of equal Dex depths.
@@ -74,6 +76,13 @@ def main(argv=None):
                          "(0.5: the median depth), e.g. 0.1,0.5,0.9; at most 64 values strictly inside (0, 1); saved as quantiles / qdepth")
     ap.add_argument("--quantile-interp", action="store_true",
                     help="--depth-quantiles: the piecewise-linear CDF inversion instead of the depth of the crossing sample")
+    ap.add_argument("--dex-refine", type=int, default=None, metavar="R",
+                    help="--depth-only --m-thres: also the refined Dex depth maps - the first crossing bracketed between two samples, halved "
+                         "R times (0..24) on the density network and interpolated (nerf.render_dex_depth(refine_steps=R)); saved as "
+                         "dex_refined beside dex; not with --depth-quantiles or --occupancy")
+    ap.add_argument("--dex-refine-width", action="store_true",
+                    help="--dex-refine: also the width of the last bracket per pixel (-1: no crossing, 0: crossing at the first sample); "
+                         "saved as dex_width")
     ap.add_argument("--normals", action="store_true",
                     help="render surface normals only (nerf.render_dex_normals: the density gradient at the samples, composited like the "
                          "depth; with --m-thres also the normal at every Dex depth); not with --precision fp16")
@@ -122,6 +131,17 @@ def main(argv=None):
         ap.error("--quantile-interp needs --depth-quantiles")
     if args.depth_only and args.m_thres <= 0 and not quantiles:
         ap.error("--depth-only renders the Dex / quantile depth maps: give --m-thres > 0 or --depth-quantiles")
+    if args.dex_refine is not None:
+        try:
+            _ops.check_refine_steps(args.dex_refine, "--dex-refine")
+        except ValueError as e:
+            ap.error(str(e))
+        if not args.depth_only or args.m_thres <= 0:
+            ap.error("--dex-refine refines the Dex depth maps of --depth-only: it needs --depth-only and --m-thres > 0")
+        if quantiles or args.occupancy:
+            ap.error("--dex-refine is not supported together with --depth-quantiles or --occupancy")
+    elif args.dex_refine_width:
+        ap.error("--dex-refine-width belongs to --dex-refine")
     if args.normals and args.precision == "fp16":
         ap.error("--normals differentiates the density network on the training kernels, which exist for fp32 and bf16: not with --precision fp16")
     if args.normals and (args.depth_only or args.apply_exposure):
@@ -293,7 +313,7 @@ def main(argv=None):
                 out = nerf.render_dex_depth(size, size, float(k_mat[0, 0]), coarse, fine, ro, rd, cfg, mode="validation",
                                             encode_position_fn=ex, encode_direction_fn=ed, m_thres_cand=thres,
                                             quantiles=quantiles or None, quantile_interp=args.quantile_interp, occupancy=grid,
-                                            cull_stats=grid is not None)
+                                            cull_stats=grid is not None, refine_steps=args.dex_refine, refine_width=args.dex_refine_width)
             torch.cuda.synchronize()
             times.append(time.perf_counter() - t0)
             if grid is not None:
@@ -307,7 +327,10 @@ def main(argv=None):
             depth = out[2] if fine is not None else out[0]
             n_dex = 0 if thres is None else len(thres)
             dex_maps, q_maps = out[4:4 + n_dex], out[4 + n_dex:]
-            frames.append((None, depth, dex_maps) + ((q_maps,) if quantiles else ()))
+            refined_maps = width_maps = ()
+            if args.dex_refine is not None:   # (never with quantiles: the maps behind the Dex maps are the refined ones, then the widths)
+                refined_maps, width_maps, q_maps = out[4 + n_dex:4 + 2 * n_dex], out[4 + 2 * n_dex:], ()
+            frames.append((None, depth, dex_maps) + ((q_maps,) if quantiles else ()) + ((refined_maps, width_maps) if refined_maps else ()))
             if args.savedir:   # the expected depth as a PNG, every map (depth + one Dex depth per threshold) as float32
                 from PIL import Image
                 d = depth.cpu().numpy()
@@ -318,6 +341,10 @@ def main(argv=None):
                     arrays.update(m_thres=np.asarray(thres, np.float32), dex=torch.stack(list(dex_maps)).cpu().numpy())
                 if quantiles:
                     arrays.update(quantiles=np.asarray(quantiles, np.float32), qdepth=torch.stack(list(q_maps)).cpu().numpy())
+                if refined_maps:
+                    arrays.update(dex_refine_steps=np.int32(args.dex_refine), dex_refined=torch.stack(list(refined_maps)).cpu().numpy())
+                if width_maps:
+                    arrays.update(dex_width=torch.stack(list(width_maps)).cpu().numpy())
                 np.savez(os.path.join(args.savedir, f"dex_{i:04d}.npz"), **arrays)
             continue
         with torch.no_grad():

@@ -81,6 +81,12 @@ OCC_FILL = -3.4028234663852886e+38  # DN_OCC_FILL: -FLT_MAX
 CULL_EXPORTS = ("dn_occupancy_compact_emit_dirs", "dn_occupancy_gather_rows")
 CULL_MAX_WIDTH = 4                  # DN_CULL_MAX_WIDTH
 
+# include/dexnerf_hip_refine.h: sub-sample Dex depths - the first crossing bracketed by the compositing pass and bisected on the density
+# network (nerf.render_dex_depth(refine_steps=...))
+REFINE_EXPORTS = ("dn_composite_density_brackets", "dn_dex_bisect", "dn_dex_refine_finish", "dn_render_depth_refined_workspace_bytes",
+                  "dn_render_rays_depth_refined")
+MAX_REFINE_STEPS = 24               # DN_MAX_REFINE_STEPS
+
 
 class MlpDesc(ctypes.Structure):
     """dn_mlp_desc (mirrors FlexibleNeRFModel.__init__, reference nerf/models.py:186-196)."""
@@ -270,6 +276,17 @@ def _declare(lib):
     lib.dn_occupancy_compact_emit_dirs.restype = c_int
     lib.dn_occupancy_gather_rows.argtypes = [vp, fp, c_int, c_int64, c_int64, c_int] + [c_float] * 4 + [fp, c_int, vp, vp, vp]
     lib.dn_occupancy_gather_rows.restype = c_int
+    # the refine header
+    lib.dn_composite_density_brackets.argtypes = [fp, fp, fp, c_int, fp, c_int, c_int64, c_int, fp, fp, fp, fp, fp, vp]
+    lib.dn_composite_density_brackets.restype = c_int
+    lib.dn_dex_bisect.argtypes = [fp, fp, fp, c_int, c_int64, fp, vp]
+    lib.dn_dex_bisect.restype = c_int
+    lib.dn_dex_refine_finish.argtypes = [fp, fp, c_int, c_int64, fp, fp, vp]
+    lib.dn_dex_refine_finish.restype = c_int
+    lib.dn_render_depth_refined_workspace_bytes.argtypes = [c_int64, c_int, c_int, c_int]
+    lib.dn_render_depth_refined_workspace_bytes.restype = c_size_t
+    lib.dn_render_rays_depth_refined.argtypes = lib.dn_render_rays_depth.argtypes[:-2] + [c_int, fp, fp, vp, vp]
+    lib.dn_render_rays_depth_refined.restype = c_int
 
 
 def lib():

@@ -1305,19 +1305,106 @@ def density_resample(rf, z, rd, num_fine, noise=None, noise_std=0.0, u=None):
     return depth, acc, z_fine
 
 
+def check_refine_steps(steps, who="refine_steps"):
+    """The host-side rule of the bisection count: an int (not a bool) in 0 .. 24.  Raises ValueError before any GPU work."""
+    if isinstance(steps, bool) or not isinstance(steps, int) or not 0 <= steps <= _hip.MAX_REFINE_STEPS:
+        raise ValueError(f"{who}: the number of bisection steps must be an int in 0 .. {_hip.MAX_REFINE_STEPS}, got {steps!r}")
+    return steps
+
+
+def check_refine_thresholds(m_thres, who="refine"):
+    """The host-side rule of the thresholds a refinement brackets (the C layer cannot read device memory): at least one, each finite
+    and >= 0 - for those relu(sigma) > m iff sigma > m, so the bracket is the Dex depth's.  Raises ValueError before any GPU work."""
+    ms = [float(m) for m in (m_thres if m_thres is not None else [])]
+    if not ms:
+        raise ValueError(f"{who}: a refinement needs at least one Dex threshold")
+    for m in ms:
+        if not (math.isfinite(m) and m >= 0.0):
+            raise ValueError(f"{who}: every refined threshold must be finite and >= 0, got {m!r}")
+    return ms
+
+
+def composite_density_brackets(rf, z, rd, m_thres):
+    """dn_composite_density_brackets: composite_density's (depth, acc, dex (K,N)) without noise, then br (N,K,4) - the bracket record
+    (z_lo, z_hi, s_lo, s_hi) of every first crossing - and z_mid (N,K), the first midpoints (include/dexnerf_hip_refine.h).  m_thres: a
+    list or a device tensor of K >= 1 thresholds, each >= 0 (a list is checked here; a tensor is the caller's to validate)."""
+    if not torch.is_tensor(m_thres):
+        check_refine_thresholds(m_thres, "composite_density_brackets")
+    c = _sigma_call(rf, z, rd, None, 0.0, m_thres)
+    if not c.k:
+        raise ValueError("composite_density_brackets: a refinement needs at least one Dex threshold")
+    depth, acc = _pass_maps(c.dev, c.n)
+    dex, br, z_mid = _empty(c.dev, c.k, c.n), _empty(c.dev, c.n, c.k, 4), _empty(c.dev, c.n, c.k)
+    check(lib().dn_composite_density_brackets(*c.head[:4], ptr(c.thres), c.k, c.n, c.s, ptr(depth), ptr(acc), ptr(dex), ptr(br), ptr(z_mid),
+                                              stream()), "dn_composite_density_brackets")
+    return depth, acc, dex, br, z_mid
+
+
+def dex_bisect(br, rf_mid, m_thres, z_mid=None):
+    """dn_dex_bisect: one bisection step IN PLACE on the records br (N,K,4) with the density network's rows rf_mid (N,K,4) at the
+    current midpoints; returns the next midpoints z_mid (N,K) (written into `z_mid` when given).  m_thres: a device tensor (K,)."""
+    n, k = br.shape[0], br.shape[1]
+    assert br.dtype == torch.float32 and br.is_contiguous() and br.shape == (n, k, 4) and m_thres.numel() == k
+    rf_mid = f32c(rf_mid)
+    assert rf_mid.numel() == n * k * 4
+    z_mid = _empty(br.device, n, k) if z_mid is None else z_mid
+    assert z_mid.dtype == torch.float32 and z_mid.is_contiguous() and z_mid.numel() == n * k
+    check(lib().dn_dex_bisect(ptr(br), ptr(rf_mid), ptr(m_thres), k, n, ptr(z_mid), stream()), "dn_dex_bisect")
+    return z_mid
+
+
+def dex_refine_finish(br, m_thres, want_width=True):
+    """dn_dex_refine_finish: (refined (K,N), width (K,N) | None) of the records br (N,K,4): the linear interpolation of the last
+    bracket; width -1 marks rays without a crossing (refined = z[0], the Dex fallback), 0 a crossing at the first sample."""
+    br = f32c(br)
+    n, k = br.shape[0], br.shape[1]
+    assert br.shape == (n, k, 4) and m_thres.numel() == k
+    refined = _empty(br.device, k, n)
+    width = _empty(br.device, k, n) if want_width else None
+    check(lib().dn_dex_refine_finish(ptr(br), ptr(m_thres), k, n, ptr(refined), ptr(width), stream()), "dn_dex_refine_finish")
+    return refined, width
+
+
+def render_refined_records_offset(n, num_coarse, num_fine):
+    """Byte offset of the bracket records br (N,K,4) in dn_render_rays_depth_refined's workspace (include/dexnerf_hip_refine.h)."""
+    return lib().dn_render_depth_workspace_bytes(n, num_coarse, num_fine) - 256
+
+
 def render_rays_depth(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, noise_std, m_thres, draws=None, quantiles=None,
-                      interp=False):
+                      interp=False, refine_steps=None, want_width=False):
     """dn_render_rays_depth: the depth-only predict_and_render_radiance forward for one ray chunk (no autograd, no colour) on
     density packs (FlexibleNeRFModel.packed_density).  m_thres: a device tensor of K thresholds (any K) or None.
     quantiles: a device tensor of Q <= 64 opacity quantiles the caller has validated (check_quantiles) - the call then goes to
     dn_render_rays_depth_quantiles (same launches, the last pass composited by the quantile kernel) and returns qdepth (Q,N) as a
-    sixth value; None: the call and the return are what they were."""
+    sixth value; None: the call and the return are what they were.
+    refine_steps: an int in 0 .. 24 - the call then goes to dn_render_rays_depth_refined (the last compositing launch writes the
+    first-crossing brackets, then `refine_steps` bisections on the last pass's density network, then the finish) and returns
+    refined (K,N) as a sixth value and, with want_width, width (K,N) as a seventh.  The thresholds must be >= 0 (the caller validates
+    them: check_refine_thresholds), noise_std 0; not together with quantiles.  None: the call and the return are what they were."""
+    if refine_steps is not None:
+        check_refine_steps(refine_steps, "render_rays_depth: refine_steps")
+        if quantiles is not None:
+            raise ValueError("render_rays_depth: refine_steps together with quantiles is not supported")
+        if float(noise_std) != 0.0:
+            raise ValueError("render_rays_depth: refine_steps brackets the raw density: noise_std must be 0")
+        if m_thres is None or not int(m_thres.numel()):
+            raise ValueError("render_rays_depth: a refinement needs at least one Dex threshold")
     c = _render_call(packed_c, packed_f, rays, num_fine, m_thres, draws)
     n, dev = c.n, c.dev
-    ws = _render_workspace(dev, lib().dn_render_depth_workspace_bytes(n, num_coarse, c.nf))
+    if refine_steps is None:
+        ws = _render_workspace(dev, lib().dn_render_depth_workspace_bytes(n, num_coarse, c.nf))
+    else:
+        ws = _render_workspace(dev, _sized(lib().dn_render_depth_refined_workspace_bytes(n, num_coarse, c.nf, c.k),
+                                           "dn_render_depth_refined_workspace_bytes"))
     maps = _pass_maps(dev, n) + _pass_maps(dev, n, c.fine) + (_empty(dev, c.k, n) if c.k else None,)
     args = [*c.net_args, packed_c.precision, ptr(c.rays), c.rays.shape[1], n, num_coarse, c.nf, int(bool(lindisp)), float(noise_std),
             ptr(m_thres) if c.k else None, c.k, *[ptr(d) for d in c.draws], *[ptr(m) for m in maps]]
+    if refine_steps is not None:
+        refined = _empty(dev, c.k, n)
+        width = _empty(dev, c.k, n) if want_width else None
+        check(lib().dn_render_rays_depth_refined(*args, refine_steps, ptr(refined), ptr(width), ptr(ws), stream()),
+              "dn_render_rays_depth_refined")
+        return maps + ((refined, width) if want_width else (refined,))
     if quantiles is None:
         check(lib().dn_render_rays_depth(*args, ptr(ws), stream()), "dn_render_rays_depth")
         return maps

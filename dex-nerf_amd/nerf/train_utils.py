@@ -523,7 +523,7 @@ def _render_dex_depth_culled(r, prec, occupancy, q_dev, interp, cull_stats, chun
 
 def render_dex_depth(height, width, focal_length, model_coarse, model_fine, ray_origins, ray_directions, options,
                      mode="validation", encode_position_fn=None, encode_direction_fn=None, m_thres_cand=None, quantiles=None,
-                     quantile_interp=False, occupancy=None, cull_stats=False):
+                     quantile_interp=False, occupancy=None, cull_stats=False, refine_steps=None, refine_width=False):
     """The depth half of run_one_iter_of_nerf and nothing else: expected depth, accumulation and the Dex first-crossing depths
     depend on sigma alone (reference nerf/volume_rendering_utils.py:33-58), so this render evaluates only the density
     sub-networks (trunk + fc_alpha: FlexibleNeRFModel.packed_density) and composites no colour (dn_render_rays_depth).
@@ -552,7 +552,30 @@ def render_dex_depth(height, width, focal_length, model_coarse, model_fine, ray_
     guarded-fp16 policy on this path is a follow-up).  It reads the kept count back once per network pass - two host reads per chunk -
     and cannot be captured into a HIP graph.  cull_stats=True (with a grid only) appends one more value to the return: dict(kept=
     (coarse, fine), total=(coarse, fine), nonfinite=...) summed over the chunks - nonfinite: the non-finite raw sigma values the kept
-    samples produced.  occupancy=None: the launches and the return are what they were."""
+    samples produced.  occupancy=None: the launches and the return are what they were.
+
+    refine_steps: an int R in 0 .. 24 - K refined maps follow the K Dex maps (dn_render_rays_depth_refined): the Dex depth is z_i of
+    the first sample whose density exceeds m, up to one sample interval late; the refined depth takes the bracket [z_{i-1}, z_i], halves
+    it R times with one evaluation of the last pass's density network at the midpoint per step, and interpolates the last bracket
+    linearly (R = 0: the interpolation of the sample bracket alone, no evaluation).  A ray whose first sample already crosses keeps z_0;
+    a ray without a crossing keeps the Dex fallback z_0.  refine_width=True: K width maps follow the refined ones - the last bracket's
+    width, 0 for a crossing at the first sample and -1 for rays without a crossing: the hit mask the Dex depth never had.  The
+    refinement finds A crossing inside the first bracket: where the field crosses m three times between two samples that need not be
+    the first one, and a crossing thinner than the sample spacing can be stepped over altogether, as by the Dex depth itself.  Judged
+    here, on the host, before any GPU work (ValueError): steps that are not an int in 0 .. 24, no thresholds, a negative or non-finite
+    threshold, a mode whose radiance_field_noise_std is not 0 (the brackets are those of the raw density), and quantiles= or occupancy=
+    together with a refinement (both are follow-ups: a culled sample's -FLT_MAX is not a density to interpolate with).  Follows
+    nerf.set_render_policy like the plain render: the midpoint evaluations report into the status words the guard reads.  No host read:
+    a chunk can be captured into a HIP graph.  refine_steps=None: the launches and the return are what they were."""
+    if refine_steps is not None:
+        _ops.check_refine_steps(refine_steps, "render_dex_depth: refine_steps")
+        _ops.check_refine_thresholds(m_thres_cand, "render_dex_depth: refine_steps")
+        if quantiles is not None or occupancy is not None:
+            raise ValueError("render_dex_depth: refine_steps together with quantiles= or occupancy= is not supported")
+        if float(getattr(options.nerf, mode).radiance_field_noise_std) != 0.0:
+            raise ValueError("render_dex_depth: refine_steps brackets the raw density: the mode's radiance_field_noise_std must be 0")
+    elif refine_width:
+        raise ValueError("render_dex_depth: refine_width reports on a refinement: give refine_steps=")
     qs = None if quantiles is None else _ops.check_quantiles(quantiles, "render_dex_depth: quantiles")
     if occupancy is None and cull_stats:
         raise ValueError("render_dex_depth: cull_stats reports on a culled render: give occupancy=")
@@ -578,10 +601,12 @@ def render_dex_depth(height, width, focal_length, model_coarse, model_fine, ray_
         if prec not in packs:
             packs[prec] = _density_packs(r, prec)
         draws = _draws(batch.shape[0], r.nc, r.nf, r.fine, r.perturb, r.std, r.dev)
-        depth_c, acc_c, depth_f, acc_f, dex, *qdepth = _ops.render_rays_depth(*packs[prec], batch, r.nc, r.nf, r.lindisp, r.std, r.m_thres, draws,
-                                                                              quantiles=q_dev, interp=quantile_interp)
+        depth_c, acc_c, depth_f, acc_f, dex, *more = _ops.render_rays_depth(*packs[prec], batch, r.nc, r.nf, r.lindisp, r.std, r.m_thres, draws,
+                                                                            quantiles=q_dev, interp=quantile_interp, refine_steps=refine_steps,
+                                                                            want_width=refine_width)
         maps = [depth_c, acc_c, depth_f, acc_f] + ([] if dex is None else [dex[k] for k in range(dex.shape[0])])
-        maps += [qdepth[0][k] for k in range(qdepth[0].shape[0])] if qdepth else []
+        for extra in more:   # qdepth (Q,N), or refined (K,N) and then width (K,N)
+            maps += [extra[k] for k in range(extra.shape[0])]
         words = _ops.render_status_words()   # (copied for unguarded chunks too, as it always was: same launches on every path)
         if guarded:
             status.append(words)
