@@ -7,15 +7,12 @@
 //   classify_kernel        one thread per 4 consecutive ray samples: keep flag (0 / -1) into slot[], the workgroup's kept count
 //   scan_totals_kernel     scan_row (scan_blocks.h) on one row; the top level is one workgroup and writes the record
 //   scan_slots_kernel      slot[p] = rank of p among the kept samples: the scan inside the workgroup plus the two scanned levels above
-//   emit_kernel            pts[slot[p]] = ro + rd * z, the bits classify_kernel judged
-//   gather_kernel          rf[p][3] = net_out[slot[p]][3] or the fill value; optionally the workgroup's count of non-finite values
-//   sum_partials_kernel    one workgroup: the sum of those counts, in a fixed order
-//
-// and the two kernels of include/dexnerf_hip_cull.h, for culled renders that read more than sigma:
-//
-//   emit_kernel<true>      also dirs[slot[p]] = columns 8..10 of the sample's ray row, in the same launch
+//   emit_kernel            pts[slot[p]] = ro + rd * z, the bits classify_kernel judged; <true> also dirs[slot[p]] = columns 8..10 of the
+//                          sample's ray row, in the same launch (include/dexnerf_hip_cull.h)
 //   gather_rows_kernel     dst[p][c] = src[slot[p]][c] or fill_c for c < width, as 32-bit words; a thread owns 4 consecutive dst rows, so
-//                          kept rows are read in ascending order; rows of 16 aligned bytes move as one dwordx4 load and store
+//                          kept rows are read in ascending order; rows of 16 aligned bytes move as one dwordx4 load and store; optionally
+//                          the workgroup's count of non-finite values.  dn_occupancy_gather is its width 1 on column 3 of 4-float rows
+//   sum_partials_kernel    one workgroup: the sum of those counts, in a fixed order
 //
 // No workgroup waits on another, no atomics, plain vector stores: the output is a function of the input.  Memory: the sample kernels
 // touch about 40 B per sample (z twice, slot written twice and read three times, 12 B per kept point, one 16-byte line share of rf).
@@ -206,31 +203,6 @@ __global__ __launch_bounds__(kThreads) void emit_kernel(Samples a, const int* __
   }
 }
 
-template <bool COUNT>
-__global__ __launch_bounds__(kThreads) void gather_kernel(const int* __restrict__ slot, const float* __restrict__ net_out, int64_t n_rows,
-                                                          int64_t n, float* __restrict__ rf, unsigned* __restrict__ partial) {
-  __shared__ unsigned lds[4];
-  const int64_t e0 = static_cast<int64_t>(blockIdx.x) * kScanElems + threadIdx.x * kPerThread;
-  unsigned bad = 0;
-#pragma unroll
-  for (int q = 0; q < kPerThread; ++q) {
-    const int64_t p = e0 + q;
-    if (p >= n) continue;
-    const int64_t s = slot[p];
-    float v = DN_OCC_FILL;
-    if (s >= 0 && s < n_rows) {
-      v = net_out[s * 4 + 3];
-      if (COUNT) bad += (__builtin_bit_cast(unsigned, v) & 0x7F800000u) == 0x7F800000u;
-    }
-    rf[p * 4 + 3] = v;
-  }
-  if (COUNT) {
-    unsigned all;
-    block_scan_exclusive(bad, lds, all);
-    if (threadIdx.x == 0) partial[blockIdx.x] = all;
-  }
-}
-
 struct Fills {
   unsigned v[DN_CULL_MAX_WIDTH];
 };
@@ -341,6 +313,64 @@ void launch_gather_rows(bool count, unsigned blocks, hipStream_t s, const int* s
                        partial);
 }
 
+// Both emit entry points.  with_dirs: dn_occupancy_compact_emit_dirs - the ray rows carry the view direction, and both outputs are wanted.
+int emit(const char* who, const float* rays, int ray_stride, const float* z, int64_t n_rays, int n_samples, const int* slot, int64_t max_points,
+         float* pts, float* dirs, bool with_dirs, dn_stream_t stream) {
+  Layout l;
+  if (int rc = samples_check(who, rays, ray_stride, z, n_rays, n_samples, l)) return rc;
+  if (with_dirs) {
+    DN_REQUIRE(ray_stride >= 11, "%s: ray_stride must be >= 11: the view direction is columns 8..10 of a ray row (got %d)", who, ray_stride);
+    DN_REQUIRE(aligned(rays, 4) && aligned(z, 4), "%s: rays and depths must be 4-byte aligned", who);
+  }
+  DN_REQUIRE(slot && aligned(slot, 4), "%s: null or unaligned slots", who);
+  DN_REQUIRE(max_points >= 0, "%s: negative capacity", who);
+  if (with_dirs) {
+    DN_REQUIRE(max_points == 0 || (pts && dirs && aligned(pts, 4) && aligned(dirs, 4)), "%s: a capacity without both of its outputs", who);
+    DN_REQUIRE(max_points == 0 || pts != dirs, "%s: the points and the directions must not be one buffer", who);
+  } else {
+    DN_REQUIRE(max_points == 0 || (pts && aligned(pts, 4)), "%s: a capacity without its output", who);
+  }
+  if (max_points == 0) return 0;
+  const Samples a{rays, ray_stride, z, l.n, n_samples};
+  if (with_dirs) hipLaunchKernelGGL(emit_kernel<true>, dim3(l.n0), dim3(kThreads), 0, as_stream(stream), a, slot, max_points, pts, dirs);
+  else hipLaunchKernelGGL(emit_kernel<false>, dim3(l.n0), dim3(kThreads), 0, as_stream(stream), a, slot, max_points, pts, static_cast<float*>(nullptr));
+  return check_launch(who);
+}
+
+// Both gather entry points.  dst_name and src_name: what the entry point calls its destination and its source in a refusal.
+int gather_rows(const char* who, const char* dst_name, const char* src_name, const int* slot, const float* src, int src_stride, int64_t n_rows,
+                int64_t n_points, int width, const float (&fills)[DN_CULL_MAX_WIDTH], float* dst, int dst_stride, void* workspace,
+                unsigned* d_record, dn_stream_t stream) {
+  DN_REQUIRE(slot && dst && aligned(slot, 4) && aligned(dst, 4), "%s: null or unaligned slots or %s", who, dst_name);
+  DN_REQUIRE(n_points >= 1 && n_points <= kMaxSamples, "%s: n_points must be 1 .. %lld (got %lld)", who, static_cast<long long>(kMaxSamples),
+             static_cast<long long>(n_points));
+  DN_REQUIRE(n_rows >= 0 && n_rows <= n_points, "%s: n_rows must be 0 .. n_points", who);
+  DN_REQUIRE(width >= 1 && width <= DN_CULL_MAX_WIDTH, "%s: width must be 1 .. %d (got %d)", who, DN_CULL_MAX_WIDTH, width);
+  DN_REQUIRE(src_stride >= width && dst_stride >= width, "%s: the strides (%d, %d floats) must be at least the width %d", who, src_stride,
+             dst_stride, width);
+  DN_REQUIRE(n_rows == 0 || (src && aligned(src, 4)), "%s: rows without %s", who, src_name);
+  DN_REQUIRE((workspace == nullptr) == (d_record == nullptr), "%s: the count needs both the workspace and the record", who);
+  DN_REQUIRE(aligned(workspace, 256) && aligned(d_record, 4), "%s: workspace must be 256-byte aligned, the record 4-byte aligned", who);
+  const unsigned blocks = blocks_for(n_points, kScanElems);
+  hipStream_t s = as_stream(stream);
+  Fills fill;
+  for (int c = 0; c < DN_CULL_MAX_WIDTH; ++c) fill.v[c] = __builtin_bit_cast(unsigned, fills[c]);
+  const unsigned* from = reinterpret_cast<const unsigned*>(src);
+  unsigned* to = reinterpret_cast<unsigned*>(dst);
+  unsigned* partial = static_cast<unsigned*>(workspace);   // the level-0 totals of the count: dead once the slots are written
+  const bool count = d_record != nullptr;
+  // (n_rows == 0 reads no source row: a NULL source passes as 16-byte aligned, and the vector kernel then only stores)
+  const bool vec = width == 4 && src_stride == 4 && dst_stride == 4 && aligned(src, 16) && aligned(dst, 16);
+  const int64_t ss = src_stride, ds = dst_stride;
+  if (vec) launch_gather_rows<4, true>(count, blocks, s, slot, from, ss, n_rows, n_points, fill, to, ds, partial);
+  else if (width == 4) launch_gather_rows<4, false>(count, blocks, s, slot, from, ss, n_rows, n_points, fill, to, ds, partial);
+  else if (width == 3) launch_gather_rows<3, false>(count, blocks, s, slot, from, ss, n_rows, n_points, fill, to, ds, partial);
+  else if (width == 2) launch_gather_rows<2, false>(count, blocks, s, slot, from, ss, n_rows, n_points, fill, to, ds, partial);
+  else launch_gather_rows<1, false>(count, blocks, s, slot, from, ss, n_rows, n_points, fill, to, ds, partial);
+  if (count) hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(kThreads), 0, s, partial, blocks, d_record);
+  return check_launch(who);
+}
+
 }  // namespace occ
 }  // namespace dn
 
@@ -412,89 +442,25 @@ extern "C" int dn_occupancy_compact_count(const float* rays, int ray_stride, con
 
 extern "C" int dn_occupancy_compact_emit(const float* rays, int ray_stride, const float* z, int64_t n_rays, int n_samples, const int* slot,
                                          int64_t max_points, float* pts, dn_stream_t stream) {
-  const char* who = "dn_occupancy_compact_emit";
-  Layout l;
-  if (int rc = samples_check(who, rays, ray_stride, z, n_rays, n_samples, l)) return rc;
-  DN_REQUIRE(slot && aligned(slot, 4), "%s: null or unaligned slots", who);
-  DN_REQUIRE(max_points >= 0, "%s: negative capacity", who);
-  DN_REQUIRE(max_points == 0 || (pts && aligned(pts, 4)), "%s: a capacity without its output", who);
-  if (max_points == 0) return 0;
-  const Samples a{rays, ray_stride, z, l.n, n_samples};
-  hipLaunchKernelGGL(emit_kernel<false>, dim3(l.n0), dim3(kThreads), 0, as_stream(stream), a, slot, max_points, pts, static_cast<float*>(nullptr));
-  return check_launch(who);
+  return emit("dn_occupancy_compact_emit", rays, ray_stride, z, n_rays, n_samples, slot, max_points, pts, nullptr, false, stream);
 }
 
 extern "C" int dn_occupancy_gather(const int* slot, const float* net_out, int64_t n_rows, int64_t n_points, float* rf, void* workspace,
                                    unsigned* d_record, dn_stream_t stream) {
-  const char* who = "dn_occupancy_gather";
-  DN_REQUIRE(slot && rf && aligned(slot, 4) && aligned(rf, 4), "%s: null or unaligned slots or rf", who);
-  DN_REQUIRE(n_points >= 1 && n_points <= kMaxSamples, "%s: n_points must be 1 .. %lld (got %lld)", who, static_cast<long long>(kMaxSamples),
-             static_cast<long long>(n_points));
-  DN_REQUIRE(n_rows >= 0 && n_rows <= n_points, "%s: n_rows must be 0 .. n_points", who);
-  DN_REQUIRE(n_rows == 0 || (net_out && aligned(net_out, 4)), "%s: rows without the network's output", who);
-  DN_REQUIRE((workspace == nullptr) == (d_record == nullptr), "%s: the count needs both the workspace and the record", who);
-  DN_REQUIRE(aligned(workspace, 256) && aligned(d_record, 4), "%s: workspace must be 256-byte aligned, the record 4-byte aligned", who);
-  const unsigned blocks = blocks_for(n_points, kScanElems);
-  hipStream_t s = as_stream(stream);
-  if (d_record) {
-    unsigned* partial = static_cast<unsigned*>(workspace);   // the level-0 totals of the count: dead once the slots are written
-    hipLaunchKernelGGL(gather_kernel<true>, dim3(blocks), dim3(kThreads), 0, s, slot, net_out, n_rows, n_points, rf, partial);
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(kThreads), 0, s, partial, blocks, d_record);
-  } else {
-    hipLaunchKernelGGL(gather_kernel<false>, dim3(blocks), dim3(kThreads), 0, s, slot, net_out, n_rows, n_points, rf, static_cast<unsigned*>(nullptr));
-  }
-  return check_launch(who);
+  // column 3 of 4-float rows on both sides (a NULL stays NULL: the refusals are judged on the pointers the caller gave)
+  return gather_rows("dn_occupancy_gather", "rf", "the network's output", slot, net_out ? net_out + 3 : nullptr, 4, n_rows, n_points, 1,
+                     {DN_OCC_FILL, 0.0f, 0.0f, 0.0f}, rf ? rf + 3 : nullptr, 4, workspace, d_record, stream);
 }
 
 // ---- include/dexnerf_hip_cull.h -----------------------------------------------------------------------------------------------------
 extern "C" int dn_occupancy_compact_emit_dirs(const float* rays, int ray_stride, const float* z, int64_t n_rays, int n_samples, const int* slot,
                                               int64_t max_points, float* pts, float* dirs, dn_stream_t stream) {
-  const char* who = "dn_occupancy_compact_emit_dirs";
-  Layout l;
-  if (int rc = samples_check(who, rays, ray_stride, z, n_rays, n_samples, l)) return rc;
-  DN_REQUIRE(ray_stride >= 11, "%s: ray_stride must be >= 11: the view direction is columns 8..10 of a ray row (got %d)", who, ray_stride);
-  DN_REQUIRE(aligned(rays, 4) && aligned(z, 4), "%s: rays and depths must be 4-byte aligned", who);
-  DN_REQUIRE(slot && aligned(slot, 4), "%s: null or unaligned slots", who);
-  DN_REQUIRE(max_points >= 0, "%s: negative capacity", who);
-  DN_REQUIRE(max_points == 0 || (pts && dirs && aligned(pts, 4) && aligned(dirs, 4)), "%s: a capacity without both of its outputs", who);
-  DN_REQUIRE(max_points == 0 || pts != dirs, "%s: the points and the directions must not be one buffer", who);
-  if (max_points == 0) return 0;
-  const Samples a{rays, ray_stride, z, l.n, n_samples};
-  hipLaunchKernelGGL(emit_kernel<true>, dim3(l.n0), dim3(kThreads), 0, as_stream(stream), a, slot, max_points, pts, dirs);
-  return check_launch(who);
+  return emit("dn_occupancy_compact_emit_dirs", rays, ray_stride, z, n_rays, n_samples, slot, max_points, pts, dirs, true, stream);
 }
 
 extern "C" int dn_occupancy_gather_rows(const int* slot, const float* src, int src_stride, int64_t n_rows, int64_t n_points, int width,
                                         float fill0, float fill1, float fill2, float fill3, float* dst, int dst_stride, void* workspace,
                                         unsigned* d_record, dn_stream_t stream) {
-  const char* who = "dn_occupancy_gather_rows";
-  DN_REQUIRE(slot && dst && aligned(slot, 4) && aligned(dst, 4), "%s: null or unaligned slots or destination", who);
-  DN_REQUIRE(n_points >= 1 && n_points <= kMaxSamples, "%s: n_points must be 1 .. %lld (got %lld)", who, static_cast<long long>(kMaxSamples),
-             static_cast<long long>(n_points));
-  DN_REQUIRE(n_rows >= 0 && n_rows <= n_points, "%s: n_rows must be 0 .. n_points", who);
-  DN_REQUIRE(width >= 1 && width <= DN_CULL_MAX_WIDTH, "%s: width must be 1 .. %d (got %d)", who, DN_CULL_MAX_WIDTH, width);
-  DN_REQUIRE(src_stride >= width && dst_stride >= width, "%s: the strides (%d, %d floats) must be at least the width %d", who, src_stride,
-             dst_stride, width);
-  DN_REQUIRE(n_rows == 0 || (src && aligned(src, 4)), "%s: rows without their source", who);
-  DN_REQUIRE((workspace == nullptr) == (d_record == nullptr), "%s: the count needs both the workspace and the record", who);
-  DN_REQUIRE(aligned(workspace, 256) && aligned(d_record, 4), "%s: workspace must be 256-byte aligned, the record 4-byte aligned", who);
-  const unsigned blocks = blocks_for(n_points, kScanElems);
-  hipStream_t s = as_stream(stream);
-  const float f[DN_CULL_MAX_WIDTH] = {fill0, fill1, fill2, fill3};
-  Fills fill;
-  for (int c = 0; c < DN_CULL_MAX_WIDTH; ++c) fill.v[c] = __builtin_bit_cast(unsigned, f[c]);
-  const unsigned* from = reinterpret_cast<const unsigned*>(src);
-  unsigned* to = reinterpret_cast<unsigned*>(dst);
-  unsigned* partial = static_cast<unsigned*>(workspace);   // the level-0 totals of the count: dead once the slots are written
-  const bool count = d_record != nullptr;
-  // (n_rows == 0 reads no source row: a NULL source passes as 16-byte aligned, and the vector kernel then only stores)
-  const bool vec = width == 4 && src_stride == 4 && dst_stride == 4 && aligned(src, 16) && aligned(dst, 16);
-  const int64_t ss = src_stride, ds = dst_stride;
-  if (vec) launch_gather_rows<4, true>(count, blocks, s, slot, from, ss, n_rows, n_points, fill, to, ds, partial);
-  else if (width == 4) launch_gather_rows<4, false>(count, blocks, s, slot, from, ss, n_rows, n_points, fill, to, ds, partial);
-  else if (width == 3) launch_gather_rows<3, false>(count, blocks, s, slot, from, ss, n_rows, n_points, fill, to, ds, partial);
-  else if (width == 2) launch_gather_rows<2, false>(count, blocks, s, slot, from, ss, n_rows, n_points, fill, to, ds, partial);
-  else launch_gather_rows<1, false>(count, blocks, s, slot, from, ss, n_rows, n_points, fill, to, ds, partial);
-  if (count) hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(kThreads), 0, s, partial, blocks, d_record);
-  return check_launch(who);
+  return gather_rows("dn_occupancy_gather_rows", "destination", "their source", slot, src, src_stride, n_rows, n_points, width,
+                     {fill0, fill1, fill2, fill3}, dst, dst_stride, workspace, d_record, stream);
 }

@@ -1284,14 +1284,20 @@ def composite_density_quantiles(rf, z, rd, noise, noise_std, m_thres, quantiles,
     """dn_composite_density_quantiles: composite_density's (depth, acc, dex (K,N) or None) and qdepth (Q,N) or None - the depth at
     which the accumulated opacity first reaches each quantile (interp: the piecewise-linear inversion instead of the sample's z)."""
     qs = check_quantiles(quantiles, "composite_density_quantiles")
+    return composite_density_quantiles_on_device(rf, z, rd, noise, noise_std, m_thres,
+                                                 torch.tensor(qs, dtype=torch.float32, device=rf.device) if qs else None, interp)
+
+
+def composite_density_quantiles_on_device(rf, z, rd, noise, noise_std, m_thres, quantiles, interp=False):
+    """composite_density_quantiles with the quantiles already judged (check_quantiles) and on the device - a float32 tensor, or None for
+    none: no host read and no copy per call."""
     c = _sigma_call(rf, z, rd, noise, noise_std, m_thres)
-    nq = len(qs)
+    nq = 0 if quantiles is None else int(quantiles.numel())
     depth, acc = _pass_maps(c.dev, c.n)
     dex = _empty(c.dev, c.k, c.n) if c.k else None
     qdepth = _empty(c.dev, nq, c.n) if nq else None
-    qt = torch.tensor(qs, dtype=torch.float32, device=c.dev) if nq else None
-    check(lib().dn_composite_density_quantiles(*c.head, ptr(c.thres), c.k, ptr(qt), nq, int(bool(interp)), c.n, c.s, ptr(depth), ptr(acc),
-                                               ptr(dex), ptr(qdepth), stream()), "dn_composite_density_quantiles")
+    check(lib().dn_composite_density_quantiles(*c.head, ptr(c.thres), c.k, ptr(quantiles), nq, int(bool(interp)), c.n, c.s, ptr(depth),
+                                               ptr(acc), ptr(dex), ptr(qdepth), stream()), "dn_composite_density_quantiles")
     return depth, acc, dex, qdepth
 
 
@@ -1921,17 +1927,27 @@ def occupancy_compact_count(rays, z, grid):
     return slot, record, ws
 
 
-def occupancy_compact_emit(rays, z, slot, max_points, pts=None):
-    """dn_occupancy_compact_emit: pts (max_points,3), row slot[p] = ro + rd * z of sample p; rows at or past max_points are not written."""
+def occupancy_compact_emit_dirs(rays, z, slot, max_points, pts=None, dirs=None, want_dirs=True):
+    """dn_occupancy_compact_emit_dirs: pts (max_points,3), row slot[p] = ro + rd * z of sample p, and, from the same launch, dirs
+    (max_points,3): row slot[p] = columns 8..10 of sample p's ray row (rays (N, >= 11)); rows at or past max_points are not written.
+    want_dirs=False: dn_occupancy_compact_emit - the points alone (rays (N, >= 8)), and None for the directions."""
     rays, z = f32c(rays), f32c(z)
     n, s = z.shape
     max_points = int(max_points)
-    if pts is None:
-        pts = torch.empty((max(max_points, 0), 3), dtype=torch.float32, device=z.device)
-    assert pts.dtype == torch.float32 and pts.shape[0] >= max_points and pts.shape[1:] == (3,)
-    check(lib().dn_occupancy_compact_emit(ptr(rays), rays.shape[1], ptr(z), n, s, ptr(slot), max_points, ptr(pts) if max_points > 0 else None,
-                                          stream()), "dn_occupancy_compact_emit")
-    return pts
+    outs = [pts, dirs] if want_dirs else [pts]
+    for i, t in enumerate(outs):
+        if t is None:
+            outs[i] = t = torch.empty((max(max_points, 0), 3), dtype=torch.float32, device=z.device)
+        assert t.dtype == torch.float32 and t.shape[0] >= max_points and t.shape[1:] == (3,)
+    name = "dn_occupancy_compact_emit_dirs" if want_dirs else "dn_occupancy_compact_emit"
+    check(getattr(lib(), name)(ptr(rays), rays.shape[1], ptr(z), n, s, ptr(slot), max_points, *[ptr(t) if max_points > 0 else None for t in outs],
+                               stream()), name)
+    return outs[0], (outs[1] if want_dirs else None)
+
+
+def occupancy_compact_emit(rays, z, slot, max_points, pts=None):
+    """dn_occupancy_compact_emit: pts (max_points,3), row slot[p] = ro + rd * z of sample p; rows at or past max_points are not written."""
+    return occupancy_compact_emit_dirs(rays, z, slot, max_points, pts, want_dirs=False)[0]
 
 
 def occupancy_gather(slot, net_out, rf, ws=None, record=None):
@@ -1944,86 +1960,12 @@ def occupancy_gather(slot, net_out, rf, ws=None, record=None):
     return rf
 
 
-def _culled_pass(packed, rays, z, grid, count_nonfinite):
-    """One network pass of the culled render: (rf (N,S,4) whose sigma column alone is written, n_kept, record)."""
-    slot, record, ws = occupancy_compact_count(rays, z, grid)
-    n_kept = int(record[0].item())   # the host read: the kept count sizes the network launch
-    net_out = run_network_pts(packed, occupancy_compact_emit(rays, z, slot, n_kept), None, 1) if n_kept else None
-    rf = torch.empty(tuple(z.shape) + (4,), dtype=torch.float32, device=z.device)
-    occupancy_gather(slot, net_out, rf, *((ws, record) if count_nonfinite else ()))
-    return rf, n_kept, record
-
-
-def render_rays_depth_culled(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, noise_std, m_thres, occupancy, draws=None, quantiles=None,
-                             interp=False, count_nonfinite=False):
-    """render_rays_depth with the network evaluated only on the samples whose occupancy cell is set, as a chain of entry points on the
-    current stream: dn_coarse_depths, dn_occupancy_compact_count, a host read of the kept count, dn_occupancy_compact_emit,
-    dn_run_network on the kept points (explicit points, one sample per "ray"; skipped when nothing is kept), dn_occupancy_gather
-    (culled samples get -FLT_MAX: no opacity, no threshold crossing), dn_density_resample, the same compaction on the fine depths for
-    the fine network, dn_composite_density or its quantile variant.  num_fine == 0 (or no fine pack) ends after a dn_composite_density
-    of the coarse pass.
-
-    Returns (render_rays_depth's maps, stats): stats = dict(kept=(coarse, fine), total=(coarse, fine), records=[the passes' device
-    records]) - the fine entries 0 without a fine pass.  Two host reads per chunk (one per network pass: the kept count sizes the
-    network launch) - the chain cannot be captured into a HIP graph.  The network runs in the packs' precision; an explicit-points
-    launch carries no fp16 range status, so the guarded-fp16 render policy does not apply here."""
-    packed_c.require_fresh_inference_stream("render_rays_depth_culled")
-    rays = f32c(rays)
-    fine = num_fine > 0 and packed_f is not None
-    if fine:
-        packed_f.require_fresh_inference_stream("render_rays_depth_culled")
-    t_rand, noise_c, u, noise_f = _draw_tensors(draws)
-    rd = rays[:, 3:6]
-    z = coarse_depths(rays, num_coarse, lindisp, t_rand)
-    rf, kept_c, rec_c = _culled_pass(packed_c, rays, z, occupancy, count_nonfinite)
-    kept, total, records = [kept_c, 0], [z.numel(), 0], [rec_c]
-    if fine:
-        depth_c, acc_c, z = density_resample(rf, z, rd, num_fine, noise_c, noise_std, u)
-        rf, kept[1], rec_f = _culled_pass(packed_f, rays, z, occupancy, count_nonfinite)
-        total[1] = z.numel()
-        records.append(rec_f)
-    noise = noise_f if fine else noise_c
-    if quantiles is None:
-        last = composite_density(rf, z, rd, noise, noise_std, m_thres)
-    else:
-        nq = int(quantiles.numel())
-        if not 1 <= nq <= _hip.MAX_QUANTILES or quantiles.dtype != torch.float32:
-            raise ValueError(f"render_rays_depth_culled: quantiles must be a float32 device tensor of 1 .. {_hip.MAX_QUANTILES} values")
-        # (composite_density_quantiles with the validated quantiles already on the device: no host read, no copy per chunk)
-        c = _sigma_call(rf, z, rd, noise, noise_std, m_thres)
-        last = _pass_maps(c.dev, c.n) + (_empty(c.dev, c.k, c.n) if c.k else None, _empty(c.dev, nq, c.n))
-        check(lib().dn_composite_density_quantiles(*c.head, ptr(c.thres), c.k, ptr(quantiles), nq, int(bool(interp)), c.n, c.s,
-                                                   *[ptr(m) for m in last], stream()), "dn_composite_density_quantiles")
-    depth, acc, dex, *qdepth = last
-    maps = ((depth_c, acc_c, depth, acc, dex) if fine else (depth, acc, None, None, dex)) + tuple(qdepth)
-    return maps, dict(kept=tuple(kept), total=tuple(total), records=records)
-
-
-# ---- culled colour and normal renders (include/dexnerf_hip_cull.h) --------------------------------------------------------------------------
-def occupancy_compact_emit_dirs(rays, z, slot, max_points, pts=None, dirs=None):
-    """dn_occupancy_compact_emit_dirs: occupancy_compact_emit's pts (max_points,3) and, from the same launch, dirs (max_points,3): row
-    slot[p] = columns 8..10 of sample p's ray row (rays (N, >= 11)); rows at or past max_points are not written."""
-    rays, z = f32c(rays), f32c(z)
-    n, s = z.shape
-    max_points = int(max_points)
-    if pts is None:
-        pts = torch.empty((max(max_points, 0), 3), dtype=torch.float32, device=z.device)
-    if dirs is None:
-        dirs = torch.empty((max(max_points, 0), 3), dtype=torch.float32, device=z.device)
-    for t in (pts, dirs):
-        assert t.dtype == torch.float32 and t.shape[0] >= max_points and t.shape[1:] == (3,)
-    some = max_points > 0
-    check(lib().dn_occupancy_compact_emit_dirs(ptr(rays), rays.shape[1], ptr(z), n, s, ptr(slot), max_points, ptr(pts) if some else None,
-                                               ptr(dirs) if some else None, stream()), "dn_occupancy_compact_emit_dirs")
-    return pts, dirs
-
-
 def occupancy_gather_rows(slot, src, dst, width, fills, ws=None, record=None):
-    """dn_occupancy_gather_rows: dst[p][c] = src[slot[p]][c] for c < width where slot[p] names one of src's rows, else fills[c] - copies
-    of bits.  src: (n_rows, >= width) fp32 with unit stride along a row (a column view like net_out[:, 3:] is read in place), or None
-    (no sample kept).  dst: (..., >= width) fp32 of slot.numel() rows, likewise a view with unit stride along a row and one stride
-    between rows; its other columns are not written.  fills: `width` numbers.  ws and record (occupancy_compact_count's) given: word 2
-    of the record becomes the number of non-finite copied values."""
+    """dn_occupancy_gather_rows (include/dexnerf_hip_cull.h): dst[p][c] = src[slot[p]][c] for c < width where slot[p] names one of src's
+    rows, else fills[c] - copies of bits.  src: (n_rows, >= width) fp32 with unit stride along a row (a column view like net_out[:, 3:]
+    is read in place), or None (no sample kept).  dst: (..., >= width) fp32 of slot.numel() rows, likewise a view with unit stride along
+    a row and one stride between rows; its other columns are not written.  fills: `width` numbers.  ws and record
+    (occupancy_compact_count's) given: word 2 of the record becomes the number of non-finite copied values."""
     width = int(width)
     fills = [float(f) for f in fills]
     if not 1 <= width <= _hip.CULL_MAX_WIDTH or len(fills) != width:
@@ -2044,27 +1986,101 @@ def occupancy_gather_rows(slot, src, dst, width, fills, ws=None, record=None):
     return dst
 
 
-def _compact(rays, z, grid, dirs):
-    """Count, the host read of the kept count (it sizes the network launch), emit -> (slot, record, ws, n_kept, pts | None,
-    view directions | None); dirs: emit a direction row per kept point from columns 8..10 of the ray rows."""
+# ---- the culled renders: depth, colour and normals over one pass ------------------------------------------------------------------------
+class _CullStats:
+    """What the passes of a culled driver report into: the kept and the total samples of pass 0 (coarse) and 1 (fine) - 0 for a pass
+    that did not run - and the passes' device records in launch order."""
+
+    def __init__(self):
+        self.kept, self.total, self.records = [0, 0], [0, 0], []
+
+    def add(self, index, n_kept, n_total, record):
+        self.kept[index], self.total[index] = n_kept, n_total
+        self.records.append(record)
+
+    def result(self):
+        return dict(kept=tuple(self.kept), total=tuple(self.total), records=self.records)
+
+
+def _culled_call(who, packed_c, packed_f, rays, num_coarse, num_fine, lindisp, draws, colour=False):
+    """The prelude of the culled drivers: the packs' inference streams fresh (refusals in `who`'s name), fp32-contiguous ray rows,
+    whether a fine pass runs, the four draw tensors (_draw_tensors), the direction columns, the coarse depths, and whether a pass emits
+    view directions - colour renders of networks that read them, which then need 11-column rays and both networks of one kind."""
+    packed_c.require_fresh_inference_stream(who)
+    rays = f32c(rays)
+    fine = num_fine > 0 and packed_f is not None
+    if fine:
+        packed_f.require_fresh_inference_stream(who)
+    dirs = colour and bool(packed_c.desc.use_viewdirs)
+    if colour and (rays.shape[1] < (11 if dirs else 8) or (fine and bool(packed_f.desc.use_viewdirs) != dirs)):
+        raise ValueError(f"{who}: networks with view directions need ray rows of 11 columns, and both networks the same kind")
+    draws = _draw_tensors(draws)
+    return rays, fine, draws, rays[:, 3:6], coarse_depths(rays, num_coarse, lindisp, draws[0]), dirs
+
+
+def _network_rows(packed):
+    """_culled_pass's `evaluate` of a network pass: its (n,4) rows at explicit points, one sample and one direction row per "ray"."""
+    return lambda pts, dirs: run_network_pts(packed, pts, dirs, 1)
+
+
+def _culled_pass(rays, z, grid, evaluate, stats, index, columns="sigma", dirs=False, count_nonfinite=False):
+    """One network pass of a culled render, the only place where the sequence stands: dn_occupancy_compact_count, the host read of the
+    kept count (it sizes the network launch), the emit (with a direction row per kept point when `dirs`), evaluate(pts, dirs | None) on
+    the kept points - skipped when nothing is kept -, the gather with its fills.  Reports (kept, total, record) into `stats` as pass
+    `index`.  columns:
+      "sigma"       evaluate gives (n,4) rows; dn_occupancy_gather of their sigma, -FLT_MAX for a culled sample -> rf (N,S,4) whose sigma
+                    column alone is written
+      "rgb sigma"   evaluate gives (n,4) rows; dn_occupancy_gather_rows of all four, (+0, +0, +0, -FLT_MAX) for a culled sample -> rf
+      "sigma grad"  evaluate gives (sigma (n,1), gradient (n,3)); dn_occupancy_gather_rows of sigma (width 1, -FLT_MAX) and of the
+                    gradient (width 3, +0: dn_composite_normals' "no normal") -> (rf as for "sigma", g_pts (N,S,3))
+    count_nonfinite: word 2 of the record becomes the number of non-finite gathered values - never of the gradient's."""
     slot, record, ws = occupancy_compact_count(rays, z, grid)
     n_kept = int(record[0].item())
-    pts = vd = None
-    if n_kept and dirs:
-        pts, vd = occupancy_compact_emit_dirs(rays, z, slot, n_kept)
-    elif n_kept:
-        pts = occupancy_compact_emit(rays, z, slot, n_kept)
-    return slot, record, ws, n_kept, pts, vd
-
-
-def _culled_colour_pass(packed, rays, z, grid, count_nonfinite):
-    """One network pass of the culled colour render: (rf (N,S,4): the network's rows at the kept samples, (+0, +0, +0, -FLT_MAX) at the
-    culled ones, n_kept, record)."""
-    slot, record, ws, n_kept, pts, vd = _compact(rays, z, grid, dirs=bool(packed.desc.use_viewdirs))
-    net_out = run_network_pts(packed, pts, vd, 1) if n_kept else None
+    stats.add(index, n_kept, z.numel(), record)
+    out = evaluate(*occupancy_compact_emit_dirs(rays, z, slot, n_kept, want_dirs=dirs)) if n_kept else None
+    counted = (ws, record) if count_nonfinite else ()
     rf = torch.empty(tuple(z.shape) + (4,), dtype=torch.float32, device=z.device)
-    occupancy_gather_rows(slot, net_out, rf, 4, (0.0, 0.0, 0.0, _hip.OCC_FILL), *((ws, record) if count_nonfinite else ()))
-    return rf, n_kept, record
+    if columns == "sigma":
+        return occupancy_gather(slot, out, rf, *counted)
+    if columns == "rgb sigma":
+        return occupancy_gather_rows(slot, out, rf, 4, (0.0, 0.0, 0.0, _hip.OCC_FILL), *counted)
+    sigma, g = out if n_kept else (None, None)
+    g_pts = torch.empty(tuple(z.shape) + (3,), dtype=torch.float32, device=z.device)
+    occupancy_gather_rows(slot, sigma, rf[..., 3:], 1, (_hip.OCC_FILL,), *counted)
+    occupancy_gather_rows(slot, g, g_pts, 3, (0.0, 0.0, 0.0))
+    return rf, g_pts
+
+
+def render_rays_depth_culled(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, noise_std, m_thres, occupancy, draws=None, quantiles=None,
+                             interp=False, count_nonfinite=False):
+    """render_rays_depth with the network evaluated only on the samples whose occupancy cell is set, as a chain of entry points on the
+    current stream: dn_coarse_depths, dn_occupancy_compact_count, a host read of the kept count, dn_occupancy_compact_emit,
+    dn_run_network on the kept points (explicit points, one sample per "ray"; skipped when nothing is kept), dn_occupancy_gather
+    (culled samples get -FLT_MAX: no opacity, no threshold crossing), dn_density_resample, the same compaction on the fine depths for
+    the fine network, dn_composite_density or its quantile variant.  num_fine == 0 (or no fine pack) ends after a dn_composite_density
+    of the coarse pass.
+
+    Returns (render_rays_depth's maps, stats): stats = dict(kept=(coarse, fine), total=(coarse, fine), records=[the passes' device
+    records]) - the fine entries 0 without a fine pass.  Two host reads per chunk (one per network pass: the kept count sizes the
+    network launch) - the chain cannot be captured into a HIP graph.  The network runs in the packs' precision; an explicit-points
+    launch carries no fp16 range status, so the guarded-fp16 render policy does not apply here."""
+    rays, fine, (_, noise_c, u, noise_f), rd, z, _ = _culled_call("render_rays_depth_culled", packed_c, packed_f, rays, num_coarse, num_fine,
+                                                                   lindisp, draws)
+    stats = _CullStats()
+    rf = _culled_pass(rays, z, occupancy, _network_rows(packed_c), stats, 0, count_nonfinite=count_nonfinite)
+    if fine:
+        depth_c, acc_c, z = density_resample(rf, z, rd, num_fine, noise_c, noise_std, u)
+        rf = _culled_pass(rays, z, occupancy, _network_rows(packed_f), stats, 1, count_nonfinite=count_nonfinite)
+    noise = noise_f if fine else noise_c
+    if quantiles is None:
+        last = composite_density(rf, z, rd, noise, noise_std, m_thres)
+    else:
+        if not 1 <= int(quantiles.numel()) <= _hip.MAX_QUANTILES or quantiles.dtype != torch.float32:
+            raise ValueError(f"render_rays_depth_culled: quantiles must be a float32 device tensor of 1 .. {_hip.MAX_QUANTILES} values")
+        last = composite_density_quantiles_on_device(rf, z, rd, noise, noise_std, m_thres, quantiles, interp)
+    depth, acc, dex, *qdepth = last
+    maps = ((depth_c, acc_c, depth, acc, dex) if fine else (depth, acc, None, None, dex)) + tuple(qdepth)
+    return maps, stats.result()
 
 
 def render_rays_culled(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, noise_std, white, m_thres, occupancy, draws=None,
@@ -2079,29 +2095,18 @@ def render_rays_culled(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, 
     Full packs (FlexibleNeRFModel.packed).  m_thres: a list of thresholds.  Returns (render_rays' seven maps, stats): stats as
     render_rays_depth_culled's.  Two host reads per chunk; the chain cannot be captured into a HIP graph.  The network runs in the
     packs' precision; the guarded-fp16 render policy does not apply (an explicit-points launch carries no range status)."""
-    packed_c.require_fresh_inference_stream("render_rays_culled")
-    rays = f32c(rays)
-    fine = num_fine > 0 and packed_f is not None
-    if fine:
-        packed_f.require_fresh_inference_stream("render_rays_culled")
-    dirs = bool(packed_c.desc.use_viewdirs)
-    if rays.shape[1] < (11 if dirs else 8) or (fine and bool(packed_f.desc.use_viewdirs) != dirs):
-        raise ValueError("render_rays_culled: networks with view directions need ray rows of 11 columns, and both networks the same kind")
-    t_rand, noise_c, u, noise_f = _draw_tensors(draws)
-    rd = rays[:, 3:6]
+    rays, fine, (_, noise_c, u, noise_f), rd, z, dirs = _culled_call("render_rays_culled", packed_c, packed_f, rays, num_coarse, num_fine,
+                                                                      lindisp, draws, colour=True)
+    stats = _CullStats()
     thres = list(m_thres) if m_thres is not None else []
-    z = coarse_depths(rays, num_coarse, lindisp, t_rand)
-    rf, kept_c, rec_c = _culled_colour_pass(packed_c, rays, z, occupancy, count_nonfinite)
-    kept, total, records = [kept_c, 0], [z.numel(), 0], [rec_c]
+    rf = _culled_pass(rays, z, occupancy, _network_rows(packed_c), stats, 0, "rgb sigma", dirs, count_nonfinite)
     rgb_c, _, acc_c, weights, depth_c, dex = volume_render_fwd(rf, z, rd, noise_c, noise_std, white, [] if fine else thres, want_weights=fine)
     rgb_f = depth_f = acc_f = None
     if fine:
         z = fine_depths(z, weights, num_fine, u)
-        rf, kept[1], rec_f = _culled_colour_pass(packed_f, rays, z, occupancy, count_nonfinite)
-        total[1] = z.numel()
-        records.append(rec_f)
+        rf = _culled_pass(rays, z, occupancy, _network_rows(packed_f), stats, 1, "rgb sigma", dirs, count_nonfinite)
         rgb_f, _, acc_f, _, depth_f, dex = volume_render_fwd(rf, z, rd, noise_f, noise_std, white, thres, want_weights=False)
-    return (rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f, dex), dict(kept=tuple(kept), total=tuple(total), records=records)
+    return (rgb_c, depth_c, acc_c, rgb_f, depth_f, acc_f, dex), stats.result()
 
 
 def density_gradient_bytes_per_point(packed_density):
@@ -2109,6 +2114,20 @@ def density_gradient_bytes_per_point(packed_density):
     the output rows, the seed, the points and their gradients."""
     n = 1 << 16
     return -(-sum(train_sizes(packed_density, n, prec=packed_density.precision)) // n) + 16 + 16 + 12 + 12
+
+
+def _density_gradient_slabs(packed, streams, pts, max_points):
+    """density_gradient on explicit points in slabs of at most max_points (None: one slab) -> (sigma (n,1), gradient (n,3)); points
+    are independent, so the values do not depend on the slabs."""
+    n = pts.shape[0]
+    step = n if max_points is None else max(1, int(max_points))
+    if n <= step:
+        sigma, g = density_gradient(packed, streams, pts=pts)
+        return sigma.unsqueeze(-1), g         # the .w column of the training forward's rows, read in place: row stride 4
+    sigma, g = torch.empty((n, 1), dtype=torch.float32, device=pts.device), torch.empty((n, 3), dtype=torch.float32, device=pts.device)
+    for p0 in range(0, n, step):
+        sigma[p0:p0 + step, 0], g[p0:p0 + step] = density_gradient(packed, streams, pts=pts[p0:p0 + step])
+    return sigma, g
 
 
 def render_rays_normals_culled(packed_c, packed_f, streams, rays, num_coarse, num_fine, lindisp, noise_std, m_thres, occupancy, draws=None,
@@ -2119,41 +2138,18 @@ def render_rays_normals_culled(packed_c, packed_f, streams, rays, num_coarse, nu
     the library has), dn_occupancy_gather_rows of its sigma (width 1, -FLT_MAX for a culled sample) and of its gradients (width 3, +0:
     a zero gradient is dn_composite_normals' "no normal"), dn_composite_normals.  max_points: the kept points are differentiated in
     slabs of at most that many (points are independent: the maps do not depend on the slabs).  Density packs and the
-    DensityGradStreams of the last pass's network.  Returns (render_rays_normals' maps, stats as render_rays_depth_culled's); the count of non-finite values covers
-    sigma, in both passes."""
-    packed_c.require_fresh_inference_stream("render_rays_normals_culled")
-    rays = f32c(rays)
-    fine = num_fine > 0 and packed_f is not None
-    if fine:
-        packed_f.require_fresh_inference_stream("render_rays_normals_culled")
-    t_rand, noise_c, u, noise_f = _draw_tensors(draws)
-    rd = rays[:, 3:6]
-    z = coarse_depths(rays, num_coarse, lindisp, t_rand)
-    kept, total, records = [0, 0], [z.numel(), 0], []
+    DensityGradStreams of the last pass's network.  Returns (render_rays_normals' maps, stats as render_rays_depth_culled's); the count
+    of non-finite values covers sigma, in both passes."""
+    rays, fine, (_, noise_c, u, noise_f), rd, z, _ = _culled_call("render_rays_normals_culled", packed_c, packed_f, rays, num_coarse, num_fine,
+                                                                   lindisp, draws)
+    stats = _CullStats()
     depth_c = acc_c = None
     if fine:
-        rf, kept[0], rec_c = _culled_pass(packed_c, rays, z, occupancy, count_nonfinite)
-        records.append(rec_c)
+        rf = _culled_pass(rays, z, occupancy, _network_rows(packed_c), stats, 0, count_nonfinite=count_nonfinite)
         depth_c, acc_c, z = density_resample(rf, z, rd, num_fine, noise_c, noise_std, u)
-        total[1] = z.numel()
     last = packed_f if fine else packed_c
-    slot, record, ws, n_kept, pts, _ = _compact(rays, z, occupancy, dirs=False)
-    kept[1 if fine else 0] = n_kept
-    records.append(record)
-    dev = z.device
-    sigma = g = None
-    step = n_kept if max_points is None else max(1, int(max_points))
-    if 0 < n_kept <= step:
-        sigma, g = density_gradient(last, streams, pts=pts)
-        sigma = sigma.unsqueeze(-1)          # the .w column of the training forward's rows, read in place: row stride 4
-    elif n_kept:
-        sigma, g = torch.empty((n_kept, 1), dtype=torch.float32, device=dev), torch.empty((n_kept, 3), dtype=torch.float32, device=dev)
-        for p0 in range(0, n_kept, step):
-            part = density_gradient(last, streams, pts=pts[p0:p0 + step])
-            sigma[p0:p0 + step, 0], g[p0:p0 + step] = part
-    rf = torch.empty(tuple(z.shape) + (4,), dtype=torch.float32, device=dev)
-    g_pts = torch.empty(tuple(z.shape) + (3,), dtype=torch.float32, device=dev)
-    occupancy_gather_rows(slot, sigma, rf[..., 3:], 1, (_hip.OCC_FILL,), *((ws, record) if count_nonfinite else ()))
-    occupancy_gather_rows(slot, g, g_pts, 3, (0.0, 0.0, 0.0))
+    rf, g_pts = _culled_pass(rays, z, occupancy, lambda pts, _: _density_gradient_slabs(last, streams, pts, max_points), stats,
+                             1 if fine else 0, "sigma grad", count_nonfinite=count_nonfinite)
     depth, acc, dex, normal, dex_normal = composite_normals(rf, z, rd, g_pts, noise_f if fine else noise_c, noise_std, m_thres)
-    return (depth_c, acc_c, depth, acc, dex, normal, dex_normal), dict(kept=tuple(kept), total=tuple(total), records=records)
+    return (depth_c, acc_c, depth, acc, dex, normal, dex_normal), stats.result()
+

@@ -320,6 +320,25 @@ def _culled_precision(who):
     return _ops._precision
 
 
+class _CullTotals:
+    """The sum of a culled render's per-chunk stats (_ops.render_rays_*_culled): the kept / total counts per pass on the host (the
+    chain reads them anyway), the non-finite counts on the device - read once, by result(), and only when `wanted` (else it gives None)."""
+
+    def __init__(self, wanted):
+        self.wanted, self.kept, self.total, self.records = wanted, [0, 0], [0, 0], []
+
+    def add(self, stats):
+        for p in range(2):
+            self.kept[p] += stats["kept"][p]
+            self.total[p] += stats["total"][p]
+        self.records.extend(stats["records"])
+
+    def result(self):
+        if not self.wanted:
+            return None
+        return dict(kept=tuple(self.kept), total=tuple(self.total), nonfinite=int(torch.stack(self.records)[:, 2].sum().item()))
+
+
 def _refuse_culled_colour(model_coarse, model_fine, ray_origins, ray_directions, options, mode, encode_position_fn, encode_direction_fn,
                           occupancy):
     """Every refusal of run_one_iter_of_nerf(occupancy=...) before any GPU work, in render_dex_depth(occupancy=...)'s order -> (the
@@ -408,9 +427,8 @@ def run_one_iter_of_nerf(height, width, focal_length, model_coarse, model_fine, 
 
 def _render_chunks_culled(rays, model_coarse, model_fine, options, mode, encode_position_fn, encode_direction_fn, thres, occupancy, culled,
                           cull_stats):
-    """run_one_iter_of_nerf's chunk loop on _ops.render_rays_culled -> (the joined maps, the stats dict | None): the draws of every
-    chunk from _draws, as without a grid; the kept / total counts summed on the host (the chain reads them anyway), the non-finite
-    counts summed on the device and read once at the end, only when the stats are asked for."""
+    """run_one_iter_of_nerf's chunk loop on _ops.render_rays_culled -> (the joined maps, the stats dict | None: _CullTotals): the draws
+    of every chunk from _draws, as without a grid."""
     prec, fine = culled
     opt = getattr(options.nerf, mode)
     nc, nf = int(opt.num_coarse), int(opt.num_fine) if fine else 0
@@ -419,22 +437,17 @@ def _render_chunks_culled(rays, model_coarse, model_fine, options, mode, encode_
     ld = encode_direction_fn.log_sampling if model_coarse.use_viewdirs else True
     pc = model_coarse.packed(lx, ld, precision=prec)
     pf = model_fine.packed(lx, ld, precision=prec) if fine else None
-    kept, total, records = [0, 0], [0, 0], []
+    totals = _CullTotals(cull_stats)
 
     def render_chunk(batch):
         draws = _draws(batch.shape[0], nc, nf, fine, bool(opt.perturb), std, batch.device)
         maps, stats = _ops.render_rays_culled(pc, pf, batch, nc, nf, bool(opt.lindisp), std, bool(opt.white_background), thres, occupancy,
                                               draws, count_nonfinite=cull_stats)
-        for p in range(2):
-            kept[p] += stats["kept"][p]
-            total[p] += stats["total"][p]
-        records.extend(stats["records"])
+        totals.add(stats)
         dex = maps[6]
         return list(maps[:6]) + ([] if dex is None else [dex[k] for k in range(dex.shape[0])])
     images = _join_chunks([render_chunk(batch) for batch in get_minibatches(rays, chunksize=opt.chunksize)])
-    if not cull_stats:
-        return images, None
-    return images, dict(kept=tuple(kept), total=tuple(total), nonfinite=int(torch.stack(records)[:, 2].sum().item()))
+    return images, totals.result()
 
 
 _THRESHOLDS_ON_DEVICE = {}   # (thresholds, device) -> device tensor: one host-to-device copy per threshold set, none per render
@@ -498,27 +511,21 @@ def _density_packs(r, prec):
 
 def _render_dex_depth_culled(r, prec, occupancy, q_dev, interp, cull_stats, chunksize, mode):
     """render_dex_depth's chunk loop on _ops.render_rays_depth_culled: the draws of every chunk from _draws, as without a grid; the
-    per-pass kept / total counts summed on the host (the chain reads them anyway), the non-finite counts summed on the device and
-    read once at the end, only when the stats are asked for."""
+    stats (_CullTotals) close the return when asked for."""
     packs = _density_packs(r, prec)
-    kept, total, records = [0, 0], [0, 0], []
+    totals = _CullTotals(cull_stats)
 
     def render_chunk(batch):
         draws = _draws(batch.shape[0], r.nc, r.nf, r.fine, r.perturb, r.std, r.dev)
         (depth_c, acc_c, depth_f, acc_f, dex, *qdepth), stats = _ops.render_rays_depth_culled(
             *packs, batch, r.nc, r.nf, r.lindisp, r.std, r.m_thres, occupancy, draws, quantiles=q_dev, interp=interp,
             count_nonfinite=cull_stats)
-        for p in range(2):
-            kept[p] += stats["kept"][p]
-            total[p] += stats["total"][p]
-        records.extend(stats["records"])
+        totals.add(stats)
         maps = [depth_c, acc_c, depth_f, acc_f] + ([] if dex is None else [dex[k] for k in range(dex.shape[0])])
         return maps + ([qdepth[0][k] for k in range(qdepth[0].shape[0])] if qdepth else [])
     maps = _join_chunks([render_chunk(batch) for batch in get_minibatches(r.rays, chunksize=chunksize)])
     out = _to_image(maps, [r.img_shape[:-1]] * len(maps)) if mode == "validation" else tuple(maps)
-    if cull_stats:
-        out += (dict(kept=tuple(kept), total=tuple(total), nonfinite=int(torch.stack(records)[:, 2].sum().item())),)
-    return out
+    return out + ((totals.result(),) if cull_stats else ())
 
 
 def render_dex_depth(height, width, focal_length, model_coarse, model_fine, ray_origins, ray_directions, options,
@@ -581,10 +588,7 @@ def render_dex_depth(height, width, focal_length, model_coarse, model_fine, ray_
         raise ValueError("render_dex_depth: cull_stats reports on a culled render: give occupancy=")
     if occupancy is not None:
         # every refusal of the culled path before any GPU work: the precision, the grid's device, then the setup's own
-        prec = _ops._precision
-        if prec == _ops._hip.PREC_F16:
-            raise RuntimeError("render_dex_depth(occupancy=...): the culled render evaluates explicit points, which carry no fp16 range "
-                               "status - it runs in 'fp32' or bf16, not under nerf.set_precision('fp16')")
+        prec = _culled_precision("render_dex_depth")
         occupancy.check_render(ray_directions.device, "render_dex_depth")
     r = _density_render_setup("render_dex_depth", "differentiable renders go through run_one_iter_of_nerf", height, width, focal_length,
                               model_coarse, model_fine, ray_origins, ray_directions, options, mode, encode_position_fn, m_thres_cand)
@@ -718,17 +722,14 @@ def render_dex_normals(height, width, focal_length, model_coarse, model_fine, ra
                 *packs, streams, batch[rows], nc, nf, r.lindisp, r.std, r.m_thres, {name: d[rows] for name, d in draws.items()})
             pieces.append([depth, acc, normal] + [dex[i] for i in range(k)] + [dex_normal[i] for i in range(k)])
         return _join_chunks(pieces)
-    kept, total, records = [0, 0], [0, 0], []
+    totals = _CullTotals(cull_stats)
     max_points = max(1, max_bytes // _ops.density_gradient_bytes_per_point(packs[1] if r.fine else packs[0])) if occupancy is not None else None
 
     def render_chunk_culled(batch):
         draws = _draws(batch.shape[0], nc, nf, r.fine, r.perturb, r.std, r.dev)
         (_, _, depth, acc, dex, normal, dex_normal), stats = _ops.render_rays_normals_culled(
             *packs, streams, batch, nc, nf, r.lindisp, r.std, r.m_thres, occupancy, draws, count_nonfinite=cull_stats, max_points=max_points)
-        for p in range(2):
-            kept[p] += stats["kept"][p]
-            total[p] += stats["total"][p]
-        records.extend(stats["records"])
+        totals.add(stats)
         return [depth, acc, normal] + [dex[i] for i in range(k)] + [dex_normal[i] for i in range(k)]
     one_chunk = render_chunk if occupancy is None else render_chunk_culled
     maps = _join_chunks([one_chunk(batch) for batch in get_minibatches(r.rays, chunksize=getattr(options.nerf, mode).chunksize)])
@@ -736,9 +737,7 @@ def render_dex_normals(height, width, focal_length, model_coarse, model_fine, ra
         flat, vec = r.img_shape[:-1], r.img_shape
         maps = _to_image(maps, [flat, flat, vec] + [flat] * k + [vec] * k)
     out = DexNormals(maps[0], maps[1], maps[2], tuple(maps[3:3 + k]), tuple(maps[3 + k:3 + 2 * k]))
-    if cull_stats:
-        return out, dict(kept=tuple(kept), total=tuple(total), nonfinite=int(torch.stack(records)[:, 2].sum().item()))
-    return out
+    return (out, totals.result()) if cull_stats else out
 
 
 # ---- the Dex threshold surface as a triangle mesh -------------------------------------------------------------------------------------

@@ -21,7 +21,10 @@ draws its density noise in the compositing kernel and a render with DEXNERF_FUSE
 folded into one digest per group of cases (fold_into).
 
 The pass that gave the density renders one driver per layer added density_renders() (its docstring lists the cases;
---density-renders runs it alone): profiles/density_render_refactor_bits_{parent,change}.json."""
+--density-renders runs it alone): profiles/density_render_refactor_bits_{parent,change}.json.
+
+The pass that collapsed the occupancy-culled path to one gather body, one emit body, one culled pass and one stats sum added
+culled_renders() (its docstring lists the cases; --culled-renders runs it alone): profiles/cull_refactor_bits_{parent,change}.json."""
 import argparse
 import ctypes
 import hashlib
@@ -119,13 +122,14 @@ def selection(dev, cams, cams_ndc, images):
     return batches
 
 
-def models_on(dev):
+def models_on(dev, **over):
     import nerf
     from nerf import synthetic as syn
+    net = dict(NET, **over)
     out = []
     for seed in (21, 22):
-        m = nerf.models.FlexibleNeRFModel(**NET)
-        m.load_state_dict({k: torch.from_numpy(v) for k, v in syn.synth_state_dict(seed, sigma_bias=-1.0, **NET).items()})
+        m = nerf.models.FlexibleNeRFModel(**net)
+        m.load_state_dict({k: torch.from_numpy(v) for k, v in syn.synth_state_dict(seed, sigma_bias=-1.0, **net).items()})
         out.append(m.to(dev))
     return out
 
@@ -483,15 +487,174 @@ def density_renders(dev):
     OUT["workspace bytes (render, depth, train, reg, normals fp32, normals bf16, backward_geom) over n x (nc, nf)"] = json.dumps(sizes)
 
 
+def culled_renders(dev):
+    """The occupancy-culled path, for the pass that gave it one gather body, one emit body, one culled pass and one stats sum.  A
+    5 x 4 x 3 grid with no cell, every cell and a seeded 40 % of the cells set.  One digest per group of cases (fold_into); the kept /
+    total counts are kept as text.
+
+    The entry points, on p = 1, 63, 64, 65, 1023, 1024, 1025 and 1024 * 1024 + 3 samples in and around the unit box (7, 3 or 1 per ray,
+    11-column rays): dn_occupancy_compact_count (slots and record); both emits at capacity 0, half the kept count and the kept count,
+    into planted buffers; dn_occupancy_gather and dn_occupancy_gather_rows (widths 1 .. 4; dense rows - width 4: the 16-byte path - and
+    column views: source stride 6, destination stride 5) with n_rows 0, half the kept count and the kept count, with and without the
+    count, the sources carrying planted non-finite values; destination and record after every call.
+
+    The drivers render_rays_depth_culled, render_rays_culled and render_rays_normals_culled on 37 and 300 rays, 16 + 16 samples and
+    coarse-only, two seeded 4 x 128 networks, fp32 and bf16, (noise_std, lindisp) in (0, off), (0.3, on) with given draws,
+    count_nonfinite off and on, three thresholds.  Depth: without quantiles and with three, interp off and on.  Colour: networks with
+    view directions (11-column rays) and without (8-column rays).  Normals: one slab, and max_points = 50 - below the kept count
+    wherever much is kept - so that the slab loop runs.  Maps, records and the kept / total counts of every call.
+
+    The image-level renders with occupancy= and cull_stats=True (render_dex_depth - also with quantiles -, run_one_iter_of_nerf,
+    render_dex_normals) on a 6 x 7 image in validation mode with chunksize 16 (three chunks), fp32 and bf16: the maps and the stats."""
+    import nerf
+    from nerf import _hip, _ops
+    cells = (5, 4, 3)
+
+    def grids(box):
+        g = torch.Generator().manual_seed(5)
+        draw = torch.rand(cells, generator=g)
+        return {name: nerf.OccupancyGrid.from_mask((draw < share).to(dev), box) for name, share in (("none", 0.0), ("all", 2.0), ("random", 0.4))}
+
+    def planted(seed, n, columns):
+        """max(n, 1) rows of normal values with non-finite ones planted"""
+        src = rand(seed, max(n, 1), columns, normal=True)
+        flat = src.view(-1)
+        flat[::97] = float("nan")
+        flat[5::131] = float("inf")
+        flat[7::173] = float("-inf")
+        return src
+
+    # ---- the entry points
+    unit = grids((0.0, 0.0, 0.0, 1.0, 1.0, 1.0))
+    fills = (-0.0, _hip.OCC_FILL, 1.5, 0.0)
+    for p in (1, 63, 64, 65, 1023, 1024, 1025, 1024 * 1024 + 3):
+        fold_into(f"culled entry points p={p}")
+        s = next(q for q in (7, 3, 1) if p % q == 0)
+        n = p // s
+        rays = torch.cat([rand(p, n, 3) * 0.6 - 0.2, rand(p + 1, n, 3) * 1.4 - 0.5, rand(p + 2, n, 5)], dim=1).contiguous()
+        z = (rand(p + 3, n, s) * 1.2).contiguous()
+        counts = []
+        for gname, grid in unit.items():
+            slot, rec, ws = _ops.occupancy_compact_count(rays, z, grid)
+            record(f"count p={p} {gname}", slot, rec)
+            n_kept = int(rec[0].item())
+            counts.append(n_kept)
+            for cap in (0, n_kept // 2, n_kept):
+                pts = torch.full((n_kept + 2, 3), 7.0, device=dev)
+                record(f"emit p={p} {gname} cap={cap}", _ops.occupancy_compact_emit(rays, z, slot, cap, pts))
+                pts, dirs = torch.full((n_kept + 2, 3), 7.0, device=dev), torch.full((n_kept + 2, 3), 9.0, device=dev)
+                record(f"emit_dirs p={p} {gname} cap={cap}", *_ops.occupancy_compact_emit_dirs(rays, z, slot, cap, pts, dirs))
+            net = planted(p + 4, n_kept, 4)
+            sources = {width: (planted(p + 5 + width, n_kept, width), planted(p + 9 + width, n_kept, 6)) for width in (1, 2, 3, 4)}
+            for n_rows in (0, n_kept // 2, n_kept):
+                for count in (True, False):
+                    what = f"p={p} {gname} n_rows={n_rows} count={count}"
+                    rf, r2 = torch.full((n, s, 4), 3.0, device=dev), rec.clone()
+                    _ops.occupancy_gather(slot, net[:n_rows] if n_rows else None, rf, *((ws, r2) if count else ()))
+                    record(f"gather {what}", rf, r2)
+                    for width in (1, 2, 3, 4):
+                        dense, wide = sources[width]
+                        for layout, src, dst in (("dense", dense, torch.full((p, width), 3.0, device=dev)),
+                                                 ("views", wide[:, 2:2 + width], torch.full((p, 5), 3.0, device=dev))):
+                            r2 = rec.clone()
+                            _ops.occupancy_gather_rows(slot, src[:n_rows] if n_rows else None, dst if layout == "dense" else dst[:, 1:1 + width],
+                                                       width, fills[:width], *((ws, r2) if count else ()))
+                            record(f"gather_rows {what} width={width} {layout}", dst, r2)
+        fold_into(None)
+        OUT[f"culled entry points p={p}: kept (none, all, random)"] = json.dumps(counts)
+
+    # ---- the drivers
+    thres = [0.05, 0.9, 1.7]
+    on_dev = lambda values: torch.tensor(values, dtype=torch.float32, device=dev)
+    world = grids((-6.0, -6.0, -6.0, 6.0, 6.0, 6.0))
+    with_dirs, without_dirs = models_on(dev), models_on(dev, use_viewdirs=False)
+
+    def rows_of(n):
+        rd = rand(70 + n, n, 3, normal=True)
+        return torch.cat([rand(80 + n, n, 3) - 0.5, rd, torch.full((n, 1), 2.0, device=dev), torch.full((n, 1), 6.0, device=dev),
+                          torch.nn.functional.normalize(rd, dim=-1)], dim=1).contiguous()
+
+    def draws_of(n, nf, std):
+        d = dict(t_rand=rand(90, n, 16), u=rand(91, n, nf) if nf else None)
+        if std:
+            d.update(noise_c=rand(92, n, 16, normal=True), noise_f=rand(93, n, 16 + nf, normal=True) if nf else None)
+        return d
+    for pname, prec in (("fp32", _hip.PREC_F32), ("bf16", _hip.PREC_BF16)):
+        full = {True: [m.packed(precision=prec) for m in with_dirs], False: [m.packed(precision=prec) for m in without_dirs]}
+        dens = [m.packed_density(True, True, precision=prec) for m in with_dirs]
+        streams = [m.packed_density_grad(True, True, precision=prec) for m in with_dirs]
+        for n in (37, 300):
+            fold_into(f"culled drivers {pname} n={n}")
+            counts = {}
+            for nf in (16, 0):
+                for gname, grid in world.items():
+                    for std, lindisp in ((0.0, False), (0.3, True)):
+                        for count in (False, True):
+                            what = f"{pname} n={n} 16+{nf} {gname} noise={std} lindisp={lindisp} count={count}"
+                            rows, draws = rows_of(n), draws_of(n, nf, std)
+                            rows8 = rows[:, :8].contiguous()
+
+                            def keep(name, maps, stats):
+                                record(name, *maps, *stats["records"])
+                                counts[name] = [list(stats["kept"]), list(stats["total"])]
+                            for qname, q, interp in (("none", None, False), ("3", on_dev([0.1, 0.5, 0.9]), False), ("3 interp", on_dev([0.1, 0.5, 0.9]), True)):
+                                keep(f"depth {what} quantiles={qname}",
+                                     *_ops.render_rays_depth_culled(*dens, rows8, 16, nf, lindisp, std, on_dev(thres), grid, draws, quantiles=q,
+                                                                    interp=interp, count_nonfinite=count))
+                            for dirs in (True, False):
+                                keep(f"colour {what} viewdirs={dirs}",
+                                     *_ops.render_rays_culled(*full[dirs], rows if dirs else rows8, 16, nf, lindisp, std, std > 0.0, thres, grid, draws,
+                                                              count_nonfinite=count))
+                            for max_points in (None, 50):
+                                keep(f"normals {what} max_points={max_points}",
+                                     *_ops.render_rays_normals_culled(*dens, streams[1 if nf else 0], rows8, 16, nf, lindisp, std, on_dev(thres), grid,
+                                                                      draws, count_nonfinite=count, max_points=max_points))
+            fold_into(None)
+            OUT[f"culled drivers {pname} n={n}: (kept, total) per call"] = json.dumps(counts, sort_keys=True)
+
+    # ---- the image-level renders: 6 x 7, validation mode, three chunks of 16, 16, 10 rays
+    from nerf import synthetic as syn
+    h, w = 6, 7
+    mode = dict(chunksize=16, lindisp=False, num_coarse=16, num_fine=16, perturb=False, radiance_field_noise_std=0.0, white_background=False)
+    cfg = nerf.CfgNode(dict(dataset=dict(near=2.0, far=6.0, no_ndc=True), nerf=dict(use_viewdirs=True, train=dict(mode), validation=dict(mode))))
+    ex, ed = nerf.get_embedding_function(10, True, True), nerf.get_embedding_function(4, True, True)
+    k_mat = torch.from_numpy(syn.intrinsic(h, w)).to(dev)
+    focal = float(k_mat[0, 0])
+    ro, rd = nerf.get_ray_bundle(h, w, focal, torch.from_numpy(syn.scene_pose(3)).to(dev), k_mat)
+    mc, mf = with_dirs
+    for precision in ("fp32", "bf16"):
+        nerf.set_precision(precision)
+        for gname, grid in world.items():
+            what = f"6 x 7 {precision} {gname}"
+            fold_into(f"culled image renders {what}")
+            kw = dict(mode="validation", encode_position_fn=ex, m_thres_cand=thres, occupancy=grid, cull_stats=True)
+            stats = []
+            with torch.no_grad():
+                for qs in (None, (0.1, 0.5, 0.9)):
+                    *maps, st = nerf.render_dex_depth(h, w, focal, mc, mf, ro, rd, cfg, quantiles=qs, **kw)
+                    record(f"render_dex_depth {what} quantiles={qs}", *maps)
+                    stats.append(st)
+                *maps, st = nerf.run_one_iter_of_nerf(h, w, focal, mc, mf, ro, rd, cfg, encode_direction_fn=ed, **kw)
+                record(f"run_one_iter_of_nerf {what}", *maps)
+                stats.append(st)
+                out, st = nerf.render_dex_normals(h, w, focal, mc, mf, ro, rd, cfg, **kw)
+                record(f"render_dex_normals {what}", out.depth, out.acc, out.normal, *out.dex_depth, *out.dex_normal)
+                stats.append(st)
+            fold_into(None)
+            OUT[f"culled image renders {what}: stats (depth, depth with quantiles, colour, normals)"] = json.dumps(stats, sort_keys=True)
+    nerf.set_precision("fp32")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tree", default="", help="import the package of this checkout (built there) instead of this script's")
     ap.add_argument("--out", required=True)
     ap.add_argument("--density-renders", action="store_true", help="the density_renders() group alone")
+    ap.add_argument("--culled-renders", action="store_true", help="the culled_renders() group alone")
     args = ap.parse_args()
     from nerf import _ops, synthetic as syn
     dev = torch.device("cuda:0")
-    if not args.density_renders:
+    if not (args.density_renders or args.culled_renders):
         e0 = torch.stack([torch.from_numpy(syn.scene_pose(v, n_views=8)) for v in range(V)]).to(dev)
         k = torch.from_numpy(syn.intrinsic(H, W)).to(dev)
         xi = torch.zeros(V, 6, device=dev)
@@ -504,7 +667,10 @@ def main():
         loss_heads(dev)
         fold_into(None)
         forward_compositing(dev)
-    density_renders(dev)
+    if not args.culled_renders:
+        density_renders(dev)
+    if not args.density_renders:
+        culled_renders(dev)
     torch.cuda.synchronize()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as fh:

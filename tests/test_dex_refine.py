@@ -210,7 +210,7 @@ def test_restatement_on_the_goldens_own_field(golden, name):
 BAD_CALLS = [dict(refine_steps=-1), dict(refine_steps=25), dict(refine_steps=2.0), dict(refine_steps="3"), dict(refine_steps=True),
              dict(refine_steps=2, m_thres_cand=None), dict(refine_steps=2, m_thres_cand=[]), dict(refine_steps=2, m_thres_cand=[5.0, -1.0]),
              dict(refine_steps=2, m_thres_cand=[float("nan")]), dict(refine_steps=2, m_thres_cand=[float("inf")]),
-             dict(refine_steps=2, quantiles=[0.5]), dict(refine_steps=2, occupancy=object()), dict(refine_steps=2, noise=0.2),
+             dict(refine_steps=2, quantiles=[0.5]), dict(refine_steps=2, occupancy="any grid"), dict(refine_steps=2, noise=0.2),
              dict(refine_width=True)]
 
 
