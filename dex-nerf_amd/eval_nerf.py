@@ -13,6 +13,11 @@ set cells; `--occupancy-check` renders every view both ways and reports, per thr
 `--occupancy N[,N,N] --occupancy-colour` culls the full colour render the same way (nerf.run_one_iter_of_nerf(occupancy=...)), and
 `--normals --occupancy N[,N,N]` the normal render (nerf.render_dex_normals(occupancy=...)); with `--occupancy-colour`, `--occupancy-check`
 also reports the largest |rgb| difference.
+`--ray-span N[,N,N] [--ray-span-pad P]` (with `--depth-only`, `--normals` or the colour render) tightens every ray's near / far to the
+occupied span of such a grid before the render (ray_span= of the three renders): the same number of samples, spent where the grid has set
+cells.  It shares --occupancy-bounds / --occupancy-level / --occupancy-dilate, which are legal with --ray-span alone; when --occupancy names
+the same cells one grid serves both.  Per view it prints the share of rays that hit a set cell and the mean of (t_hi - t_lo) / (far - near)
+over them.
 `--normals` renders density-gradient surface normals (nerf.render_dex_normals) instead: normal_<view>.npy holds the expected normal
 (H,W,3) (not renormalised: its length is a confidence), normal_<view>.png shows (n/|n| + 1)/2, black where n = 0; with `--m-thres M` the
 same pair per threshold, dex_normal_<view>_m<threshold>.npy / .png - the normal at the sample the Dex depth reports.
@@ -110,6 +115,12 @@ def main(argv=None):
                     help="--occupancy: render every view with and without the grid (both in the configured precision) and print, per "
                          "threshold, the share of pixels with equal Dex depth and the largest depth difference - how to find the cells and "
                          "the dilation a scene needs")
+    ap.add_argument("--ray-span", default="", metavar="N[,N,N]",
+                    help="tighten every ray's near / far to the occupied span of an occupancy grid of this many cells per axis before the "
+                         "render (ray_span= of render_dex_depth, render_dex_normals and run_one_iter_of_nerf); shares --occupancy-bounds / "
+                         "-level / -dilate, and the grid itself when --occupancy names the same cells")
+    ap.add_argument("--ray-span-pad", type=float, default=None, metavar="P",
+                    help="--ray-span: widen each span by P cells of travel at both ends (default 1)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"])
     ap.add_argument("--savedir", default="")
     ap.add_argument("--quiet", action="store_true")
@@ -168,7 +179,34 @@ def main(argv=None):
         mesh_res = mesh_res * 3 if len(mesh_res) == 1 else mesh_res
     elif args.mesh_bounds or args.mesh_thres is not None:
         ap.error("--mesh-bounds / --mesh-thres belong to --mesh")
-    occ_cells = None
+    def grid_cells(flag, text):
+        try:
+            cells = [int(v) for v in text.split(",") if v.strip()]
+        except ValueError as e:
+            ap.error(f"{flag}: {e}")
+        if len(cells) not in (1, 3):
+            ap.error(f"{flag} takes N or cx,cy,cz")
+        cells = cells * 3 if len(cells) == 1 else cells
+        try:
+            _ops.check_occupancy_grid(args.occupancy_bounds or (0, 0, 0, 1, 1, 1), cells, flag)
+        except ValueError as e:
+            ap.error(str(e))
+        if not np.isfinite(np.float32(args.occupancy_level)):
+            ap.error("--occupancy-level must be finite")
+        if not 0 <= args.occupancy_dilate <= 8:
+            ap.error("--occupancy-dilate must be 0..8")
+        return cells
+    occ_cells = span_cells = None
+    if args.ray_span:
+        if args.mesh:
+            ap.error("--ray-span tightens the rays of a render: not with --mesh")
+        span_cells = grid_cells("--ray-span", args.ray_span)
+        try:
+            _ops.check_ray_span_pad(1.0 if args.ray_span_pad is None else args.ray_span_pad, "--ray-span-pad")
+        except ValueError as e:
+            ap.error(str(e))
+    elif args.ray_span_pad is not None:
+        ap.error("--ray-span-pad belongs to --ray-span")
     if args.occupancy:
         if not (args.depth_only or args.occupancy_colour or args.normals):
             ap.error("--occupancy culls the depth-only render: it needs --depth-only (or --occupancy-colour for the colour render, "
@@ -179,26 +217,13 @@ def main(argv=None):
             ap.error("--occupancy-check compares depth-only or colour renders: not with --normals")
         if args.precision == "fp16":
             ap.error("--occupancy evaluates explicit points, which run in fp32 or bf16: not with --precision fp16")
-        try:
-            occ_cells = [int(v) for v in args.occupancy.split(",") if v.strip()]
-        except ValueError as e:
-            ap.error(f"--occupancy: {e}")
-        if len(occ_cells) not in (1, 3):
-            ap.error("--occupancy takes N or cx,cy,cz")
-        occ_cells = occ_cells * 3 if len(occ_cells) == 1 else occ_cells
-        try:
-            _ops.check_occupancy_grid(args.occupancy_bounds or (0, 0, 0, 1, 1, 1), occ_cells, "--occupancy")
-        except ValueError as e:
-            ap.error(str(e))
-        if not np.isfinite(np.float32(args.occupancy_level)):
-            ap.error("--occupancy-level must be finite")
-        if not 0 <= args.occupancy_dilate <= 8:
-            ap.error("--occupancy-dilate must be 0..8")
+        occ_cells = grid_cells("--occupancy", args.occupancy)
         if args.occupancy_check and args.m_thres <= 0 and not args.occupancy_colour:
             ap.error("--occupancy-check compares Dex depths: it needs --m-thres > 0")
-    elif (args.occupancy_bounds is not None or args.occupancy_check or args.occupancy_colour or args.occupancy_level != 0.0
-          or args.occupancy_dilate != 1):
-        ap.error("--occupancy-bounds / --occupancy-level / --occupancy-dilate / --occupancy-check / --occupancy-colour belong to --occupancy")
+    elif args.occupancy_check or args.occupancy_colour:
+        ap.error("--occupancy-check / --occupancy-colour belong to --occupancy")
+    elif not span_cells and (args.occupancy_bounds is not None or args.occupancy_level != 0.0 or args.occupancy_dilate != 1):
+        ap.error("--occupancy-bounds / --occupancy-level / --occupancy-dilate belong to --occupancy or --ray-span")
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     nerf.set_precision(args.precision)
     ck = torch.load(args.checkpoint, map_location="cpu")
@@ -255,7 +280,7 @@ def main(argv=None):
             cull["kept"][p] += stats["kept"][p]
             cull["total"][p] += stats["total"][p]
         cull["nonfinite"] += stats["nonfinite"]
-    if occ_cells:
+    def build_grid(cells, what):
         bounds = args.occupancy_bounds
         if bounds is None:      # the box around the corner rays of every camera between near and far: it holds every sample
             corners = []
@@ -270,15 +295,34 @@ def main(argv=None):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         with torch.no_grad():
-            grid = nerf.OccupancyGrid.from_networks([coarse, fine], ex, bounds, occ_cells, level=args.occupancy_level,
+            grid = nerf.OccupancyGrid.from_networks([coarse, fine], ex, bounds, cells, level=args.occupancy_level,
                                                     dilate=args.occupancy_dilate)
         torch.cuda.synchronize()
-        if args.occupancy_check and args.precision == "bf16":
-            nerf.set_render_policy("bf16")      # the culled render runs in bf16: compare it with a bf16 full render, not the guarded fp16 one
         if not args.quiet:
-            print(f"occupancy grid {occ_cells[0]}x{occ_cells[1]}x{occ_cells[2]} over {[round(float(b), 4) for b in grid.bounds]}: "
+            print(f"{what} grid {cells[0]}x{cells[1]}x{cells[2]} over {[round(float(b), 4) for b in grid.bounds]}: "
                   f"{100 * grid.occupied_fraction():.2f} % of the cells set (level {args.occupancy_level:g}, dilate {args.occupancy_dilate}) "
                   f"in {time.perf_counter() - t0:.3f} s", flush=True)
+        return grid
+    span_grid, span_rows = None, []
+    span_kw = {}
+    if occ_cells:
+        grid = build_grid(occ_cells, "occupancy and ray-span" if span_cells == occ_cells else "occupancy")
+        if args.occupancy_check and args.precision == "bf16":
+            nerf.set_render_policy("bf16")      # the culled render runs in bf16: compare it with a bf16 full render, not the guarded fp16 one
+    if span_cells:
+        span_grid = grid if span_cells == occ_cells else build_grid(span_cells, "ray-span")
+        span_kw = dict(ray_span=span_grid, ray_span_pad=args.ray_span_pad)
+
+    def report_spans(view, ro, rd):
+        """(outside the timed render) the share of rays that hit a set cell and the mean span fraction over them"""
+        rows = _ops.pack_ray_rows(ro.reshape(-1, 3).contiguous(), rd.reshape(-1, 3).contiguous(), None, args.near, args.far)
+        span, visits = span_grid.ray_spans(rows, pad_cells=1.0 if args.ray_span_pad is None else args.ray_span_pad)
+        hit = visits > 0
+        share = float(hit.float().mean())
+        fraction = float(((span[:, 1] - span[:, 0]) / (args.far - args.near))[hit].mean()) if bool(hit.any()) else float("nan")
+        span_rows.append(dict(view=view, hit_share=share, mean_span_fraction=fraction))
+        if not args.quiet:
+            print(f"ray span view {view}: {100 * share:.2f} % of the rays hit a set cell, mean span {100 * fraction:.2f} % of [near, far]", flush=True)
     for i, (pose, k_mat) in enumerate(cameras):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -287,9 +331,11 @@ def main(argv=None):
                 ro, rd = nerf.get_ray_bundle(size, size, float(k_mat[0, 0]), pose, k_mat)
                 out = nerf.render_dex_normals(size, size, float(k_mat[0, 0]), coarse, fine, ro, rd, cfg, mode="validation",
                                               encode_position_fn=ex, encode_direction_fn=ed, m_thres_cand=thres, occupancy=grid,
-                                              cull_stats=grid is not None)
+                                              cull_stats=grid is not None, **span_kw)
             torch.cuda.synchronize()
             times.append(time.perf_counter() - t0)
+            if span_grid is not None:
+                report_spans(i, ro, rd)
             if grid is not None:
                 out, stats = out
                 tally(stats)
@@ -313,9 +359,12 @@ def main(argv=None):
                 out = nerf.render_dex_depth(size, size, float(k_mat[0, 0]), coarse, fine, ro, rd, cfg, mode="validation",
                                             encode_position_fn=ex, encode_direction_fn=ed, m_thres_cand=thres,
                                             quantiles=quantiles or None, quantile_interp=args.quantile_interp, occupancy=grid,
-                                            cull_stats=grid is not None, refine_steps=args.dex_refine, refine_width=args.dex_refine_width)
+                                            cull_stats=grid is not None, refine_steps=args.dex_refine, refine_width=args.dex_refine_width,
+                                            **span_kw)
             torch.cuda.synchronize()
             times.append(time.perf_counter() - t0)
+            if span_grid is not None:
+                report_spans(i, ro, rd)
             if grid is not None:
                 *out, stats = out
                 tally(stats)
@@ -351,9 +400,11 @@ def main(argv=None):
             ro, rd = nerf.get_ray_bundle(size, size, float(k_mat[0, 0]), pose, k_mat)
             out = nerf.run_one_iter_of_nerf(size, size, float(k_mat[0, 0]), coarse, fine, ro, rd, cfg, mode="validation",
                                             encode_position_fn=ex, encode_direction_fn=ed, m_thres_cand=thres, occupancy=grid,
-                                            cull_stats=grid is not None)
+                                            cull_stats=grid is not None, **span_kw)
         torch.cuda.synchronize()
         times.append(time.perf_counter() - t0)
+        if span_grid is not None:
+            report_spans(i, ro, rd)
         if grid is not None:
             *out, stats = out
             tally(stats)
@@ -381,6 +432,8 @@ def main(argv=None):
     if not args.quiet:
         print(f"Avg time per image: {avg:.4f} s ({size}x{size}, {size * size / avg:.0f} rays/s, {args.precision})", flush=True)
     result = dict(avg_seconds=avg, frames=frames, times=times)
+    if span_grid is not None:
+        result.update(ray_span=span_grid, ray_spans=span_rows)
     if grid is not None:
         result.update(occupancy=grid, cull=cull)
         if not args.quiet:

@@ -87,6 +87,10 @@ REFINE_EXPORTS = ("dn_composite_density_brackets", "dn_dex_bisect", "dn_dex_refi
                   "dn_render_rays_depth_refined")
 MAX_REFINE_STEPS = 24               # DN_MAX_REFINE_STEPS
 
+# include/dexnerf_hip_span.h: a ray's near / far tightened to the occupied span of an occupancy grid (nerf.OccupancyGrid.ray_spans,
+# nerf.render_dex_depth(ray_span=...))
+SPAN_EXPORTS = ("dn_occupancy_ray_spans",)
+
 
 class MlpDesc(ctypes.Structure):
     """dn_mlp_desc (mirrors FlexibleNeRFModel.__init__, reference nerf/models.py:186-196)."""
@@ -287,6 +291,9 @@ def _declare(lib):
     lib.dn_render_depth_refined_workspace_bytes.restype = c_size_t
     lib.dn_render_rays_depth_refined.argtypes = lib.dn_render_rays_depth.argtypes[:-2] + [c_int, fp, fp, vp, vp]
     lib.dn_render_rays_depth_refined.restype = c_int
+    # the span header
+    lib.dn_occupancy_ray_spans.argtypes = [fp, c_int, c_int64, vp, c_int, c_int, c_int] + [c_float] * 10 + [c_int, fp, vp, vp]
+    lib.dn_occupancy_ray_spans.restype = c_int
 
 
 def lib():

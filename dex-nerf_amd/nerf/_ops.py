@@ -1986,6 +1986,53 @@ def occupancy_gather_rows(slot, src, dst, width, fills, ws=None, record=None):
     return dst
 
 
+# ---- a ray's near / far tightened to the occupied span of the grid (include/dexnerf_hip_span.h) -----------------------------------------
+def check_ray_span_pad(pad_cells, who="ray_span_pad"):
+    """The pad of a span in cells of travel: a number, finite as fp32 and >= 0 -> its fp32 value.  Raises ValueError before any GPU work."""
+    try:
+        pad = float(pad_cells)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: the pad is a number of cells, got {pad_cells!r}") from None
+    if not (math.isfinite(pad) and pad >= 0.0 and math.isfinite(ctypes.c_float(pad).value)):
+        raise ValueError(f"{who}: the pad must be finite as fp32 and >= 0 cells, got {pad_cells!r}")
+    return ctypes.c_float(pad).value
+
+
+def occupancy_ray_spans(rays, grid, pad_cells=1.0, apply=False):
+    """dn_occupancy_ray_spans of the ray rows (N, >= 8) fp32 against `grid` (bits, cells, bounds, scale: an nerf.OccupancyGrid) ->
+    (span (N,2) fp32, visits (N) int32): the depth range in which the ray can meet a set cell, widened by pad_cells cells of travel and
+    clipped to the row's [near, far], and the number of set cells the ray walks through; a ray that meets none keeps (near, far) and 0.
+    apply=True also writes the span into columns 6 and 7 of the hit rays' rows, IN PLACE - so `rays` must then be a contiguous fp32
+    device tensor (a copy would take the writes with it).  One launch, no host read."""
+    pad = check_ray_span_pad(pad_cells, "occupancy_ray_spans: pad_cells")
+    if not (torch.is_tensor(rays) and rays.dim() == 2 and rays.shape[1] >= 8 and rays.dtype == torch.float32):
+        raise ValueError("occupancy_ray_spans: rays are fp32 rows (N, >= 8): origin, direction, near, far")
+    if grid.bits.device != rays.device:
+        raise ValueError(f"occupancy_ray_spans: the occupancy grid lives on {grid.bits.device} and the rays on {rays.device}; move it with grid.to(device)")
+    if not rays.is_cuda:
+        raise RuntimeError("occupancy_ray_spans: runs on the ROCm device only (got a host tensor); move the rays to 'cuda'")
+    if apply and not rays.is_contiguous():
+        raise ValueError("occupancy_ray_spans: apply=True writes the rows in place and needs contiguous rays")
+    rays = rays.contiguous()
+    n = rays.shape[0]
+    span = torch.empty((n, 2), dtype=torch.float32, device=rays.device)
+    visits = torch.empty(n, dtype=torch.int32, device=rays.device)
+    if n:
+        check(lib().dn_occupancy_ray_spans(ptr(rays), rays.shape[1], n, ptr(grid.bits), *grid.cells, *grid.bounds, *grid.scale, pad,
+                                           int(bool(apply)), ptr(span), ptr(visits), stream()), "dn_occupancy_ray_spans")
+    return span, visits
+
+
+def tighten_ray_rows(rays, grid, pad):
+    """The renders' use of dn_occupancy_ray_spans: columns 6 and 7 of the hit rows of `rays` (contiguous fp32 device rows the caller
+    owns, a grid on their device, a pad from check_ray_span_pad) rewritten in place, no other output -> rays."""
+    assert rays.dtype == torch.float32 and rays.is_contiguous() and rays.shape[1] >= 8 and grid.bits.device == rays.device
+    if rays.shape[0]:
+        check(lib().dn_occupancy_ray_spans(ptr(rays), rays.shape[1], rays.shape[0], ptr(grid.bits), *grid.cells, *grid.bounds, *grid.scale,
+                                           pad, 1, None, None, stream()), "dn_occupancy_ray_spans")
+    return rays
+
+
 # ---- the culled renders: depth, colour and normals over one pass ------------------------------------------------------------------------
 class _CullStats:
     """What the passes of a culled driver report into: the kept and the total samples of pass 0 (coarse) and 1 (fine) - 0 for a pass

@@ -85,6 +85,18 @@ class OccupancyGrid:
         bits = torch.as_tensor(state["bits"], dtype=torch.int32)
         return cls(bits if device is None else bits.to(device), state["bounds"], state["cells"])
 
+    def ray_spans(self, rays, pad_cells=1.0, apply=False):
+        """(span (N,2), visits (N) int32) of the ray rows (N, >= 8: origin, direction, near, far) - include/dexnerf_hip_span.h: each
+        ray walks the grid cell by cell; span is the depth range from the entry of the first set cell to the exit of the last one,
+        widened by pad_cells cells of travel and clipped to the row's [near, far]; visits counts the set cells on the way.  A ray that
+        meets no set cell is a miss: it keeps its (near, far) and visits 0.  apply=True also writes the span into columns 6 and 7 of
+        the hit rows, in place.  nerf.render_dex_depth(ray_span=grid) does exactly that before it renders.
+
+        What the span does not promise: a ray that grazes a cell boundary within fp32 rounding can lose samples the culling
+        classification would keep - the pad and the grid's `dilate` are the margins for that; and the grid is a sampled approximation
+        of the field."""
+        return _ops.occupancy_ray_spans(rays, self, pad_cells, apply)
+
     def check_render(self, device, who):
         """The refusals of a render with this grid, before any GPU work."""
         if self.bits.device != device:

@@ -320,6 +320,22 @@ def _culled_precision(who):
     return _ops._precision
 
 
+def _check_ray_span(who, ray_span, ray_span_pad, models, ray_origins, ray_directions):
+    """Every refusal of ray_span= / ray_span_pad= before any GPU work -> the pad as an fp32 value, or None without a grid
+    (ray_span_pad=None stands for 1 cell)."""
+    if ray_span is None:
+        if ray_span_pad is not None:
+            raise ValueError(f"{who}: ray_span_pad widens a ray's span: give ray_span=")
+        return None
+    pad = _ops.check_ray_span_pad(1.0 if ray_span_pad is None else ray_span_pad, f"{who}: ray_span_pad")
+    ray_span.check_render(ray_directions.device, who)
+    if _wants_grad(*models) or inputs_need_grad(ray_origins, ray_directions):
+        raise RuntimeError(f"{who}(ray_span=...) is a no-grad render: the tightening replaces each ray's near and far by values read "
+                           "from the grid, which would cut the near/far gradient of the rays; call it under torch.no_grad() (or with "
+                           "parameters and rays that do not require grad); training with spans is not provided")
+    return pad
+
+
 class _CullTotals:
     """The sum of a culled render's per-chunk stats (_ops.render_rays_*_culled): the kept / total counts per pass on the host (the
     chain reads them anyway), the non-finite counts on the device - read once, by result(), and only when `wanted` (else it gives None)."""
@@ -363,7 +379,7 @@ def _refuse_culled_colour(model_coarse, model_fine, ray_origins, ray_directions,
 
 def run_one_iter_of_nerf(height, width, focal_length, model_coarse, model_fine, ray_origins, ray_directions, options,
                          mode="train", encode_position_fn=None, encode_direction_fn=None, m_thres_cand=None, occupancy=None,
-                         cull_stats=False):
+                         cull_stats=False, ray_span=None, ray_span_pad=None):
     """Pack rays, chunk, render, concatenate (reference train_utils.py:205-288).
 
     Output order: rgb_coarse, depth_coarse, acc_coarse, rgb_fine, depth_fine, acc_fine, *dex_fine[K]; flat
@@ -377,9 +393,14 @@ def run_one_iter_of_nerf(height, width, focal_length, model_coarse, model_fine, 
     chunk, no HIP-graph capture.  No-grad only, device tensors only, networks the fused kernels cover only: anything else raises before
     any GPU work.  cull_stats=True (with a grid only) appends render_dex_depth's dict(kept=, total=, nonfinite=) to the return -
     nonfinite counts all four columns of the kept rows.  occupancy=None: the launches and the return are what they were.
+
+    ray_span: an nerf.OccupancyGrid on the rays' device - a no-grad render whose ray rows are tightened once, right after they are
+    packed (and after the NDC warp where there is one): render_dex_depth's ray_span=, with the same ray_span_pad, the same refusals
+    and the same limits; it works with and without occupancy=.  ray_span=None: the launches and the return are what they were.
     """
     if occupancy is None and cull_stats:
         raise ValueError("run_one_iter_of_nerf: cull_stats reports on a culled render: give occupancy=")
+    span_pad = _check_ray_span("run_one_iter_of_nerf", ray_span, ray_span_pad, [model_coarse, model_fine], ray_origins, ray_directions)
     culled = None
     if occupancy is not None:
         culled = _refuse_culled_colour(model_coarse, model_fine, ray_origins, ray_directions, options, mode, encode_position_fn,
@@ -407,6 +428,8 @@ def run_one_iter_of_nerf(height, width, focal_length, model_coarse, model_fine, 
         far = options.dataset.far * torch.ones_like(rd[..., :1])
         parts = [ro, rd, near, far] + ([viewdirs] if viewdirs is not None else [])
         rays = torch.cat(parts, dim=-1).float()
+    if ray_span is not None:
+        rays = _ops.tighten_ray_rows(rays.contiguous(), ray_span, span_pad)
 
     def render_chunk(batch, status):
         return _render_chunk(batch, model_coarse, model_fine, options, mode, encode_position_fn, encode_direction_fn, thres,
@@ -476,11 +499,12 @@ _DensityRender = collections.namedtuple("_DensityRender", "rays img_shape dev nc
 
 
 def _density_render_setup(who, instead, height, width, focal_length, model_coarse, model_fine, ray_origins, ray_directions, options, mode,
-                          encode_position_fn, m_thres_cand):
+                          encode_position_fn, m_thres_cand, ray_span=None, span_pad=None):
     """What the density renders (render_dex_depth, render_dex_normals) settle before their chunk loops, every refusal before any GPU
     work: no autograd (`instead`: where the message sends the caller), device rays, density networks the fused kernels cover; then
-    the NDC warp, the ray rows without view-direction columns (the density sub-network does not read them), the mode's options and
-    the thresholds on the device.  nf is 0 without a fine pass."""
+    the NDC warp, the ray rows without view-direction columns (the density sub-network does not read them) - tightened to the occupied
+    span of the grid `ray_span` where one is given (span_pad: _check_ray_span's) -, the mode's options and the thresholds on the
+    device.  nf is 0 without a fine pass."""
     opt = getattr(options.nerf, mode)
     nc, nf = int(opt.num_coarse), int(opt.num_fine)
     fine = nf > 0 and bool(model_fine)
@@ -499,6 +523,8 @@ def _density_render_setup(who, instead, height, width, focal_length, model_coars
         ro, rd = ray_origins, ray_directions
     ro, rd = ro.reshape((-1, 3)).float(), rd.reshape((-1, 3)).float()
     rays = _ops.pack_ray_rows(ro.contiguous(), rd.contiguous(), None, options.dataset.near, options.dataset.far)
+    if ray_span is not None:
+        _ops.tighten_ray_rows(rays, ray_span, span_pad)
     return _DensityRender(rays, ray_directions.shape, dev, nc, nf if fine else 0, fine, models, bool(opt.lindisp),
                           float(opt.radiance_field_noise_std), bool(opt.perturb), encode_position_fn.log_sampling,
                           _threshold_tensor(_thresholds(m_thres_cand), dev))
@@ -530,7 +556,8 @@ def _render_dex_depth_culled(r, prec, occupancy, q_dev, interp, cull_stats, chun
 
 def render_dex_depth(height, width, focal_length, model_coarse, model_fine, ray_origins, ray_directions, options,
                      mode="validation", encode_position_fn=None, encode_direction_fn=None, m_thres_cand=None, quantiles=None,
-                     quantile_interp=False, occupancy=None, cull_stats=False, refine_steps=None, refine_width=False):
+                     quantile_interp=False, occupancy=None, cull_stats=False, refine_steps=None, refine_width=False, ray_span=None,
+                     ray_span_pad=None):
     """The depth half of run_one_iter_of_nerf and nothing else: expected depth, accumulation and the Dex first-crossing depths
     depend on sigma alone (reference nerf/volume_rendering_utils.py:33-58), so this render evaluates only the density
     sub-networks (trunk + fc_alpha: FlexibleNeRFModel.packed_density) and composites no colour (dn_render_rays_depth).
@@ -573,7 +600,23 @@ def render_dex_depth(height, width, focal_length, model_coarse, model_fine, ray_
     threshold, a mode whose radiance_field_noise_std is not 0 (the brackets are those of the raw density), and quantiles= or occupancy=
     together with a refinement (both are follow-ups: a culled sample's -FLT_MAX is not a density to interpolate with).  Follows
     nerf.set_render_policy like the plain render: the midpoint evaluations report into the status words the guard reads.  No host read:
-    a chunk can be captured into a HIP graph.  refine_steps=None: the launches and the return are what they were."""
+    a chunk can be captured into a HIP graph.  refine_steps=None: the launches and the return are what they were.
+
+    ray_span: an nerf.OccupancyGrid on the rays' device (the same grid as occupancy=, or another) - the ray rows are tightened once,
+    right after they are packed (and after the NDC warp where there is one: the grid lives in the space of the sampled points): one
+    launch of dn_occupancy_ray_spans walks every ray through the grid and replaces its near and far by the depth range from the entry
+    of the first set cell to the exit of the last one, widened by ray_span_pad cells of travel (None: 1) and clipped to the dataset's
+    [near, far].  Everything downstream is what it was - the same number of samples, now spent where the grid has cells, so the Dex
+    depth's one-sample-interval error shrinks with the span.  A ray that meets no set cell keeps its [near, far] and renders as
+    before (a culled render skips its samples anyway).  No host read: it can be captured into a HIP graph, follows the render policy,
+    and works with and without occupancy=, with refine_steps= and with quantiles=.  What the span does not promise: a ray that grazes
+    a cell boundary within fp32 rounding can lose samples that occupancy='s classification would keep - the pad and the grid's
+    `dilate` are the margins for that; the grid is a sampled approximation of the field; and the reference's 1e10 last interval is
+    unchanged, so everything past the tightened far is treated as what the grid says it is: empty.  Refused before any GPU work: a
+    grid on another device, a pad that is not finite or is below 0 (ValueError), ray_span_pad without ray_span (ValueError), and a
+    call that wants gradients (RuntimeError: the tightening would cut the near/far gradient).  ray_span=None: the launches and the
+    return are what they were."""
+    span_pad = _check_ray_span("render_dex_depth", ray_span, ray_span_pad, [model_coarse, model_fine], ray_origins, ray_directions)
     if refine_steps is not None:
         _ops.check_refine_steps(refine_steps, "render_dex_depth: refine_steps")
         _ops.check_refine_thresholds(m_thres_cand, "render_dex_depth: refine_steps")
@@ -591,7 +634,8 @@ def render_dex_depth(height, width, focal_length, model_coarse, model_fine, ray_
         prec = _culled_precision("render_dex_depth")
         occupancy.check_render(ray_directions.device, "render_dex_depth")
     r = _density_render_setup("render_dex_depth", "differentiable renders go through run_one_iter_of_nerf", height, width, focal_length,
-                              model_coarse, model_fine, ray_origins, ray_directions, options, mode, encode_position_fn, m_thres_cand)
+                              model_coarse, model_fine, ray_origins, ray_directions, options, mode, encode_position_fn, m_thres_cand,
+                              ray_span, span_pad)
     q_dev = _threshold_tensor(qs, r.dev) if qs else None   # (the same cache: one host-to-device copy per quantile set)
     if occupancy is not None:
         return _render_dex_depth_culled(r, prec, occupancy, q_dev, quantile_interp, cull_stats, getattr(options.nerf, mode).chunksize, mode)
@@ -669,7 +713,7 @@ def _rays_within_workspace(packs, n, nc, nf, max_bytes):
 
 def render_dex_normals(height, width, focal_length, model_coarse, model_fine, ray_origins, ray_directions, options,
                        mode="validation", encode_position_fn=None, encode_direction_fn=None, m_thres_cand=None,
-                       max_workspace_bytes=2 ** 31, occupancy=None, cull_stats=False):
+                       max_workspace_bytes=2 ** 31, occupancy=None, cull_stats=False, ray_span=None, ray_span_pad=None):
     """render_dex_depth's last pass with surface normals: the density sub-network of the last pass (the fine one; the coarse one
     without a fine pass) is differentiated w.r.t. its input points, and n = -grad sigma_raw / |grad sigma_raw| is composited beside
     the depths (dn_render_rays_normals).
@@ -696,15 +740,20 @@ def render_dex_normals(height, width, focal_length, model_coarse, model_fine, ra
     capture); max_workspace_bytes then bounds the saved tensors of the kept points, which are differentiated in slabs (points are
     independent: the maps do not depend on the slabs), not the rays of a chunk.  cull_stats=True (with
     a grid only) returns (DexNormals, dict(kept=, total=, nonfinite=)).  occupancy=None: the launches and the return are what they
-    were."""
+    were.
+
+    ray_span: an nerf.OccupancyGrid on the rays' device - the ray rows are tightened to the occupied span of the grid once, before
+    the chunk loop: render_dex_depth's ray_span=, with the same ray_span_pad, the same refusals and the same limits; it works with
+    and without occupancy=.  ray_span=None: the launches and the return are what they were."""
     if occupancy is None and cull_stats:
         raise ValueError("render_dex_normals: cull_stats reports on a culled render: give occupancy=")
+    span_pad = _check_ray_span("render_dex_normals", ray_span, ray_span_pad, [model_coarse, model_fine], ray_origins, ray_directions)
     prec = _normals_precision("render_dex_normals")
     if occupancy is not None:
         occupancy.check_render(ray_directions.device, "render_dex_normals")
     r = _density_render_setup("render_dex_normals", "gradients through the normals are second order and not provided", height, width,
                               focal_length, model_coarse, model_fine, ray_origins, ray_directions, options, mode, encode_position_fn,
-                              m_thres_cand)
+                              m_thres_cand, ray_span, span_pad)
     nc, nf = r.nc, r.nf
     k = 0 if r.m_thres is None else int(r.m_thres.numel())
     packs = _density_packs(r, prec)
