@@ -9,6 +9,7 @@
 #include "../../include/dexnerf_hip_ext.h"
 #include "../../include/dexnerf_hip_normals.h"
 #include "../../include/dexnerf_hip_quantile.h"
+#include "../../include/dexnerf_hip_layers.h"
 #include "../../include/dexnerf_hip_refine.h"
 #include "dn_common.h"
 #include "composite_body.h"
@@ -68,6 +69,7 @@ struct Carver {
 struct Workspace {
   float *z_c, *rf_c, *w_c, *z_f, *rf_f, *g_rf;
   float *br, *z_mid, *rf_mid;   // dn_render_rays_depth_refined: the bracket records (N,K,4), their midpoints (N,K), the network's rows there
+  float* thres_rep;             // dn_render_rays_depth_layers: the thresholds repeated 2L times each (its records are (N, K*2L, 4))
   unsigned* absmax_part;   // training: one word per workgroup of the compositing backward (largest |gradient| it stored)
   unsigned* status;   // the last 256 bytes: word 0 = non-finite raw radiance-field values met by this call's compositing
   size_t bytes;
@@ -81,8 +83,9 @@ enum WorkspaceKind { kRender, kTrain, kDepth };
 // density instances, which do not claim tiles: they pass none.
 constexpr int kStatusTilesCoarse = 16, kStatusTilesFine = 32;
 
-// k_refine > 0 (kDepth): the refined render's three regions for k_refine thresholds, between the passes' regions and the status block
-static Workspace carve(void* base, int64_t n, int nc, int nf, WorkspaceKind kind = kRender, int k_refine = 0) {
+// k_refine > 0 (kDepth): the refined render's three regions for k_refine thresholds, between the passes' regions and the status block;
+// rep: the layers render's repeated thresholds behind them (it has k_refine = K*2L records per ray)
+static Workspace carve(void* base, int64_t n, int nc, int nf, WorkspaceKind kind = kRender, int k_refine = 0, bool rep = false) {
   Workspace w{};
   Carver c{base};
   const size_t rays = static_cast<size_t>(n);
@@ -101,6 +104,7 @@ static Workspace carve(void* base, int64_t n, int nc, int nf, WorkspaceKind kind
     w.br = c.floats(rays * k_refine * 4);
     w.z_mid = c.floats(rays * k_refine);
     w.rf_mid = c.floats(rays * k_refine * 4);
+    if (rep) w.thres_rep = c.floats(static_cast<size_t>(k_refine));
   }
   w.status = static_cast<unsigned*>(c.take(256));
   w.bytes = c.off;
@@ -245,19 +249,29 @@ struct RefineArgs {
   float *refined, *width;
 };
 
-// the one driver of dn_render_rays_depth, dn_render_rays_depth_quantiles and dn_render_rays_depth_refined (`who`: the entry point, for
-// messages): with n_quant > 0 the last pass is composited by composite_quantile_kernel, with `refine` by composite_brackets_kernel,
-// otherwise by composite_density_kernel - the launches are the same in number; `refine` then adds its bisection steps and the finish
+// what dn_render_rays_depth_layers adds to the driver below (include/dexnerf_hip_layers.h); steps -1: sample mode
+struct LayersArgs {
+  int n_layers, steps;
+  float* events;
+  int* count;
+  float* width;
+};
+
+// the one driver of dn_render_rays_depth, dn_render_rays_depth_quantiles, dn_render_rays_depth_refined and dn_render_rays_depth_layers
+// (`who`: the entry point, for messages): with n_quant > 0 the last pass is composited by composite_quantile_kernel, with `refine` by
+// composite_brackets_kernel, with `layers` by composite_layers_kernel, otherwise by composite_density_kernel - the launches are the same
+// in number; `refine` and `layers` then add their bisection steps and the finish
 static int render_rays_depth_impl(const char* who, const dn_mlp_desc* desc_coarse, const void* packed_coarse, const dn_mlp_desc* desc_fine,
                                   const void* packed_fine, int precision, const float* rays, int ray_stride, int64_t n_rays,
                                   int num_coarse, int num_fine, int lindisp, float noise_std, const float* d_m_thres, int n_thres,
                                   const float* t_rand, const float* noise_c, const float* u, const float* noise_f, float* depth_c,
                                   float* acc_c, float* depth_f, float* acc_f, float* dex_f, const float* d_quantiles, int n_quant,
-                                  int interp, float* qdepth, void* workspace, dn_stream_t stream, const RefineArgs* refine = nullptr) {
+                                  int interp, float* qdepth, void* workspace, dn_stream_t stream, const RefineArgs* refine = nullptr,
+                                  const LayersArgs* layers = nullptr) {
   // every argument is judged before any GPU work
   int rc;
   if ((rc = check_density_render(who, desc_coarse, packed_coarse, desc_fine, packed_fine, rays, ray_stride, n_rays, num_coarse, num_fine, n_thres,
-                                 workspace, !refine || refine->refined)))
+                                 workspace, (!refine || refine->refined) && (!layers || (layers->events && layers->count)))))
     return rc;
   DN_REQUIRE(n_thres == 0 || (d_m_thres && dex_f), "%s: thresholds given without dex output", who);
   if ((rc = quantile_args_check(who, d_quantiles, n_quant, interp, qdepth))) return rc;
@@ -267,10 +281,16 @@ static int render_rays_depth_impl(const char* who, const dn_mlp_desc* desc_coars
     DN_REQUIRE(noise_std == 0.0f, "%s: the brackets are those of the raw density: noise_std must be 0", who);
     DN_REQUIRE(n_rays <= INT64_C(0x7fffffff) / n_thres, "%s: at most 2^31 - 1 records (n_rays * n_thres)", who);
   }
+  if (layers) {
+    if ((rc = layers_check(who, n_thres, layers->n_layers, n_rays))) return rc;
+    DN_REQUIRE(layers->steps >= -1 && layers->steps <= DN_MAX_REFINE_STEPS, "%s: need -1 <= refine_steps <= %d", who, DN_MAX_REFINE_STEPS);
+    DN_REQUIRE(noise_std == 0.0f, "%s: the events are those of the raw density: noise_std must be 0", who);
+  }
   if ((rc = validate_desc(desc_coarse, precision))) return rc;
   if (num_fine > 0 && (rc = validate_desc(desc_fine, precision))) return rc;
   if (n_rays == 0) return 0;
-  const Workspace w = carve(workspace, n_rays, num_coarse, num_fine, kDepth, refine ? n_thres : 0);
+  const int n_records = layers ? n_thres * 2 * layers->n_layers : n_thres;   // per ray
+  const Workspace w = carve(workspace, n_rays, num_coarse, num_fine, kDepth, (refine || layers) ? n_records : 0, layers != nullptr);
   if ((rc = zero_status(who, w.status, stream))) return rc;
   if ((rc = density_coarse_pass(desc_coarse, packed_coarse, precision, rays, ray_stride, n_rays, num_coarse, num_fine, lindisp, noise_std, t_rand,
                                 noise_c, u, depth_c, acc_c, w, stream)))
@@ -285,6 +305,20 @@ static int render_rays_depth_impl(const char* who, const dn_mlp_desc* desc_coars
     return rc;
   const SigmaCompositeArgs last{rf_last, z_last, rays + 3, ray_stride, fine ? noise_f : noise_c, noise_std, d_m_thres, n_thres, n_rays, samples,
                                 fine ? depth_f : depth_c, fine ? acc_f : acc_c, dex_f, w.status, d_quantiles, n_quant, interp, qdepth};
+  if (layers) {
+    // the events of the last pass, then per step the last pass's network at the midpoints (K*2L "samples" per ray, the same range word)
+    // and dn_dex_bisect's kernel on the thresholds repeated 2L times each; the finish reads the records alone
+    if ((rc = composite_layers_counting(last, layers->n_layers, w.br, w.z_mid, layers->count, stream))) return rc;
+    if (layers->steps > 0 && (rc = layers_thresholds_launch(d_m_thres, n_thres, layers->n_layers, w.thres_rep, stream))) return rc;
+    for (int step = 0; step < layers->steps; ++step) {
+      if ((rc = run_network_flagged(fine ? desc_fine : desc_coarse, precision, fine ? packed_fine : packed_coarse, nullptr, nullptr, rays,
+                                    ray_stride, w.z_mid, n_rays, n_records, w.rf_mid, w.status + 1, stream)))
+        return rc;
+      if ((rc = dex_bisect_launch(w.br, w.rf_mid, w.thres_rep, n_records, n_rays, w.z_mid, stream))) return rc;
+    }
+    return dex_layers_finish_launch(w.br, d_m_thres, n_thres, layers->n_layers, layers->steps >= 0, n_rays, layers->events, layers->width,
+                                    stream);
+  }
   if (!refine) return n_quant > 0 ? composite_quantile_counting(last, stream) : composite_density_counting(last, stream);
   // the brackets of the last pass, then per step the last pass's network at the midpoints (K "samples" per ray, the same range word:
   // the guarded-fp16 policy covers these launches) and the bisection; the finish reads the records alone
@@ -313,6 +347,25 @@ extern "C" int dn_render_rays_depth_refined(const dn_mlp_desc* desc_coarse, cons
   return render_rays_depth_impl("dn_render_rays_depth_refined", desc_coarse, packed_coarse, desc_fine, packed_fine, precision, rays, ray_stride,
                                 n_rays, num_coarse, num_fine, lindisp, noise_std, d_m_thres, n_thres, t_rand, noise_c, u, noise_f, depth_c,
                                 acc_c, depth_f, acc_f, dex_f, nullptr, 0, 0, nullptr, workspace, stream, &refine);
+}
+
+extern "C" size_t dn_render_depth_layers_workspace_bytes(int64_t n_rays, int num_coarse, int num_fine, int n_thres, int n_layers) {
+  if (n_rays < 0 || num_coarse < 1 || num_fine < 0 || n_thres < 1 || n_layers < 1 || n_layers > DN_MAX_LAYERS ||
+      n_thres > DN_MAX_LAYER_RECORDS / (2 * n_layers) || n_rays > INT64_C(0x7fffffff) / (static_cast<int64_t>(n_thres) * 2 * n_layers))
+    return 0;
+  return carve(nullptr, n_rays, num_coarse, num_fine, kDepth, n_thres * 2 * n_layers, true).bytes;
+}
+
+extern "C" int dn_render_rays_depth_layers(const dn_mlp_desc* desc_coarse, const void* packed_coarse, const dn_mlp_desc* desc_fine,
+                                           const void* packed_fine, int precision, const float* rays, int ray_stride, int64_t n_rays,
+                                           int num_coarse, int num_fine, int lindisp, float noise_std, const float* d_m_thres, int n_thres,
+                                           const float* t_rand, const float* noise_c, const float* u, const float* noise_f, float* depth_c,
+                                           float* acc_c, float* depth_f, float* acc_f, float* dex_f, int n_layers, int refine_steps,
+                                           float* events, int* count, float* width, void* workspace, dn_stream_t stream) {
+  const LayersArgs layers{n_layers, refine_steps, events, count, width};
+  return render_rays_depth_impl("dn_render_rays_depth_layers", desc_coarse, packed_coarse, desc_fine, packed_fine, precision, rays, ray_stride,
+                                n_rays, num_coarse, num_fine, lindisp, noise_std, d_m_thres, n_thres, t_rand, noise_c, u, noise_f, depth_c,
+                                acc_c, depth_f, acc_f, dex_f, nullptr, 0, 0, nullptr, workspace, stream, nullptr, &layers);
 }
 
 extern "C" int dn_render_rays_depth(const dn_mlp_desc* desc_coarse, const void* packed_coarse, const dn_mlp_desc* desc_fine,

@@ -75,6 +75,14 @@ int composite_brackets_counting(const SigmaCompositeArgs& a, float* br, float* z
 int dex_bisect_launch(float* br, const float* rf_mid, const float* d_m_thres, int n_thres, int64_t n_rays, float* z_mid, dn_stream_t stream);
 int dex_refine_finish_launch(const float* br, const float* d_m_thres, int n_thres, int64_t n_rays, float* refined, float* width,
                              dn_stream_t stream);
+// the Dex depth layers (include/dexnerf_hip_layers.h; composite_layers.hip): the shape rule of n_thres / n_layers / n_rays under the
+// entry point's name, dn_composite_density_layers (a.noise is not read), the thresholds repeated 2 n_layers times each for
+// dex_bisect_launch on the records (N, K*2L), and dn_dex_layers_finish
+int layers_check(const char* who, int n_thres, int n_layers, int64_t n_rays);
+int composite_layers_counting(const SigmaCompositeArgs& a, int n_layers, float* br, float* z_mid, int* count, dn_stream_t stream);
+int layers_thresholds_launch(const float* d_m_thres, int n_thres, int n_layers, float* out, dn_stream_t stream);
+int dex_layers_finish_launch(const float* br, const float* d_m_thres, int n_thres, int n_layers, int interp, int64_t n_rays, float* events,
+                             float* width, dn_stream_t stream);
 // composite_quantile.hip: the quantile arguments' rule (`who`: the entry point, for messages) and dn_composite_density_quantiles
 int quantile_args_check(const char* who, const float* d_quantiles, int n_quant, int interp, const float* qdepth);
 int composite_quantile_counting(const SigmaCompositeArgs& a, dn_stream_t stream);

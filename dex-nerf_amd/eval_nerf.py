@@ -7,6 +7,8 @@ is written, and the maps go to dex_<view>.npz beside depth_<view>.png.  `--depth
 opacity-quantile depth maps (0.5: the median depth) to the same render and the same file (quantiles / qdepth), with or without --m-thres.
 `--depth-only --m-thres M --dex-refine R [--dex-refine-width]` adds the refined Dex depth maps (nerf.render_dex_depth(refine_steps=R): the first
 crossing bracketed between two samples, halved R times on the density network, interpolated) as dex_refined / dex_width in the same file.
+`--depth-only --m-thres M --dex-layers L [--dex-refine R] [--dex-refine-width]` adds the depth layers (nerf.render_dex_layers: every entry
+into and exit from the region above the threshold, the first L layers stored) as dex_events / dex_event_count (/ dex_event_width).
 `--depth-only --occupancy N[,N,N] [--occupancy-bounds x0 y0 z0 x1 y1 z1] [--occupancy-level L] [--occupancy-dilate D]` builds an
 occupancy grid of the two networks (nerf.OccupancyGrid.from_networks) and renders with the networks evaluated only on the samples in
 set cells; `--occupancy-check` renders every view both ways and reports, per threshold, the share of equal Dex depths.
@@ -88,6 +90,12 @@ def main(argv=None):
     ap.add_argument("--dex-refine-width", action="store_true",
                     help="--dex-refine: also the width of the last bracket per pixel (-1: no crossing, 0: crossing at the first sample); "
                          "saved as dex_width")
+    ap.add_argument("--dex-layers", type=int, default=None, metavar="L",
+                    help="--depth-only --m-thres: also the depth layers - every entry into and exit from the region above the threshold "
+                         "along each ray, the first L layers (1..8) stored (nerf.render_dex_layers, one more depth-only render per view); "
+                         "saved as dex_events (K,2L,H,W; +inf: no such event) and dex_event_count (K,H,W) beside dex; with --dex-refine R "
+                         "the events are refined like dex_refined, with --dex-refine-width dex_event_width is saved too; not with "
+                         "--depth-quantiles")
     ap.add_argument("--normals", action="store_true",
                     help="render surface normals only (nerf.render_dex_normals: the density gradient at the samples, composited like the "
                          "depth; with --m-thres also the normal at every Dex depth); not with --precision fp16")
@@ -151,8 +159,17 @@ def main(argv=None):
             ap.error("--dex-refine refines the Dex depth maps of --depth-only: it needs --depth-only and --m-thres > 0")
         if quantiles or args.occupancy:
             ap.error("--dex-refine is not supported together with --depth-quantiles or --occupancy")
-    elif args.dex_refine_width:
+    elif args.dex_refine_width and args.dex_layers is None:
         ap.error("--dex-refine-width belongs to --dex-refine")
+    if args.dex_layers is not None:
+        try:
+            _ops.check_layers(args.dex_layers, "--dex-layers")
+        except ValueError as e:
+            ap.error(str(e))
+        if not args.depth_only or args.m_thres <= 0:
+            ap.error("--dex-layers reads the layers of the Dex thresholds of --depth-only: it needs --depth-only and --m-thres > 0")
+        if quantiles:
+            ap.error("--dex-layers is not supported together with --depth-quantiles")
     if args.normals and args.precision == "fp16":
         ap.error("--normals differentiates the density network on the training kernels, which exist for fp32 and bf16: not with --precision fp16")
     if args.normals and (args.depth_only or args.apply_exposure):
@@ -359,8 +376,8 @@ def main(argv=None):
                 out = nerf.render_dex_depth(size, size, float(k_mat[0, 0]), coarse, fine, ro, rd, cfg, mode="validation",
                                             encode_position_fn=ex, encode_direction_fn=ed, m_thres_cand=thres,
                                             quantiles=quantiles or None, quantile_interp=args.quantile_interp, occupancy=grid,
-                                            cull_stats=grid is not None, refine_steps=args.dex_refine, refine_width=args.dex_refine_width,
-                                            **span_kw)
+                                            cull_stats=grid is not None, refine_steps=args.dex_refine,
+                                            refine_width=args.dex_refine_width and args.dex_refine is not None, **span_kw)
             torch.cuda.synchronize()
             times.append(time.perf_counter() - t0)
             if span_grid is not None:
@@ -379,7 +396,15 @@ def main(argv=None):
             refined_maps = width_maps = ()
             if args.dex_refine is not None:   # (never with quantiles: the maps behind the Dex maps are the refined ones, then the widths)
                 refined_maps, width_maps, q_maps = out[4 + n_dex:4 + 2 * n_dex], out[4 + 2 * n_dex:], ()
-            frames.append((None, depth, dex_maps) + ((q_maps,) if quantiles else ()) + ((refined_maps, width_maps) if refined_maps else ()))
+            dex_layers = None
+            if args.dex_layers is not None:   # (a render of its own, after the clock has stopped: the time per image is the depth render's)
+                with torch.no_grad():
+                    dex_layers = nerf.render_dex_layers(size, size, float(k_mat[0, 0]), coarse, fine, ro, rd, cfg, mode="validation",
+                                                        encode_position_fn=ex, encode_direction_fn=ed, m_thres_cand=thres,
+                                                        layers=args.dex_layers, refine_steps=args.dex_refine,
+                                                        want_width=args.dex_refine_width, occupancy=grid, **span_kw)
+            frames.append((None, depth, dex_maps) + ((q_maps,) if quantiles else ()) + ((refined_maps, width_maps) if refined_maps else ())
+                          + ((dex_layers,) if dex_layers is not None else ()))
             if args.savedir:   # the expected depth as a PNG, every map (depth + one Dex depth per threshold) as float32
                 from PIL import Image
                 d = depth.cpu().numpy()
@@ -394,6 +419,10 @@ def main(argv=None):
                     arrays.update(dex_refine_steps=np.int32(args.dex_refine), dex_refined=torch.stack(list(refined_maps)).cpu().numpy())
                 if width_maps:
                     arrays.update(dex_width=torch.stack(list(width_maps)).cpu().numpy())
+                if dex_layers is not None:
+                    arrays.update(dex_events=dex_layers.events.cpu().numpy(), dex_event_count=dex_layers.count.cpu().numpy())
+                    if dex_layers.width is not None:
+                        arrays.update(dex_event_width=dex_layers.width.cpu().numpy())
                 np.savez(os.path.join(args.savedir, f"dex_{i:04d}.npz"), **arrays)
             continue
         with torch.no_grad():

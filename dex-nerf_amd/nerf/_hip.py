@@ -91,6 +91,12 @@ MAX_REFINE_STEPS = 24               # DN_MAX_REFINE_STEPS
 # nerf.render_dex_depth(ray_span=...))
 SPAN_EXPORTS = ("dn_occupancy_ray_spans",)
 
+# include/dexnerf_hip_layers.h: Dex depth layers - every entry into and exit from {sigma > m} along a ray (nerf.render_dex_layers)
+LAYERS_EXPORTS = ("dn_composite_density_layers", "dn_dex_layers_finish", "dn_render_depth_layers_workspace_bytes",
+                  "dn_render_rays_depth_layers")
+MAX_LAYERS = 8                      # DN_MAX_LAYERS
+MAX_LAYER_RECORDS = 2048            # DN_MAX_LAYER_RECORDS
+
 
 class MlpDesc(ctypes.Structure):
     """dn_mlp_desc (mirrors FlexibleNeRFModel.__init__, reference nerf/models.py:186-196)."""
@@ -294,6 +300,15 @@ def _declare(lib):
     # the span header
     lib.dn_occupancy_ray_spans.argtypes = [fp, c_int, c_int64, vp, c_int, c_int, c_int] + [c_float] * 10 + [c_int, fp, vp, vp]
     lib.dn_occupancy_ray_spans.restype = c_int
+    # the layers header
+    lib.dn_composite_density_layers.argtypes = [fp, fp, fp, c_int, fp, c_int, c_int, c_int64, c_int, fp, fp, fp, fp, fp, vp, vp]
+    lib.dn_composite_density_layers.restype = c_int
+    lib.dn_dex_layers_finish.argtypes = [fp, fp, c_int, c_int, c_int, c_int64, fp, fp, vp]
+    lib.dn_dex_layers_finish.restype = c_int
+    lib.dn_render_depth_layers_workspace_bytes.argtypes = [c_int64, c_int, c_int, c_int, c_int]
+    lib.dn_render_depth_layers_workspace_bytes.restype = c_size_t
+    lib.dn_render_rays_depth_layers.argtypes = lib.dn_render_rays_depth.argtypes[:-2] + [c_int, c_int, fp, vp, fp, vp, vp]
+    lib.dn_render_rays_depth_layers.restype = c_int
 
 
 def lib():

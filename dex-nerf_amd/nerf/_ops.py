@@ -1423,6 +1423,84 @@ def render_rays_depth(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, n
     return maps + (qdepth,)
 
 
+# ---- Dex depth layers (include/dexnerf_hip_layers.h) --------------------------------------------------------------------------------
+def check_layers(layers, who="layers"):
+    """The host-side rule of the layer count: an int (not a bool) in 1 .. 8.  Raises ValueError before any GPU work."""
+    if isinstance(layers, bool) or not isinstance(layers, int) or not 1 <= layers <= _hip.MAX_LAYERS:
+        raise ValueError(f"{who}: the number of layers must be an int in 1 .. {_hip.MAX_LAYERS}, got {layers!r}")
+    return layers
+
+
+def _check_layer_records(who, n, k, layers):
+    if k * 2 * layers > _hip.MAX_LAYER_RECORDS:
+        raise ValueError(f"{who}: at most {_hip.MAX_LAYER_RECORDS} records per ray (thresholds * 2 layers), got {k} * {2 * layers}")
+    if n * k * 2 * layers > 2 ** 31 - 1:
+        raise ValueError(f"{who}: at most 2^31 - 1 records (rays * thresholds * 2 layers), got {n} * {k} * {2 * layers}")
+
+
+def composite_density_layers(rf, z, rd, m_thres, layers):
+    """dn_composite_density_layers: composite_density's (depth, acc, dex (K,N)) without noise, then br (N,K,2L,4) - the bracket records
+    (z_lo, z_hi, s_lo, s_hi) of the first 2L entries into / exits from {sigma > m} -, z_mid (N,K*2L), their first midpoints, and
+    count (K,N) int32, the number of events of every ray (include/dexnerf_hip_layers.h).  m_thres: a list or a device tensor of K >= 1
+    thresholds, each >= 0 (a list is checked here; a tensor is the caller's to validate)."""
+    check_layers(layers, "composite_density_layers")
+    if not torch.is_tensor(m_thres):
+        check_refine_thresholds(m_thres, "composite_density_layers")
+    c = _sigma_call(rf, z, rd, None, 0.0, m_thres)
+    if not c.k:
+        raise ValueError("composite_density_layers: the layers need at least one Dex threshold")
+    _check_layer_records("composite_density_layers", c.n, c.k, layers)
+    depth, acc = _pass_maps(c.dev, c.n)
+    dex, br, z_mid = _empty(c.dev, c.k, c.n), _empty(c.dev, c.n, c.k, 2 * layers, 4), _empty(c.dev, c.n, c.k * 2 * layers)
+    count = torch.empty((c.k, c.n), dtype=torch.int32, device=c.dev)
+    check(lib().dn_composite_density_layers(*c.head[:4], ptr(c.thres), c.k, layers, c.n, c.s, ptr(depth), ptr(acc), ptr(dex), ptr(br),
+                                            ptr(z_mid), ptr(count), stream()), "dn_composite_density_layers")
+    return depth, acc, dex, br, z_mid, count
+
+
+def dex_layers_finish(br, m_thres, interp, want_width=True):
+    """dn_dex_layers_finish: (events (K,2L,N), width (K,2L,N) | None) of the records br (N,K,2L,4).  interp False: the depth of the
+    sample at which the state changes; True: the linear interpolation of the bracket.  A missing event: depth +inf, width -1."""
+    br = f32c(br)
+    n, k, e = br.shape[0], br.shape[1], br.shape[2]
+    assert br.shape == (n, k, e, 4) and e % 2 == 0 and m_thres.numel() == k
+    events = _empty(br.device, k, e, n)
+    width = _empty(br.device, k, e, n) if want_width else None
+    check(lib().dn_dex_layers_finish(ptr(br), ptr(m_thres), k, e // 2, int(bool(interp)), n, ptr(events), ptr(width), stream()),
+          "dn_dex_layers_finish")
+    return events, width
+
+
+def render_rays_depth_layers(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, noise_std, m_thres, layers, refine_steps=None,
+                             want_width=False, draws=None):
+    """dn_render_rays_depth_layers: render_rays_depth's five maps for one ray chunk on density packs, then events (K,2L,N), count (K,N)
+    int32 and width (K,2L,N) | None - the depth layers of the last pass (include/dexnerf_hip_layers.h).  m_thres: a device tensor of
+    K >= 1 thresholds, each >= 0 (the caller validates them: check_refine_thresholds).  refine_steps None: sample mode - no network
+    launch beyond the render's; an int in 0 .. 24: interpolated mode after that many bisections on the last pass's density network.
+    noise_std must be 0.  The workspace is render_rays_depth's cached one: render_status_words reads this call's status block."""
+    check_layers(layers, "render_rays_depth_layers")
+    if refine_steps is not None:
+        check_refine_steps(refine_steps, "render_rays_depth_layers: refine_steps")
+    if float(noise_std) != 0.0:
+        raise ValueError("render_rays_depth_layers: the events are those of the raw density: noise_std must be 0")
+    if m_thres is None or not int(m_thres.numel()):
+        raise ValueError("render_rays_depth_layers: the layers need at least one Dex threshold")
+    c = _render_call(packed_c, packed_f, rays, num_fine, m_thres, draws)
+    n, dev = c.n, c.dev
+    _check_layer_records("render_rays_depth_layers", n, c.k, layers)
+    ws = _render_workspace(dev, _sized(lib().dn_render_depth_layers_workspace_bytes(n, num_coarse, c.nf, c.k, layers),
+                                       "dn_render_depth_layers_workspace_bytes"))
+    maps = _pass_maps(dev, n) + _pass_maps(dev, n, c.fine) + (_empty(dev, c.k, n),)
+    events = _empty(dev, c.k, 2 * layers, n)
+    count = torch.empty((c.k, n), dtype=torch.int32, device=dev)
+    width = _empty(dev, c.k, 2 * layers, n) if want_width else None
+    check(lib().dn_render_rays_depth_layers(
+        *c.net_args, packed_c.precision, ptr(c.rays), c.rays.shape[1], n, num_coarse, c.nf, int(bool(lindisp)), float(noise_std), ptr(m_thres),
+        c.k, *[ptr(d) for d in c.draws], *[ptr(m) for m in maps], layers, -1 if refine_steps is None else refine_steps, ptr(events),
+        ptr(count), ptr(width), ptr(ws), stream()), "dn_render_rays_depth_layers")
+    return maps + (events, count, width)
+
+
 # ---- density-gradient surface normals (include/dexnerf_hip_normals.h) ---------------------------------------------------------------
 class DensityGradStreams:
     """The backward-data and input-gradient streams of the DENSITY sub-network a PackedDensityMLP holds (dn_mlp_pack_backward /
@@ -2099,7 +2177,7 @@ def _culled_pass(rays, z, grid, evaluate, stats, index, columns="sigma", dirs=Fa
 
 
 def render_rays_depth_culled(packed_c, packed_f, rays, num_coarse, num_fine, lindisp, noise_std, m_thres, occupancy, draws=None, quantiles=None,
-                             interp=False, count_nonfinite=False):
+                             interp=False, count_nonfinite=False, layers=None, want_width=False):
     """render_rays_depth with the network evaluated only on the samples whose occupancy cell is set, as a chain of entry points on the
     current stream: dn_coarse_depths, dn_occupancy_compact_count, a host read of the kept count, dn_occupancy_compact_emit,
     dn_run_network on the kept points (explicit points, one sample per "ray"; skipped when nothing is kept), dn_occupancy_gather
@@ -2110,7 +2188,20 @@ def render_rays_depth_culled(packed_c, packed_f, rays, num_coarse, num_fine, lin
     Returns (render_rays_depth's maps, stats): stats = dict(kept=(coarse, fine), total=(coarse, fine), records=[the passes' device
     records]) - the fine entries 0 without a fine pass.  Two host reads per chunk (one per network pass: the kept count sizes the
     network launch) - the chain cannot be captured into a HIP graph.  The network runs in the packs' precision; an explicit-points
-    launch carries no fp16 range status, so the guarded-fp16 render policy does not apply here."""
+    launch carries no fp16 range status, so the guarded-fp16 render policy does not apply here.
+
+    layers: an int L in 1 .. 8 - the last dn_composite_density becomes dn_composite_density_layers followed by dn_dex_layers_finish in
+    sample mode, and the maps are followed by events (K,2L,N), count (K,N) int32 and width (K,2L,N) | None (want_width): a culled
+    sample's -FLT_MAX is "not above".  Needs thresholds >= 0 (the caller validates them) and noise_std 0; not together with quantiles.
+    None: the launches and the return are what they were."""
+    if layers is not None:
+        check_layers(layers, "render_rays_depth_culled: layers")
+        if quantiles is not None:
+            raise ValueError("render_rays_depth_culled: layers together with quantiles is not supported")
+        if float(noise_std) != 0.0:
+            raise ValueError("render_rays_depth_culled: the events are those of the raw density: noise_std must be 0")
+        if m_thres is None or not int(m_thres.numel()):
+            raise ValueError("render_rays_depth_culled: the layers need at least one Dex threshold")
     rays, fine, (_, noise_c, u, noise_f), rd, z, _ = _culled_call("render_rays_depth_culled", packed_c, packed_f, rays, num_coarse, num_fine,
                                                                    lindisp, draws)
     stats = _CullStats()
@@ -2119,7 +2210,11 @@ def render_rays_depth_culled(packed_c, packed_f, rays, num_coarse, num_fine, lin
         depth_c, acc_c, z = density_resample(rf, z, rd, num_fine, noise_c, noise_std, u)
         rf = _culled_pass(rays, z, occupancy, _network_rows(packed_f), stats, 1, count_nonfinite=count_nonfinite)
     noise = noise_f if fine else noise_c
-    if quantiles is None:
+    if layers is not None:
+        depth, acc, dex, br, _, count = composite_density_layers(rf, z, rd, m_thres, layers)
+        events, width = dex_layers_finish(br, m_thres, False, want_width)
+        last = (depth, acc, dex, events, count, width)
+    elif quantiles is None:
         last = composite_density(rf, z, rd, noise, noise_std, m_thres)
     else:
         if not 1 <= int(quantiles.numel()) <= _hip.MAX_QUANTILES or quantiles.dtype != torch.float32:

@@ -663,8 +663,106 @@ def render_dex_depth(height, width, focal_length, model_coarse, model_fine, ray_
     return _to_image(maps, [r.img_shape[:-1]] * len(maps)) if mode == "validation" else tuple(maps)
 
 
+# ---- Dex depth layers ----------------------------------------------------------------------------------------------------------------
+DexLayers = collections.namedtuple("DexLayers", "depth acc dex events count width")
+
+
+def render_dex_layers(height, width, focal_length, model_coarse, model_fine, ray_origins, ray_directions, options, mode="validation",
+                      encode_position_fn=None, encode_direction_fn=None, m_thres_cand=None, layers=1, refine_steps=None, want_width=False,
+                      ray_span=None, ray_span_pad=None, occupancy=None):
+    """The depth-only render (render_dex_depth: density sub-networks, no colour) with EVERY entry into and exit from the region
+    {sigma > m} along each ray, not the first entry alone (include/dexnerf_hip_layers.h): the back face and the wall thickness of a
+    glass, the second wall of a hollow object, a floater in front of the surface as a thin first layer.
+
+    Returns DexLayers(depth, acc, dex, events, count, width): depth, acc and dex (K, ...) are the last pass's maps - the fine pass's,
+    or the coarse one's without a fine pass - with render_dex_depth's bits; events (K, 2L, ...) the depths of the first 2L events of
+    every ray and threshold - events 0, 2, ... are entries, 1, 3, ... exits, +inf where the ray has no such event (a ray still inside
+    the region at its last sample has an open last layer: an entry without an exit); count (K, ...) int32 the number of events of the
+    ray, not capped at 2L; width (K, 2L, ...) with want_width=True, else None - the width of the bracket an event was read from, 0 for
+    an entry at the first sample, -1 where there is no event.  The maps are image-shaped in validation mode and flat in train mode.
+
+    refine_steps=None is the sample mode: an event's depth is that of the sample at which the state changes, as for the Dex depth -
+    where count > 0, events[:, 0] carries dex's bits.  refine_steps=R, an int in 0 .. 24, is the interpolated mode: every event's
+    bracket between two samples is halved R times on the last pass's density network (K*2L evaluations per ray and step) and
+    interpolated linearly - events[:, 0] then carries the bits of render_dex_depth(refine_steps=R)'s refined maps where count > 0.  As
+    there, a refined event is A crossing inside its sample bracket, and a layer thinner than the sample spacing can be stepped over.
+
+    Judged here, on the host, before any GPU work (ValueError): layers that is not an int in 1 .. 8, no thresholds, a negative or
+    non-finite threshold, more than 2048 records per ray (K * 2L), refine_steps that is not an int in 0 .. 24, a mode whose
+    radiance_field_noise_std is not 0 (the events are those of the raw density).  Follows nerf.set_render_policy like render_dex_depth;
+    no host read: a chunk can be captured into a HIP graph.  ray_span= / ray_span_pad=: render_dex_depth's.
+
+    occupancy: an nerf.OccupancyGrid - sample mode only: each chunk goes through the culled depth chain
+    (_ops.render_rays_depth_culled) with its last compositing launch replaced by the layers one; a culled sample's -FLT_MAX is "not
+    above".  With refine_steps= it is refused, for render_dex_depth's reason: a culled sample's -FLT_MAX is not a density to
+    interpolate with."""
+    who = "render_dex_layers"
+    span_pad = _check_ray_span(who, ray_span, ray_span_pad, [model_coarse, model_fine], ray_origins, ray_directions)
+    _ops.check_layers(layers, f"{who}: layers")
+    thres = _ops.check_refine_thresholds(m_thres_cand, who)
+    if len(thres) * 2 * layers > _ops._hip.MAX_LAYER_RECORDS:
+        raise ValueError(f"{who}: at most {_ops._hip.MAX_LAYER_RECORDS} records per ray (thresholds * 2 layers), got {len(thres)} * {2 * layers}")
+    if refine_steps is not None:
+        _ops.check_refine_steps(refine_steps, f"{who}: refine_steps")
+        if occupancy is not None:
+            raise ValueError(f"{who}: refine_steps together with occupancy= is not supported")
+    if float(getattr(options.nerf, mode).radiance_field_noise_std) != 0.0:
+        raise ValueError(f"{who}: the events are those of the raw density: the mode's radiance_field_noise_std must be 0")
+    if occupancy is not None:
+        culled_prec = _culled_precision(who)
+        occupancy.check_render(ray_directions.device, who)
+    r = _density_render_setup(who, "differentiable renders go through run_one_iter_of_nerf", height, width, focal_length, model_coarse,
+                              model_fine, ray_origins, ray_directions, options, mode, encode_position_fn, m_thres_cand, ray_span, span_pad)
+    chunksize = getattr(options.nerf, mode).chunksize
+    last = slice(2, 4) if r.fine else slice(0, 2)
+
+    def columns(maps):   # one chunk's (depth_c, acc_c, depth_f, acc_f, dex, events, count, width) -> rows to join: the ray axis first
+        dex, events, count, wd = maps[4:]
+        return list(maps[last]) + [dex.t(), events.permute(2, 0, 1), count.t()] + ([wd.permute(2, 0, 1)] if want_width else [])
+    if occupancy is not None:
+        packs = _density_packs(r, culled_prec)
+
+        def render_culled(batch):
+            draws = _draws(batch.shape[0], r.nc, r.nf, r.fine, r.perturb, r.std, r.dev)
+            return columns(_ops.render_rays_depth_culled(*packs, batch, r.nc, r.nf, r.lindisp, r.std, r.m_thres, occupancy, draws, layers=layers,
+                                                         want_width=want_width)[0])
+        cols = _join_chunks([render_culled(batch) for batch in get_minibatches(r.rays, chunksize=chunksize)])
+    else:
+        guard = _fp16_guard(r.models, density=True)
+        packs = {}   # precision code -> the density packs, as in render_dex_depth
+
+        def render_chunk(batch, status):
+            prec, guarded = guard if status is not None else (_ops._precision, False)
+            if prec not in packs:
+                packs[prec] = _density_packs(r, prec)
+            draws = _draws(batch.shape[0], r.nc, r.nf, r.fine, r.perturb, r.std, r.dev)
+            maps = _ops.render_rays_depth_layers(*packs[prec], batch, r.nc, r.nf, r.lindisp, r.std, r.m_thres, layers, refine_steps=refine_steps,
+                                                 want_width=want_width, draws=draws)
+            words = _ops.render_status_words()
+            if guarded:
+                status.append(words)
+            return columns(maps)
+        cols = _render_chunks(r.rays, chunksize, render_chunk)
+    depth, acc, dex, events, count = cols[:5]
+    shape = tuple(r.img_shape[:-1]) if mode == "validation" else (depth.shape[0],)
+    k = dex.shape[1]
+    return DexLayers(depth.reshape(shape), acc.reshape(shape), dex.t().reshape((k,) + shape),
+                     events.permute(1, 2, 0).reshape((k, 2 * layers) + shape), count.t().reshape((k,) + shape),
+                     cols[5].permute(1, 2, 0).reshape((k, 2 * layers) + shape) if want_width else None)
+
+
+def dex_thickness(layers_result, layer=0):
+    """exit - entry of layer `layer` of a DexLayers: (K, ...) like its dex maps; NaN where the ray has no such closed layer
+    (count < 2 * layer + 2) - an open last layer among them.  Plain torch: a convenience, not a hot path."""
+    events, count = layers_result.events, layers_result.count
+    if isinstance(layer, bool) or not isinstance(layer, int) or not 0 <= layer < events.shape[1] // 2:
+        raise ValueError(f"dex_thickness: layer must be an int in 0 .. {events.shape[1] // 2 - 1} (the layers stored), got {layer!r}")
+    closed = count >= 2 * layer + 2
+    return torch.where(closed, events[:, 2 * layer + 1] - events[:, 2 * layer], torch.full_like(events[:, 0], float("nan")))
+
+
 # ---- density-gradient surface normals ------------------------------------------------------------------------------------------------
-DexNormals = collections.namedtuple("DexNormals", "depth acc normal dex_depth dex_normal")
+DexNormals =collections.namedtuple("DexNormals", "depth acc normal dex_depth dex_normal")
 
 
 def _normals_precision(who):
