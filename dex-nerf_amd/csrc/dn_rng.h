@@ -15,7 +15,8 @@
 
 namespace dn {
 
-enum : uint32_t { kRngStreamJitter = 0, kRngStreamNoiseCoarse = 1, kRngStreamU = 2, kRngStreamNoiseFine = 3, kRngStreamPixels = 4, kRngStreamView = 5 };
+enum : uint32_t { kRngStreamJitter = 0, kRngStreamNoiseCoarse = 1, kRngStreamU = 2, kRngStreamNoiseFine = 3, kRngStreamPixels = 4, kRngStreamView = 5,
+                  kRngStreamCell = 6 };   // the cell points of a live occupancy grid, drawn from the grid's own record (occupancy_live.hip)
 
 struct RngRef {
   const uint32_t* state;   // device record {seed_lo, seed_hi, cur, nxt}, or NULL: no in-kernel draws

@@ -17,6 +17,7 @@
 // No workgroup waits on another, no atomics, plain vector stores: the output is a function of the input.  Memory: the sample kernels
 // touch about 40 B per sample (z twice, slot written twice and read three times, 12 B per kept point, one 16-byte line share of rf).
 #include "../../include/dexnerf_hip_cull.h"
+#include "occupancy_grid.h"
 #include "scan_blocks.h"
 
 namespace dn {
@@ -28,11 +29,6 @@ constexpr int64_t kMaxCells = DN_OCC_MAX_CELLS;
 constexpr int64_t kMaxSamples = DN_OCC_MAX_SAMPLES;
 static_assert(kMaxSamples <= static_cast<int64_t>(kScanElems) * kScanElems * kScanElems && kMaxSamples < (int64_t{1} << 31), "limits");
 static_assert(DN_OCC_MAX_AXIS_CELLS <= (1 << 24), "(float)cells must be exact");
-
-struct Cells {
-  int cx, cy, cz;
-  int64_t n;   // cx * cy * cz
-};
 
 __device__ __forceinline__ bool hot(float x, float level) {
   const bool finite = (__builtin_bit_cast(unsigned, x) & 0x7F800000u) != 0x7F800000u;
@@ -272,6 +268,11 @@ bool cells_of(int cx, int cy, int cz, Cells& g) {
 int64_t words_of(const Cells& g) { return (g.n + 31) / 32; }
 unsigned blocks_for(int64_t n, int per_block) { return static_cast<unsigned>((n + per_block - 1) / per_block); }
 
+void launch_dilate(const unsigned* raw, const Cells& g, int d, int accumulate, unsigned* out, hipStream_t s) {
+  const int64_t n_words = words_of(g);
+  hipLaunchKernelGGL(dilate_kernel, dim3(blocks_for(n_words, kThreads)), dim3(kThreads), 0, s, raw, g, d, accumulate, n_words, out);
+}
+
 struct Layout {
   int64_t n;              // P
   unsigned n0, n1;        // totals at scan level 0 and 1
@@ -401,7 +402,7 @@ extern "C" int dn_occupancy_build(const float* field, int field_stride, int cx, 
     hipLaunchKernelGGL(raw_bits_kernel, dim3(blocks), dim3(kThreads), 0, s, field, static_cast<int64_t>(field_stride), g, level, acc, n_words, bits);
   } else {
     hipLaunchKernelGGL(raw_bits_kernel, dim3(blocks), dim3(kThreads), 0, s, field, static_cast<int64_t>(field_stride), g, level, 0, n_words, scratch);
-    hipLaunchKernelGGL(dilate_kernel, dim3(blocks), dim3(kThreads), 0, s, scratch, g, dilate, acc, n_words, bits);
+    launch_dilate(scratch, g, dilate, acc, bits, s);
   }
   return check_launch("dn_occupancy_build");
 }

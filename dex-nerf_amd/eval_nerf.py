@@ -123,10 +123,11 @@ def main(argv=None):
                     help="--occupancy: render every view with and without the grid (both in the configured precision) and print, per "
                          "threshold, the share of pixels with equal Dex depth and the largest depth difference - how to find the cells and "
                          "the dilation a scene needs")
-    ap.add_argument("--ray-span", default="", metavar="N[,N,N]",
+    ap.add_argument("--ray-span", default="", metavar="N[,N,N] | checkpoint",
                     help="tighten every ray's near / far to the occupied span of an occupancy grid of this many cells per axis before the "
                          "render (ray_span= of render_dex_depth, render_dex_normals and run_one_iter_of_nerf); shares --occupancy-bounds / "
-                         "-level / -dilate, and the grid itself when --occupancy names the same cells")
+                         "-level / -dilate, and the grid itself when --occupancy names the same cells.  `checkpoint`: the grid stored in the "
+                         "checkpoint by train_dexnerf.py --train-occupancy instead of one built here")
     ap.add_argument("--ray-span-pad", type=float, default=None, metavar="P",
                     help="--ray-span: widen each span by P cells of travel at both ends (default 1)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"])
@@ -217,7 +218,12 @@ def main(argv=None):
     if args.ray_span:
         if args.mesh:
             ap.error("--ray-span tightens the rays of a render: not with --mesh")
-        span_cells = grid_cells("--ray-span", args.ray_span)
+        if args.ray_span == "checkpoint":      # the grid train_dexnerf.py --train-occupancy kept beside the networks and stored with them
+            if args.occupancy_bounds is not None or args.occupancy_level != 0.0 or args.occupancy_dilate != 1:
+                ap.error("--ray-span checkpoint uses the stored grid as it is: --occupancy-bounds / -level / -dilate belong to a grid built here")
+            span_cells = "checkpoint"
+        else:
+            span_cells = grid_cells("--ray-span", args.ray_span)
         try:
             _ops.check_ray_span_pad(1.0 if args.ray_span_pad is None else args.ray_span_pad, "--ray-span-pad")
         except ValueError as e:
@@ -327,7 +333,15 @@ def main(argv=None):
         if args.occupancy_check and args.precision == "bf16":
             nerf.set_render_policy("bf16")      # the culled render runs in bf16: compare it with a bf16 full render, not the guarded fp16 one
     if span_cells:
-        span_grid = grid if span_cells == occ_cells else build_grid(span_cells, "ray-span")
+        if span_cells == "checkpoint":
+            if ck.get("train_occupancy") is None:
+                ap.error("--ray-span checkpoint: the checkpoint carries no occupancy grid (train_dexnerf.py --train-occupancy writes one)")
+            span_grid = nerf.LiveOccupancyGrid.from_state_dict(ck["train_occupancy"], dev).grid
+            if not args.quiet:
+                print(f"ray-span grid {'x'.join(str(c) for c in span_grid.cells)} over {[round(float(b), 4) for b in span_grid.bounds]} from the "
+                      f"checkpoint: {100 * span_grid.occupied_fraction():.2f} % of the cells set", flush=True)
+        else:
+            span_grid = grid if span_cells == occ_cells else build_grid(span_cells, "ray-span")
         span_kw = dict(ray_span=span_grid, ray_span_pad=args.ray_span_pad)
 
     def report_spans(view, ro, rd):

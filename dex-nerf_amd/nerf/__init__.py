@@ -17,7 +17,7 @@ from .models import *  # noqa: F401,F403
 from .nerf_helpers import *  # noqa: F401,F403
 from .train_utils import *  # noqa: F401,F403
 from .volume_rendering_utils import *  # noqa: F401,F403
-from .occupancy import OccupancyGrid  # noqa: F401
+from .occupancy import LiveOccupancyGrid, OccupancyGrid  # noqa: F401
 from .pose import FusedJointStep, FusedPoseStep, MultiPoseRefiner, PoseRefiner, se3_exp  # noqa: F401
 
 

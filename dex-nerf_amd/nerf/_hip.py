@@ -97,6 +97,11 @@ LAYERS_EXPORTS = ("dn_composite_density_layers", "dn_dex_layers_finish", "dn_ren
 MAX_LAYERS = 8                      # DN_MAX_LAYERS
 MAX_LAYER_RECORDS = 2048            # DN_MAX_LAYER_RECORDS
 
+# include/dexnerf_hip_live.h: an occupancy grid refreshed on the device while the networks train (nerf.LiveOccupancyGrid,
+# nerf.FusedTrainStep(ray_span=...))
+LIVE_EXPORTS = ("dn_occupancy_cell_points", "dn_occupancy_ema_workspace_bytes", "dn_occupancy_ema_update")
+RNG_STREAM_CELL = 6                 # kRngStreamCell (csrc/dn_rng.h)
+
 
 class MlpDesc(ctypes.Structure):
     """dn_mlp_desc (mirrors FlexibleNeRFModel.__init__, reference nerf/models.py:186-196)."""
@@ -309,6 +314,13 @@ def _declare(lib):
     lib.dn_render_depth_layers_workspace_bytes.restype = c_size_t
     lib.dn_render_rays_depth_layers.argtypes = lib.dn_render_rays_depth.argtypes[:-2] + [c_int, c_int, fp, vp, fp, vp, vp]
     lib.dn_render_rays_depth_layers.restype = c_int
+    # the live-grid header
+    lib.dn_occupancy_cell_points.argtypes = [c_int, c_int, c_int] + [c_float] * 6 + [c_int64, c_int64, vp, fp, vp]
+    lib.dn_occupancy_cell_points.restype = c_int
+    lib.dn_occupancy_ema_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
+    lib.dn_occupancy_ema_workspace_bytes.restype = c_size_t
+    lib.dn_occupancy_ema_update.argtypes = [fp, c_int, fp, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_int, fp, vp, vp, vp, vp]
+    lib.dn_occupancy_ema_update.restype = c_int
 
 
 def lib():

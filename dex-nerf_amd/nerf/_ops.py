@@ -2111,6 +2111,79 @@ def tighten_ray_rows(rays, grid, pad):
     return rays
 
 
+# ---- an occupancy grid refreshed while the networks train (include/dexnerf_hip_live.h) --------------------------------------------------
+def check_live_occupancy(level, decay, dilate, who="LiveOccupancyGrid"):
+    """The host-side rule of a live grid's settings: level finite as fp32 and >= 0, decay in (0, 1] as fp32, dilate 0 .. 8 ->
+    (level, decay) as the Python floats of their fp32 values and dilate as an int.  Raises ValueError before any GPU work."""
+    try:
+        level, decay, dilate = float(level), float(decay), int(dilate)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: level and decay are numbers and dilate an integer, got {level!r}, {decay!r}, {dilate!r}") from None
+    if not (math.isfinite(level) and level >= 0.0 and math.isfinite(ctypes.c_float(level).value)):
+        raise ValueError(f"{who}: level must be finite as fp32 and >= 0, got {level!r}")
+    d32 = ctypes.c_float(decay).value if math.isfinite(decay) else decay
+    if not 0.0 < d32 <= 1.0:
+        raise ValueError(f"{who}: decay must be in (0, 1] as fp32, got {decay!r}")
+    if not 0 <= dilate <= _hip.OCC_MAX_DILATE:
+        raise ValueError(f"{who}: dilate must be 0 .. {_hip.OCC_MAX_DILATE}, got {dilate}")
+    return ctypes.c_float(level).value, d32, dilate
+
+
+def occupancy_cell_sizes(bounds, cells):
+    """h_a = (b1_a - b0_a) / cells_a of a checked grid: formed in float64 from the fp32 bounds and rounded to fp32 once."""
+    h = tuple(ctypes.c_float((bounds[a + 3] - bounds[a]) / cells[a]).value for a in range(3))
+    if not all(math.isfinite(v) and v > 0.0 for v in h):
+        raise ValueError(f"occupancy: (b1 - b0) / cells must be finite and > 0 as fp32, got {h}")
+    return h
+
+
+def occupancy_cell_points(bounds, cells, sizes, c0, n, rng_state, pts=None):
+    """dn_occupancy_cell_points: the jittered points of the cells c0 .. c0 + n - 1 -> pts (n,3) fp32, drawn from the grid's own record
+    `rng_state` (int32 x 4 on the device); the call with c0 == 0 draws from the record's next iteration and makes it the current one."""
+    if not (torch.is_tensor(rng_state) and rng_state.dtype == torch.int32 and rng_state.numel() == 4):
+        raise ValueError("occupancy_cell_points: the rng record is an int32 tensor of 4 words")
+    if not rng_state.is_cuda:
+        raise RuntimeError("occupancy_cell_points: runs on the ROCm device only (got a host tensor); move the record to 'cuda'")
+    c0, n = int(c0), int(n)
+    if pts is None:
+        pts = torch.empty((max(n, 0), 3), dtype=torch.float32, device=rng_state.device)
+    assert pts.dtype == torch.float32 and pts.is_contiguous() and pts.shape == (n, 3) and pts.device == rng_state.device
+    check(lib().dn_occupancy_cell_points(*cells, *bounds[:3], *sizes, c0, n, ptr(rng_state), ptr(pts), stream()), "dn_occupancy_cell_points")
+    return pts
+
+
+def occupancy_ema_workspace_words(cells, dilate):
+    return int(lib().dn_occupancy_ema_workspace_bytes(*cells, int(dilate))) // 4
+
+
+def occupancy_ema_update(columns, cells, decay, level, write_bits, dilate, ema, bits, scratch, rng_state):
+    """dn_occupancy_ema_update: ema[c] = max(ema[c] * decay, the larger of the columns at c) - a cell with a non-finite value only
+    decays and is set -, and with write_bits the grid's bits = dilate(non-finite || ema > level), in place.  columns: one or two 1-D
+    fp32 device views of one value per cell, read in place at their stride (rows[:, 3] of dn_run_network's output)."""
+    n = int(cells[0]) * int(cells[1]) * int(cells[2])
+    if not 1 <= len(columns) <= 2:
+        raise ValueError(f"occupancy_ema_update: one or two density columns, got {len(columns)}")
+    args = []
+    for t in columns:
+        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 1 and t.numel() == n):
+            raise ValueError(f"occupancy_ema_update: a density column is a 1-D fp32 tensor of {n} values, one per cell")
+        if not t.is_cuda:
+            raise RuntimeError("occupancy_ema_update: runs on the ROCm device only (got a host tensor); move the densities to 'cuda'")
+        stride = int(t.stride(0)) if n > 1 else 1
+        if not 1 <= stride < 2 ** 31:
+            raise ValueError(f"occupancy_ema_update: a density column needs a stride of 1 .. 2^31 - 1 floats, got {stride}")
+        args += [c_void_p(t.data_ptr()), stride]
+    if len(columns) == 1:
+        args += [None, 0]
+    dev = columns[0].device
+    assert ema.dtype == torch.float32 and ema.is_contiguous() and ema.numel() == n and ema.device == dev
+    assert bits.dtype == torch.int32 and bits.is_contiguous() and bits.numel() == occupancy_words(cells) and bits.device == dev
+    assert scratch is None or (scratch.dtype == torch.int32 and scratch.numel() >= bits.numel() and scratch.device == dev)
+    assert rng_state.dtype == torch.int32 and rng_state.numel() == 4 and rng_state.device == dev
+    check(lib().dn_occupancy_ema_update(*args, *cells, decay, level, int(bool(write_bits)), int(dilate), ptr(ema), ptr(bits), ptr(scratch),
+                                        ptr(rng_state), stream()), "dn_occupancy_ema_update")
+
+
 # ---- the culled renders: depth, colour and normals over one pass ------------------------------------------------------------------------
 class _CullStats:
     """What the passes of a culled driver report into: the kept and the total samples of pass 0 (coarse) and 1 (fine) - 0 for a pass

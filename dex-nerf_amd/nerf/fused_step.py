@@ -26,6 +26,10 @@ encoding_anneal (nerf.EncodingAnneal) given: three launches more on one rank in 
 ahead of everything, dn_encoding_anneal_scale_weights_pair ahead of the pack, dn_encoding_anneal_scale_grads_pair behind the backward
 (the per-network packs and the two halves of a data-parallel step: one dn_encoding_anneal_scale_weights / _scale_grads per network).
 
+ray_span (an nerf.OccupancyGrid or an nerf.LiveOccupancyGrid) given: one launch more, dn_occupancy_ray_spans right after the draw - every
+row's near / far tightened to its occupied span of the grid -, and with a live grid its refresh (LiveOccupancyGrid.update) before every
+occupancy_update_every-th iteration, outside the replayed graph (refresh_occupancy(), called by GraphedTrainStep.step).
+
 Per-view exposure rows (refine_exposure=, dn_render_loss_exposure) belong to the steps that own the cameras, nerf.FusedPoseStep /
 nerf.FusedJointStep; this step trains on fixed cameras and has none.
 
@@ -39,13 +43,15 @@ import torch
 from . import _ops
 from ._train import train_fused_ok
 from .loss import distortion_weight_settings, fused_loss_head, loss_head_settings
+from .occupancy import LiveOccupancyGrid, OccupancyGrid
 from .train_utils import _fusable
 
 
 class FusedTrainStep:
     def __init__(self, model_coarse, model_fine, selector, options, bucket, encode_position_fn, encode_direction_fn, num_rays, seed=0,
                  luminance=False, first_iteration=0, draw_view=False, ndc_focal=None, depth_images=None, loss_weights=(1.0, 1.0),
-                 depth_weights=(0.0, 0.0), depth_range=(0.0, float("inf")), distortion_weights=(0.0, 0.0), encoding_anneal=None):
+                 depth_weights=(0.0, 0.0), depth_range=(0.0, float("inf")), distortion_weights=(0.0, 0.0), encoding_anneal=None,
+                 ray_span=None, ray_span_pad=1.0, occupancy_update_every=16):
         if not (isinstance(draw_view, bool) or draw_view == "rays"):
             raise ValueError(f"FusedTrainStep: draw_view must be False, True or \"rays\" (got {draw_view!r})")
         # the distortion regulariser of each network's sample weights (dn_render_rays_backward_reg); (0, 0): the backward as ever
@@ -74,6 +80,25 @@ class FusedTrainStep:
         if not self.applicable(model_coarse, model_fine, options, encode_position_fn, encode_direction_fn, num_rays, ndc_focal):
             raise ValueError("FusedTrainStep: configuration outside the fused training kernels (see FusedTrainStep.applicable)")
         dev = next(model_coarse.parameters()).device
+        # ray_span: an nerf.OccupancyGrid, or an nerf.LiveOccupancyGrid that refresh_occupancy() keeps up to date - every drawn row's
+        # near / far is tightened to its occupied span right after the draw (dn_occupancy_ray_spans: one launch, no host read).  The rows
+        # are in the networks' input space there - NDC space with ndc_focal -, which is where a grid lives.  None: the launches as ever
+        self.live = ray_span if isinstance(ray_span, LiveOccupancyGrid) else None
+        self.span_grid = ray_span.grid if self.live is not None else ray_span
+        self.span_pad = None
+        self.update_every = int(occupancy_update_every)
+        if ray_span is not None:
+            if not isinstance(self.span_grid, OccupancyGrid):
+                raise ValueError(f"FusedTrainStep: ray_span is an nerf.OccupancyGrid or an nerf.LiveOccupancyGrid, got {type(ray_span).__name__}")
+            self.span_pad = _ops.check_ray_span_pad(ray_span_pad, "FusedTrainStep: ray_span_pad")
+            if self.update_every < 1:
+                raise ValueError(f"FusedTrainStep: occupancy_update_every must be >= 1, got {occupancy_update_every}")
+            self.span_grid.check_render(dev, "FusedTrainStep")
+            if self.live is not None and encoding_anneal is not None:
+                raise ValueError("FusedTrainStep: a LiveOccupancyGrid reads the networks' density without the encoding anneal's band "
+                                 "amplitudes; give one of the two")
+        self.encode_position_fn = encode_position_fn
+        self.iteration = int(first_iteration)      # host side: the iteration the next refresh_occupancy() stands before
         self.rng_state = _ops.new_rng_state(seed, dev, first_iteration)
         # [mean L_ray coarse, mean L_ray fine] of the latest step (a network with weight 0: 0); None without the regulariser.  Not part
         # of loss3 / loss6, which keep their meaning: the step minimises loss3[0] + w_c reg2[0] + w_f reg2[1]
@@ -137,6 +162,8 @@ class FusedTrainStep:
         rays, target, *drawn = draw(sel.height, sel.width, sel.cams, *view, sel.near, sel.far, self.rng_state, self.num_rays, sel.images,
                                     want_pixels=gather, ndc_focal=self.ndc_focal, ndc_near=1.0)
         pix, views = (drawn + [None, None])[:2]
+        if self.span_grid is not None:
+            _ops.tighten_ray_rows(rays, self.span_grid, self.span_pad)
         pc, pf, prec = _ops.pack_train_pair(mc, mf, self.logs)
         maps, saved = _ops.render_rays_train(pc, pf, rays, self.nc, self.nf, self.lindisp, self.noise_std, self.white, [], None, prec=prec,
                                              rng_state=self.rng_state, perturb=self.perturb)
@@ -161,6 +188,14 @@ class FusedTrainStep:
         self._keep[0].append(_ops.render_rays_backward(pc, pf, saved, g_c, (None, None, None), views_c, views_f, nets=1, reg=self._reg))
         if self.anneal is not None:
             self.anneal.scale_grads(self.models[0], views_c)
+
+    def refresh_occupancy(self):
+        """Call once before every iteration (GraphedTrainStep.step does): with a LiveOccupancyGrid, refreshes it from both networks'
+        density before iteration i whenever i % occupancy_update_every == 0, i counted on the host from first_iteration.  Ordinary
+        launches on the current stream, never part of a captured step: eager and replayed loops refresh at the same iterations."""
+        if self.live is not None and self.iteration % self.update_every == 0:
+            self.live.update(list(self.models), self.encode_position_fn)
+        self.iteration += 1
 
     def latest_draw(self):
         """(view_index (N) int32 | None, pixel_index (N) int64 | None, rows, target) of the latest step - the pairs only with
@@ -247,6 +282,7 @@ class GraphedTrainStep:
 
     def step(self):
         """One training iteration.  The loss of the iteration is in self.fused.loss3 (device)."""
+        self.fused.refresh_occupancy()      # outside every graph: where _eager and _replay both pass through
         if self.graphs is not None:
             return self._replay()
         if self.eager_left > 0 or not self.use_graphs:

@@ -1,11 +1,12 @@
 """nerf.OccupancyGrid: a bit per cell of a box in the network's input space - set where the density field may exceed a level - that
 nerf.render_dex_depth(occupancy=...) uses to evaluate the density networks only on the ray samples that fall into set cells
-(include/dexnerf_hip_occupancy.h has the definition of the bits and of a sample's cell)."""
+(include/dexnerf_hip_occupancy.h has the definition of the bits and of a sample's cell), and nerf.LiveOccupancyGrid: such a grid kept
+up to date on the device beside networks that are still training (include/dexnerf_hip_live.h)."""
 import numpy as np
 import torch
 
 from . import _hip, _ops
-from .train_utils import density_grid
+from .train_utils import _density_pack, density_grid
 
 
 class OccupancyGrid:
@@ -101,3 +102,123 @@ class OccupancyGrid:
         """The refusals of a render with this grid, before any GPU work."""
         if self.bits.device != device:
             raise ValueError(f"{who}: the occupancy grid lives on {self.bits.device} and the rays on {device}; move it with grid.to(device)")
+
+
+class LiveOccupancyGrid:
+    """An occupancy grid that lives beside networks while they train (include/dexnerf_hip_live.h has the definition): `ema`, one fp32
+    per cell, is a decayed running maximum of the raw density the networks give at one jittered point of the cell per refresh, and the
+    cell's bit is set while that exceeds `level` (strict, fp32: the Dex comparison) or the density there was not finite, dilated by
+    `dilate` cells.  nerf.FusedTrainStep(ray_span=live) refreshes it every occupancy_update_every iterations and tightens every training
+    ray's near / far to its occupied span (OccupancyGrid.ray_spans).
+
+    The bits start ALL SET and the first `warmup_updates` refreshes only feed `ema`: until then the grid tightens nothing.  `bits` is
+    allocated once and only ever written in place, so a captured HIP graph that reads it sees every refresh.  The points are drawn from
+    the grid's own rng record (seed, refreshes so far) - not the training step's -, so every rank of a data-parallel run refreshes the
+    same bits from the same weights, and a grid resumed from state_dict() continues with the same draws.
+
+    What it does not promise: one point per cell and refresh is a sample, and the networks' density early in training is not the
+    scene's - a level or a warm-up that is too eager clears cells the scene occupies, and rays through them then get no samples there
+    (a missed ray keeps its whole [near, far])."""
+
+    def __init__(self, bounds, cells, device, level=0.01, decay=0.95, dilate=1, warmup_updates=4, seed=0):
+        b, c, _ = _ops.check_occupancy_grid(bounds, cells, "LiveOccupancyGrid")
+        self.level, self.decay, self.dilate = _ops.check_live_occupancy(level, decay, dilate, "LiveOccupancyGrid")
+        self.sizes = _ops.occupancy_cell_sizes(b, c)
+        self.warmup_updates, self.seed = int(warmup_updates), int(seed)
+        if self.warmup_updates < 0:
+            raise ValueError(f"LiveOccupancyGrid: warmup_updates must be >= 0, got {warmup_updates}")
+        device = torch.device(device)
+        n = c[0] * c[1] * c[2]
+        n_words = _ops.occupancy_words(c)
+        words = np.full(n_words, 0xFFFFFFFF, np.uint32)
+        if n % 32:
+            words[-1] = (1 << (n % 32)) - 1          # the bits past the last cell are 0, as in every grid
+        self._grid = OccupancyGrid(torch.from_numpy(words.view(np.int32).copy()).to(device), b, c)
+        self.ema = torch.zeros(n, dtype=torch.float32, device=device)
+        self.scratch = torch.zeros(n_words, dtype=torch.int32, device=device) if self.dilate > 0 else None
+        self.rng_state = _ops.new_rng_state(self.seed, device)
+        self.updates_done = 0                         # host side: refreshes so far
+
+    @property
+    def grid(self):
+        """The OccupancyGrid of the bits - the same object and the same tensor for the life of this grid."""
+        return self._grid
+
+    @property
+    def bits(self):
+        return self._grid.bits
+
+    @property
+    def bounds(self):
+        return self._grid.bounds
+
+    @property
+    def cells(self):
+        return self._grid.cells
+
+    @property
+    def device(self):
+        return self._grid.bits.device
+
+    def update(self, models, encode_position_fn, max_points=1 << 22):
+        """One refresh: the cell points (dn_occupancy_cell_points, in slabs of at most max_points cells), the raw density of each
+        model's density pack on them (_ops.run_network_pts: no-grad, nerf.set_precision's 'fp32' or bf16, 'fp16' raises - density_grid's
+        guards), and dn_occupancy_ema_update, which writes the bits once `warmup_updates` refreshes have gone before.  No host read;
+        ordinary launches on the current stream - legal between two replays of a captured step, not inside a capture of one that
+        is to refresh more than once (the warm-up is counted on the host)."""
+        models = [m for m in (models if isinstance(models, (list, tuple)) else [models]) if m is not None]
+        if not 1 <= len(models) <= 2:
+            raise ValueError(f"LiveOccupancyGrid.update: one or two density networks, got {len(models)}")
+        max_points = int(max_points)
+        if max_points < 1:
+            raise ValueError("LiveOccupancyGrid.update: max_points must be at least 1")
+        with torch.no_grad():
+            packs = [_density_pack(m, encode_position_fn, "LiveOccupancyGrid.update") for m in models]
+        dev = self.device
+        if not dev.type == "cuda":
+            raise RuntimeError("LiveOccupancyGrid.update: runs on the ROCm device only (the grid lives on the host); build it with device='cuda'")
+        for m in models:
+            if m.layer1.weight.device != dev:
+                raise ValueError(f"LiveOccupancyGrid.update: the grid lives on {dev} and a network on {m.layer1.weight.device}")
+        g = self._grid
+        n = self.ema.numel()
+        with torch.no_grad():
+            if n <= max_points:
+                pts = _ops.occupancy_cell_points(g.bounds, g.cells, self.sizes, 0, n, self.rng_state)
+                columns = [_ops.run_network_pts(pack, pts, None, 1)[:, 3] for pack in packs]
+            else:
+                sigma = torch.empty((len(packs), n), dtype=torch.float32, device=dev)
+                for c0 in range(0, n, max_points):
+                    count = min(max_points, n - c0)
+                    pts = _ops.occupancy_cell_points(g.bounds, g.cells, self.sizes, c0, count, self.rng_state)
+                    for q, pack in enumerate(packs):
+                        sigma[q, c0:c0 + count] = _ops.run_network_pts(pack, pts, None, 1)[:, 3]
+                columns = [sigma[q] for q in range(len(packs))]
+            _ops.occupancy_ema_update(columns, g.cells, self.decay, self.level, self.updates_done >= self.warmup_updates, self.dilate,
+                                      self.ema, g.bits, self.scratch, self.rng_state)
+        self.updates_done += 1
+
+    def occupied_fraction(self):
+        """Set cells / cells (a host read)."""
+        return self._grid.occupied_fraction()
+
+    def state_dict(self):
+        """ema, bits, bounds, cells, the settings, the rng record and the refresh counter, on the host."""
+        return dict(ema=self.ema.detach().cpu(), bits=self._grid.bits.detach().cpu(), bounds=tuple(self.bounds), cells=tuple(self.cells),
+                    level=self.level, decay=self.decay, dilate=self.dilate, warmup_updates=self.warmup_updates, seed=self.seed,
+                    rng_state=self.rng_state.detach().cpu(), updates_done=int(self.updates_done))
+
+    @classmethod
+    def from_state_dict(cls, state, device=None):
+        """The grid `state` was taken from: the next update() draws what the original's next update() draws."""
+        ema = torch.as_tensor(state["ema"], dtype=torch.float32)
+        live = cls(state["bounds"], state["cells"], ema.device if device is None else device, level=state["level"], decay=state["decay"],
+                   dilate=state["dilate"], warmup_updates=state["warmup_updates"], seed=state["seed"])
+        bits, rng = torch.as_tensor(state["bits"], dtype=torch.int32), torch.as_tensor(state["rng_state"], dtype=torch.int32)
+        if ema.shape != live.ema.shape or bits.shape != live.bits.shape or rng.shape != live.rng_state.shape:
+            raise ValueError(f"LiveOccupancyGrid.from_state_dict: ema, bits and the rng record do not fit cells {live.cells}")
+        live.ema.copy_(ema); live.bits.copy_(bits); live.rng_state.copy_(rng)
+        live.updates_done = int(state["updates_done"])
+        if live.updates_done < 0:
+            raise ValueError("LiveOccupancyGrid.from_state_dict: a negative refresh counter")
+        return live

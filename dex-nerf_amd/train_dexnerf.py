@@ -285,6 +285,22 @@ def build_parser():
                          "between iterations START and END (nerf.EncodingAnneal on the fused steps; with and without --refine-poses). The "
                          "checkpoint stores the schedule; --load-checkpoint resumes it")
     ap.add_argument("--anneal-xyz-only", action="store_true", help="--anneal-encoding: leave the view-direction encoding un-annealed")
+    ap.add_argument("--train-occupancy", type=int, default=None, metavar="CELLS",
+                    help="keep an occupancy grid of CELLS^3 cells live beside the networks (nerf.LiveOccupancyGrid: a decayed running maximum "
+                         "of their density at one jittered point per cell, refreshed on the device) and tighten every training ray's near / "
+                         "far to its occupied span (nerf.FusedTrainStep(ray_span=...)).  The checkpoint stores the grid (train_occupancy); "
+                         "--load-checkpoint resumes it and eval_nerf.py --ray-span checkpoint renders with it")
+    ap.add_argument("--occupancy-bounds", type=float, nargs=6, default=None, metavar=("x0", "y0", "z0", "x1", "y1", "z1"),
+                    help="--train-occupancy: the grid's box in the networks' input space (required; NDC space for NDC rays)")
+    ap.add_argument("--occupancy-level", type=float, default=None, metavar="L",
+                    help="--train-occupancy: a cell is set while the running density exceeds L (default 0.01; >= 0)")
+    ap.add_argument("--occupancy-decay", type=float, default=None, metavar="D",
+                    help="--train-occupancy: the running maximum is multiplied by D at every refresh (default 0.95; in (0, 1])")
+    ap.add_argument("--occupancy-every", type=int, default=None, metavar="K", help="--train-occupancy: refresh before every K-th iteration (default 16)")
+    ap.add_argument("--occupancy-warmup", type=int, default=None, metavar="U",
+                    help="--train-occupancy: the first U refreshes only feed the running density; the grid stays all set (default 4)")
+    ap.add_argument("--ray-span-pad", type=float, default=None, metavar="P",
+                    help="--train-occupancy: widen each span by P cells of travel at both ends (default 1)")
     ap.add_argument("--pose-noise", type=float, nargs=2, default=None, metavar=("ROT", "TRANS"),
                     help="perturb the loaded training poses (all but --fix-views) by seeded twists of ROT radians and TRANS scene units "
                          "before training: for experiments and tests")
@@ -346,6 +362,37 @@ def parse_args(argv=None):
             ap.error("--distortion-weight does not run with --refine-poses yet: the geometry route (nerf.FusedJointStep) takes no distortion regulariser")
         if args.autograd_step:
             ap.error("--distortion-weight runs on the fused step (nerf.FusedTrainStep), not with --autograd-step")
+    occupancy_flags = (("--occupancy-bounds", args.occupancy_bounds), ("--occupancy-level", args.occupancy_level),
+                       ("--occupancy-decay", args.occupancy_decay), ("--occupancy-every", args.occupancy_every),
+                       ("--occupancy-warmup", args.occupancy_warmup), ("--ray-span-pad", args.ray_span_pad))
+    if args.train_occupancy is None:
+        for flag, value in occupancy_flags:
+            if value is not None:
+                ap.error(f"{flag} needs --train-occupancy")
+    else:
+        from nerf import _ops
+        if args.autograd_step or args.refine_poses:
+            ap.error("--train-occupancy runs on nerf.FusedTrainStep: not with --autograd-step, and not with --refine-poses (the rewrite "
+                     "of near / far cuts their gradient and the cameras move)")
+        if args.anneal_encoding is not None:
+            ap.error("--train-occupancy reads the networks' density without the encoding anneal's amplitudes: not with --anneal-encoding")
+        if args.occupancy_bounds is None:
+            ap.error("--train-occupancy needs --occupancy-bounds x0 y0 z0 x1 y1 z1")
+        args.occupancy_level = 0.01 if args.occupancy_level is None else args.occupancy_level
+        args.occupancy_decay = 0.95 if args.occupancy_decay is None else args.occupancy_decay
+        args.occupancy_every = 16 if args.occupancy_every is None else args.occupancy_every
+        args.occupancy_warmup = 4 if args.occupancy_warmup is None else args.occupancy_warmup
+        args.ray_span_pad = 1.0 if args.ray_span_pad is None else args.ray_span_pad
+        try:
+            _ops.check_occupancy_grid(args.occupancy_bounds, args.train_occupancy, "--train-occupancy")
+            _ops.check_live_occupancy(args.occupancy_level, args.occupancy_decay, 1, "--train-occupancy")
+            _ops.check_ray_span_pad(args.ray_span_pad, "--ray-span-pad")
+        except ValueError as e:
+            ap.error(str(e))
+        if args.occupancy_every < 1:
+            ap.error("--occupancy-every must be >= 1")
+        if args.occupancy_warmup < 0:
+            ap.error("--occupancy-warmup must be >= 0")
     if args.depth_weight < 0.0:
         ap.error("--depth-weight must be >= 0")
     if args.depth_weight > 0.0:
@@ -455,6 +502,17 @@ def main(argv=None):
                                          images=torch.stack([images[v].reshape(hw[0], hw[1], 3) for v in train_ids]), device=dev)
     loss_t = torch.zeros((), dtype=torch.float32, device=dev)
     fused = None
+    # the occupancy grid that lives beside the networks: the command line's, or - resuming - the one the checkpoint stored, which goes
+    # on with the same draws.  Every rank keeps its own copy, refreshed from bit-identical weights and the grid's own seed: no exchange
+    live = None
+    if args.train_occupancy is not None:
+        if not fused_ok:
+            raise SystemExit("--train-occupancy: this configuration is outside nerf.FusedTrainStep (see FusedTrainStep.applicable)")
+        if args.load_checkpoint and ck.get("train_occupancy") is not None:
+            live = nerf.LiveOccupancyGrid.from_state_dict(ck["train_occupancy"], dev)
+        else:
+            live = nerf.LiveOccupancyGrid(args.occupancy_bounds, args.train_occupancy, dev, level=args.occupancy_level,
+                                          decay=args.occupancy_decay, warmup_updates=args.occupancy_warmup, seed=args.seed)
     head = {}
     if args.depth_weight > 0.0:
         if not fused_ok:
@@ -518,7 +576,9 @@ def main(argv=None):
     if fused_ok:
         fused = nerf.FusedTrainStep(student[0], student[1], selector, cfg, bucket, ex, ed, args.num_random_rays, seed=args.seed + 7919 * rank,
                                     luminance=args.ir, first_iteration=start, draw_view="rays" if args.mix_views else True,
-                                    ndc_focal=ndc_focal, distortion_weights=distortion, encoding_anneal=anneal, **head)
+                                    ndc_focal=ndc_focal, distortion_weights=distortion, encoding_anneal=anneal,
+                                    **(dict(ray_span=live, ray_span_pad=args.ray_span_pad, occupancy_update_every=args.occupancy_every)
+                                       if live is not None else {}), **head)
     graphed = nerf.GraphedTrainStep(fused, opt, eager_iterations=3, use_graphs=use_graph) if fused is not None else None
     use_graph = use_graph and world == 1      # (the autograd step's single graph below: one rank only)
 
@@ -651,6 +711,9 @@ def main(argv=None):
         result["s8_saturated_max"] = s8_saturated_max
     if args.save and rank != 0 and os.environ.get("DEXNERF_SAVE_ALL_RANKS"):   # rehearsals: compare the replicas
         torch.save({"model_coarse_state_dict": student[0].state_dict(), "model_fine_state_dict": student[1].state_dict()}, args.save)
+    if live is not None:
+        result["train_occupancy"] = live
+        result["occupied_fraction"] = live.occupied_fraction()
     if anneal is not None:
         anneal.set_iteration(args.iters)
         result["encoding_amplitudes"] = anneal.amplitudes().tolist()
@@ -674,6 +737,8 @@ def main(argv=None):
             extra = joint_checkpoint_entries(joint, train_ids, extrinsics0) if joint is not None else {}
             if anneal is not None:
                 extra["encoding_anneal"] = anneal.state_dict(iteration=args.iters)
+            if live is not None:
+                extra["train_occupancy"] = live.state_dict()
             torch.save({"iter": args.iters, "model_coarse_state_dict": student[0].state_dict(),
                         "model_fine_state_dict": student[1].state_dict(), "optimizer_state_dict": opt_state,
                         "loss": loss_val, "psnr": psnr, **extra}, args.save)
